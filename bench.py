@@ -9,7 +9,10 @@ winner record for every pose.  With N > 1 every rank (one process per GPU) evalu
 every pose (weak scaling) and the ranks meet in one RCCL all-reduce(MIN) of the packed (cost, index) keys plus the
 all-reduce(SUM) that distributes the winners' records.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline (with the
+`roofline` of the timed launches); `--full` adds everything else the line has carried - the one-solve latencies, the
+closed-loop replays, the secondary kernels, BASELINE configs 3-5, the particle filter, the CPU baselines and, with N > 1,
+the sharded solve.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -72,7 +75,15 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-single-solve", action="store_true",
-                    help="skip the extra 'single_solve' block (one 4096-candidate problem per launch: latency)")
+                    help="(with --full) skip the extra 'single_solve' block (one 4096-candidate problem per launch: latency) "
+                         "and the blocks behind it")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line reports: single_solve, the closed-loop "
+                         "replays, secondary_kernels, config3/4/5, particle_filter, cpu_baseline and (N > 1) sharded_solve")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0): records.npy, the winners' "
+                         "records [P][record floats] float32, and costs.npy, the per-candidate costs [rows][N] float32 of "
+                         "every pose or, above 32 MB, of a fixed seeded sample of poses (cost_rows.npy: which, float64)")
     args = ap.parse_args()
     if args.scaling == "strong":   # configs[3]: the track, horizon and TOTAL candidate count are the configuration
         args.track, args.horizon, args.layout, args.mode = "nordschleife", 80, 1, "S"
@@ -873,6 +884,24 @@ def sharded_solve_latency(workloads, Engine, ShardedRollout, world, rank, local_
                         "max over ranks per solve"}
 
 
+DUMP_COST_BYTES = 32 << 20   # costs.npy at most this large: beyond it a fixed seeded sample of the poses' rows
+
+
+def dump_outputs(directory, records, costs):
+    """--dump-outputs: the last timed step's results as a caller of the step receives them - the winners' records (every
+    pose) and the per-candidate costs (every pose, or a seeded sample of poses that is the same for the same arguments)."""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "records.npy"), records.cpu().numpy().astype(np.float32, copy=False))
+    if costs is None:
+        return
+    P, N = costs.shape
+    rows = min(P, max(1, DUMP_COST_BYTES // (4 * N)))
+    pick = np.arange(P) if rows == P else np.sort(np.random.default_rng(0).choice(P, rows, replace=False))
+    np.save(os.path.join(directory, "costs.npy"),
+            costs[torch.from_numpy(pick).to(costs.device)].cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(directory, "cost_rows.npy"), pick.astype(np.float64))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -969,7 +998,8 @@ def main():
         engine.set_paths(batch.tables)
         engine.sync_tables(stream)
         engines.append(engine)
-    batch.coef_host = [engines[0].coefficients(p) for p in range(min(32, P))]
+    if args.full:   # (the CPU baselines' inputs)
+        batch.coef_host = [engines[0].coefficients(p) for p in range(min(32, P))]
     x0 = torch.tensor(batch.x0 if mode == 0 else batch.pose0, device=device)
     # Synthetic control matrices, produced on the device by the library's counter-based sampler: candidate
     # (rank * N + c) of pose p in buffer b = clip(u_ref + amplitude * sigma * smooth noise), candidate 0 = u_ref.
@@ -1004,10 +1034,10 @@ def main():
 
             def step(self, x0_, U_, seed=None):
                 # N ranks: rollout, the all-reduce(MIN) of the keys, the records
-                if self.streamed:
-                    self.slot.step_stream(x0_, U_, stream, seed=seed)
+                if self.streamed:   # (the stream alternates two record buffers: keep this batch's)
+                    self.records = self.slot.step_stream(x0_, U_, stream, seed=seed)
                 else:
-                    self.slot.step(x0_, U_, stream, seed=seed)
+                    self.records = self.slot.step(x0_, U_, stream, seed=seed)
                 return self.slot
 
             def drain(self):
@@ -1056,6 +1086,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kernel_times = np.concatenate([engine.profile_collect() for engine in engines])
+    if args.dump_outputs and rank == 0:   # (outside the timed region; before anything below launches again)
+        dump_outputs(args.dump_outputs, last.records if args.pipeline else pipe.records, last.costs)
     step_latency = None
     if args.scaling == "strong":
         # the number a controller feels: one step at a time (rollout of this rank's slice, the all-reduce(MIN) of the
@@ -1094,7 +1126,7 @@ def main():
         kernel_ms = float(kernel_times.mean())
 
     sharded_solve = None
-    if world > 1 and args.scaling == "weak" and not args.no_single_solve:
+    if args.full and world > 1 and args.scaling == "weak" and not args.no_single_solve:
         # (every rank: it contains collectives; after the timed region, so it cannot disturb the headline)
         try:
             sharded_solve = sharded_solve_latency(workloads, Engine, ShardedRollout, world, rank, local_rank, device,
@@ -1160,7 +1192,7 @@ def main():
             out["mpc_solve_latency_ms"] = {"p50": sharded_solve["solve_us_p50"] * 1e-3,
                                            "p99": sharded_solve["solve_us_p99"] * 1e-3,
                                            "of": "one sharded solve (sharded_solve workload)"}
-        if world == 1 and not args.no_single_solve and args.scaling == "weak":
+        if args.full and world == 1 and not args.no_single_solve and args.scaling == "weak":
             out["single_solve"] = single_solve(workloads, Engine, args.track, H, N, mode, args.layout, device)
             out["closed_loop_replay"] = closed_loop_replay(workloads)
             # the same loop with north_star's literal rollout (Cartesian bicycle + nearest waypoint) behind get_control
@@ -1185,7 +1217,7 @@ def main():
             # the review reads - north_star's literal kernel, the one-solve configurations, the tick, the particle filter -
             # are copied here as scalars (the blocks they come from stay in the line).
             out["roofline"].update(secondary_scalars(out))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             gpu_costs = last.costs[:32].cpu().numpy()  # costs of the last step = controls[(steps-1) % buffers]
             out["cpu_baseline"] = cpu_baseline(batch, mode, controls[(args.steps - 1) % args.buffers], args.layout, N,
                                                n, gpu_costs, args.cpu_seconds)

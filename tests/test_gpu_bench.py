@@ -19,8 +19,8 @@ def _last_json(text):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--poses", "32", "--steps", "5", "--warmup",
-                           "2", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600)
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--poses", "32", "--steps", "5",
+                           "--warmup", "2", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     out = _last_json(proc.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -82,6 +82,38 @@ def test_single_gpu_line_has_the_contract_fields():
     assert roof["config3_single_us_p50"] == out["config3_single"]["device_resident_us_p50"]
 
 
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline and its `roofline` alone.  --dump-outputs writes the last timed step's
+    records and costs: the same bits from run to run, and every pose's winner cost is the least of its candidates' costs."""
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import acmpc_oracle as orc
+    import bench
+    dumps = []
+    for run in range(2):
+        folder = tmp_path / ("run%d" % run)
+        proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--poses", "32", "--steps", "7", "--warmup",
+                               "2", "--dump-outputs", str(folder)], capture_output=True, text=True, timeout=600)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        out = _last_json(proc.stdout)
+        assert out["steps"] == 7 and out["ms_per_step"] > 0 and out["value"] > 1e6 and out["dtype"] == "f32"
+        assert out["higher_is_better"] is True and out["unit"] == "candidate-trajectories/s"
+        for key in ("cpu_baseline", "single_solve", "closed_loop_replay", "secondary_kernels", "config5_host_pointer",
+                    "particle_filter", "mpc_solve_latency_ms"):
+            assert key not in out, key
+        assert not set(bench.SECONDARY_SCALARS) & set(out["roofline"]) and 0 < out["roofline"]["frac"] < 1
+        dumps.append({name: np.load(str(folder / (name + ".npy"))) for name in ("records", "costs", "cost_rows")})
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name], err_msg=name)
+    records, costs = dumps[0]["records"], dumps[0]["costs"]
+    assert records.dtype == np.float32 and records.shape[0] == 32 and costs.dtype == np.float32
+    assert costs.shape == (32, 4096) and np.array_equal(dumps[0]["cost_rows"], np.arange(32))
+    assert np.isfinite(records[:, 0]).all()
+    assert [float(r) for r in records[:, 0]] == [orc.pick_best(c)[1] for c in costs]
+
+
 def test_stream_of_batches_is_the_default_and_two_launches_the_option():
     """One rank: the previous batch's argmin and records run inside the next batch's rollout launch
     (acmpc_solve_stream_device, the default); the line names the kernel that carried them, and the step is that kernel and a
@@ -136,7 +168,7 @@ def test_two_rank_rehearsal_agrees_across_ranks():
         port = sock.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--poses", "16", "--steps", "5", "--warmup", "2"]
+           "--full", "--poses", "16", "--steps", "5", "--warmup", "2"]
     proc = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, (proc.stdout + proc.stderr)[-3000:]   # a rank disagreement exits non-zero
     out = _last_json(proc.stdout)

@@ -10,7 +10,8 @@ TAG=${1:-r03}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 $ROOT/tools/profile.sh $TAG > $ROOT/gpurun_out/final_profile_$TAG.log 2>&1
 echo "profile.sh done"
-(cd /tmp && export TMPDIR=/tmp && rm -rf $ROOT/gpurun_out/allk_$TAG && rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/gpurun_out/allk_$TAG -- python3 $ROOT/bench.py --steps 50 --warmup 10 > $ROOT/gpurun_out/allk_$TAG.json 2> $ROOT/gpurun_out/allk_$TAG.err)
+RUNS=$(dirname "$(ls -d $ROOT/*/prof_$TAG | head -1)")   # where profile.sh put prof_<tag>: every run of this script goes there
+(cd /tmp && export TMPDIR=/tmp && rm -rf $RUNS/allk_$TAG && rocprofv3 --kernel-trace --stats --output-format csv -d $RUNS/allk_$TAG -- python3 $ROOT/bench.py --full --steps 50 --warmup 10 > $RUNS/allk_$TAG.json 2> $RUNS/allk_$TAG.err)
 echo "all-kernels trace done"
 for spec in "f_S50 S 50 - -" "f_S25 S 25 - -" "f_S100 S 100 - -" "f_S50_pair S 50 ACMPC_NO_QUAD_ROUNDS -" "f_T50 T 50 - -" \
             "f_T50_one T 50 ACMPC_NO_TRIO_ROUNDS -" "f_T50_w25 T 50 - 2,5"; do

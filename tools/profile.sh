@@ -18,5 +18,5 @@ rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_I
   --kernel-trace --output-format csv -d "$OUT/pmc_sq" -- $SHORT > /dev/null 2> "$OUT/pmc_sq.err"
 rocprofv3 --pmc FETCH_SIZE GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -- $SHORT > /dev/null 2> "$OUT/pmc_fetch.err"
 rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d "$OUT/pmc_write" -- $SHORT > /dev/null 2> "$OUT/pmc_write.err"
-python3 $ROOT/bench.py --steps 200 --warmup 20 $* > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err"
+python3 $ROOT/bench.py --full --steps 200 --warmup 20 $* > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err"
 cat "$OUT/bench_plain.json"
