@@ -3,13 +3,16 @@
 `build_mpc` / `SpatialMPC` keep the reference's surface (src/acmpc/control/controller.py:19-29,
 spatial_mpc.py:20-217); `Engine` is the thin object over the C ABI (include/acmpc.h).
 """
-from ._capi import (Engine, EngineError, LAYOUT_CANDIDATE_MAJOR, LAYOUT_STEP_MAJOR, MODE_SPATIAL,  # noqa: F401
-                    MODE_TEMPORAL, load_library)
+from ._capi import (Engine, EngineError, LAYOUT_CANDIDATE_MAJOR, LAYOUT_STEP_MAJOR, MODE_DYNAMIC,  # noqa: F401
+                    MODE_SPATIAL, MODE_TEMPORAL, load_library)
+from .dynamic_model import DynamicBicycleParams  # noqa: F401
+from .dynamic_solver import DynamicSamplingSolver  # noqa: F401
 from .bicycle_model import SpatialBicycleModel  # noqa: F401
 from .command_selection import TemporalCommandInterpolator, TemporalCommandSelector, steer_target  # noqa: F401
 from .mpc import SpatialMPC, build_mpc  # noqa: F401
 from .reference_path import ReferencePath  # noqa: F401
 
-__all__ = ["Engine", "EngineError", "load_library", "MODE_SPATIAL", "MODE_TEMPORAL", "LAYOUT_CANDIDATE_MAJOR",
+__all__ = ["Engine", "EngineError", "load_library", "MODE_SPATIAL", "MODE_TEMPORAL", "MODE_DYNAMIC",
+           "DynamicBicycleParams", "DynamicSamplingSolver", "LAYOUT_CANDIDATE_MAJOR",
            "LAYOUT_STEP_MAJOR", "build_mpc", "SpatialMPC", "SpatialBicycleModel", "ReferencePath",
            "TemporalCommandSelector", "TemporalCommandInterpolator", "steer_target"]

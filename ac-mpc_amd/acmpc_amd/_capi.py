@@ -15,9 +15,11 @@ import numpy as np
 from . import _build
 
 OK, EINVAL, EHIP, ENODEVICE, ECAPACITY, ESTATE = 0, -1, -2, -3, -4, -5
-MODE_SPATIAL, MODE_TEMPORAL = 0, 1
+MODE_SPATIAL, MODE_TEMPORAL, MODE_DYNAMIC = 0, 1, 2
+DYNAMICS_COUNT = 26   # ACMPC_DYNAMICS_COUNT: doubles in mode D's vehicle block
 LAYOUT_CANDIDATE_MAJOR, LAYOUT_STEP_MAJOR = 0, 1
-COEF_STRIDE = {MODE_SPATIAL: 12, MODE_TEMPORAL: 8}
+COEF_STRIDE = {MODE_SPATIAL: 12, MODE_TEMPORAL: 8, MODE_DYNAMIC: 8}
+STATE_FLOATS = {MODE_SPATIAL: 3, MODE_TEMPORAL: 3, MODE_DYNAMIC: 6}   # a start state x0
 REC_COST, REC_VIOLATION, REC_NFEASIBLE, REC_OWNER, REC_HEADER = 0, 1, 2, 3, 4
 
 
@@ -141,6 +143,7 @@ SIGNATURES = {
     "acmpc_rollout_start_clocks": (C.c_int, [_CTX, C.c_void_p, C.c_int32, _I32P]),
     "acmpc_last_error": (C.c_char_p, [_CTX]),
     "acmpc_set_paths": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
+    "acmpc_set_dynamics": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
     "acmpc_get_coefficients": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_set_coefficients": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_record_floats": (C.c_int32, [C.c_int32]),
@@ -493,6 +496,12 @@ class Engine:
         self._check(self._lib.acmpc_set_paths(self._ctx, t.ctypes.data, t.shape[0], t.shape[2]))
         self.P, self.n = t.shape[0], t.shape[2]
 
+    def set_dynamics(self, params):
+        """Mode D's vehicle (acmpc_set_dynamics): a DynamicBicycleParams, or the 26 doubles of the block in ABI order."""
+        block = params.coefficients() if hasattr(params, "coefficients") else params
+        block = np.ascontiguousarray(block, dtype=np.float64).ravel()
+        self._check(self._lib.acmpc_set_dynamics(self._ctx, block.ctypes.data, block.size))
+
     def set_coefficients(self, coef: np.ndarray):
         """The packed float32 tables themselves, [P, n, 12] (mode S) / [P, n, 8] (mode T) or one [n, stride] table
         (acmpc_set_coefficients): e.g. what `tick_device_tables` read back."""
@@ -512,8 +521,9 @@ class Engine:
 
     # -- host-pointer solve -------------------------------------------------------------------------------
     def solve(self, x0: np.ndarray, U: np.ndarray, layout: int = LAYOUT_CANDIDATE_MAJOR, want_costs: bool = True):
-        """x0 [P,3], U [P,N,n,2] (layout 0) or [P,n,2,N] (layout 1) -> dict(best_idx, costs, record fields)."""
-        x0 = np.ascontiguousarray(x0, dtype=np.float32).reshape(-1, 3)
+        """x0 [P,3] ([P,6] in mode D), U [P,N,n,2] (layout 0) or [P,n,2,N] (layout 1) -> dict(best_idx, costs, record
+        fields)."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float32).reshape(-1, STATE_FLOATS[self.mode])
         U = np.ascontiguousarray(U, dtype=np.float32)
         if U.ndim == 3:
             U = U[None]
@@ -572,8 +582,8 @@ class Engine:
 
     def optimize(self, x0: np.ndarray, centre: np.ndarray, u_ref, n_candidates: int, rounds: int, sigma,
                  shrink: float = 0.5, seed: int = 0):
-        """Sampling optimisation entirely on the device; x0 [P,3], centre/u_ref [P,n,2] -> record fields."""
-        x0 = np.ascontiguousarray(x0, dtype=np.float32).reshape(-1, 3)
+        """Sampling optimisation entirely on the device; x0 [P,3] ([P,6] in mode D), centre/u_ref [P,n,2] -> record fields."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float32).reshape(-1, STATE_FLOATS[self.mode])
         centre = np.ascontiguousarray(centre, dtype=np.float32)
         if centre.ndim == 2:
             centre = centre[None]

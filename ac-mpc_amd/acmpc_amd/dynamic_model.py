@@ -1,0 +1,125 @@
+"""Mode D's vehicle: the six-state dynamic bicycle with Pacejka lateral tyre forces of the reference
+(src/acmpc/control/dynamic_bicycle_model.py) - its parameters as the ABI's vehicle block, and a float64 host mirror of
+its Euler step.
+
+The reference's fitted drive, brake and friction maps are in newtons while its tyre forces come out in kilonewtons (mass
+1.160 t, F_z0 = 3): taken literally, 20 m/s at pedal 0.5 becomes 145 m/s after one 50 ms step.  The coefficients are
+therefore data ("Mode D"): `DynamicBicycleParams.reference(literal=True)` is the reference's block bit
+for bit (the parity tests use it), `reference()` - the default vehicle - the same block with the nine longitudinal
+coefficients in kilonewtons."""
+from __future__ import annotations
+
+import dataclasses
+from typing import Tuple
+
+import numpy as np
+
+# ABI order of the vehicle block (include/acmpc.h: acmpc_set_dynamics)
+FIELDS = ("F_z0", "Bf", "Cf", "Df", "Ef", "epsf", "Br", "Cr", "Dr", "Er", "epsr", "mass", "Iz", "g", "lf", "lr",
+          "brake_bias", "Cm1", "Cm2", "Cm3", "Cb1", "Cb2", "Cb3", "Cfric1", "Cfric2", "Cfric3")
+LONGITUDINAL = ("Cm1", "Cm2", "Cm3", "Cb1", "Cb2", "Cb3", "Cfric1", "Cfric2", "Cfric3")
+
+# what the reference's two curve_fit calls return (dynamic_bicycle_model.py:57-77; recorded in tests/golden/dynamic_bicycle.npz)
+_FITTED = dict(Cm1=6634.272598708605, Cm2=-44.729701293631884, Cm3=1.789313054496502, Cb1=16807.528158800185,
+               Cb2=-15.288256364280713, Cb3=0.3838603329874931, Cfric1=22.272598708604782, Cfric2=13.412206693199884,
+               Cfric3=0.5405221569587206)
+
+
+@dataclasses.dataclass
+class DynamicBicycleParams:
+    """The vehicle block, fields named as the reference names them (dynamic_bicycle_model.py:7-77)."""
+    F_z0: float = 3.0
+    Bf: float = 9.62
+    Cf: float = 2.59
+    Df: float = 4.120
+    Ef: float = 1.0
+    epsf: float = -0.0813
+    Br: float = 8.62
+    Cr: float = 2.65
+    Dr: float = 4.617
+    Er: float = 1.0
+    epsr: float = -0.1263
+    mass: float = 1.160
+    Iz: float = 1.260
+    g: float = 9.81
+    lf: float = 1.51
+    lr: float = 1.388
+    brake_bias: float = 0.7
+    Cm1: float = _FITTED["Cm1"] * 1e-3
+    Cm2: float = _FITTED["Cm2"] * 1e-3
+    Cm3: float = _FITTED["Cm3"] * 1e-3
+    Cb1: float = _FITTED["Cb1"] * 1e-3
+    Cb2: float = _FITTED["Cb2"] * 1e-3
+    Cb3: float = _FITTED["Cb3"] * 1e-3
+    Cfric1: float = _FITTED["Cfric1"] * 1e-3
+    Cfric2: float = _FITTED["Cfric2"] * 1e-3
+    Cfric3: float = _FITTED["Cfric3"] * 1e-3
+
+    @classmethod
+    def reference(cls, literal: bool = False) -> "DynamicBicycleParams":
+        """The reference's vehicle: `literal=True` its numbers exactly as it holds them (longitudinal maps in N against
+        tyre forces in kN); the default the kN-consistent block (the nine longitudinal coefficients times 1e-3)."""
+        if literal:
+            return cls(**_FITTED)
+        return cls()
+
+    @classmethod
+    def from_coefficients(cls, coef) -> "DynamicBicycleParams":
+        coef = np.asarray(coef, dtype=np.float64).ravel()
+        if coef.size != len(FIELDS):
+            raise ValueError("a vehicle block has %d values" % len(FIELDS))
+        return cls(**{k: float(v) for k, v in zip(FIELDS, coef)})
+
+    def coefficients(self) -> np.ndarray:
+        """The ABI block: float64 [26] in FIELDS order (acmpc_set_dynamics)."""
+        return np.array([getattr(self, k) for k in FIELDS], dtype=np.float64)
+
+    @property
+    def F_zf(self) -> float:
+        return self.mass * self.g * self.lr / (self.lr + self.lf)
+
+    @property
+    def F_zr(self) -> float:
+        return self.mass * self.g * self.lf / (self.lr + self.lf)
+
+    def predict_next_state(self, state, u, dt: float = 0.05) -> Tuple[np.ndarray, np.ndarray, list]:
+        """One explicit Euler step in float64: state (X, Y, yaw, vx, vy, r), u = (delta, pedal) with the pedal in
+        [-1, 1].  Returns (next_state, x_dot, [F_fy, F_ry, F_fx, F_rx]) like the reference; the caller clips vx >= 0
+        (the reference's loop does, dynamic_bicycle_model.py:180; so do the kernels, inside the step)."""
+        delta, pedal = float(u[0]), float(u[1])
+        X, Y, yaw, vx, vy, r = (float(s) for s in state)
+        den = vx + 1e-3
+        alpha_f = delta - np.arctan((r * self.lf + vy) / den)
+        alpha_r = np.arctan((r * self.lr - vy) / den)
+        F_fy = self._lateral(alpha_f, self.Bf, self.Cf, self.Df, self.Ef, self.epsf, self.F_zf)
+        F_ry = self._lateral(alpha_r, self.Br, self.Cr, self.Dr, self.Er, self.epsr, self.F_zr)
+        brake = self.Cb1 - self.Cb2 * vx - self.Cb3 * vx ** 2
+        motor = self.Cm1 - self.Cm2 * vx - self.Cm3 * vx ** 2
+        F_fric = -self.Cfric1 - self.Cfric2 * vx - self.Cfric3 * vx ** 2
+        braking = min(0.0, pedal)
+        F_rx = brake * (1 - self.brake_bias) * braking + motor * max(0.0, pedal)
+        F_fx = brake * self.brake_bias * braking
+        sd, cd = np.sin(delta), np.cos(delta)
+        x_dot = np.array([
+            vx * np.cos(yaw) - vy * np.sin(yaw),
+            vx * np.sin(yaw) + vy * np.cos(yaw),
+            r,
+            (F_rx + F_fx + F_fric - F_fy * sd + self.mass * vy * r) / self.mass,
+            (F_ry + F_fy * cd - self.mass * vx * r) / self.mass,
+            (F_fy * self.lf * cd - F_ry * self.lr) / self.Iz,
+        ])
+        return np.asarray(state, dtype=np.float64) + x_dot * dt, x_dot, [F_fy, F_ry, F_fx, F_rx]
+
+    def _lateral(self, alpha, B, C, D, E, eps, F_z):
+        """Pacejka's magic formula with the load-dependent peak D (1 + eps F_z / F_z0) F_z / F_z0."""
+        ba = B * alpha
+        return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0 * np.sin(C * np.arctan(ba - E * (ba - np.arctan(ba))))
+
+    def rollout(self, state, U, dt: float = 0.05) -> np.ndarray:
+        """The mirror over a control sequence U [n, 2] with vx clipped after every step: states [n + 1, 6]."""
+        out = [np.asarray(state, dtype=np.float64)]
+        for u in np.asarray(U, dtype=np.float64):
+            nxt = self.predict_next_state(out[-1], u, dt)[0]
+            nxt[3] = max(nxt[3], 0.0)
+            out.append(nxt)
+        return np.stack(out)

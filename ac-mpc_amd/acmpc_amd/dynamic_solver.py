@@ -1,0 +1,82 @@
+"""`DynamicSamplingSolver`: the sampling controller with mode D's vehicle - candidates (delta, pedal) rolled through the
+dynamic (Pacejka) bicycle on the GPU (csrc/acmpc_dynamic.hip), scored with mode T's nearest-waypoint cost, the cheapest
+kept (`acmpc_optimize`: sample -> rollout -> finalize per round).  The seam is ControlSolver's: `solve(state, path) ->
+obj` with `obj.x` laid out `[x_0 .. x_n ; u_0 .. u_{n-1}]` (x = (X, Y, yaw), u = (delta, pedal)) and `obj.info.status`.
+
+Optional config keys, as sampling_solver.py reads them: `n_candidates`, `sampling_rounds`, `sampling_sigma` (delta rad,
+pedal), `sampling_seed`, `w_bound`, `nn_window`, `rollout_dt`; the weights `step_cost` (e_y, e_psi, -), `r_term` (speed
+error, steering against delta_ref), `final_cost`; the input box `u_min` / `u_max` (default delta +-0.3 rad, pedal +-1).
+The warm start is the previous plan shifted by one step."""
+from __future__ import annotations
+
+from types import SimpleNamespace
+from typing import Dict, Optional
+
+import numpy as np
+
+from . import _capi
+from .dynamic_model import DynamicBicycleParams
+
+SOLVED = "solved"
+DEFAULT_CANDIDATES = 16384
+DEFAULT_ROUNDS = 2
+DEFAULT_SIGMA = (0.05, 0.3)
+DEFAULT_U_MIN = (-0.3, -1.0)
+DEFAULT_U_MAX = (0.3, 1.0)
+
+
+class DynamicSamplingSolver:
+    def __init__(self, config: Dict, params: Optional[DynamicBicycleParams] = None, device: int = -1):
+        self._n = int(config["horizon"]) - 1
+        self._N = int(config.get("n_candidates", DEFAULT_CANDIDATES))
+        self._rounds = int(config.get("sampling_rounds", DEFAULT_ROUNDS))
+        self._sigma = np.asarray(config.get("sampling_sigma", DEFAULT_SIGMA), dtype=np.float64)
+        self._seed = int(config.get("sampling_seed", 0))
+        self._dt = float(config.get("rollout_dt", 0.05))
+        self._params = params if params is not None else DynamicBicycleParams.reference()
+        nn_window = config.get("nn_window")
+        self._engine = _capi.Engine(
+            mode=_capi.MODE_DYNAMIC, max_problems=1, max_candidates=self._N, max_steps=self._n,
+            step_cost=config.get("step_cost", (1.0, 1.0, 0.0)), r_term=config.get("r_term", (0.5, 10.0)),
+            final_cost=config.get("final_cost", (1.0, 1.0, 0.0)), u_min=config.get("u_min", DEFAULT_U_MIN),
+            u_max=config.get("u_max", DEFAULT_U_MAX), margin=float(config.get("margin", 0.0)),
+            wheelbase=self._params.lf + self._params.lr, dt=self._dt, w_bound=float(config.get("w_bound", 1.0e6)),
+            device=device, nn_window=None if nn_window is None else tuple(nn_window))
+        self._engine.set_dynamics(self._params)
+        self._plan: Optional[np.ndarray] = None
+        self._calls = 0
+
+    @property
+    def engine(self):
+        return self._engine
+
+    def warm_start(self) -> np.ndarray:
+        """The centre of the next solve: the last plan shifted by one step (its last control repeated), zeros at first."""
+        if self._plan is None:
+            return np.zeros((self._n, 2), dtype=np.float32)
+        return np.concatenate([self._plan[1:], self._plan[-1:]]).astype(np.float32)
+
+    def solve(self, state, reference_path):
+        """state (X, Y, yaw, vx, vy, r); reference_path a [7, n] table (rows x, y, psi, kappa, ds, width, v) or an object
+        with `as_table()` / `_reference_path` giving one."""
+        table = reference_path
+        if hasattr(reference_path, "as_table"):
+            table = reference_path.as_table()
+        elif hasattr(reference_path, "_reference_path"):
+            table = reference_path._reference_path
+        table = np.asarray(table, dtype=np.float64)[:, : self._n]
+        self._engine.set_paths(table)
+        out = self._engine.optimize(np.asarray(state, dtype=np.float32).reshape(1, 6), self.warm_start()[None], None,
+                                    self._N, self._rounds, self._sigma, seed=self._seed + self._calls)
+        self._calls += 1
+        u = np.asarray(out["u"][0], dtype=np.float64).reshape(self._n, 2)
+        x = np.asarray(out["x"][0], dtype=np.float64).reshape(self._n + 1, 3)
+        ok = bool(np.isfinite(out["cost"][0]))
+        if ok:
+            self._plan = u.astype(np.float32)
+        status = SOLVED if ok else "failed"
+        return SimpleNamespace(x=np.concatenate([x.ravel(), u.ravel()]), info=SimpleNamespace(status=status),
+                               cost=float(out["cost"][0]), violation=float(out["violation"][0]))
+
+    def close(self):
+        self._engine.close()

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/acmpc.h"
+#include "acmpc_dynamic.h"
 #include "acmpc_frames.h"
 #include "acmpc_kernels.h"
 #include "acmpc_lq.h"
@@ -169,6 +170,10 @@ struct acmpc_ctx {
   std::vector<hipEvent_t> prof_start, prof_stop;
   size_t prof_used = 0;
 
+  // mode D: the vehicle's float32 constants (acmpc_set_dynamics)
+  bool has_dynamics = false;
+  acmpc::Vehicle vehicle{};
+
   mutable std::string err;
 };
 
@@ -319,6 +324,8 @@ int upload_frames(acmpc_ctx* c, hipStream_t s) {
 int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call = false) {
   if (c->stream_pending && !stream_call)
     return fail(c, ACMPC_ESTATE, "a batch of acmpc_solve_stream_device is pending: acmpc_solve_stream_flush first");
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC && !c->has_dynamics)
+    return fail(c, ACMPC_ESTATE, "mode D: acmpc_set_dynamics has not been called");
   if (P < 1 || N < 1 || n < 1) return fail(c, ACMPC_EINVAL, "P, N and n must be positive");
   if (layout != ACMPC_LAYOUT_CANDIDATE_MAJOR && layout != ACMPC_LAYOUT_STEP_MAJOR)
     return fail(c, ACMPC_EINVAL, "unknown layout");
@@ -340,6 +347,24 @@ int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call 
 
 int rollout(acmpc_ctx* c, const float* d_x0, const float* d_U, int P, int N, int n, int layout, int64_t offset,
             float* d_costs, hipStream_t s, acmpc::LaunchShape* shape_out) {
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC) {   // mode D: its own kernel (acmpc_dynamic.hip)
+    acmpc::RolloutArgs a{};
+    a.U = d_U;
+    a.x0 = d_x0;
+    a.coef = c->d_coef;
+    a.costs = d_costs;
+    a.partial_keys = c->d_partial_keys;
+    a.partial_feas = c->d_partial_feas;
+    a.P = P;
+    a.N = N;
+    a.n = n;
+    a.index_offset = offset;
+    a.w = c->w;
+    ACMPC_HIP(c, acmpc::launch_rollout_dynamic(layout, a, c->vehicle, s));
+    *shape_out = acmpc::LaunchShape{};
+    shape_out->blocks_per_problem = acmpc::dynamic_blocks_per_problem(P, N);
+    return ACMPC_OK;
+  }
   const acmpc::LaunchShape shape = acmpc::choose_shape(P, N, layout, c->prm.mode, n, c->opt);
   acmpc::RolloutArgs a{};
   a.U = d_U;
@@ -412,6 +437,11 @@ int finalize(acmpc_ctx* c, const int64_t* d_keys_in, int64_t* d_keys_out, const 
   a.n = n;
   a.index_offset = offset;
   a.w = c->w;
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC) {
+    if (regen != nullptr) return fail(c, ACMPC_ESTATE, "mode D re-rolls its winners from U: no re-drawn candidates");
+    ACMPC_HIP(c, acmpc::launch_finalize_dynamic(layout, a, c->vehicle, s));
+    return ACMPC_OK;
+  }
   ACMPC_HIP(c, acmpc::launch_finalize(c->prm.mode, layout, a, s, c->opt));
   return ACMPC_OK;
 }
@@ -616,7 +646,8 @@ int ensure_staging(acmpc_ctx* c) {
   ACMPC_HIP(c, alloc_once(&c->d_uref, static_cast<size_t>(p.max_problems) * p.max_steps * 2 * sizeof(float)));
   if (c->stream == nullptr) ACMPC_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   ACMPC_HIP(c, alloc_once(&c->d_U, cand * p.max_steps * 2 * sizeof(float)));
-  ACMPC_HIP(c, alloc_once(&c->d_x0, static_cast<size_t>(p.max_problems) * 3 * sizeof(float)));
+  const size_t state_floats = p.mode == ACMPC_MODE_DYNAMIC ? acmpc::kDynamicStateFloats : 3;
+  ACMPC_HIP(c, alloc_once(&c->d_x0, static_cast<size_t>(p.max_problems) * state_floats * sizeof(float)));
   ACMPC_HIP(c, alloc_once(&c->d_costs, cand * sizeof(float)));
   ACMPC_HIP(c, alloc_once(&c->d_records,
                           static_cast<size_t>(p.max_problems) * acmpc_record_floats(p.max_steps) * sizeof(float)));
@@ -624,7 +655,7 @@ int ensure_staging(acmpc_ctx* c) {
   const int rc_tail = ensure_tail_buffers(c);
   if (rc_tail != ACMPC_OK) return rc_tail;
   ACMPC_HIP(c, host_alloc_once(&c->h_keys, static_cast<size_t>(p.max_problems) * sizeof(int64_t)));
-  ACMPC_HIP(c, host_alloc_once(&c->h_io, (static_cast<size_t>(p.max_problems) * (3 + acmpc_record_floats(p.max_steps)) + 4) * sizeof(float)));
+  ACMPC_HIP(c, host_alloc_once(&c->h_io, (static_cast<size_t>(p.max_problems) * (state_floats + acmpc_record_floats(p.max_steps)) + 4) * sizeof(float)));
   if (p.lq_candidate != 0 && c->h_lq == nullptr) {
     const size_t lq_bytes = static_cast<size_t>(p.max_problems) * p.max_steps * 2 * sizeof(float);
     ACMPC_HIP(c, host_alloc_once(&c->h_lq, lq_bytes));
@@ -766,8 +797,12 @@ int acmpc_create(const acmpc_params* params, acmpc_ctx** out) {
   if (params == nullptr || out == nullptr) return fail(nullptr, ACMPC_EINVAL, "null argument");
   *out = nullptr;
   if (params->struct_size != sizeof(acmpc_params)) return fail(nullptr, ACMPC_EINVAL, "acmpc_params size mismatch");
-  if (params->mode != ACMPC_MODE_SPATIAL && params->mode != ACMPC_MODE_TEMPORAL)
+  if (params->mode != ACMPC_MODE_SPATIAL && params->mode != ACMPC_MODE_TEMPORAL && params->mode != ACMPC_MODE_DYNAMIC)
     return fail(nullptr, ACMPC_EINVAL, "unknown mode");
+  if (params->mode == ACMPC_MODE_DYNAMIC && params->lq_candidate != 0)
+    return fail(nullptr, ACMPC_EINVAL, "mode D: lq_candidate must be 0 (the LQ plan is for the spatial model)");
+  if (params->mode == ACMPC_MODE_DYNAMIC && params->max_steps > acmpc::kDynamicMaxSteps)
+    return fail(nullptr, ACMPC_EINVAL, "mode D: max_steps <= 512");
   if (params->max_problems < 1 || params->max_candidates < 1 || params->max_steps < 1)
     return fail(nullptr, ACMPC_EINVAL, "capacities must be positive");
   if (params->nn_ahead >= 0 && (params->nn_back < 0 || params->nn_back + params->nn_ahead + 1 > 64))
@@ -1013,8 +1048,9 @@ int acmpc_finalize_device(acmpc_ctx* c, const int64_t* d_keys, const float* d_x0
   int rc = check_shape(c, P, N, n, layout);
   if (rc != ACMPC_OK) return rc;
   if (!c->device_ready) return fail(c, ACMPC_ESTATE, "acmpc_rollout_device must run first");
-  const acmpc::LaunchShape shape = acmpc::choose_shape(P, N, layout, c->prm.mode, n, c->opt);
-  return finalize(c, d_keys, nullptr, d_x0, d_U, P, N, n, layout, index_offset, d_records, shape.blocks_per_problem,
+  const int blocks = c->prm.mode == ACMPC_MODE_DYNAMIC ? acmpc::dynamic_blocks_per_problem(P, N)
+                                                       : acmpc::choose_shape(P, N, layout, c->prm.mode, n, c->opt).blocks_per_problem;
+  return finalize(c, d_keys, nullptr, d_x0, d_U, P, N, n, layout, index_offset, d_records, blocks,
                   static_cast<hipStream_t>(stream));
 }
 
@@ -1039,6 +1075,8 @@ int acmpc_solve_sampled_device(acmpc_ctx* c, const float* d_x0, const float* d_U
                                double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round, float* d_costs,
                                int64_t* d_keys, float* d_records, void* stream) {
   if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC)
+    return fail(c, ACMPC_ESTATE, "mode D re-rolls its winners from U: use acmpc_solve_device / acmpc_finalize_device");
   if (d_x0 == nullptr || d_U == nullptr || d_centre == nullptr || d_records == nullptr)
     return fail(c, ACMPC_EINVAL, "null device pointer");
   if (centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
@@ -1068,6 +1106,8 @@ int acmpc_solve_stream_device(acmpc_ctx* c, const float* d_x0, const float* d_U,
                               double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round, float* d_costs,
                               int64_t* d_keys, float* d_records, void* stream) {
   if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC)
+    return fail(c, ACMPC_ESTATE, "mode D re-rolls its winners from U: use acmpc_solve_device / acmpc_finalize_device");
   if (d_x0 == nullptr || d_U == nullptr || d_records == nullptr) return fail(c, ACMPC_EINVAL, "null device pointer");
   if (d_centre != nullptr && centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
   int rc = check_shape(c, P, N, n, layout, true);
@@ -1145,6 +1185,116 @@ int acmpc_solve_stream_device(acmpc_ctx* c, const float* d_x0, const float* d_U,
   return ACMPC_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// acmpc_solve in mode D: copies up, rollout + finalize (acmpc_dynamic.hip), copies down
+int solve_dynamic_host(acmpc_ctx* c, const float* x0, const float* U, int P, int N, int n, int layout, float* costs,
+                       int32_t* best_idx, float* records) {
+  hipStream_t s = c->stream;
+  const size_t cand = static_cast<size_t>(P) * N;
+  ACMPC_HIP(c, hipMemcpyAsync(c->d_x0, x0, static_cast<size_t>(P) * acmpc::kDynamicStateFloats * sizeof(float),
+                              hipMemcpyHostToDevice, s));
+  ACMPC_HIP(c, hipMemcpyAsync(c->d_U, U, cand * n * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+  acmpc::LaunchShape shape;
+  int rc = rollout(c, c->d_x0, c->d_U, P, N, n, layout, 0, costs != nullptr ? c->d_costs : nullptr, s, &shape);
+  if (rc != ACMPC_OK) return rc;
+  rc = finalize(c, nullptr, c->d_keys, c->d_x0, c->d_U, P, N, n, layout, 0, records != nullptr ? c->d_records : nullptr,
+                shape.blocks_per_problem, s);
+  if (rc != ACMPC_OK) return rc;
+  ACMPC_HIP(c, hipMemcpyAsync(c->h_keys, c->d_keys, static_cast<size_t>(P) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  if (records != nullptr)
+    ACMPC_HIP(c, hipMemcpyAsync(records, c->d_records, static_cast<size_t>(P) * acmpc_record_floats(n) * sizeof(float),
+                                hipMemcpyDeviceToHost, s));
+  if (costs != nullptr) ACMPC_HIP(c, hipMemcpyAsync(costs, c->d_costs, cand * sizeof(float), hipMemcpyDeviceToHost, s));
+  ACMPC_HIP(c, hipStreamSynchronize(s));
+  if (best_idx != nullptr)
+    for (int p = 0; p < P; ++p) best_idx[p] = static_cast<int32_t>(acmpc_key_index(c->h_keys[p]));
+  return ACMPC_OK;
+}
+
+// acmpc_optimize in mode D: per round sample -> rollout -> finalize, three launches; round r samples round the u block
+// of round r - 1's record, with the spread sigma shrink^r (acmpc_optimize's own schedule)
+int optimize_dynamic(acmpc_ctx* c, const float* x0, const float* centre, const float* u_ref, int P, int N, int n,
+                     int rounds, const double sigma[2], double shrink, uint64_t seed, float* records) {
+  hipStream_t s = c->stream;
+  const size_t path_bytes = static_cast<size_t>(P) * n * 2 * sizeof(float);
+  const int layout = ACMPC_LAYOUT_STEP_MAJOR;
+  const int rec_floats = acmpc_record_floats(n);
+  int rc = upload_tables(c, s);
+  if (rc != ACMPC_OK) return rc;
+  ACMPC_HIP(c, hipMemcpyAsync(c->d_x0, x0, static_cast<size_t>(P) * acmpc::kDynamicStateFloats * sizeof(float),
+                              hipMemcpyHostToDevice, s));
+  ACMPC_HIP(c, hipMemcpyAsync(c->d_centre, centre, path_bytes, hipMemcpyHostToDevice, s));
+  if (u_ref != nullptr) ACMPC_HIP(c, hipMemcpyAsync(c->d_uref, u_ref, path_bytes, hipMemcpyHostToDevice, s));
+  double scale = 1.0;
+  for (int r = 0; r < rounds; ++r, scale *= shrink) {
+    const float* d_c = (r == 0) ? c->d_centre : c->d_records + ACMPC_REC_HEADER;
+    rc = sample(c, d_c, (r == 0) ? 2 * n : rec_floats, u_ref != nullptr ? c->d_uref : nullptr, P, N, n, layout, 0,
+                sigma[0] * scale, sigma[1] * scale, seed, static_cast<uint32_t>(r), c->d_U, s);
+    if (rc != ACMPC_OK) return rc;
+    acmpc::LaunchShape shape;
+    rc = rollout(c, c->d_x0, c->d_U, P, N, n, layout, 0, nullptr, s, &shape);
+    if (rc != ACMPC_OK) return rc;
+    rc = finalize(c, nullptr, nullptr, c->d_x0, c->d_U, P, N, n, layout, 0, c->d_records, shape.blocks_per_problem, s);
+    if (rc != ACMPC_OK) return rc;
+  }
+  ACMPC_HIP(c, hipMemcpyAsync(records, c->d_records, static_cast<size_t>(P) * rec_floats * sizeof(float),
+                              hipMemcpyDeviceToHost, s));
+  ACMPC_HIP(c, hipStreamSynchronize(s));
+  return ACMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int acmpc_set_dynamics(acmpc_ctx* c, const double* coef, int32_t count) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics needs a mode D handle");
+  if (coef == nullptr) return fail(c, ACMPC_EINVAL, "null vehicle block");
+  if (count != acmpc::kDynamicsCount) return fail(c, ACMPC_EINVAL, "the vehicle block has ACMPC_DYNAMICS_COUNT = 26 values");
+  for (int q = 0; q < count; ++q)
+    if (!std::isfinite(coef[q])) return fail(c, ACMPC_EINVAL, "non-finite value in the vehicle block");
+  const double F_z0 = coef[0], Bf = coef[1], Cf = coef[2], Df = coef[3], Ef = coef[4], epsf = coef[5], Br = coef[6],
+               Cr = coef[7], Dr = coef[8], Er = coef[9], epsr = coef[10], mass = coef[11], Iz = coef[12], g = coef[13],
+               lf = coef[14], lr = coef[15], bias = coef[16];
+  if (!(mass > 0.0) || !(Iz > 0.0)) return fail(c, ACMPC_EINVAL, "mass and Iz must be positive");
+  if (F_z0 == 0.0 || lr + lf == 0.0) return fail(c, ACMPC_EINVAL, "F_z0 and lf + lr must not be zero");
+  // float64, the reference's association, each constant rounded to float32 once ("Mode D")
+  const double F_zf = mass * g * lr / (lr + lf);
+  const double F_zr = mass * g * lf / (lr + lf);
+  acmpc::Vehicle& v = c->vehicle;
+  v.lf = static_cast<float>(lf);
+  v.lr = static_cast<float>(lr);
+  v.Bf = static_cast<float>(Bf);
+  v.Cf = static_cast<float>(Cf);
+  v.Ef = static_cast<float>(Ef);
+  v.Pf = static_cast<float>(Df * (1 + epsf * F_zf / F_z0) * F_zf / F_z0);
+  v.Br = static_cast<float>(Br);
+  v.Cr = static_cast<float>(Cr);
+  v.Er = static_cast<float>(Er);
+  v.Pr = static_cast<float>(Dr * (1 + epsr * F_zr / F_z0) * F_zr / F_z0);
+  v.mass = static_cast<float>(mass);
+  v.inv_mass = static_cast<float>(1.0 / mass);
+  v.inv_Iz = static_cast<float>(1.0 / Iz);
+  v.Cm1 = static_cast<float>(coef[17]);
+  v.Cm2 = static_cast<float>(coef[18]);
+  v.Cm3 = static_cast<float>(coef[19]);
+  v.Cb1 = static_cast<float>(coef[20]);
+  v.Cb2 = static_cast<float>(coef[21]);
+  v.Cb3 = static_cast<float>(coef[22]);
+  v.fric0 = static_cast<float>(-coef[23]);
+  v.Cfric2 = static_cast<float>(coef[24]);
+  v.Cfric3 = static_cast<float>(coef[25]);
+  v.bias_front = static_cast<float>(bias);
+  v.bias_rear = static_cast<float>(1 - bias);
+  v.wheelbase = static_cast<float>(c->prm.wheelbase);
+  c->has_dynamics = true;
+  return ACMPC_OK;
+}
+
 int acmpc_solve(acmpc_ctx* c, const float* x0, const float* U, int32_t P, int32_t N, int32_t n, int32_t layout,
                 float* costs, int32_t* best_idx, float* records) {
   if (c == nullptr) return ACMPC_EINVAL;
@@ -1158,6 +1308,7 @@ int acmpc_solve(acmpc_ctx* c, const float* x0, const float* U, int32_t P, int32_
   hipStream_t s = c->stream;
   rc = upload_tables(c, s);
   if (rc != ACMPC_OK) return rc;
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC) return solve_dynamic_host(c, x0, U, P, N, n, layout, costs, best_idx, records);
   const size_t cand = static_cast<size_t>(P) * N;
   const size_t rec_bytes = static_cast<size_t>(P) * acmpc_record_floats(n) * sizeof(float);
   // Nothing small crosses the host link as a copy of its own (round 4): the start states are written into the handle's
@@ -1255,6 +1406,8 @@ int acmpc_finalize_sampled_device(acmpc_ctx* c, const int64_t* d_keys, const flo
                                   double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round, float* d_records,
                                   void* stream) {
   if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC)
+    return fail(c, ACMPC_ESTATE, "mode D re-rolls its winners from U: use acmpc_solve_device / acmpc_finalize_device");
   if (d_x0 == nullptr || d_centre == nullptr || d_records == nullptr) return fail(c, ACMPC_EINVAL, "null device pointer");
   if (centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
   int rc = check_shape(c, P, N, n, ACMPC_LAYOUT_STEP_MAJOR);
@@ -1472,6 +1625,10 @@ int acmpc_optimize(acmpc_ctx* c, const float* x0, const float* centre, const flo
   if (rc != ACMPC_OK) return rc;
   rc = ensure_staging(c);
   if (rc != ACMPC_OK) return rc;
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC) {
+    if (c->prm.centre_update != 0) return fail(c, ACMPC_ESTATE, "mode D: acmpc_optimize recentres on the argmin only");
+    return optimize_dynamic(c, x0, centre, u_ref, P, N, n, rounds, sigma, shrink, seed, records);
+  }
   hipStream_t s = c->stream;
   const size_t x0_bytes = static_cast<size_t>(P) * 3 * sizeof(float);
   const size_t path_bytes = static_cast<size_t>(P) * n * 2 * sizeof(float);
@@ -1711,6 +1868,8 @@ int acmpc_control_tick(acmpc_ctx* c, const acmpc_tick* t, const double* coords, 
   if (t->struct_size != sizeof(acmpc_tick)) return fail(c, ACMPC_EINVAL, "acmpc_tick size mismatch");
   if (c->stream_pending)
     return fail(c, ACMPC_ESTATE, "a batch of acmpc_solve_stream_device is pending: acmpc_solve_stream_flush first");
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC)
+    return fail(c, ACMPC_ESTATE, "mode D has no control tick: use acmpc_set_paths + acmpc_optimize");
   if (c->prm.centre_update != 0) return fail(c, ACMPC_ESTATE, "acmpc_control_tick needs a handle with centre_update = 0");
   const bool temporal = c->prm.mode == ACMPC_MODE_TEMPORAL;
   if (temporal && !(c->prm.dt > 0.0)) return fail(c, ACMPC_ESTATE, "mode T needs a positive dt");

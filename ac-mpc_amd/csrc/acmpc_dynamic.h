@@ -1,0 +1,176 @@
+// Mode D: candidates scored through the dynamic (Pacejka) bicycle of the reference (src/acmpc/control/
+// dynamic_bicycle_model.py) - device arithmetic and the launchers of its two kernels (acmpc_dynamic.hip).
+//
+// The float32 "spec order" of DESIGN.md section 2 ("Mode D"), restated bit for bit by tests/dynamic_spec.py: the
+// reference's expression tree evaluated left to right, no fused multiply-add except inside the named polynomial kernels
+// (atan_spec here, sincos_spec / wrap_spec of acmpc_device.h, the search key and the cost accumulators of mode T),
+// divisions IEEE and correctly rounded (hipcc's default for `/` on float: v_div_scale / v_div_fmas / v_div_fixup), no
+// library or hardware transcendental.  Every function is written once for F = float (one candidate per lane) and
+// F = f32x2 (two candidates per lane in v_pk_* instructions); per element the operations and their order do not depend
+// on F.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "acmpc_device.h"
+#include "acmpc_kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace acmpc {
+
+constexpr int kDynamicsCount = 26;   // ACMPC_DYNAMICS_COUNT: doubles in the vehicle block of acmpc_set_dynamics
+constexpr int kDynamicStateFloats = 6;
+constexpr int kDynamicMaxSteps = 512;   // the rollout's LDS tables (64 B per waypoint) and the finalize's record image
+
+// The float32 constants of the step, derived by the host in float64 from the vehicle block and rounded once each
+// (acmpc_capi.hip: acmpc_set_dynamics; tests/dynamic_spec.py: derived_constants - same list, same order).  Passed by value
+// in the kernel arguments: SGPRs.
+struct Vehicle {
+  float lf, lr;
+  float Bf, Cf, Ef, Pf;   // Pf = Df (1 + epsf F_zf / F_z0) F_zf / F_z0, F_zf = mass g lr / (lr + lf)
+  float Br, Cr, Er, Pr;   // Pr = Dr (1 + epsr F_zr / F_z0) F_zr / F_z0, F_zr = mass g lf / (lr + lf)
+  float mass, inv_mass, inv_Iz;
+  float Cm1, Cm2, Cm3;    // drive map   (Cm1 - Cm2 vx - Cm3 vx^2) max(pedal, 0)
+  float Cb1, Cb2, Cb3;    // brake map   (Cb1 - Cb2 vx - Cb3 vx^2) min(pedal, 0), split front / rear by the bias
+  float fric0, Cfric2, Cfric3;   // fric0 = -Cfric1: F_fric = (-Cfric1 - Cfric2 vx) - Cfric3 vx^2
+  float bias_front, bias_rear;   // brake_bias, 1 - brake_bias
+  float wheelbase;        // acmpc_params::wheelbase: delta_ref = atan_spec(wheelbase * k_ref) of the waypoint rows
+};
+
+// atan t = t + t^3 P(t^2) on [0, 1], P of degree 7 in t^2 (tools/fit_atan.py: Lawson-weighted least squares, float32
+// coefficients, Horner with fused multiply-adds): |error| < 6.8e-8 on [0, 1], < 2e-7 (1.53e-7 measured) on the real line
+constexpr float kAtanC[8] = {-0.33332985639572144f, 0.1999039649963379f,  -0.1418597251176834f,   0.10573919117450714f,
+                             -0.0736667662858963f,  0.041121501475572586f, -0.015132308006286621f, 0.0026221852749586105f};
+constexpr float kHalfPi = 1.5707963267948966f;
+constexpr float kVxEps = 1.0e-3f;   // dynamic_bicycle_model.py:97-98
+
+// Arctangent of the specification, defined for every input: t = |x|, or 1 / |x| (IEEE division) when |x| > 1; the odd
+// polynomial; pi/2 - a beyond 1; the sign of x.  atan(+-0) = +-0, atan(+-inf) = +-pi/2, a NaN stays NaN.
+template <typename F>
+__device__ __forceinline__ F atan_spec(F x) {
+  using I = typename IndexOf<F>::type;
+  const F ax = abs_(x);
+  const auto small = ax <= splat<F>(1.0f);
+  const F inv = splat<F>(1.0f) / ax;
+  const F t = small ? ax : inv;
+  const F t2 = t * t;
+  F p = fma_(t2, splat<F>(kAtanC[7]), splat<F>(kAtanC[6]));
+#pragma unroll
+  for (int q = 5; q >= 0; --q) p = fma_(t2, p, splat<F>(kAtanC[q]));
+  const F a = fma_(t * t2, p, t);
+  const F r = small ? a : (splat<F>(kHalfPi) - a);
+  return __builtin_bit_cast(F, (__builtin_bit_cast(I, r) & 0x7fffffff) | (__builtin_bit_cast(I, x) & I(0x80000000)));
+}
+
+template <typename F>
+__device__ __forceinline__ F sin_spec(F x) {
+  F s, c;
+  sincos_spec<F>(x, s, c);
+  return s;
+}
+
+// The mode-T state (pose in the path's own frame, Frenet errors, cost sums) plus the velocities of the dynamic model.
+template <typename F>
+struct StateD_ {
+  StateT_<F> t;   // t.X, t.Y, t.phi = yaw
+  F vx, vy, r;
+};
+using StateD = StateD_<float>;
+
+// x0 = (X, Y, yaw, vx, vy, r) in the caller's frame; positions move into the path's own frame (start_temporal)
+template <typename F>
+__device__ __forceinline__ StateD_<F> start_dynamic(const float* __restrict__ x0, const float* __restrict__ coef) {
+  StateD_<F> s;
+  s.t = start_temporal<F>(x0, coef);
+  s.vx = splat<F>(x0[3]);
+  s.vy = splat<F>(x0[4]);
+  s.r = splat<F>(x0[5]);
+  return s;
+}
+
+// Pacejka's lateral force of one axle: P sin(C atan(B a - E (B a - atan(B a))))
+template <typename F>
+__device__ __forceinline__ F pacejka(F alpha, float B, float C, float E, float P) {
+  const F ba = B * alpha;
+  const F y = ba - E * (ba - atan_spec<F>(ba));
+  return P * sin_spec<F>(C * atan_spec<F>(y));
+}
+
+// One explicit Euler step of predict_next_state (dynamic_bicycle_model.py:88-160) with u = (delta, pedal), then
+// vx = max(vx, 0) (the reference's loop, :180; maxNum: a NaN vx becomes 0).
+template <typename F>
+__device__ __forceinline__ void dynamic_advance(StateD_<F>& s, F delta, F pedal, const Vehicle& k, float dt) {
+  const F vx = s.vx, vy = s.vy, r = s.r;
+  const F den = vx + kVxEps;
+  const F qf = (r * k.lf + vy) / den;
+  const F qr = (r * k.lr - vy) / den;
+  const F a_f = delta - atan_spec<F>(qf);   // the reference's -atan(q) + delta: the same float
+  const F a_r = atan_spec<F>(qr);
+  const F F_fy = pacejka<F>(a_f, k.Bf, k.Cf, k.Ef, k.Pf);
+  const F F_ry = pacejka<F>(a_r, k.Br, k.Cr, k.Er, k.Pr);
+  const F vx2 = vx * vx;
+  const F F_fric = (k.fric0 - k.Cfric2 * vx) - k.Cfric3 * vx2;
+  const F brake = (k.Cb1 - k.Cb2 * vx) - k.Cb3 * vx2;
+  const F motor = (k.Cm1 - k.Cm2 * vx) - k.Cm3 * vx2;
+  const F p_neg = __builtin_elementwise_min(pedal, splat<F>(0.0f));
+  const F p_pos = vmax(pedal, splat<F>(0.0f));
+  const F F_rx = (brake * k.bias_rear) * p_neg + motor * p_pos;
+  const F F_fx = (brake * k.bias_front) * p_neg;
+  F sd, cd, sy, cy;
+  sincos_spec<F>(delta, sd, cd);
+  sincos_spec<F>(s.t.phi, sy, cy);
+  const F xd0 = vx * cy - vy * sy;
+  const F xd1 = vx * sy + vy * cy;
+  const F xd3 = k.inv_mass * ((((F_rx + F_fx) + F_fric) - F_fy * sd) + (k.mass * vy) * r);
+  const F xd4 = k.inv_mass * ((F_ry + F_fy * cd) - (k.mass * vx) * r);
+  const F xd5 = k.inv_Iz * ((F_fy * k.lf) * cd - F_ry * k.lr);
+  s.t.X = s.t.X + xd0 * dt;
+  s.t.Y = s.t.Y + xd1 * dt;
+  s.t.phi = s.t.phi + r * dt;
+  s.vx = vmax(vx + xd3 * dt, splat<F>(0.0f));
+  s.vy = vy + xd4 * dt;
+  s.r = r + xd5 * dt;
+}
+
+// mode T's temporal_cost with the input terms of this model: dv = vx - v_ref, dk = delta - delta_ref (row[7], staged
+// once per waypoint), the input box on (delta, pedal).  g = a derived waypoint row (stage_dynamic_tables).
+template <typename F>
+__device__ __forceinline__ void dynamic_cost(StateD_<F>& s, const F (&g)[kCoefT], F delta, F pedal, const Weights& w) {
+  StateT_<F>& t = s.t;
+  t.ey = fma_(g[2], t.Y, fma_(g[1], t.X, g[0]));
+  t.ep = wrap_spec<F>(t.phi - g[3]);
+  const F dv = s.vx - g[5];
+  const F dk = delta - g[7];
+  t.S0 = fma_(t.ey, t.ey, t.S0);
+  t.S1 = fma_(t.ep, t.ep, t.S1);
+  t.S2 = fma_(dv, dv, t.S2);
+  t.S3 = fma_(dk, dk, t.S3);
+  const F hd = delta - med3_(delta, splat<F>(w.ulo0), splat<F>(w.uhi0));
+  t.V = fma_(hd, hd, t.V);
+  const F hp = pedal - med3_(pedal, splat<F>(w.ulo1), splat<F>(w.uhi1));
+  t.V = fma_(hp, hp, t.V);
+  const F hc = vmax(abs_(t.ey) - g[6], splat<F>(0.0f));
+  t.V = fma_(hc, hc, t.V);
+}
+
+// mode T's tables (stage_temporal_tables) with delta_ref = atan_spec(wheelbase * k_ref) in the row's eighth float
+__device__ __forceinline__ void stage_dynamic_tables(const float* __restrict__ coef, int n, int tid, int threads,
+                                                     float wheelbase, float* rows, float* abc) {
+  stage_temporal_tables(coef, n, tid, threads, rows, abc);
+  for (int m = tid; m < n; m += threads) rows[m * kCoefT + 7] = atan_spec<float>(wheelbase * coef[m * kCoefT + 5]);
+}
+
+// ---- launchers (acmpc_dynamic.hip) ----------------------------------------------------------------------------------
+// Candidates per lane of the rollout for a launch of P x N: two (v_pk_* pairs) once the launch fills the chip many
+// times over, one below that (a small solve is latency: more lanes, shorter per-lane work).
+int dynamic_candidates_per_lane(int P, int N);
+int dynamic_blocks_per_problem(int P, int N);
+// rollout: costs [P][N] (or nullptr) and one (cost, index) partial key + feasible count per workgroup, x0 [P][6]
+hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const Vehicle& vehicle, hipStream_t s);
+// argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
+// pedal), x = (X, Y, yaw) in the caller's frame.  Reads args.U / x0 / coef / partial_* / keys_in / index_offset / n / N / P
+// / blocks_per_problem / w; `regenerate` and `controls_only` are not supported (hipErrorInvalidValue).
+hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const Vehicle& vehicle, hipStream_t s);
+
+}  // namespace acmpc

@@ -50,6 +50,18 @@ extern "C" {
 #define ACMPC_MODE_TEMPORAL 1 /* Cartesian kinematic Euler step (localisation/localiser.py:66-95) with
                                  nearest-waypoint Frenet projection (localiser.py:282-289, dynamics.py:23-40)
                                  ("mode T")                                                               */
+#define ACMPC_MODE_DYNAMIC 2  /* the six-state dynamic bicycle with Pacejka lateral tyre forces
+                                 (control/dynamic_bicycle_model.py:88-160, one explicit Euler step of dt with vx
+                                 clipped at 0 after it), scored with mode T's nearest-waypoint projection and cost
+                                 ("mode D").  Start states x0 [P][6] = (X, Y, yaw, vx, vy, r); a candidate is n pairs
+                                 (delta, pedal), the pedal in [-1, 1]; the vehicle comes from acmpc_set_dynamics.
+                                 Tables as mode T's (acmpc_set_paths); max_steps <= 512; lq_candidate must be 0.
+                                 Takes acmpc_set_paths / acmpc_set_coefficients, acmpc_solve, acmpc_solve_device,
+                                 acmpc_rollout_device + acmpc_finalize_device (index_offset, acmpc_reduce_across_ranks),
+                                 acmpc_softmin_device, acmpc_sample_device and acmpc_optimize (sample -> rollout ->
+                                 finalize per round, three launches).  ACMPC_ESTATE from acmpc_control_tick and from the
+                                 calls that re-draw a winner from its index (acmpc_finalize_sampled_device,
+                                 acmpc_solve_sampled_device, acmpc_solve_stream_device).  DESIGN.md section 2 "Mode D". */
 
 /* Memory layout of the control-sample matrix U. */
 #define ACMPC_LAYOUT_CANDIDATE_MAJOR 0 /* U[P][N][n][2]  - what NumPy host code naturally holds          */
@@ -182,19 +194,35 @@ int acmpc_set_paths(acmpc_ctx* ctx, const double* tables, int32_t P, int32_t n);
  * without the plan (candidate 2 is then an ordinary sample).  Call acmpc_set_paths again to plan for new paths. */
 int acmpc_set_coefficients(acmpc_ctx* ctx, const float* coef, int32_t P, int32_t n);
 
+/* Mode D's vehicle: ACMPC_DYNAMICS_COUNT doubles in this order (the names of control/dynamic_bicycle_model.py:7-77):
+ *    0 F_z0   1 Bf   2 Cf   3 Df   4 Ef   5 epsf   6 Br   7 Cr   8 Dr   9 Er   10 epsr
+ *   11 mass  12 Iz  13 g   14 lf  15 lr  16 brake_bias
+ *   17 Cm1   18 Cm2 19 Cm3  20 Cb1  21 Cb2  22 Cb3  23 Cfric1  24 Cfric2  25 Cfric3
+ * Lateral forces are D (1 + eps F_z / F_z0) F_z / F_z0 sin(C atan(B a - E (B a - atan(B a)))) with F_zf = mass g lr /
+ * (lr + lf), F_zr = mass g lf / (lr + lf); the drive, brake and friction maps are (Cm1 - Cm2 vx - Cm3 vx^2) max(pedal, 0),
+ * (Cb1 - Cb2 vx - Cb3 vx^2) min(pedal, 0) split brake_bias front / 1 - brake_bias rear, and -Cfric1 - Cfric2 vx - Cfric3 vx^2.
+ * The block is data: its forces must share one unit with mass and Iz (the reference's literal block does not -
+ * DESIGN.md section 2; acmpc_amd.DynamicBicycleParams.reference() is the consistent one).  The host derives the float32
+ * constants of the kernels from it (in float64, each rounded once).  No device work.  ACMPC_EINVAL for a count other
+ * than ACMPC_DYNAMICS_COUNT, a non-finite value, mass <= 0, Iz <= 0, F_z0 == 0, lf + lr == 0, or a handle whose mode
+ * is not ACMPC_MODE_DYNAMIC. */
+#define ACMPC_DYNAMICS_COUNT 26
+int acmpc_set_dynamics(acmpc_ctx* ctx, const double* coef, int32_t count);
+
 /* Copies the packed float32 table of problem `problem` (n rows of ACMPC_COEF_STRIDE_* floats) to `out`.
  * Host only; lets CPU tests pin the host-side arithmetic against the oracle. */
 int acmpc_get_coefficients(const acmpc_ctx* ctx, int32_t problem, float* out, int32_t capacity_floats);
 
 /* Floats in one winner record: ACMPC_REC_HEADER + 2 n + 3 (n + 1) =
  *   [cost, violation, n_feasible, owner, u_0 .. u_{n-1} (2 each), x_0 .. x_n (3 each)]
- * x is (e_y, e_psi, t) in mode S and (X, Y, phi) in mode T.  The u / x blocks are what
+ * x is (e_y, e_psi, t) in mode S and (X, Y, phi) in modes T and D (u = (delta, pedal) in mode D).  The u / x blocks are what
  * spatial_mpc.py:193-202 slices out of OSQP's dec.x ([x_0..x_n ; u_0..u_{n-1}], control.py:121-158). */
 int32_t acmpc_record_floats(int32_t n);
 
 /* Replaces: ControlSolver.solve (control.py:15-24) for host-resident inputs - one blocking call doing H2D,
  * rollout + cost + argmin, and D2H.
- *   x0        [P][3]   mode S: t2s(...) output (e_y, e_psi, t) (dynamics.py:23-40); mode T: pose (X, Y, phi)
+ *   x0        [P][3]   mode S: t2s(...) output (e_y, e_psi, t) (dynamics.py:23-40); mode T: pose (X, Y, phi);
+ *             [P][6]   mode D: (X, Y, yaw, vx, vy, r)
  *   U         control-sample matrix in `layout`
  *   costs     [P][N] or NULL
  *   best_idx  [P] index of the cheapest candidate (lowest index on ties; non-finite costs rank last)

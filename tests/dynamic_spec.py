@@ -1,0 +1,246 @@
+"""Mode D's float32 specification restated in NumPy ("Mode D"): the dynamic (Pacejka) bicycle's
+explicit Euler step, its arctangent, and the rollout cost - the same operations in the same order as
+csrc/acmpc_dynamic.h, so that every result is bit-identical to the kernels.  A helper of the tests, not a test file.
+
+Conventions of the restatement: every array is float32 and every operation a float32 operation (NumPy rounds each
+elementwise +, -, *, / of float32 operands once, as the device does); fused multiply-adds only where the specification
+names them, through the oracle's exact fma32; min / max are IEEE minNum / maxNum (np.fmin / np.fmax: a NaN operand loses)."""
+from __future__ import annotations
+
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (os.path.join(_HERE, "..", "oracle"), os.path.join(_HERE, "..", "ac-mpc_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from acmpc_oracle import fma32, sincos_spec, wrap_spec  # noqa: E402
+
+T = np.float32
+
+# atan t = t + t^3 P(t^2) on [0, 1] (tools/fit_atan.py: Lawson-weighted least squares, float32 coefficients, Horner in
+# t^2 with fused multiply-adds): |error| < 6.8e-8 on [0, 1]; with the reduction pi/2 - atan(1/x) below 2e-7 everywhere
+ATAN_C = (-0.33332985639572144, 0.1999039649963379, -0.1418597251176834, 0.10573919117450714, -0.0736667662858963,
+          0.041121501475572586, -0.015132308006286621, 0.0026221852749586105)
+HALF_PI = 1.5707963267948966     # rounded to float32 where it is used
+ATAN_ERROR_BOUND = 2.0e-7
+VX_EPS = 1.0e-3                  # dynamic_bicycle_model.py:97-98
+
+# The vehicle block of acmpc_set_dynamics, in ABI order (include/acmpc.h ACMPC_DYNAMICS_COUNT)
+FIELDS = ("F_z0", "Bf", "Cf", "Df", "Ef", "epsf", "Br", "Cr", "Dr", "Er", "epsr", "mass", "Iz", "g", "lf", "lr",
+          "brake_bias", "Cm1", "Cm2", "Cm3", "Cb1", "Cb2", "Cb3", "Cfric1", "Cfric2", "Cfric3")
+
+
+def derived_constants(coef):
+    """The float32 constants of the step, derived on the host in float64 and rounded ONCE each, in the order of the
+    kernel argument (csrc/acmpc_dynamic.h: struct Vehicle)."""
+    v = dict(zip(FIELDS, (float(x) for x in coef)))
+    F_zf = v["mass"] * v["g"] * v["lr"] / (v["lr"] + v["lf"])
+    F_zr = v["mass"] * v["g"] * v["lf"] / (v["lr"] + v["lf"])
+    peak_f = v["Df"] * (1 + v["epsf"] * F_zf / v["F_z0"]) * F_zf / v["F_z0"]
+    peak_r = v["Dr"] * (1 + v["epsr"] * F_zr / v["F_z0"]) * F_zr / v["F_z0"]
+    order = (("lf", v["lf"]), ("lr", v["lr"]), ("Bf", v["Bf"]), ("Cf", v["Cf"]), ("Ef", v["Ef"]), ("Pf", peak_f),
+             ("Br", v["Br"]), ("Cr", v["Cr"]), ("Er", v["Er"]), ("Pr", peak_r), ("mass", v["mass"]),
+             ("inv_mass", 1.0 / v["mass"]), ("inv_Iz", 1.0 / v["Iz"]), ("Cm1", v["Cm1"]), ("Cm2", v["Cm2"]),
+             ("Cm3", v["Cm3"]), ("Cb1", v["Cb1"]), ("Cb2", v["Cb2"]), ("Cb3", v["Cb3"]), ("fric0", -v["Cfric1"]),
+             ("Cfric2", v["Cfric2"]), ("Cfric3", v["Cfric3"]), ("bias_front", v["brake_bias"]),
+             ("bias_rear", 1 - v["brake_bias"]))
+    return {k: T(x) for k, x in order}
+
+
+def atan_spec(x):
+    """float32 arctangent of the specification: t = |x| or 1 / |x| (IEEE division) beyond 1, the odd polynomial with
+    fused multiply-adds, pi/2 - a for |x| > 1, the sign of x.  atan(+-0) = +-0, atan(+-inf) = +-pi/2, NaN propagates."""
+    x = np.asarray(x, dtype=T)
+    ax = np.abs(x)
+    small = ax <= T(1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = T(1.0) / ax
+    t = np.where(small, ax, inv).astype(T)
+    t2 = t * t
+    p = np.full_like(t, T(ATAN_C[-1]))
+    for c in ATAN_C[-2::-1]:
+        p = fma32(t2, p, T(c))
+    a = fma32(t * t2, p, t)
+    r = np.where(small, a, T(HALF_PI) - a).astype(T)
+    return np.copysign(r, x).astype(T)
+
+
+def sin_spec(x):
+    return sincos_spec(x, T)[0]
+
+
+def dynamic_step(state, delta, pedal, k, dt):
+    """One step of the specification: state = (X, Y, yaw, vx, vy, r) float32 arrays, k = derived_constants(...),
+    dt float32.  Returns the next state with vx clipped at 0 (dynamic_bicycle_model.py:180)."""
+    X, Y, yaw, vx, vy, r = (np.asarray(s, dtype=T) for s in state)
+    delta = np.asarray(delta, dtype=T)
+    pedal = np.asarray(pedal, dtype=T)
+    dt = T(dt)
+    with np.errstate(all="ignore"):
+        den = vx + T(VX_EPS)
+        qf = (r * k["lf"] + vy) / den
+        qr = (r * k["lr"] - vy) / den
+        a_f = delta - atan_spec(qf)
+        a_r = atan_spec(qr)
+        bf = k["Bf"] * a_f
+        yf = bf - k["Ef"] * (bf - atan_spec(bf))
+        F_fy = k["Pf"] * sin_spec(k["Cf"] * atan_spec(yf))
+        br = k["Br"] * a_r
+        yr = br - k["Er"] * (br - atan_spec(br))
+        F_ry = k["Pr"] * sin_spec(k["Cr"] * atan_spec(yr))
+        vx2 = vx * vx
+        F_fric = (k["fric0"] - k["Cfric2"] * vx) - k["Cfric3"] * vx2
+        brake = (k["Cb1"] - k["Cb2"] * vx) - k["Cb3"] * vx2
+        motor = (k["Cm1"] - k["Cm2"] * vx) - k["Cm3"] * vx2
+        p_neg = np.fmin(pedal, T(0.0))
+        p_pos = np.fmax(pedal, T(0.0))
+        F_rx = (brake * k["bias_rear"]) * p_neg + motor * p_pos
+        F_fx = (brake * k["bias_front"]) * p_neg
+        sd, cd = sincos_spec(delta, T)
+        sy, cy = sincos_spec(yaw, T)
+        xd0 = vx * cy - vy * sy
+        xd1 = vx * sy + vy * cy
+        xd3 = k["inv_mass"] * ((((F_rx + F_fx) + F_fric) - F_fy * sd) + (k["mass"] * vy) * r)
+        xd4 = k["inv_mass"] * ((F_ry + F_fy * cd) - (k["mass"] * vx) * r)
+        xd5 = k["inv_Iz"] * ((F_fy * k["lf"]) * cd - F_ry * k["lr"])
+        Xn = X + xd0 * dt
+        Yn = Y + xd1 * dt
+        yawn = yaw + r * dt
+        vxn = np.fmax(vx + xd3 * dt, T(0.0))
+        vyn = vy + xd4 * dt
+        rn = r + xd5 * dt
+    return tuple(np.asarray(a, dtype=T) for a in (Xn, Yn, yawn, vxn, vyn, rn))
+
+
+def rollout_dynamic(x0, wp, U, vehicle, Q, R, QN, u_lo, u_hi, w_bound, dt, wheelbase, nn_window=None,
+                    return_states=False):
+    """Mode D's cost of every candidate, bit for bit: x0 = (X, Y, yaw, vx, vy, r), wp [n, 8] the packed mode-T table,
+    U [N, n, 2] = (delta, pedal), `vehicle` the 26 doubles of the block.  Nearest waypoint, stage cost, bounds and
+    terminal cost are mode T's (oracle rollout_temporal) with dv = vx - v_ref, dk = delta - atan_spec(L k_ref)."""
+    k = derived_constants(vehicle)
+    U = np.asarray(U, dtype=T)
+    wp = np.asarray(wp, dtype=T)
+    N, n, _ = U.shape
+    Q, R, QN = (np.asarray(a, dtype=T) for a in (Q, R, QN))
+    lo, hi = np.asarray(u_lo, dtype=T), np.asarray(u_hi, dtype=T)
+    half, zero, wb, dtT = T(0.5), T(0.0), T(w_bound), T(dt)
+    hQ, hR, hQN = half * Q, half * R, half * QN
+    ox, oy = wp[0, 0], wp[0, 1]
+    wx, wy = wp[:, 0] - ox, wp[:, 1] - oy
+    key_a, key_b = T(-2.0) * wx, T(-2.0) * wy
+    key_c = fma32(wy, wy, wx * wx)
+    row_k = fma32(wp[:, 3], wx, -(wp[:, 2] * wy))
+    row_ns = -wp[:, 3]
+    delta_ref = atan_spec(T(wheelbase) * wp[:, 5])
+    x0 = np.asarray(x0, dtype=T)
+    st = [np.full(N, x0[0] - ox, dtype=T), np.full(N, x0[1] - oy, dtype=T)] + [np.full(N, x0[q], dtype=T) for q in range(2, 6)]
+    S0, S1, S2, S3, V = (np.zeros(N, dtype=T) for _ in range(5))
+    ey = np.zeros(N, dtype=T)
+    ep = np.zeros(N, dtype=T)
+    j_prev = np.zeros(N, dtype=np.int64)
+    X_out = np.zeros((N, n + 1, 3), dtype=T) if return_states else None
+    if return_states:
+        X_out[:, 0] = np.stack([st[0] + ox, st[1] + oy, st[2]], axis=1)
+    for i in range(n):
+        d, p = U[:, i, 0], U[:, i, 1]
+        st = list(dynamic_step(st, d, p, k, dtT))
+        X, Y, psi, vx = st[0], st[1], st[2], st[3]
+        best = np.full(N, np.inf, dtype=T)
+        if nn_window is None:
+            j = np.zeros(N, dtype=np.int64)
+            cand = range(n)
+            for w in cand:
+                dd = fma32(Y, key_b[w], fma32(X, key_a[w], key_c[w]))
+                better = dd < best
+                best = np.where(better, dd, best)
+                j = np.where(better, w, j)
+        else:
+            back, ahead = nn_window
+            width = back + ahead + 1
+            lo_w = np.maximum(np.minimum(j_prev - back, n - width), 0)
+            hi_w = np.minimum(lo_w + width, n) - 1
+            j = lo_w.copy()
+            for m in range(width):
+                w = np.minimum(lo_w + m, hi_w)
+                dd = fma32(Y, key_b[w], fma32(X, key_a[w], key_c[w]))
+                better = dd < best
+                best = np.where(better, dd, best)
+                j = np.where(better, w, j)
+        j_prev = j
+        g = wp[j]
+        with np.errstate(all="ignore"):
+            ey = fma32(g[:, 2], Y, fma32(row_ns[j], X, row_k[j]))
+            ep = wrap_spec(psi - g[:, 4], T)
+            dv = vx - g[:, 6]
+            dk = d - delta_ref[j]
+            S0 = fma32(ey, ey, S0)
+            S1 = fma32(ep, ep, S1)
+            S2 = fma32(dv, dv, S2)
+            S3 = fma32(dk, dk, S3)
+            hd = d - np.fmin(np.fmax(d, lo[0]), hi[0])
+            V = fma32(hd, hd, V)
+            hp = p - np.fmin(np.fmax(p, lo[1]), hi[1])
+            V = fma32(hp, hp, V)
+            hc = np.fmax(np.abs(ey) - g[:, 7], zero)
+            V = fma32(hc, hc, V)
+        if return_states:
+            X_out[:, i + 1] = np.stack([X + ox, Y + oy, psi], axis=1)
+    with np.errstate(all="ignore"):
+        tN = T(n) * dtT
+        J = hQ[0] * S0
+        J = fma32(hQ[1], S1, J)
+        J = fma32(hR[0], S2, J)
+        J = fma32(hR[1], S3, J)
+        s = (hQN[0] * ey) * ey
+        s = fma32(hQN[1] * ep, ep, s)
+        s = fma32(hQN[2] * tN, tN, s)
+        J = J + s
+        cost = fma32(wb, V, J)
+    cost = np.asarray(cost, dtype=T)
+    return (cost, V, X_out) if return_states else (cost, V)
+
+
+# ---- test problems ----------------------------------------------------------------------------------------------
+U_MIN = (-0.3, -1.0)    # (delta rad, pedal)
+U_MAX = (0.3, 1.0)
+
+
+def make_dynamic_problem(orc, track, H, N, seed, origin=(0.0, 0.0), vx0=None, yaw_turns=0):
+    """A mode D problem on test_support.make_problem's path: table [7, n], x0 (X, Y, yaw, vx, vy, r), U [N, n, 2]
+    (delta, pedal) - noise round delta_ref and a mild pedal, a few candidates outside the box - and the engine's
+    weights.  `origin` moves the path and the start (the far-from-origin frame test), `yaw_turns` adds whole turns to the
+    start yaw (beyond +-pi), `vx0` overrides the start speed (0: the standstill)."""
+    from test_support import engine_kwargs, make_problem
+    prob = make_problem(orc, track, H, N, seed)
+    table = prob["table"].copy()
+    table[0] += origin[0]
+    table[1] += origin[1]
+    n = H - 1
+    rng = np.random.default_rng(5000 + seed)
+    L = float(prob["limits"].length)
+    v0 = float(table[orc.ROW_V][0]) if vx0 is None else float(vx0)
+    x0 = np.array([prob["pose0"][0] + origin[0], prob["pose0"][1] + origin[1],
+                   prob["pose0"][2] + 2.0 * np.pi * yaw_turns, v0, 0.0, 0.0], dtype=np.float32)
+    d_ref = np.arctan(L * table[orc.ROW_KAPPA])
+    U = np.empty((N, n, 2), dtype=np.float32)
+    spread = rng.uniform(0.05, 1.0, (N, 1))
+    U[:, :, 0] = d_ref[None, :n] + rng.standard_normal((N, n)) * 0.05 * spread
+    U[:, :, 1] = np.clip(rng.uniform(-0.3, 0.5, (N, 1)) + rng.standard_normal((N, n)) * 0.2 * spread, -1.0, 1.0)
+    U[:, :, 0] = np.clip(U[:, :, 0], U_MIN[0], U_MAX[0])
+    if N > 3:
+        U[3, n // 2, 0] = U_MAX[0] + 0.2
+        U[2, 0, 1] = U_MIN[1] - 0.5
+    kw = engine_kwargs(prob, 2, 1, N, n, u_min=U_MIN, u_max=U_MAX, r_term=(0.5, 10.0))
+    return dict(table=table, x0=x0, U=U.astype(np.float32), kw=kw, prob=prob)
+
+
+def spec_costs(orc, dp, coef, vehicle, nn_window=None, U=None, return_states=False):
+    """The specification's costs of problem `dp` (make_dynamic_problem) on the packed table `coef` [n, 8]."""
+    kw = dp["kw"]
+    return rollout_dynamic(dp["x0"], coef, dp["U"] if U is None else U, vehicle, kw["step_cost"], kw["r_term"],
+                           kw["final_cost"], kw["u_min"], kw["u_max"], kw["w_bound"], kw["dt"], kw["wheelbase"],
+                           nn_window=nn_window, return_states=return_states)

@@ -29,6 +29,9 @@ ENTRIES = {
     # the fused sample + rollout round: its step loop comes in several unrolled pieces of one mix; the largest stands for it
     # (the SQ count per candidate-step also holds the Philox draws and the staging, priced with the same mix)
     "fused_round": ("acmpc_kernels.hip", "rollout_sampled_kernelILi0E", None),
+    # mode D (the dynamic bicycle, two candidates per lane, step-major): the largest step loop - a windowed search's, whose
+    # trip is the dynamics + an unrolled window + the cost; the exhaustive form adds its waypoint loop to the same trip
+    "dynamic": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2EE", None),
 }
 CANDIDATES_PER_LANE = {"fused_round": 1}
 
