@@ -17,6 +17,9 @@ from . import _build
 OK, EINVAL, EHIP, ENODEVICE, ECAPACITY, ESTATE = 0, -1, -2, -3, -4, -5
 MODE_SPATIAL, MODE_TEMPORAL, MODE_DYNAMIC = 0, 1, 2
 DYNAMICS_COUNT = 26   # ACMPC_DYNAMICS_COUNT: doubles in mode D's vehicle block
+MAX_VEHICLES = 8      # ACMPC_MAX_VEHICLES: vehicles in a mode D ensemble
+ENSEMBLE_MEAN, ENSEMBLE_MAX = 0, 1
+ENSEMBLE_REDUCE = {"mean": ENSEMBLE_MEAN, "max": ENSEMBLE_MAX}
 LAYOUT_CANDIDATE_MAJOR, LAYOUT_STEP_MAJOR = 0, 1
 COEF_STRIDE = {MODE_SPATIAL: 12, MODE_TEMPORAL: 8, MODE_DYNAMIC: 8}
 STATE_FLOATS = {MODE_SPATIAL: 3, MODE_TEMPORAL: 3, MODE_DYNAMIC: 6}   # a start state x0
@@ -144,6 +147,7 @@ SIGNATURES = {
     "acmpc_last_error": (C.c_char_p, [_CTX]),
     "acmpc_set_paths": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_set_dynamics": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
+    "acmpc_set_dynamics_ensemble": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "acmpc_get_coefficients": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_set_coefficients": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_record_floats": (C.c_int32, [C.c_int32]),
@@ -419,6 +423,18 @@ class _TickBuffers:
         return out
 
 
+def ensemble_blocks(vehicles) -> np.ndarray:
+    """The [K, 26] float64 blocks of an ensemble given as DynamicBicycleParams, blocks, or one [K, 26] array."""
+    if isinstance(vehicles, np.ndarray):
+        rows = list(vehicles.reshape(-1, DYNAMICS_COUNT)) if vehicles.ndim == 2 else [vehicles]
+    else:
+        rows = list(vehicles)
+    blocks = [np.asarray(v.coefficients() if hasattr(v, "coefficients") else v, dtype=np.float64).ravel() for v in rows]
+    if not blocks or any(b.size != DYNAMICS_COUNT for b in blocks):
+        raise ValueError("an ensemble is 1 .. %d vehicle blocks of %d values" % (MAX_VEHICLES, DYNAMICS_COUNT))
+    return np.ascontiguousarray(np.stack(blocks))
+
+
 class Engine:
     """Owns one acmpc_ctx.  Construction does no device work (fork-safe, controller.py:293-297)."""
 
@@ -501,6 +517,22 @@ class Engine:
         block = params.coefficients() if hasattr(params, "coefficients") else params
         block = np.ascontiguousarray(block, dtype=np.float64).ravel()
         self._check(self._lib.acmpc_set_dynamics(self._ctx, block.ctypes.data, block.size))
+
+    def set_dynamics_ensemble(self, vehicles, weights=None, reduce: str = "mean"):
+        """Mode D's ensemble (acmpc_set_dynamics_ensemble): `vehicles` a list of DynamicBicycleParams / 26-double blocks,
+        or a [K, 26] array; `weights` K positive numbers or None (equal); `reduce` "mean" or "max".  Each candidate's
+        cost is then the weighted mean or the max of its K costs, its violation the max."""
+        blocks = ensemble_blocks(vehicles)
+        if reduce not in ENSEMBLE_REDUCE:
+            raise ValueError("reduce is 'mean' or 'max', not %r" % (reduce,))
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if w.size != blocks.shape[0]:
+                raise ValueError("%d weights for %d vehicles" % (w.size, blocks.shape[0]))
+        self._check(self._lib.acmpc_set_dynamics_ensemble(self._ctx, blocks.ctypes.data, blocks.shape[0],
+                                                          None if w is None else w.ctypes.data,
+                                                          ENSEMBLE_REDUCE[reduce]))
 
     def set_coefficients(self, coef: np.ndarray):
         """The packed float32 tables themselves, [P, n, 12] (mode S) / [P, n, 8] (mode T) or one [n, stride] table

@@ -70,6 +70,16 @@ class DynamicBicycleParams:
             raise ValueError("a vehicle block has %d values" % len(FIELDS))
         return cls(**{k: float(v) for k, v in zip(FIELDS, coef)})
 
+    def with_grip(self, scale: float) -> "DynamicBicycleParams":
+        """A copy on a road with `scale` times the grip: the Pacejka peak factors Df and Dr (proportional to the road's
+        friction coefficient) scaled, nothing else.  The drive, brake and friction maps are left alone: this model has no
+        friction circle, so its longitudinal forces do not depend on the tyres' grip.  An ensemble of grips
+        (DynamicSamplingSolver's `grip_ensemble`) scores every candidate on several such roads."""
+        scale = float(scale)
+        if not (np.isfinite(scale) and scale > 0.0):
+            raise ValueError("a grip scale is finite and positive, not %r" % (scale,))
+        return dataclasses.replace(self, Df=self.Df * scale, Dr=self.Dr * scale)
+
     def coefficients(self) -> np.ndarray:
         """The ABI block: float64 [26] in FIELDS order (acmpc_set_dynamics)."""
         return np.array([getattr(self, k) for k in FIELDS], dtype=np.float64)

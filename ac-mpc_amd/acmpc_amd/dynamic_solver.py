@@ -6,7 +6,13 @@ obj` with `obj.x` laid out `[x_0 .. x_n ; u_0 .. u_{n-1}]` (x = (X, Y, yaw), u =
 Optional config keys, as sampling_solver.py reads them: `n_candidates`, `sampling_rounds`, `sampling_sigma` (delta rad,
 pedal), `sampling_seed`, `w_bound`, `nn_window`, `rollout_dt`; the weights `step_cost` (e_y, e_psi, -), `r_term` (speed
 error, steering against delta_ref), `final_cost`; the input box `u_min` / `u_max` (default delta +-0.3 rad, pedal +-1).
-The warm start is the previous plan shifted by one step."""
+The warm start is the previous plan shifted by one step.
+
+Robust scoring (acmpc_set_dynamics_ensemble): `vehicle_ensemble` - a list of DynamicBicycleParams or 26-double blocks -
+or `grip_ensemble` - grip scales, each giving `params.with_grip(scale)` - scores every candidate under each vehicle;
+`ensemble_weights` (positive, default equal) and `ensemble_reduce` ("mean", the default, or "max": the worst case) say
+how the costs combine.  The two ensemble keys are mutually exclusive; with neither, the solver scores the one vehicle
+`params` (acmpc_set_dynamics)."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -25,6 +31,31 @@ DEFAULT_U_MIN = (-0.3, -1.0)
 DEFAULT_U_MAX = (0.3, 1.0)
 
 
+def ensemble_vehicles(config: Dict, params: DynamicBicycleParams) -> Optional[list]:
+    """The vehicles a config asks to score under (`vehicle_ensemble` or `grip_ensemble`), or None for `params` alone."""
+    has_vehicles, has_grips = config.get("vehicle_ensemble") is not None, config.get("grip_ensemble") is not None
+    if has_vehicles and has_grips:
+        raise ValueError("vehicle_ensemble and grip_ensemble are mutually exclusive")
+    if not has_vehicles and not has_grips:
+        for key in ("ensemble_weights", "ensemble_reduce"):
+            if config.get(key) is not None:
+                raise ValueError("%s needs vehicle_ensemble or grip_ensemble" % key)
+        return None
+    if config.get("ensemble_reduce", "mean") not in _capi.ENSEMBLE_REDUCE:
+        raise ValueError("ensemble_reduce is 'mean' or 'max', not %r" % (config.get("ensemble_reduce"),))
+    if has_grips:
+        vehicles = [params.with_grip(g) for g in config["grip_ensemble"]]
+    else:
+        vehicles = [v if isinstance(v, DynamicBicycleParams) else DynamicBicycleParams.from_coefficients(v)
+                    for v in config["vehicle_ensemble"]]
+    if not 1 <= len(vehicles) <= _capi.MAX_VEHICLES:
+        raise ValueError("an ensemble has 1 .. %d vehicles, not %d" % (_capi.MAX_VEHICLES, len(vehicles)))
+    weights = config.get("ensemble_weights")
+    if weights is not None and len(weights) != len(vehicles):
+        raise ValueError("%d ensemble_weights for %d vehicles" % (len(weights), len(vehicles)))
+    return vehicles
+
+
 class DynamicSamplingSolver:
     def __init__(self, config: Dict, params: Optional[DynamicBicycleParams] = None, device: int = -1):
         self._n = int(config["horizon"]) - 1
@@ -34,6 +65,7 @@ class DynamicSamplingSolver:
         self._seed = int(config.get("sampling_seed", 0))
         self._dt = float(config.get("rollout_dt", 0.05))
         self._params = params if params is not None else DynamicBicycleParams.reference()
+        vehicles = ensemble_vehicles(config, self._params)   # (a config error raises before any handle exists)
         nn_window = config.get("nn_window")
         self._engine = _capi.Engine(
             mode=_capi.MODE_DYNAMIC, max_problems=1, max_candidates=self._N, max_steps=self._n,
@@ -42,7 +74,11 @@ class DynamicSamplingSolver:
             u_max=config.get("u_max", DEFAULT_U_MAX), margin=float(config.get("margin", 0.0)),
             wheelbase=self._params.lf + self._params.lr, dt=self._dt, w_bound=float(config.get("w_bound", 1.0e6)),
             device=device, nn_window=None if nn_window is None else tuple(nn_window))
-        self._engine.set_dynamics(self._params)
+        if vehicles is None:
+            self._engine.set_dynamics(self._params)
+        else:
+            self._engine.set_dynamics_ensemble(vehicles, config.get("ensemble_weights"),
+                                               config.get("ensemble_reduce", "mean"))
         self._plan: Optional[np.ndarray] = None
         self._calls = 0
 

@@ -170,9 +170,9 @@ struct acmpc_ctx {
   std::vector<hipEvent_t> prof_start, prof_stop;
   size_t prof_used = 0;
 
-  // mode D: the vehicle's float32 constants (acmpc_set_dynamics)
+  // mode D: the vehicles' float32 constants, one (acmpc_set_dynamics) or an ensemble (acmpc_set_dynamics_ensemble)
   bool has_dynamics = false;
-  acmpc::Vehicle vehicle{};
+  acmpc::VehicleEnsemble vehicles{};
 
   mutable std::string err;
 };
@@ -360,9 +360,9 @@ int rollout(acmpc_ctx* c, const float* d_x0, const float* d_U, int P, int N, int
     a.n = n;
     a.index_offset = offset;
     a.w = c->w;
-    ACMPC_HIP(c, acmpc::launch_rollout_dynamic(layout, a, c->vehicle, s));
+    ACMPC_HIP(c, acmpc::launch_rollout_dynamic(layout, a, c->vehicles, s));
     *shape_out = acmpc::LaunchShape{};
-    shape_out->blocks_per_problem = acmpc::dynamic_blocks_per_problem(P, N);
+    shape_out->blocks_per_problem = acmpc::dynamic_blocks_per_problem(P, N, c->vehicles.K);
     return ACMPC_OK;
   }
   const acmpc::LaunchShape shape = acmpc::choose_shape(P, N, layout, c->prm.mode, n, c->opt);
@@ -439,7 +439,7 @@ int finalize(acmpc_ctx* c, const int64_t* d_keys_in, int64_t* d_keys_out, const 
   a.w = c->w;
   if (c->prm.mode == ACMPC_MODE_DYNAMIC) {
     if (regen != nullptr) return fail(c, ACMPC_ESTATE, "mode D re-rolls its winners from U: no re-drawn candidates");
-    ACMPC_HIP(c, acmpc::launch_finalize_dynamic(layout, a, c->vehicle, s));
+    ACMPC_HIP(c, acmpc::launch_finalize_dynamic(layout, a, c->vehicles, s));
     return ACMPC_OK;
   }
   ACMPC_HIP(c, acmpc::launch_finalize(c->prm.mode, layout, a, s, c->opt));
@@ -1048,7 +1048,7 @@ int acmpc_finalize_device(acmpc_ctx* c, const int64_t* d_keys, const float* d_x0
   int rc = check_shape(c, P, N, n, layout);
   if (rc != ACMPC_OK) return rc;
   if (!c->device_ready) return fail(c, ACMPC_ESTATE, "acmpc_rollout_device must run first");
-  const int blocks = c->prm.mode == ACMPC_MODE_DYNAMIC ? acmpc::dynamic_blocks_per_problem(P, N)
+  const int blocks = c->prm.mode == ACMPC_MODE_DYNAMIC ? acmpc::dynamic_blocks_per_problem(P, N, c->vehicles.K)
                                                        : acmpc::choose_shape(P, N, layout, c->prm.mode, n, c->opt).blocks_per_problem;
   return finalize(c, d_keys, nullptr, d_x0, d_U, P, N, n, layout, index_offset, d_records, blocks,
                   static_cast<hipStream_t>(stream));
@@ -1246,26 +1246,23 @@ int optimize_dynamic(acmpc_ctx* c, const float* x0, const float* centre, const f
   return ACMPC_OK;
 }
 
-}  // namespace
+static_assert(acmpc::kMaxVehicles == ACMPC_MAX_VEHICLES && acmpc::kEnsembleMean == ACMPC_ENSEMBLE_MEAN &&
+                  acmpc::kEnsembleMax == ACMPC_ENSEMBLE_MAX,
+              "the ensemble constants of acmpc_dynamic.h are the header's");
 
-extern "C" {
-
-int acmpc_set_dynamics(acmpc_ctx* c, const double* coef, int32_t count) {
-  if (c == nullptr) return ACMPC_EINVAL;
-  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics needs a mode D handle");
-  if (coef == nullptr) return fail(c, ACMPC_EINVAL, "null vehicle block");
-  if (count != acmpc::kDynamicsCount) return fail(c, ACMPC_EINVAL, "the vehicle block has ACMPC_DYNAMICS_COUNT = 26 values");
-  for (int q = 0; q < count; ++q)
-    if (!std::isfinite(coef[q])) return fail(c, ACMPC_EINVAL, "non-finite value in the vehicle block");
+// mode D's float32 constants of one vehicle block (acmpc_set_dynamics): nullptr, or why the block is refused
+const char* derive_vehicle(const double* coef, double wheelbase, acmpc::Vehicle* out) {
+  for (int q = 0; q < acmpc::kDynamicsCount; ++q)
+    if (!std::isfinite(coef[q])) return "non-finite value in the vehicle block";
   const double F_z0 = coef[0], Bf = coef[1], Cf = coef[2], Df = coef[3], Ef = coef[4], epsf = coef[5], Br = coef[6],
                Cr = coef[7], Dr = coef[8], Er = coef[9], epsr = coef[10], mass = coef[11], Iz = coef[12], g = coef[13],
                lf = coef[14], lr = coef[15], bias = coef[16];
-  if (!(mass > 0.0) || !(Iz > 0.0)) return fail(c, ACMPC_EINVAL, "mass and Iz must be positive");
-  if (F_z0 == 0.0 || lr + lf == 0.0) return fail(c, ACMPC_EINVAL, "F_z0 and lf + lr must not be zero");
+  if (!(mass > 0.0) || !(Iz > 0.0)) return "mass and Iz must be positive";
+  if (F_z0 == 0.0 || lr + lf == 0.0) return "F_z0 and lf + lr must not be zero";
   // float64, the reference's association, each constant rounded to float32 once ("Mode D")
   const double F_zf = mass * g * lr / (lr + lf);
   const double F_zr = mass * g * lf / (lr + lf);
-  acmpc::Vehicle& v = c->vehicle;
+  acmpc::Vehicle& v = *out;
   v.lf = static_cast<float>(lf);
   v.lr = static_cast<float>(lr);
   v.Bf = static_cast<float>(Bf);
@@ -1290,7 +1287,56 @@ int acmpc_set_dynamics(acmpc_ctx* c, const double* coef, int32_t count) {
   v.Cfric3 = static_cast<float>(coef[25]);
   v.bias_front = static_cast<float>(bias);
   v.bias_rear = static_cast<float>(1 - bias);
-  v.wheelbase = static_cast<float>(c->prm.wheelbase);
+  v.wheelbase = static_cast<float>(wheelbase);
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int acmpc_set_dynamics(acmpc_ctx* c, const double* coef, int32_t count) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics needs a mode D handle");
+  if (coef == nullptr) return fail(c, ACMPC_EINVAL, "null vehicle block");
+  if (count != acmpc::kDynamicsCount) return fail(c, ACMPC_EINVAL, "the vehicle block has ACMPC_DYNAMICS_COUNT = 26 values");
+  // an ensemble of one (omega_0 = 1, MEAN): the single-vehicle kernels
+  acmpc::VehicleEnsemble e{};
+  const char* why = derive_vehicle(coef, c->prm.wheelbase, &e.v[0]);
+  if (why != nullptr) return fail(c, ACMPC_EINVAL, why);
+  e.omega[0] = 1.0f;
+  e.K = 1;
+  e.reduce = ACMPC_ENSEMBLE_MEAN;
+  c->vehicles = e;
+  c->has_dynamics = true;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_ensemble(acmpc_ctx* c, const double* coef, int32_t K, const double* weights, int32_t reduce) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics_ensemble needs a mode D handle");
+  if (coef == nullptr) return fail(c, ACMPC_EINVAL, "null vehicle blocks");
+  if (K < 1 || K > ACMPC_MAX_VEHICLES) return fail(c, ACMPC_EINVAL, "an ensemble has 1 .. ACMPC_MAX_VEHICLES = 8 vehicles");
+  if (reduce != ACMPC_ENSEMBLE_MEAN && reduce != ACMPC_ENSEMBLE_MAX) return fail(c, ACMPC_EINVAL, "unknown reduce");
+  // everything is checked before anything is kept: a refused ensemble leaves the handle's vehicle(s) as they were
+  acmpc::VehicleEnsemble e{};
+  double total = 0.0;
+  for (int k = 0; k < K; ++k) {
+    if (weights != nullptr) {
+      if (!std::isfinite(weights[k]) || !(weights[k] > 0.0))
+        return fail(c, ACMPC_EINVAL, "vehicle " + std::to_string(k) + ": a weight must be finite and positive");
+      total += weights[k];
+    }
+    const char* why = derive_vehicle(coef + static_cast<size_t>(k) * acmpc::kDynamicsCount, c->prm.wheelbase, &e.v[k]);
+    if (why != nullptr) return fail(c, ACMPC_EINVAL, "vehicle " + std::to_string(k) + ": " + why);
+  }
+  if (weights != nullptr && !std::isfinite(total)) return fail(c, ACMPC_EINVAL, "the weights' sum is not finite");
+  // omega_k = w_k / sum_j w_j in float64 (the sum in k order), each rounded once; no weights: float32(1 / K)
+  for (int k = 0; k < K; ++k)
+    e.omega[k] = static_cast<float>(weights != nullptr ? weights[k] / total : 1.0 / K);
+  e.K = K;
+  e.reduce = reduce;
+  c->vehicles = e;
   c->has_dynamics = true;
   return ACMPC_OK;
 }

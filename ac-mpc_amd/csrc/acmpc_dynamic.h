@@ -38,6 +38,34 @@ struct Vehicle {
   float wheelbase;        // acmpc_params::wheelbase: delta_ref = atan_spec(wheelbase * k_ref) of the waypoint rows
 };
 
+// An ensemble of vehicles (acmpc_set_dynamics_ensemble, DESIGN.md section 2 "Mode D", "Ensembles"): every candidate is
+// rolled under each of the K vehicles from the same x0 and controls, and its cost is the MEAN (omega_0 c_0, then
+// fma(omega_k, c_k, J) in k order) or the MAX (NaN if any is NaN) of the K costs; its violation is the max of the K
+// violations (NaN if any is NaN).  omega = the weights normalised on the host in float64, each rounded once.  One vehicle
+// (acmpc_set_dynamics) is K = 1 and runs the single-vehicle kernels.  A kernel argument: the vehicle of a wavefront is
+// indexed by a wave-uniform value, so its constants are read by scalar loads into SGPRs, as one Vehicle's are.
+constexpr int kMaxVehicles = 8;   // ACMPC_MAX_VEHICLES
+constexpr int kEnsembleMean = 0;  // ACMPC_ENSEMBLE_MEAN
+constexpr int kEnsembleMax = 1;   // ACMPC_ENSEMBLE_MAX
+struct VehicleEnsemble {
+  Vehicle v[kMaxVehicles];
+  float omega[kMaxVehicles];
+  int K;
+  int reduce;
+};
+
+// J and V of one candidate from its K per-vehicle costs c[k * stride] and violations v[k * stride], in k order
+__device__ __forceinline__ void ensemble_combine(const float* c, const float* v, int stride, const VehicleEnsemble& e,
+                                                 float& J, float& V) {
+  J = (e.reduce == kEnsembleMean) ? e.omega[0] * c[0] : c[0];
+  V = v[0];
+  for (int k = 1; k < e.K; ++k) {
+    const float ck = c[k * stride], vk = v[k * stride];
+    J = (e.reduce == kEnsembleMean) ? fma_(e.omega[k], ck, J) : ((ck > J || ck != ck) ? ck : J);
+    V = (vk > V || vk != vk) ? vk : V;
+  }
+}
+
 // atan t = t + t^3 P(t^2) on [0, 1], P of degree 7 in t^2 (tools/fit_atan.py: Lawson-weighted least squares, float32
 // coefficients, Horner with fused multiply-adds): |error| < 6.8e-8 on [0, 1], < 2e-7 (1.53e-7 measured) on the real line
 constexpr float kAtanC[8] = {-0.33332985639572144f, 0.1999039649963379f,  -0.1418597251176834f,   0.10573919117450714f,
@@ -162,15 +190,18 @@ __device__ __forceinline__ void stage_dynamic_tables(const float* __restrict__ c
 }
 
 // ---- launchers (acmpc_dynamic.hip) ----------------------------------------------------------------------------------
-// Candidates per lane of the rollout for a launch of P x N: two (v_pk_* pairs) once the launch fills the chip many
-// times over, one below that (a small solve is latency: more lanes, shorter per-lane work).
-int dynamic_candidates_per_lane(int P, int N);
-int dynamic_blocks_per_problem(int P, int N);
-// rollout: costs [P][N] (or nullptr) and one (cost, index) partial key + feasible count per workgroup, x0 [P][6]
-hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const Vehicle& vehicle, hipStream_t s);
+// Candidates per lane of the rollout for a launch of P x N (x K vehicles): two (v_pk_* pairs) once the launch fills the
+// chip many times over, one below that (a small solve is latency: more lanes, shorter per-lane work).
+int dynamic_candidates_per_lane(int P, int N, int K = 1);
+// partial keys per problem of the rollout: one per 256-lane workgroup (K = 1), one per K-wave workgroup of 64 lanes (K > 1)
+int dynamic_blocks_per_problem(int P, int N, int K = 1);
+// rollout: costs [P][N] (or nullptr) and one (cost, index) partial key + feasible count per workgroup, x0 [P][6].  K = 1:
+// rollout_dynamic_kernel with the one vehicle; K > 1: rollout_dynamic_ensemble_kernel.
+hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
-// pedal), x = (X, Y, yaw) in the caller's frame.  Reads args.U / x0 / coef / partial_* / keys_in / index_offset / n / N / P
-// / blocks_per_problem / w; `regenerate` and `controls_only` are not supported (hipErrorInvalidValue).
-hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const Vehicle& vehicle, hipStream_t s);
+// pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
+// index_offset / n / N / P / blocks_per_problem / w; `regenerate` and `controls_only` are not supported
+// (hipErrorInvalidValue).
+hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles, hipStream_t s);
 
 }  // namespace acmpc

@@ -54,7 +54,11 @@ extern "C" {
                                  (control/dynamic_bicycle_model.py:88-160, one explicit Euler step of dt with vx
                                  clipped at 0 after it), scored with mode T's nearest-waypoint projection and cost
                                  ("mode D").  Start states x0 [P][6] = (X, Y, yaw, vx, vy, r); a candidate is n pairs
-                                 (delta, pedal), the pedal in [-1, 1]; the vehicle comes from acmpc_set_dynamics.
+                                 (delta, pedal), the pedal in [-1, 1]; the vehicle comes from acmpc_set_dynamics,
+                                 or K vehicles from acmpc_set_dynamics_ensemble: every candidate is then scored under
+                                 each, its cost the weighted MEAN or the MAX of the K costs, its violation the max of
+                                 the K violations, the record's x its trajectory under vehicle 0 - through every call
+                                 form below, unchanged.
                                  Tables as mode T's (acmpc_set_paths); max_steps <= 512; lq_candidate must be 0.
                                  Takes acmpc_set_paths / acmpc_set_coefficients, acmpc_solve, acmpc_solve_device,
                                  acmpc_rollout_device + acmpc_finalize_device (index_offset, acmpc_reduce_across_ranks),
@@ -208,6 +212,24 @@ int acmpc_set_coefficients(acmpc_ctx* ctx, const float* coef, int32_t P, int32_t
  * is not ACMPC_MODE_DYNAMIC. */
 #define ACMPC_DYNAMICS_COUNT 26
 int acmpc_set_dynamics(acmpc_ctx* ctx, const double* coef, int32_t count);
+
+/* Mode D's ensemble (scenario-based robust scoring): K vehicle blocks, coef [K][ACMPC_DYNAMICS_COUNT], each validated as
+ * acmpc_set_dynamics validates one, with positive weights [K] (or NULL: equal) and a reduce.  Every candidate is rolled
+ * from the same x0 and controls under each vehicle k, giving c_k and V_k; weights are normalised on the host in float64,
+ * omega_k = w_k / sum_j w_j, each rounded once to float32 (NULL: float32(1 / K)).  The candidate's cost J is
+ *   ACMPC_ENSEMBLE_MEAN  J = omega_0 c_0, then J = fma(omega_k, c_k, J) for k = 1 .. K-1, in that order;
+ *   ACMPC_ENSEMBLE_MAX   the largest c_k, NaN if any c_k is NaN;
+ * its violation V = max_k V_k (NaN if any is NaN), so a feasible candidate is feasible under every vehicle.  J is what
+ * `costs`, the keys and the record's cost hold; the record's violation is V, n_feasible counts V == 0, u is the winner's
+ * controls and x its trajectory under vehicle 0 (the nominal one).  K = 1 with MEAN is acmpc_set_dynamics bit for bit,
+ * and acmpc_set_dynamics after an ensemble goes back to one vehicle.  No device work.  ACMPC_EINVAL for a handle whose
+ * mode is not ACMPC_MODE_DYNAMIC, K outside 1 .. ACMPC_MAX_VEHICLES, an unknown reduce, a weight that is not finite or
+ * not > 0, or any block acmpc_set_dynamics refuses; the handle then keeps its previous vehicle(s).  DESIGN.md section 2
+ * "Mode D", "Ensembles". */
+#define ACMPC_MAX_VEHICLES 8
+#define ACMPC_ENSEMBLE_MEAN 0
+#define ACMPC_ENSEMBLE_MAX 1
+int acmpc_set_dynamics_ensemble(acmpc_ctx* ctx, const double* coef, int32_t K, const double* weights, int32_t reduce);
 
 /* Copies the packed float32 table of problem `problem` (n rows of ACMPC_COEF_STRIDE_* floats) to `out`.
  * Host only; lets CPU tests pin the host-side arithmetic against the oracle. */

@@ -9,7 +9,12 @@
     profiles/*_valu_probe.json (eight waves per SIMD) over 1 024 SIMDs, with its check that the mix was compiled from the
     loaded sources (`opcode_mix_matches_loaded_sources`).
 
-usage: python3 tools/bench_dynamic.py [--reps 20]"""
+With `--vehicles K` every figure is measured with an ensemble of K vehicles (acmpc_set_dynamics_ensemble: the default
+vehicle at grips 1.0, 0.9, 1.1, 0.8, ...) combined by `--reduce`; rates then count vehicle-candidate-steps too, and the roof
+prices the `dynamic_ensemble` entry's mix over P N K candidates.  A comma list (`--vehicles 1,4`) measures each K in the
+same process and adds the ratios of each K to the first.
+
+usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max]"""
 import argparse
 import json
 import os
@@ -23,14 +28,15 @@ for _p in (ROOT, os.path.join(ROOT, "ac-mpc_amd"), os.path.join(ROOT, "oracle"),
     sys.path.insert(0, _p)
 
 
-def issue_roof(bench, candidates, steps, kernel_s):
-    """bench.valu_roofline for the `dynamic` entry: the step loop's static VALU count per candidate-step (the isa mix, whose
-    sources must be the loaded build's - `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
+def issue_roof(bench, candidates, steps, kernel_s, name="dynamic"):
+    """bench.valu_roofline for the `dynamic` entry (`dynamic_ensemble`: candidates = vehicle-candidates): the step loop's
+    static VALU count per candidate-step (the isa mix, whose sources must be the loaded build's -
+    `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
     mix, mix_path = bench.newest_profile("isa_mix.json")
-    entry = mix["entries"]["dynamic"]
+    entry = mix["entries"][name]
     per_step = sum(entry["valu"].values()) / float(entry["candidates_per_lane"])
     counted = (per_step, mix_path + " (static count of the step loop)", {"source_sha256": mix.get("source_sha256")})
-    roof, _ = bench.valu_roofline(counted, candidates, steps, kernel_s, mix_entry="dynamic",
+    roof, _ = bench.valu_roofline(counted, candidates, steps, kernel_s, mix_entry=name,
                                   cpt=entry["candidates_per_lane"])
     return roof
 
@@ -39,7 +45,35 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--quick", action="store_true", help="fewer repetitions (a profiler run)")
+    ap.add_argument("--vehicles", default=None, help="K, or a comma list of K: an ensemble of K vehicles")
+    ap.add_argument("--reduce", default="mean", choices=("mean", "max"))
     args = ap.parse_args()
+    if args.vehicles is None:
+        print(json.dumps(measure(args, 1)))
+        return
+    ks = [int(k) for k in args.vehicles.split(",")]
+    by_k = {k: measure(args, k) for k in ks}
+    if len(ks) == 1:
+        print(json.dumps(by_k[ks[0]]))
+        return
+    first = by_k[ks[0]]
+    out = {"tool": "tools/bench_dynamic.py --vehicles %s --reduce %s" % (args.vehicles, args.reduce),
+           "by_vehicles": {str(k): v for k, v in by_k.items()}, "ratios_to_K%d" % ks[0]: {}}
+    for k in ks[1:]:
+        f = by_k[k]
+        out["ratios_to_K%d" % ks[0]][str(k)] = {
+            "vehicle_candidate_steps_per_s_4096x4096": f["4096x4096"]["vehicle_candidate_steps_per_s"]
+            / first["4096x4096"]["vehicle_candidate_steps_per_s"],
+            "vehicle_candidate_steps_per_s_1M": f["1M"]["vehicle_candidate_steps_per_s"]
+            / first["1M"]["vehicle_candidate_steps_per_s"],
+            "solve_16384_p50": f["solve_16384"]["p50_ms"] / first["solve_16384"]["p50_ms"]}
+    print(json.dumps(out))
+
+
+GRIPS = (1.0, 0.9, 1.1, 0.8, 1.2, 0.7, 1.05, 0.95)
+
+
+def measure(args, K):
     import torch
     import acmpc_oracle as orc
     import bench
@@ -53,11 +87,17 @@ def main():
     s = torch.cuda.current_stream().cuda_stream
     reps = 3 if args.quick else args.reps
     out = {"tool": "tools/bench_dynamic.py", "horizon": H, "search": "window (2, 5)"}
+    if K > 1:
+        out.update(vehicles=K, reduce=args.reduce, grips=list(GRIPS[:K]))
 
     def engine(P, N):
         kw = dict(dp["kw"], max_problems=P, max_candidates=N, max_steps=n, nn_window=(2, 5))
         eng = Engine(**kw)
-        eng.set_dynamics(DynamicBicycleParams.reference())
+        if K == 1:
+            eng.set_dynamics(DynamicBicycleParams.reference())
+        else:
+            eng.set_dynamics_ensemble([DynamicBicycleParams.reference().with_grip(g) for g in GRIPS[:K]],
+                                      reduce=args.reduce)
         eng.set_paths(np.repeat(dp["table"][None], P, axis=0))
         eng.sync_tables(s)
         return eng
@@ -84,7 +124,8 @@ def main():
             torch.cuda.synchronize()
             times.append(e0.elapsed_time(e1) * 1e-3)
         t = float(np.median(times))
-        out[name] = dict(P=P, N=N, ms=t * 1e3, traj_per_s=P * N / t, candidate_steps_per_s=P * N * n / t)
+        out[name] = dict(P=P, N=N, ms=t * 1e3, traj_per_s=P * N / t, candidate_steps_per_s=P * N * n / t,
+                         vehicle_candidate_steps_per_s=P * N * K * n / t)
         eng.close()
         del U
         torch.cuda.empty_cache()
@@ -107,13 +148,14 @@ def main():
     out["solve_16384"] = dict(p50_ms=float(np.percentile(lat, 50)) * 1e3, p99_ms=float(np.percentile(lat, 99)) * 1e3,
                               calls=len(lat))
     one_m = out["1M"]
-    roof = issue_roof(bench, one_m["P"] * one_m["N"], n, one_m["ms"] * 1e-3)
+    roof = issue_roof(bench, one_m["P"] * one_m["N"] * K, n, one_m["ms"] * 1e-3,
+                      "dynamic" if K == 1 else "dynamic_ensemble")
     out["valu_per_candidate_step"] = roof["valu_instructions_per_candidate_step"]
     out["vector_issue_roof"] = roof
     if not roof["opcode_mix_matches_loaded_sources"]:
         print("warning: profiles/*_isa_mix.json does not describe the loaded sources: python3 tools/isa_mix.py <tag>",
               file=sys.stderr)
-    print(json.dumps(out))
+    return out
 
 
 if __name__ == "__main__":

@@ -32,6 +32,8 @@ ENTRIES = {
     # mode D (the dynamic bicycle, two candidates per lane, step-major): the largest step loop - a windowed search's, whose
     # trip is the dynamics + an unrolled window + the cost; the exhaustive form adds its waypoint loop to the same trip
     "dynamic": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2EE", None),
+    # mode D with an ensemble of vehicles (one wavefront per vehicle): the same step loop under wave k's vehicle
+    "dynamic_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2EE", None),
 }
 CANDIDATES_PER_LANE = {"fused_round": 1}
 
