@@ -28,6 +28,7 @@ ATAN_C = (-0.33332985639572144, 0.1999039649963379, -0.1418597251176834, 0.10573
 HALF_PI = 1.5707963267948966     # rounded to float32 where it is used
 ATAN_ERROR_BOUND = 2.0e-7
 VX_EPS = 1.0e-3                  # dynamic_bicycle_model.py:97-98
+SCAN_BLOCK = 32                  # waypoints per NumPy call of the nearest-waypoint scan (speed only)
 
 # The vehicle block of acmpc_set_dynamics, in ABI order (include/acmpc.h ACMPC_DYNAMICS_COUNT)
 FIELDS = ("F_z0", "Bf", "Cf", "Df", "Ef", "epsf", "Br", "Cr", "Dr", "Er", "epsr", "mass", "Iz", "g", "lf", "lr",
@@ -117,10 +118,11 @@ def dynamic_step(state, delta, pedal, k, dt):
 
 
 def rollout_dynamic(x0, wp, U, vehicle, Q, R, QN, u_lo, u_hi, w_bound, dt, wheelbase, nn_window=None,
-                    return_states=False):
+                    return_states=False, trace=None):
     """Mode D's cost of every candidate, bit for bit: x0 = (X, Y, yaw, vx, vy, r), wp [n, 8] the packed mode-T table,
     U [N, n, 2] = (delta, pedal), `vehicle` the 26 doubles of the block.  Nearest waypoint, stage cost, bounds and
-    terminal cost are mode T's (oracle rollout_temporal) with dv = vx - v_ref, dk = delta - atan_spec(L k_ref)."""
+    terminal cost are mode T's (oracle rollout_temporal) with dv = vx - v_ref, dk = delta - atan_spec(L k_ref).
+    `trace`: a dict that receives e_y [N, n] and the nearest index j [N, n] of every step (for measurements)."""
     k = derived_constants(vehicle)
     U = np.asarray(U, dtype=T)
     wp = np.asarray(wp, dtype=T)
@@ -142,6 +144,7 @@ def rollout_dynamic(x0, wp, U, vehicle, Q, R, QN, u_lo, u_hi, w_bound, dt, wheel
     ey = np.zeros(N, dtype=T)
     ep = np.zeros(N, dtype=T)
     j_prev = np.zeros(N, dtype=np.int64)
+    rows = np.arange(N)
     X_out = np.zeros((N, n + 1, 3), dtype=T) if return_states else None
     if return_states:
         X_out[:, 0] = np.stack([st[0] + ox, st[1] + oy, st[2]], axis=1)
@@ -149,27 +152,26 @@ def rollout_dynamic(x0, wp, U, vehicle, Q, R, QN, u_lo, u_hi, w_bound, dt, wheel
         d, p = U[:, i, 0], U[:, i, 1]
         st = list(dynamic_step(st, d, p, k, dtT))
         X, Y, psi, vx = st[0], st[1], st[2], st[3]
-        best = np.full(N, np.inf, dtype=T)
+        # the first minimum of the search key under `<` from best = +inf, scanned in waypoint order (a NaN or +inf key
+        # never wins; the search's first waypoint when none does) - SCAN_BLOCK waypoints of every candidate at a time
         if nn_window is None:
-            j = np.zeros(N, dtype=np.int64)
-            cand = range(n)
-            for w in cand:
-                dd = fma32(Y, key_b[w], fma32(X, key_a[w], key_c[w]))
-                better = dd < best
-                best = np.where(better, dd, best)
-                j = np.where(better, w, j)
+            w = np.broadcast_to(np.arange(n), (N, n))
         else:
             back, ahead = nn_window
             width = back + ahead + 1
             lo_w = np.maximum(np.minimum(j_prev - back, n - width), 0)
             hi_w = np.minimum(lo_w + width, n) - 1
-            j = lo_w.copy()
-            for m in range(width):
-                w = np.minimum(lo_w + m, hi_w)
-                dd = fma32(Y, key_b[w], fma32(X, key_a[w], key_c[w]))
-                better = dd < best
-                best = np.where(better, dd, best)
-                j = np.where(better, w, j)
+            w = np.minimum(lo_w[:, None] + np.arange(width)[None, :], hi_w[:, None])
+        best = np.full(N, np.inf, dtype=T)
+        j = w[:, 0].copy()
+        for b in range(0, w.shape[1], SCAN_BLOCK):
+            block = w[:, b:b + SCAN_BLOCK]
+            dd = fma32(Y[:, None], key_b[block], fma32(X[:, None], key_a[block], key_c[block]))
+            first = np.argmin(np.where(np.isnan(dd), T(np.inf), dd), axis=1)
+            dd = dd[rows, first]
+            better = dd < best
+            best = np.where(better, dd, best)
+            j = np.where(better, block[rows, first], j)
         j_prev = j
         g = wp[j]
         with np.errstate(all="ignore"):
@@ -187,6 +189,9 @@ def rollout_dynamic(x0, wp, U, vehicle, Q, R, QN, u_lo, u_hi, w_bound, dt, wheel
             V = fma32(hp, hp, V)
             hc = np.fmax(np.abs(ey) - g[:, 7], zero)
             V = fma32(hc, hc, V)
+        if trace is not None:
+            trace.setdefault("e_y", []).append(ey.copy())
+            trace.setdefault("j", []).append(j.copy())
         if return_states:
             X_out[:, i + 1] = np.stack([X + ox, Y + oy, psi], axis=1)
     with np.errstate(all="ignore"):
@@ -201,6 +206,8 @@ def rollout_dynamic(x0, wp, U, vehicle, Q, R, QN, u_lo, u_hi, w_bound, dt, wheel
         J = J + s
         cost = fma32(wb, V, J)
     cost = np.asarray(cost, dtype=T)
+    if trace is not None:
+        trace["e_y"], trace["j"] = np.stack(trace["e_y"], axis=1), np.stack(trace["j"], axis=1)
     return (cost, V, X_out) if return_states else (cost, V)
 
 
