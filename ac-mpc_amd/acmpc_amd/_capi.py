@@ -170,6 +170,9 @@ SIGNATURES = {
     "acmpc_solve_sampled_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_uint64,
                                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acmpc_rollout_sampled_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_uint64, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "acmpc_solve_stream_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_uint64,
                                             C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -599,6 +602,14 @@ class Engine:
         self._check(self._lib.acmpc_solve_sampled_device(self._ctx, d_x0, d_U, d_centre, centre_stride, d_u_ref or None, P,
                                                          N, n, layout, float(sigma[0]), float(sigma[1]), seed, round_,
                                                          d_costs or None, d_keys or None, d_records, stream or None))
+
+    def rollout_sampled_device(self, d_x0: int, d_centre: int, centre_stride: int, d_u_ref: int, P: int, N: int, n: int,
+                               index_offset: int, sigma, seed: int, round_: int, d_costs: int, d_keys: int, stream: int = 0):
+        """Mode D: sample_device + rollout_device without the control matrix - the candidates (global indices index_offset ..
+        index_offset + N) are drawn inside the rollout kernel (acmpc_rollout_sampled_device).  sigma = (delta, pedal)."""
+        self._check(self._lib.acmpc_rollout_sampled_device(self._ctx, d_x0, d_centre, centre_stride, d_u_ref or None, P, N,
+                                                           n, index_offset, float(sigma[0]), float(sigma[1]), seed, round_,
+                                                           d_costs or None, d_keys or None, stream or None))
 
     def solve_stream_device(self, d_x0: int, d_U: int, d_centre: int, centre_stride: int, d_u_ref: int, P: int, N: int,
                             n: int, layout: int, sigma, seed: int, round_: int, d_costs: int, d_keys: int, d_records: int,

@@ -163,7 +163,8 @@ struct acmpc_ctx {
   struct Switches {
     bool no_verified_search = false, no_solo = false, no_fused_finalize = false, no_traced_finalize = false,
          no_chained_rounds = false, no_chained_stream = false, no_graph = false, no_fused_sampling = false, tick_graph = false, tick_no_flag = false, tick_no_inline_path = false, no_zero_copy = false,
-         tailed_rollout = false;
+         tailed_rollout = false,
+         dynamic_matrix_rounds = false;   // mode D's acmpc_optimize through the control matrix: sample -> rollout -> finalize
   } sw;
 
   // optional timing of the rollout dispatches (acmpc_profile_*): event pairs attached to the launches
@@ -438,7 +439,6 @@ int finalize(acmpc_ctx* c, const int64_t* d_keys_in, int64_t* d_keys_out, const 
   a.index_offset = offset;
   a.w = c->w;
   if (c->prm.mode == ACMPC_MODE_DYNAMIC) {
-    if (regen != nullptr) return fail(c, ACMPC_ESTATE, "mode D re-rolls its winners from U: no re-drawn candidates");
     ACMPC_HIP(c, acmpc::launch_finalize_dynamic(layout, a, c->vehicles, s));
     return ACMPC_OK;
   }
@@ -510,6 +510,37 @@ int sample(acmpc_ctx* c, const float* d_centre, int centre_stride, const float* 
   a.spec = make_spec(c, sigma_v, sigma_k, seed, round);
   a.spec.seed_ptr = d_seed;
   ACMPC_HIP(c, acmpc::launch_sample(layout, a, s));
+  return ACMPC_OK;
+}
+
+// mode D: the rollout that draws its own candidates (acmpc_dynamic.hip: launch_rollout_dynamic_sampled) - what sample() into
+// a matrix and rollout() of it compute, without the matrix
+int rollout_sampled_dynamic(acmpc_ctx* c, const float* d_x0, const float* d_centre, int centre_stride, const float* d_uref,
+                            int P, int N, int n, int64_t offset, double sigma_d, double sigma_p, uint64_t seed, uint32_t round,
+                            float* d_costs, hipStream_t s) {
+  const int rc = upload_segments(c, n, s);
+  if (rc != ACMPC_OK) return rc;
+  acmpc::RolloutArgs a{};
+  a.x0 = d_x0;
+  a.coef = c->d_coef;
+  a.costs = d_costs;
+  a.partial_keys = c->d_partial_keys;
+  a.partial_feas = c->d_partial_feas;
+  a.P = P;
+  a.N = N;
+  a.n = n;
+  a.index_offset = offset;
+  a.w = c->w;
+  acmpc::SampleArgs smp{};
+  smp.centre = d_centre;
+  smp.u_ref = d_uref;
+  smp.centre_stride = centre_stride;
+  smp.P = P;
+  smp.N = N;
+  smp.n = n;
+  smp.index_offset = offset;
+  smp.spec = make_spec(c, sigma_d, sigma_p, seed, round);
+  ACMPC_HIP(c, acmpc::launch_rollout_dynamic_sampled(a, smp, c->vehicles, s));
   return ACMPC_OK;
 }
 
@@ -637,6 +668,14 @@ int solve_batched(acmpc_ctx* c, const float* d_x0, const float* d_U, int P, int 
   return ACMPC_OK;
 }
 
+// the control matrix of the host-pointer entry points.  Mode D allocates it on first use: its acmpc_optimize draws the
+// candidates inside the rollout and needs none (acmpc_solve and ACMPC_DYNAMIC_MATRIX_ROUNDS do)
+int ensure_matrix(acmpc_ctx* c) {
+  const acmpc_params& p = c->prm;
+  ACMPC_HIP(c, alloc_once(&c->d_U, static_cast<size_t>(p.max_problems) * p.max_candidates * p.max_steps * 2 * sizeof(float)));
+  return ACMPC_OK;
+}
+
 int ensure_staging(acmpc_ctx* c) {
   if (c->staging_ready) return ACMPC_OK;
   c->touched_device = true;
@@ -645,7 +684,10 @@ int ensure_staging(acmpc_ctx* c) {
   ACMPC_HIP(c, alloc_once(&c->d_centre, static_cast<size_t>(p.max_problems) * p.max_steps * 2 * sizeof(float)));
   ACMPC_HIP(c, alloc_once(&c->d_uref, static_cast<size_t>(p.max_problems) * p.max_steps * 2 * sizeof(float)));
   if (c->stream == nullptr) ACMPC_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  ACMPC_HIP(c, alloc_once(&c->d_U, cand * p.max_steps * 2 * sizeof(float)));
+  if (p.mode != ACMPC_MODE_DYNAMIC) {
+    const int rc_matrix = ensure_matrix(c);
+    if (rc_matrix != ACMPC_OK) return rc_matrix;
+  }
   const size_t state_floats = p.mode == ACMPC_MODE_DYNAMIC ? acmpc::kDynamicStateFloats : 3;
   ACMPC_HIP(c, alloc_once(&c->d_x0, static_cast<size_t>(p.max_problems) * state_floats * sizeof(float)));
   ACMPC_HIP(c, alloc_once(&c->d_costs, cand * sizeof(float)));
@@ -671,7 +713,7 @@ const char* const kOptionNames[] = {
     "ACMPC_NO_QUAD_ROUNDS", "ACMPC_NO_PAIR_ROUNDS", "ACMPC_SOLO_REGISTERS", "ACMPC_SOLO_SPLIT", "ACMPC_NO_VERIFIED_SEARCH",
     "ACMPC_NO_SOLO", "ACMPC_NO_FUSED_FINALIZE", "ACMPC_NO_TRACED_FINALIZE", "ACMPC_NO_CHAINED_ROUNDS", "ACMPC_NO_GRAPH",
     "ACMPC_NO_FUSED_SAMPLING", "ACMPC_TICK_GRAPH", "ACMPC_TICK_NO_FLAG", "ACMPC_TICK_NO_INLINE_PATH", "ACMPC_NO_ZERO_COPY", "ACMPC_TAILED_ROLLOUT", "ACMPC_NO_GROUP_FINALIZE", "ACMPC_FINALIZE_WAVES",
-    "ACMPC_NO_CHAINED_STREAM", "ACMPC_LQ_BOX_ITERATIONS", "ACMPC_START_CLOCKS",
+    "ACMPC_NO_CHAINED_STREAM", "ACMPC_LQ_BOX_ITERATIONS", "ACMPC_START_CLOCKS", "ACMPC_DYNAMIC_MATRIX_ROUNDS",
     "ACMPC_CONFORMANT_SYNC"};   // (last: it sets several of the switches above, and wins over them when both are in the environment)
 
 bool apply_option(acmpc_ctx* c, const char* name, const char* value) {
@@ -711,6 +753,7 @@ bool apply_option(acmpc_ctx* c, const char* name, const char* value) {
   if (key == "ACMPC_NO_ZERO_COPY") { w.no_zero_copy = on; return true; }
   if (key == "ACMPC_TAILED_ROLLOUT") { w.tailed_rollout = on; return true; }
   if (key == "ACMPC_START_CLOCKS") { c->want_start_clocks = on; return true; }
+  if (key == "ACMPC_DYNAMIC_MATRIX_ROUNDS") { w.dynamic_matrix_rounds = on; return true; }
   if (key == "ACMPC_CONFORMANT_SYNC") {
     // ONE switch for the forms that stay inside the HSA memory model and HIP's barrier rule (include/acmpc.h): every solve,
     // round and batch as separate launches, nothing published between workgroups of one launch, no wave of a workgroup
@@ -1075,8 +1118,6 @@ int acmpc_solve_sampled_device(acmpc_ctx* c, const float* d_x0, const float* d_U
                                double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round, float* d_costs,
                                int64_t* d_keys, float* d_records, void* stream) {
   if (c == nullptr) return ACMPC_EINVAL;
-  if (c->prm.mode == ACMPC_MODE_DYNAMIC)
-    return fail(c, ACMPC_ESTATE, "mode D re-rolls its winners from U: use acmpc_solve_device / acmpc_finalize_device");
   if (d_x0 == nullptr || d_U == nullptr || d_centre == nullptr || d_records == nullptr)
     return fail(c, ACMPC_EINVAL, "null device pointer");
   if (centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
@@ -1090,6 +1131,12 @@ int acmpc_solve_sampled_device(acmpc_ctx* c, const float* d_x0, const float* d_U
   rc = upload_segments(c, n, s);
   if (rc != ACMPC_OK) return rc;
   const Regenerate regen{d_centre, centre_stride, d_u_ref, make_spec(c, sigma_v, sigma_kappa, seed, round)};
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC) {   // two launches: the rollout of d_U, the finalize that re-draws the winners
+    acmpc::LaunchShape used;
+    rc = rollout(c, d_x0, d_U, P, N, n, layout, 0, d_costs, s, &used);
+    if (rc != ACMPC_OK) return rc;
+    return finalize(c, nullptr, d_keys, d_x0, nullptr, P, N, n, layout, 0, d_records, used.blocks_per_problem, s, &regen);
+  }
   return solve_batched(c, d_x0, d_U, P, N, n, layout, d_costs, d_keys, d_records, s, &regen);
 }
 
@@ -1107,7 +1154,7 @@ int acmpc_solve_stream_device(acmpc_ctx* c, const float* d_x0, const float* d_U,
                               int64_t* d_keys, float* d_records, void* stream) {
   if (c == nullptr) return ACMPC_EINVAL;
   if (c->prm.mode == ACMPC_MODE_DYNAMIC)
-    return fail(c, ACMPC_ESTATE, "mode D re-rolls its winners from U: use acmpc_solve_device / acmpc_finalize_device");
+    return fail(c, ACMPC_ESTATE, "mode D has no stream of batches: use acmpc_solve_device / acmpc_solve_sampled_device");
   if (d_x0 == nullptr || d_U == nullptr || d_records == nullptr) return fail(c, ACMPC_EINVAL, "null device pointer");
   if (d_centre != nullptr && centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
   int rc = check_shape(c, P, N, n, layout, true);
@@ -1194,6 +1241,8 @@ int solve_dynamic_host(acmpc_ctx* c, const float* x0, const float* U, int P, int
                        int32_t* best_idx, float* records) {
   hipStream_t s = c->stream;
   const size_t cand = static_cast<size_t>(P) * N;
+  const int rc_matrix = ensure_matrix(c);
+  if (rc_matrix != ACMPC_OK) return rc_matrix;
   ACMPC_HIP(c, hipMemcpyAsync(c->d_x0, x0, static_cast<size_t>(P) * acmpc::kDynamicStateFloats * sizeof(float),
                               hipMemcpyHostToDevice, s));
   ACMPC_HIP(c, hipMemcpyAsync(c->d_U, U, cand * n * 2 * sizeof(float), hipMemcpyHostToDevice, s));
@@ -1214,8 +1263,10 @@ int solve_dynamic_host(acmpc_ctx* c, const float* x0, const float* U, int P, int
   return ACMPC_OK;
 }
 
-// acmpc_optimize in mode D: per round sample -> rollout -> finalize, three launches; round r samples round the u block
-// of round r - 1's record, with the spread sigma shrink^r (acmpc_optimize's own schedule)
+// acmpc_optimize in mode D: per round the rollout that draws its own candidates and the finalize that re-draws the winner
+// from its index - two launches, no control matrix; round r samples round the u block of round r - 1's record, with the
+// spread sigma shrink^r (acmpc_optimize's own schedule).  ACMPC_DYNAMIC_MATRIX_ROUNDS keeps sample -> rollout -> finalize
+// through the matrix (three launches): the same records bit for bit.
 int optimize_dynamic(acmpc_ctx* c, const float* x0, const float* centre, const float* u_ref, int P, int N, int n,
                      int rounds, const double sigma[2], double shrink, uint64_t seed, float* records) {
   hipStream_t s = c->stream;
@@ -1224,6 +1275,10 @@ int optimize_dynamic(acmpc_ctx* c, const float* x0, const float* centre, const f
   const int rec_floats = acmpc_record_floats(n);
   int rc = upload_tables(c, s);
   if (rc != ACMPC_OK) return rc;
+  if (c->sw.dynamic_matrix_rounds) {
+    rc = ensure_matrix(c);
+    if (rc != ACMPC_OK) return rc;
+  }
   ACMPC_HIP(c, hipMemcpyAsync(c->d_x0, x0, static_cast<size_t>(P) * acmpc::kDynamicStateFloats * sizeof(float),
                               hipMemcpyHostToDevice, s));
   ACMPC_HIP(c, hipMemcpyAsync(c->d_centre, centre, path_bytes, hipMemcpyHostToDevice, s));
@@ -1231,8 +1286,21 @@ int optimize_dynamic(acmpc_ctx* c, const float* x0, const float* centre, const f
   double scale = 1.0;
   for (int r = 0; r < rounds; ++r, scale *= shrink) {
     const float* d_c = (r == 0) ? c->d_centre : c->d_records + ACMPC_REC_HEADER;
-    rc = sample(c, d_c, (r == 0) ? 2 * n : rec_floats, u_ref != nullptr ? c->d_uref : nullptr, P, N, n, layout, 0,
-                sigma[0] * scale, sigma[1] * scale, seed, static_cast<uint32_t>(r), c->d_U, s);
+    const int stride = (r == 0) ? 2 * n : rec_floats;
+    const float* d_ref = u_ref != nullptr ? c->d_uref : nullptr;
+    if (!c->sw.dynamic_matrix_rounds) {
+      rc = rollout_sampled_dynamic(c, c->d_x0, d_c, stride, d_ref, P, N, n, 0, sigma[0] * scale, sigma[1] * scale, seed,
+                                   static_cast<uint32_t>(r), nullptr, s);
+      if (rc != ACMPC_OK) return rc;
+      // (the centre may be the u block of c->d_records itself: the finalize reads it before it rewrites the record)
+      const Regenerate regen{d_c, stride, d_ref, make_spec(c, sigma[0] * scale, sigma[1] * scale, seed, static_cast<uint32_t>(r))};
+      rc = finalize(c, nullptr, nullptr, c->d_x0, nullptr, P, N, n, layout, 0, c->d_records,
+                    acmpc::dynamic_blocks_per_problem(P, N, c->vehicles.K), s, &regen);
+      if (rc != ACMPC_OK) return rc;
+      continue;
+    }
+    rc = sample(c, d_c, stride, d_ref, P, N, n, layout, 0, sigma[0] * scale, sigma[1] * scale, seed,
+                static_cast<uint32_t>(r), c->d_U, s);
     if (rc != ACMPC_OK) return rc;
     acmpc::LaunchShape shape;
     rc = rollout(c, c->d_x0, c->d_U, P, N, n, layout, 0, nullptr, s, &shape);
@@ -1452,8 +1520,6 @@ int acmpc_finalize_sampled_device(acmpc_ctx* c, const int64_t* d_keys, const flo
                                   double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round, float* d_records,
                                   void* stream) {
   if (c == nullptr) return ACMPC_EINVAL;
-  if (c->prm.mode == ACMPC_MODE_DYNAMIC)
-    return fail(c, ACMPC_ESTATE, "mode D re-rolls its winners from U: use acmpc_solve_device / acmpc_finalize_device");
   if (d_x0 == nullptr || d_centre == nullptr || d_records == nullptr) return fail(c, ACMPC_EINVAL, "null device pointer");
   if (centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
   int rc = check_shape(c, P, N, n, ACMPC_LAYOUT_STEP_MAJOR);
@@ -1463,9 +1529,34 @@ int acmpc_finalize_sampled_device(acmpc_ctx* c, const int64_t* d_keys, const flo
   rc = upload_segments(c, n, s);
   if (rc != ACMPC_OK) return rc;
   Regenerate regen{d_centre, centre_stride, d_u_ref, make_spec(c, sigma_v, sigma_kappa, seed, round)};
-  const acmpc::LaunchShape shape = acmpc::choose_shape(P, N, ACMPC_LAYOUT_STEP_MAJOR, c->prm.mode, n, c->opt);
-  return finalize(c, d_keys, nullptr, d_x0, nullptr, P, N, n, ACMPC_LAYOUT_STEP_MAJOR, 0, d_records,
-                  shape.blocks_per_problem, s, &regen);
+  const int blocks = c->prm.mode == ACMPC_MODE_DYNAMIC
+                         ? acmpc::dynamic_blocks_per_problem(P, N, c->vehicles.K)
+                         : acmpc::choose_shape(P, N, ACMPC_LAYOUT_STEP_MAJOR, c->prm.mode, n, c->opt).blocks_per_problem;
+  return finalize(c, d_keys, nullptr, d_x0, nullptr, P, N, n, ACMPC_LAYOUT_STEP_MAJOR, 0, d_records, blocks, s, &regen);
+}
+
+int acmpc_rollout_sampled_device(acmpc_ctx* c, const float* d_x0, const float* d_centre, int32_t centre_stride,
+                                 const float* d_u_ref, int32_t P, int32_t N, int32_t n, int64_t index_offset,
+                                 double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round, float* d_costs,
+                                 int64_t* d_keys, void* stream) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (d_x0 == nullptr || d_centre == nullptr) return fail(c, ACMPC_EINVAL, "null device pointer");
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC)
+    return fail(c, ACMPC_ESTATE, "acmpc_rollout_sampled_device is mode D's: modes S and T draw inside acmpc_optimize");
+  if (centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
+  if (index_offset < 0 || index_offset + N > 0xffffffffLL) return fail(c, ACMPC_EINVAL, "global index exceeds 32 bits");
+  int rc = check_shape(c, P, N, n, ACMPC_LAYOUT_STEP_MAJOR);
+  if (rc != ACMPC_OK) return rc;
+  rc = ensure_device(c);
+  if (rc != ACMPC_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  rc = upload_tables(c, s);
+  if (rc != ACMPC_OK) return rc;
+  rc = rollout_sampled_dynamic(c, d_x0, d_centre, centre_stride, d_u_ref, P, N, n, index_offset, sigma_v, sigma_kappa, seed,
+                               round, d_costs, s);
+  if (rc != ACMPC_OK || d_keys == nullptr) return rc;
+  return finalize(c, nullptr, d_keys, d_x0, nullptr, P, N, n, ACMPC_LAYOUT_STEP_MAJOR, index_offset, nullptr,
+                  acmpc::dynamic_blocks_per_problem(P, N, c->vehicles.K), s);
 }
 
 extern "C++" {

@@ -1,5 +1,5 @@
 // Mode D: candidates scored through the dynamic (Pacejka) bicycle of the reference (src/acmpc/control/
-// dynamic_bicycle_model.py) - device arithmetic and the launchers of its two kernels (acmpc_dynamic.hip).
+// dynamic_bicycle_model.py) - device arithmetic and the launchers of its kernels (acmpc_dynamic.hip).
 //
 // The float32 "spec order" of DESIGN.md section 2 ("Mode D"), restated bit for bit by tests/dynamic_spec.py: the
 // reference's expression tree evaluated left to right, no fused multiply-add except inside the named polynomial kernels
@@ -198,10 +198,17 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // rollout: costs [P][N] (or nullptr) and one (cost, index) partial key + feasible count per workgroup, x0 [P][6].  K = 1:
 // rollout_dynamic_kernel with the one vehicle; K > 1: rollout_dynamic_ensemble_kernel.
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles, hipStream_t s);
+// the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
+// index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
+// seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
+// input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
+hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
+                                          hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
-// index_offset / n / N / P / blocks_per_problem / w; `regenerate` and `controls_only` are not supported
-// (hipErrorInvalidValue).
+// index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
+// index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
+// complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles, hipStream_t s);
 
 }  // namespace acmpc

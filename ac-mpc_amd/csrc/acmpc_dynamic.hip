@@ -9,7 +9,13 @@
 //   finalize_dynamic_kernel  one wavefront per problem: argmin over the partial keys, then the winner's trajectory on
 //                            broadcast operands with the lanes scanning the waypoints side by side for the search.
 //
-// An ensemble of K > 1 vehicles (VehicleEnsemble, acmpc_dynamic.h) runs two kernels of its own, with ONE WAVEFRONT PER
+//   rollout_dynamic_sampled_kernel   the rollout without a control matrix: a lane draws its candidates' normals (Philox,
+//                            sample_kernel's candidates bit for bit) and blends each step's control as it goes; the
+//                            knot table, the centre and the reference controls are staged in LDS beside the tables.
+//   finalize_dynamic_kernel with FinalizeArgs::regenerate re-draws the winner from the global index in its key instead of
+//                            loading it from U (every rank can, after one all-reduce(MIN) of the keys).
+//
+// An ensemble of K > 1 vehicles (VehicleEnsemble, acmpc_dynamic.h) runs kernels of its own, with ONE WAVEFRONT PER
 // VEHICLE: wave k's vehicle index is wave-uniform, so its constants are scalar as one vehicle's are and the step loop is
 // the one above.
 //   rollout_dynamic_ensemble_kernel   K waves per workgroup over the same 64 CPT candidates; the tables are staged once
@@ -18,10 +24,13 @@
 //   finalize_dynamic_ensemble_kernel  K waves per problem: wave k re-rolls the winner under vehicle k (one re-roll of
 //                                     latency, not K); the K results are combined as in the rollout; wave 0's
 //                                     trajectory is the record's x.
+//   rollout_dynamic_sampled_ensemble_kernel   the ensemble rollout without a control matrix: every wave draws the
+//                                     workgroup's candidates for itself.
 //
 // Built with -ffp-contract=off: see acmpc_device.h.
 #include "acmpc_dynamic.h"
 
+#include <cstring>
 #include <type_traits>
 
 #pragma clang fp contract(off)
@@ -189,6 +198,231 @@ __global__ void __launch_bounds__(kDynBlock) rollout_dynamic_kernel(const Rollou
   }
 }
 
+// ---- candidates drawn inside the rollout (launch_rollout_dynamic_sampled) -----------------------------------------------
+// What a mode D kernel needs of SampleArgs to draw its own candidates - sample_kernel's candidates, bit for bit: Philox
+// counter (uint32(index_offset + c), problem, round, draw), key = seed, draw_normal_block / candidate_amplitude /
+// blend_control of acmpc_device.h.  A handful of scalars: the input box is the Weights' (the launcher checks that the
+// spec's is the same), the knot table is staged in LDS, and the nine knot bounds of SampleSpec stay out of the SGPRs.
+struct DynamicDraw {
+  const float* centre;     // [P] x centre_stride floats
+  const float* u_ref;      // [P][n][2] or nullptr: candidate 1
+  const float* segments;   // [n][2]: left knot (as float), weight of the left knot
+  const uint32_t* seed_ptr;
+  int centre_stride;
+  uint32_t seed_lo, seed_hi, round;
+  float sigma_d, sigma_p;
+};
+
+constexpr int kDrawFloatsPerStep = 6;   // LDS behind the tables: [n][2] knot table | [n][2] centre | [n][2] reference
+constexpr int kDrawSlots = 4;           // knots' pairs of normals resident per candidate (two Philox blocks): roll_sampled
+
+__device__ __forceinline__ SampleSpec draw_spec(const DynamicDraw& d, const Weights& w) {
+  SampleSpec sp{};
+  sp.seed_lo = d.seed_ptr != nullptr ? d.seed_ptr[0] : d.seed_lo;
+  sp.seed_hi = d.seed_ptr != nullptr ? d.seed_ptr[1] : d.seed_hi;
+  sp.seed_ptr = nullptr;
+  sp.round = d.round;
+  sp.sigma_v = d.sigma_d;
+  sp.sigma_k = d.sigma_p;
+  sp.ulo0 = w.ulo0;
+  sp.ulo1 = w.ulo1;
+  sp.uhi0 = w.uhi0;
+  sp.uhi1 = w.uhi1;
+  return sp;
+}
+
+// knot table, centre and reference controls (the centre again when there are none) of problem p -> LDS, by the workgroup
+__device__ __forceinline__ void stage_draw_tables(const DynamicDraw& d, int p, int n, int tid, int threads, float* s_seg,
+                                                  float* s_centre, float* s_ref) {
+  const float* __restrict__ centre = d.centre + static_cast<size_t>(p) * d.centre_stride;
+  const float* __restrict__ ref = d.u_ref != nullptr ? d.u_ref + static_cast<size_t>(p) * n * 2 : centre;
+  for (int e = tid; e < 2 * n; e += threads) {
+    s_seg[e] = d.segments[e];
+    s_centre[e] = centre[e];
+    s_ref[e] = ref[e];
+  }
+}
+
+// The step loop of rollout_dynamic_kernel with the controls drawn as it goes.  The normals stay out of the registers (the
+// step loop has none to spare): knot k's pair lives in LDS slot k & 3 of its lane - s_z
+// [4][row][CPT] pairs - which holds two Philox blocks (block b = knots 2b, 2b + 1) at a time, and a step reads the two knots
+// that bracket it.  When the step's left knot changes - a wave-uniform event, at most seven times a rollout - the blocks of
+// the new pair are drawn unless resident: four draws per candidate, as draw_normals() makes.  SHARED (the ensemble: the K
+// waves of a workgroup roll the same candidates): one wave draws for all, between two barriers that every wave reaches -
+// the knot changes are the same steps in every wave.
+template <int CPT, bool SHARED, typename F>
+__device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& sp, const Vehicle& veh, const Weights& w,
+                                             const int p, const int n, const uint32_t (&gidx)[CPT], const bool has_ref,
+                                             const float* s_wp, const float* s_xy, const float* s_seg,
+                                             const float* s_centre, const float* s_ref, f32x2* s_z, const int row,
+                                             const int zi, const bool draws) {
+  using I = typename IndexOf<F>::type;
+  float amp[CPT];
+  const float* cen[CPT];
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) {
+    const bool use_ref = has_ref && gidx[j] == 1u;   // candidate 1 = the reference controls: amplitude 0, own centre
+    amp[j] = use_ref ? 0.0f : candidate_amplitude(gidx[j]);
+    cen[j] = use_ref ? s_ref : s_centre;
+  }
+  int resident[2] = {-1, -1};   // the Philox block in slots 0, 1 and in slots 2, 3
+  int knot = -1;
+  I nearest = I(0);
+  with_search_kind(w, n, [&](auto kind) {
+    constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
+    for (int i = 0; i < n; ++i) {
+      const int k0 = __builtin_amdgcn_readfirstlane(static_cast<int>(s_seg[2 * i]));
+      if (k0 != knot) {
+        knot = k0;
+        if constexpr (SHARED) __syncthreads();   // every wave has read the old pair for the last time
+#pragma nounroll
+        for (int b = k0 >> 1; b <= (k0 + 1) >> 1; ++b) {
+          if (resident[b & 1] == b) continue;
+          resident[b & 1] = b;
+          if (draws) {
+#pragma nounroll
+            for (int j = 0; j < CPT; ++j) {   // (one candidate at a time: two interleaved Philox blocks cost a wave of occupancy)
+              float z[4];
+              draw_normal_block(sp, j == 0 ? gidx[0] : gidx[CPT - 1], static_cast<uint32_t>(p), static_cast<uint32_t>(b), z);
+              s_z[((2 * (b & 1)) * row + zi) * CPT + j] = f32x2{z[0], z[1]};
+              s_z[((2 * (b & 1) + 1) * row + zi) * CPT + j] = f32x2{z[2], z[3]};
+            }
+          }
+        }
+        if constexpr (SHARED) __syncthreads();
+      }
+      const float w0 = s_seg[2 * i + 1];
+      const f32x2* zl = s_z + ((k0 & 3) * row + zi) * CPT;
+      const f32x2* zr = s_z + (((k0 + 1) & 3) * row + zi) * CPT;
+      float dj[CPT], qj[CPT];
+#pragma unroll
+      for (int j = 0; j < CPT; ++j) {
+        const f32x2 l = zl[j], r = zr[j];
+        blend_control(sp, amp[j], w0, cen[j][2 * i], cen[j][2 * i + 1], l[0], l[1], r[0], r[1], dj[j], qj[j]);
+      }
+      F d, q;
+      if constexpr (CPT == 2) {
+        d = f32x2{dj[0], dj[1]};
+        q = f32x2{qj[0], qj[1]};
+      } else {
+        d = dj[0];
+        q = qj[0];
+      }
+      dynamic_advance<F>(st, d, q, veh, w.dt);
+      nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
+      dynamic_settle(st, s_wp, nearest, d, q, w);
+    }
+  });
+}
+
+// rollout_dynamic_kernel without a control matrix: the same workgroup shape, tail rule (lanes past N repeat candidate
+// N - 1 unreported), costs, partial keys and feasible counts.
+template <int CPT>
+__global__ void __launch_bounds__(kDynBlock)
+    rollout_dynamic_sampled_kernel(const RolloutArgs a, const DynamicDraw smp, const Vehicle veh) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  // carve: [0, 32) wave keys | [32, 48) wave feasible counts | [64, ...) the lanes' normals [4][256][CPT] pairs, waypoint
+  // rows, search keys, the draw's tables
+  int64_t* s_key = reinterpret_cast<int64_t*>(smem);
+  int* s_feas = reinterpret_cast<int*>(smem + 32);
+  f32x2* s_z = reinterpret_cast<f32x2*>(smem + 64);
+  float* s_wp = reinterpret_cast<float*>(s_z + kDrawSlots * kDynBlock * CPT);
+  const int n = a.n;
+  float* s_xy = s_wp + n * kCoefT;
+  float* s_seg = s_xy + n * kKeyStride;
+  float* s_centre = s_seg + 2 * n;
+  float* s_ref = s_centre + 2 * n;
+  const int p = static_cast<int>(blockIdx.y);
+  const int tid = static_cast<int>(threadIdx.x);
+  const int c0 = (static_cast<int>(blockIdx.x) * kDynBlock + tid) * CPT;
+  const Weights w = a.w;
+  const float* __restrict__ coef = a.coef + static_cast<size_t>(p) * n * kCoefT;
+  const float* __restrict__ x0 = a.x0 + static_cast<size_t>(p) * kDynamicStateFloats;
+  stage_dynamic_tables(coef, n, tid, kDynBlock, veh.wheelbase, s_wp, s_xy);
+  stage_draw_tables(smp, p, n, tid, kDynBlock, s_seg, s_centre, s_ref);
+  __syncthreads();
+
+  using F = typename std::conditional<CPT == 2, f32x2, float>::type;
+  uint32_t gidx[CPT];
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) gidx[j] = static_cast<uint32_t>(a.index_offset + min(c0 + j, a.N - 1));
+  StateD_<F> st = start_dynamic<F>(x0, coef);
+  roll_sampled<CPT, false, F>(st, draw_spec(smp, w), veh, w, p, n, gidx, smp.u_ref != nullptr, s_wp, s_xy, s_seg, s_centre,
+                              s_ref, s_z, kDynBlock, tid, true);
+  const F cost_v = finish_temporal<F>(st.t, n, w);
+  float cost[CPT];
+  bool feas[CPT];
+  if constexpr (CPT == 2) {
+    cost[0] = cost_v[0];
+    cost[1] = cost_v[1];
+    feas[0] = st.t.V[0] == 0.0f;
+    feas[1] = st.t.V[1] == 0.0f;
+  } else {
+    cost[0] = cost_v;
+    feas[0] = st.t.V == 0.0f;
+  }
+  int64_t key = kKeyMax;
+  int nfeas = 0;
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) {
+    if (c0 + j < a.N) {
+      if (a.costs != nullptr) a.costs[static_cast<size_t>(p) * a.N + c0 + j] = cost[j];
+      const int64_t kj = pack_key(cost[j], static_cast<uint32_t>(a.index_offset + c0 + j));
+      key = (kj < key) ? kj : key;
+      nfeas += feas[j] ? 1 : 0;
+    }
+  }
+  key = wave_min_key(key);
+  nfeas = wave_sum_int(nfeas);
+  constexpr int kWaves = kDynBlock / kWave;
+  const int lane = tid & (kWave - 1);
+  const int wave = tid / kWave;
+  if (lane == 0) {
+    s_key[wave] = key;
+    s_feas[wave] = nfeas;
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int q = 1; q < kWaves; ++q) {
+      key = (s_key[q] < key) ? s_key[q] : key;
+      nfeas += s_feas[q];
+    }
+    const size_t slot = static_cast<size_t>(p) * gridDim.x + blockIdx.x;
+    a.partial_keys[slot] = key;
+    a.partial_feas[slot] = nfeas;
+  }
+}
+
+// The winner's controls re-drawn from its global index (FinalizeArgs::regenerate) into the record image's u block: every
+// lane draws the candidate's normals (the same for all), lane `first` + m `stride` blends step first + m stride -
+// sample_kernel's arithmetic on the same operands, the bracketing knots picked by a select chain.
+__device__ __forceinline__ void regenerate_dynamic_controls(const FinalizeArgs& a, int p, uint32_t gidx, int first,
+                                                            int stride, float* su) {
+  const int n = a.n;
+  float z[kKnots][2];
+  draw_normals(a.spec, gidx, static_cast<uint32_t>(p), z);
+  const bool use_ref = gidx == 1u && a.u_ref != nullptr;
+  const float amp = use_ref ? 0.0f : candidate_amplitude(gidx);
+  // (not __restrict__: the centre may be the u block of the very record this launch rewrites - read before the barrier
+  // that precedes the record's stores)
+  const float* centre = use_ref ? a.u_ref + static_cast<size_t>(p) * n * 2 : a.centre + static_cast<size_t>(p) * a.centre_stride;
+  for (int i = first; i < n; i += stride) {
+    const int k0 = static_cast<int>(a.spec.segments[2 * i]);
+    float z0d = z[0][0], z0p = z[0][1], z1d = z[1][0], z1p = z[1][1];
+#pragma unroll
+    for (int knot = 1; knot < kKnots - 1; ++knot) {
+      const bool hit = (k0 == knot);
+      z0d = hit ? z[knot][0] : z0d;
+      z0p = hit ? z[knot][1] : z0p;
+      z1d = hit ? z[knot + 1][0] : z1d;
+      z1p = hit ? z[knot + 1][1] : z1p;
+    }
+    blend_control(a.spec, amp, a.spec.segments[2 * i + 1], centre[2 * i], centre[2 * i + 1], z0d, z0p, z1d, z1p, su[2 * i],
+                  su[2 * i + 1]);
+  }
+}
+
 template <int LAYOUT>
 __global__ void __launch_bounds__(kWave) finalize_dynamic_kernel(const FinalizeArgs a, const Vehicle veh) {
   extern __shared__ __attribute__((aligned(16))) float s_rec[];   // record image, then the waypoint rows and keys
@@ -212,7 +446,8 @@ __global__ void __launch_bounds__(kWave) finalize_dynamic_kernel(const FinalizeA
   const int rec_floats = 4 + 2 * n + 3 * (n + 1);
   float* __restrict__ rec = a.records + static_cast<size_t>(p) * rec_floats;
   const int64_t local = static_cast<int64_t>(static_cast<uint32_t>(key & 0xffffffffLL)) - a.index_offset;
-  if (!(local >= 0 && local < a.N)) {   // the winner lives on another rank (or nothing was found): a blank record
+  // a winner on another rank (or nothing found): a blank record - unless it is re-drawn from its index, which any rank can
+  if (!a.regenerate && !(local >= 0 && local < a.N)) {
     for (int e = lane; e < rec_floats; e += kWave) rec[e] = (e == 2) ? static_cast<float>(nfeas) : 0.0f;
     return;
   }
@@ -225,7 +460,11 @@ __global__ void __launch_bounds__(kWave) finalize_dynamic_kernel(const FinalizeA
   float* s_wp = s_rec + ((rec_floats + 3) & ~3);
   float* s_abc = s_wp + n * kCoefT;
   stage_dynamic_tables(coef, n, lane, kWave, veh.wheelbase, s_wp, s_abc);
-  for (int i = lane; i < n; i += kWave) load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, c, su[2 * i], su[2 * i + 1]);
+  if (a.regenerate) {
+    regenerate_dynamic_controls(a, p, static_cast<uint32_t>(key & 0xffffffffLL), lane, kWave, su);
+  } else {
+    for (int i = lane; i < n; i += kWave) load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, c, su[2 * i], su[2 * i + 1]);
+  }
   StateD st = start_dynamic<float>(x0, coef);
   if (lane == 0) {
     sx[0] = st.t.X + coef[0];   // (poses leave in the caller's frame: start_temporal())
@@ -365,6 +604,79 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   }
 }
 
+// rollout_dynamic_ensemble_kernel without a control matrix: wave 0 draws the workgroup's 64 CPT candidates for the K waves
+// (roll_sampled's SHARED form)
+template <int CPT>
+__global__ void __launch_bounds__(kWave * kMaxVehicles)
+    rollout_dynamic_sampled_ensemble_kernel(const RolloutArgs a, const DynamicDraw smp, const VehicleEnsemble e) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  // carve: [K][64 CPT] per-vehicle costs | [K][64 CPT] per-vehicle violations | the candidates' normals [4][64][CPT] pairs |
+  // waypoint rows | search keys | draw tables
+  constexpr int kPerGroup = kWave * CPT;
+  const int K = e.K;
+  float* s_c = reinterpret_cast<float*>(smem);
+  float* s_v = s_c + K * kPerGroup;
+  f32x2* s_z = reinterpret_cast<f32x2*>(s_v + K * kPerGroup);
+  float* s_wp = reinterpret_cast<float*>(s_z + kDrawSlots * kWave * CPT);
+  const int n = a.n;
+  float* s_xy = s_wp + n * kCoefT;
+  float* s_seg = s_xy + n * kKeyStride;
+  float* s_centre = s_seg + 2 * n;
+  float* s_ref = s_centre + 2 * n;
+  const int p = static_cast<int>(blockIdx.y);
+  const int tid = static_cast<int>(threadIdx.x);
+  const int lane = tid & (kWave - 1);
+  const int k = __builtin_amdgcn_readfirstlane(tid / kWave);   // this wave's vehicle
+  const int c0 = (static_cast<int>(blockIdx.x) * kWave + lane) * CPT;
+  const Weights w = a.w;
+  const float* __restrict__ coef = a.coef + static_cast<size_t>(p) * n * kCoefT;
+  const float* __restrict__ x0 = a.x0 + static_cast<size_t>(p) * kDynamicStateFloats;
+  stage_dynamic_tables(coef, n, tid, kWave * K, e.v[0].wheelbase, s_wp, s_xy);
+  stage_draw_tables(smp, p, n, tid, kWave * K, s_seg, s_centre, s_ref);
+  __syncthreads();
+
+  const Vehicle veh = e.v[k];
+  using F = typename std::conditional<CPT == 2, f32x2, float>::type;
+  uint32_t gidx[CPT];
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) gidx[j] = static_cast<uint32_t>(a.index_offset + min(c0 + j, a.N - 1));
+  StateD_<F> st = start_dynamic<F>(x0, coef);
+  roll_sampled<CPT, true, F>(st, draw_spec(smp, w), veh, w, p, n, gidx, smp.u_ref != nullptr, s_wp, s_xy, s_seg, s_centre,
+                             s_ref, s_z, kWave, lane, k == 0);
+  const F cost_v = finish_temporal<F>(st.t, n, w);
+  if constexpr (CPT == 2) {
+    s_c[k * kPerGroup + 2 * lane] = cost_v[0];
+    s_c[k * kPerGroup + 2 * lane + 1] = cost_v[1];
+    s_v[k * kPerGroup + 2 * lane] = st.t.V[0];
+    s_v[k * kPerGroup + 2 * lane + 1] = st.t.V[1];
+  } else {
+    s_c[k * kPerGroup + lane] = cost_v;
+    s_v[k * kPerGroup + lane] = st.t.V;
+  }
+  __syncthreads();
+  if (k != 0) return;   // (wave-uniform: no barrier follows)
+  int64_t key = kKeyMax;
+  int nfeas = 0;
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) {
+    float J, V;
+    ensemble_combine(s_c + CPT * lane + j, s_v + CPT * lane + j, kPerGroup, e, J, V);
+    if (c0 + j < a.N) {
+      if (a.costs != nullptr) a.costs[static_cast<size_t>(p) * a.N + c0 + j] = J;
+      const int64_t kj = pack_key(J, static_cast<uint32_t>(a.index_offset + c0 + j));
+      key = (kj < key) ? kj : key;
+      nfeas += (V == 0.0f) ? 1 : 0;
+    }
+  }
+  key = wave_min_key(key);
+  nfeas = wave_sum_int(nfeas);
+  if (lane == 0) {
+    const size_t slot = static_cast<size_t>(p) * gridDim.x + blockIdx.x;
+    a.partial_keys[slot] = key;
+    a.partial_feas[slot] = nfeas;
+  }
+}
+
 template <int LAYOUT>
 __global__ void __launch_bounds__(kWave * kMaxVehicles)
     finalize_dynamic_ensemble_kernel(const FinalizeArgs a, const VehicleEnsemble e) {
@@ -394,7 +706,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   const int rec_floats = 4 + 2 * n + 3 * (n + 1);
   float* __restrict__ rec = a.records + static_cast<size_t>(p) * rec_floats;
   const int64_t local = static_cast<int64_t>(static_cast<uint32_t>(key & 0xffffffffLL)) - a.index_offset;
-  if (!(local >= 0 && local < a.N)) {   // the winner lives on another rank (or nothing was found): a blank record
+  // a winner on another rank (or nothing found): a blank record - unless it is re-drawn from its index, which any rank can
+  if (!a.regenerate && !(local >= 0 && local < a.N)) {
     for (int q = tid; q < rec_floats; q += threads) rec[q] = (q == 2) ? static_cast<float>(nfeas) : 0.0f;
     return;
   }
@@ -408,7 +721,11 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   float* s_wp = s_ck + 2 * kMaxVehicles;
   float* s_abc = s_wp + n * kCoefT;
   stage_dynamic_tables(coef, n, tid, threads, e.v[0].wheelbase, s_wp, s_abc);
-  for (int i = tid; i < n; i += threads) load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, c, su[2 * i], su[2 * i + 1]);
+  if (a.regenerate) {
+    regenerate_dynamic_controls(a, p, static_cast<uint32_t>(key & 0xffffffffLL), tid, threads, su);
+  } else {
+    for (int i = tid; i < n; i += threads) load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, c, su[2 * i], su[2 * i + 1]);
+  }
   StateD st = start_dynamic<float>(x0, coef);
   const bool writer = (k == 0 && lane == 0);   // vehicle 0's trajectory is the record's
   if (writer) {
@@ -518,9 +835,55 @@ hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const Veh
   return hipGetLastError();
 }
 
+hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
+                                          hipStream_t s) {
+  (void)hipGetLastError();
+  if (args.n < 1 || args.n > kDynamicMaxSteps || args.N < 1 || args.P < 1) return hipErrorInvalidValue;
+  if (vehicles.K < 1 || vehicles.K > kMaxVehicles) return hipErrorInvalidValue;
+  if (sample.P != args.P || sample.N != args.N || sample.n != args.n || sample.index_offset != args.index_offset)
+    return hipErrorInvalidValue;
+  if (sample.centre == nullptr || sample.spec.segments == nullptr || sample.centre_stride < 2 * args.n) return hipErrorInvalidValue;
+  if (sample.u_extra != nullptr || sample.prev_keys != nullptr) return hipErrorInvalidValue;   // (mode D has no candidate 2)
+  const SampleSpec& sp = sample.spec;
+  const float box_s[4] = {sp.ulo0, sp.ulo1, sp.uhi0, sp.uhi1};
+  const float box_w[4] = {args.w.ulo0, args.w.ulo1, args.w.uhi0, args.w.uhi1};
+  if (std::memcmp(box_s, box_w, sizeof box_s) != 0) return hipErrorInvalidValue;   // the kernels clip to the Weights' box
+  DynamicDraw d{};
+  d.centre = sample.centre;
+  d.u_ref = sample.u_ref;
+  d.segments = sp.segments;
+  d.seed_ptr = sp.seed_ptr;
+  d.centre_stride = sample.centre_stride;
+  d.seed_lo = sp.seed_lo;
+  d.seed_hi = sp.seed_hi;
+  d.round = sp.round;
+  d.sigma_d = sp.sigma_v;
+  d.sigma_p = sp.sigma_k;
+  const int K = vehicles.K;
+  const int cpt = dynamic_candidates_per_lane(args.P, args.N, K);
+  const dim3 grid(dynamic_blocks_per_problem(args.P, args.N, K), args.P);
+  const size_t tables = static_cast<size_t>(args.n) * (kCoefT + kKeyStride + kDrawFloatsPerStep) * sizeof(float);
+  if (K == 1) {
+    const Vehicle& vehicle = vehicles.v[0];
+    const dim3 block(kDynBlock);
+    const size_t lds = 64 + static_cast<size_t>(kDrawSlots) * kDynBlock * cpt * sizeof(f32x2) + tables;   // <= 60 KB
+    if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<2>), grid, block, lds, s, args, d, vehicle);
+    else hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<1>), grid, block, lds, s, args, d, vehicle);
+    return hipGetLastError();
+  }
+  const dim3 block(kWave * K);
+  const size_t lds = 2 * static_cast<size_t>(K) * kWave * cpt * sizeof(float) +
+                     static_cast<size_t>(kDrawSlots) * kWave * cpt * sizeof(f32x2) + tables;
+  if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<2>), grid, block, lds, s, args, d, vehicles);
+  else hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<1>), grid, block, lds, s, args, d, vehicles);
+  return hipGetLastError();
+}
+
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles, hipStream_t s) {
   (void)hipGetLastError();
-  if (args.regenerate || args.controls_only || args.n < 1 || args.n > kDynamicMaxSteps) return hipErrorInvalidValue;
+  if (args.controls_only || args.n < 1 || args.n > kDynamicMaxSteps) return hipErrorInvalidValue;
+  if (args.regenerate && (args.centre == nullptr || args.spec.segments == nullptr || args.u_extra != nullptr))
+    return hipErrorInvalidValue;
   if (vehicles.K < 1 || vehicles.K > kMaxVehicles || (layout != 0 && layout != 1)) return hipErrorInvalidValue;
   const size_t rec_floats = static_cast<size_t>(4 + 2 * args.n + 3 * (args.n + 1));
   const size_t tables = static_cast<size_t>(args.n) * (kCoefT + kKeyStride);

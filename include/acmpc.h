@@ -62,10 +62,14 @@ extern "C" {
                                  Tables as mode T's (acmpc_set_paths); max_steps <= 512; lq_candidate must be 0.
                                  Takes acmpc_set_paths / acmpc_set_coefficients, acmpc_solve, acmpc_solve_device,
                                  acmpc_rollout_device + acmpc_finalize_device (index_offset, acmpc_reduce_across_ranks),
-                                 acmpc_softmin_device, acmpc_sample_device and acmpc_optimize (sample -> rollout ->
-                                 finalize per round, three launches).  ACMPC_ESTATE from acmpc_control_tick and from the
-                                 calls that re-draw a winner from its index (acmpc_finalize_sampled_device,
-                                 acmpc_solve_sampled_device, acmpc_solve_stream_device).  DESIGN.md section 2 "Mode D". */
+                                 acmpc_softmin_device, acmpc_sample_device, the calls that re-draw a winner from its
+                                 index (acmpc_finalize_sampled_device, acmpc_solve_sampled_device: sigma_v, sigma_kappa
+                                 = sigma_delta, sigma_pedal; candidate 2 does not exist), acmpc_rollout_sampled_device
+                                 (the rollout that draws its own candidates: no control matrix) and acmpc_optimize
+                                 (that rollout + the re-drawing finalize per round, two launches;
+                                 ACMPC_DYNAMIC_MATRIX_ROUNDS keeps sample -> rollout -> finalize through the matrix,
+                                 the same bits).  ACMPC_ESTATE from acmpc_control_tick and acmpc_solve_stream_device.
+                                 DESIGN.md section 2 "Mode D". */
 
 /* Memory layout of the control-sample matrix U. */
 #define ACMPC_LAYOUT_CANDIDATE_MAJOR 0 /* U[P][N][n][2]  - what NumPy host code naturally holds          */
@@ -332,6 +336,19 @@ int acmpc_solve_sampled_device(acmpc_ctx* ctx, const float* d_x0, const float* d
                                int32_t centre_stride, const float* d_u_ref, int32_t P, int32_t N, int32_t n, int32_t layout,
                                double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round, float* d_costs,
                                int64_t* d_keys, float* d_records, void* stream);
+
+/* Mode D only: acmpc_sample_device into a matrix + acmpc_rollout_device of it WITHOUT the matrix - every lane draws its
+ * candidate (global index index_offset + c: the same candidate as acmpc_sample_device's, bit for bit) inside the rollout
+ * kernel and blends each step's control as it goes (csrc/acmpc_dynamic.hip rollout_dynamic_sampled_kernel).  d_x0 [P][6];
+ * d_centre / centre_stride / d_u_ref / sigma_v, sigma_kappa (= sigma_delta, sigma_pedal) / seed / round as
+ * acmpc_sample_device takes them; d_costs [P][N] or NULL and d_keys [P] or NULL as acmpc_rollout_device leaves them - the
+ * same bits.  Follow it with acmpc_finalize_sampled_device (after acmpc_reduce_across_ranks when the candidates are spread
+ * over ranks).  ACMPC_ESTATE on a mode S or mode T handle (their rounds draw inside acmpc_optimize), and without a vehicle or
+ * paths; ACMPC_EINVAL for a null pointer, ACMPC_ECAPACITY for a shape beyond the handle's - all before any device work. */
+int acmpc_rollout_sampled_device(acmpc_ctx* ctx, const float* d_x0, const float* d_centre, int32_t centre_stride,
+                                 const float* d_u_ref, int32_t P, int32_t N, int32_t n, int64_t index_offset,
+                                 double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round, float* d_costs,
+                                 int64_t* d_keys, void* stream);
 
 /* A STREAM of batches on one rank: acmpc_solve_device (d_centre NULL: the winners are read from d_U) or
  * acmpc_solve_sampled_device (d_centre given: re-drawn) with the argmin and the winners' records of one call DEFERRED -

@@ -14,7 +14,14 @@ vehicle at grips 1.0, 0.9, 1.1, 0.8, ...) combined by `--reduce`; rates then cou
 prices the `dynamic_ensemble` entry's mix over P N K candidates.  A comma list (`--vehicles 1,4`) measures each K in the
 same process and adds the ratios of each K to the first.
 
-usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max]"""
+With `--sampled` the rollout that draws its own candidates (acmpc_rollout_sampled_device) is measured against the pair it
+replaces - acmpc_sample_device into a matrix + acmpc_rollout_device of it - at the same two sizes, in the same process:
+pair / sample / rollout / fused times, fused over pair and over the rollout alone, the fused kernel's fraction of the
+vector-issue roof (entry `dynamic_sampled` / `dynamic_sampled_ensemble`); and one acmpc_optimize of 16 384 x 49, 2 rounds
+(p50 / p99, host-synchronised) in its two-launch form and with ACMPC_DYNAMIC_MATRIX_ROUNDS=1.  `--optimize` measures that
+acmpc_optimize alone, through nothing newer than Engine.optimize - the form to run from a checkout of an earlier commit.
+
+usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--sampled | --optimize]"""
 import argparse
 import json
 import os
@@ -47,7 +54,15 @@ def main():
     ap.add_argument("--quick", action="store_true", help="fewer repetitions (a profiler run)")
     ap.add_argument("--vehicles", default=None, help="K, or a comma list of K: an ensemble of K vehicles")
     ap.add_argument("--reduce", default="mean", choices=("mean", "max"))
+    ap.add_argument("--sampled", action="store_true", help="the fused sample + rollout against the matrix pair, and acmpc_optimize")
+    ap.add_argument("--optimize", action="store_true", help="acmpc_optimize 16 384 x 49, 2 rounds, alone")
     args = ap.parse_args()
+    if args.sampled or args.optimize:
+        ks = [int(k) for k in (args.vehicles or "1").split(",")]
+        run = measure_sampled if args.sampled else measure_optimize
+        print(json.dumps({"tool": "tools/bench_dynamic.py " + ("--sampled" if args.sampled else "--optimize"),
+                          "by_vehicles": {str(k): run(args, k) for k in ks}}))
+        return
     if args.vehicles is None:
         print(json.dumps(measure(args, 1)))
         return
@@ -71,6 +86,122 @@ def main():
 
 
 GRIPS = (1.0, 0.9, 1.1, 0.8, 1.2, 0.7, 1.05, 0.95)
+
+
+def _engine(dp, P, N, n, K, reduce, stream):
+    from acmpc_amd import DynamicBicycleParams, Engine
+    eng = Engine(**dict(dp["kw"], max_problems=P, max_candidates=N, max_steps=n, nn_window=(2, 5)))
+    if K == 1:
+        eng.set_dynamics(DynamicBicycleParams.reference())
+    else:
+        eng.set_dynamics_ensemble([DynamicBicycleParams.reference().with_grip(g) for g in GRIPS[:K]], reduce=reduce)
+    eng.set_paths(np.repeat(dp["table"][None], P, axis=0))
+    eng.sync_tables(stream)
+    return eng
+
+
+def _centre(dp, P, n):
+    import acmpc_oracle as orc
+    d_ref = np.arctan(float(dp["kw"]["wheelbase"]) * dp["table"][orc.ROW_KAPPA])[:n]
+    return np.repeat(np.stack([d_ref, np.full(n, 0.2)], axis=1)[None], P, axis=0).astype(np.float32)
+
+
+SIGMA = (0.05, 0.3)
+
+
+def measure_optimize(args, K, out=None):
+    """p50 / p99 of one acmpc_optimize, 16 384 candidates x 49 steps, 2 rounds (host-synchronised: the call returns the
+    record); with the handle's ACMPC_DYNAMIC_MATRIX_ROUNDS too where the library knows the option."""
+    import torch
+    import acmpc_oracle as orc
+    import dynamic_spec as ds
+    from acmpc_amd import EngineError
+
+    H, N, rounds = 50, 16384, 2
+    n = H - 1
+    dp = ds.make_dynamic_problem(orc, "monza", H, 8, 0)
+    out = {} if out is None else out
+    eng = _engine(dp, 1, N, n, K, args.reduce, torch.cuda.current_stream().cuda_stream)
+    x0, centre = dp["x0"][None], _centre(dp, 1, n)
+    forms = [("optimize_16384x2", None)]
+    try:
+        eng.set_option("ACMPC_DYNAMIC_MATRIX_ROUNDS", None)
+        forms.append(("optimize_16384x2_matrix_rounds", "1"))
+    except EngineError:
+        pass   # (an earlier library: three launches per round is all it has)
+    for name, option in forms:
+        if option is not None:
+            eng.set_option("ACMPC_DYNAMIC_MATRIX_ROUNDS", option)
+        lat = []
+        for i in range(20 + (20 if args.quick else 400)):
+            t0 = time.perf_counter()
+            eng.optimize(x0, centre, None, N, rounds, SIGMA, shrink=0.5, seed=i)
+            if i >= 20:
+                lat.append(time.perf_counter() - t0)
+        out[name] = dict(p50_ms=float(np.percentile(lat, 50)) * 1e3, p99_ms=float(np.percentile(lat, 99)) * 1e3,
+                         calls=len(lat))
+    eng.close()
+    return out
+
+
+def measure_sampled(args, K):
+    import torch
+    import acmpc_oracle as orc
+    import bench
+    import dynamic_spec as ds
+
+    H = 50
+    n = H - 1
+    dp = ds.make_dynamic_problem(orc, "monza", H, 8, 0)
+    dev = torch.device("cuda", 0)
+    s = torch.cuda.current_stream().cuda_stream
+    reps = 3 if args.quick else args.reps
+    out = {"tool": "tools/bench_dynamic.py --sampled", "horizon": H, "search": "window (2, 5)", "vehicles": K}
+    entry = "dynamic_sampled" if K == 1 else "dynamic_sampled_ensemble"
+    for name, P, N in (("4096x4096", 4096, 4096), ("1M", 256, 4096)):
+        eng = _engine(dp, P, N, n, K, args.reduce, s)
+        U = torch.empty(P, n, 2, N, device=dev)
+        x0 = torch.tensor(np.repeat(dp["x0"][None], P, axis=0), device=dev)
+        centre = torch.tensor(_centre(dp, P, n), device=dev)
+
+        def sample():
+            eng.sample_device(centre.data_ptr(), 2 * n, 0, P, N, n, 1, 0, SIGMA, 7, 1, U.data_ptr(), s)
+
+        def rollout():
+            eng.rollout_device(x0.data_ptr(), U.data_ptr(), P, N, n, 1, 0, 0, 0, s)
+
+        def pair():
+            sample()
+            rollout()
+
+        def fused():
+            eng.rollout_sampled_device(x0.data_ptr(), centre.data_ptr(), 2 * n, 0, P, N, n, 0, SIGMA, 7, 1, 0, 0, s)
+
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ms = {}
+        for _ in range(2):   # (the whole set twice, the second kept: every form measured warm, interleaved with the others)
+            for label, call in (("pair", pair), ("sample", sample), ("rollout", rollout), ("fused", fused)):
+                call()
+                torch.cuda.synchronize()
+                times = []
+                for _ in range(reps):
+                    e0.record()
+                    call()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times.append(e0.elapsed_time(e1))
+                ms[label] = float(np.median(times))
+        roof = issue_roof(bench, P * N * K, n, ms["fused"] * 1e-3, entry)
+        out[name] = dict(P=P, N=N, pair_ms=ms["pair"], sample_ms=ms["sample"], rollout_ms=ms["rollout"], fused_ms=ms["fused"],
+                         fused_over_pair=ms["fused"] / ms["pair"], fused_over_rollout=ms["fused"] / ms["rollout"],
+                         fused_vehicle_candidate_steps_per_s=P * N * K * n / (ms["fused"] * 1e-3),
+                         matrix_bytes=P * N * n * 8, fused_vector_issue_roof_frac=roof["frac"],
+                         valu_per_candidate_step=roof["valu_instructions_per_candidate_step"],
+                         opcode_mix_matches_loaded_sources=roof["opcode_mix_matches_loaded_sources"])
+        eng.close()
+        del U
+        torch.cuda.empty_cache()
+    return measure_optimize(args, K, out)
 
 
 def measure(args, K):

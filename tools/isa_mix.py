@@ -34,8 +34,14 @@ ENTRIES = {
     "dynamic": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2EE", None),
     # mode D with an ensemble of vehicles (one wavefront per vehicle): the same step loop under wave k's vehicle
     "dynamic_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2EE", None),
+    # mode D drawing its own candidates (two per lane): the same step loop with the blend of the step's control in front.
+    # The loop holds the Philox draws as loops of its own, run on at most seven of a rollout's trips: the mix is the trip
+    # without them (OUTER)
+    "dynamic_sampled": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_kernelILi2EE", None),
+    "dynamic_sampled_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_ensemble_kernelILi2EE", None),
 }
 CANDIDATES_PER_LANE = {"fused_round": 1}
+OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble")
 
 
 def source_hash():
@@ -65,7 +71,7 @@ def main():
         for entry, (source, kernel, signature) in ENTRIES.items():
             if source not in cache:
                 cache[source] = assembly(source, scratch)
-            every = loops(cache[source], kernel)
+            every = loops(cache[source], kernel, outer=entry in OUTER)
             if signature is None:
                 found = [max(every, key=lambda lh: sum(lh[1].values()))]
             else:
