@@ -1254,7 +1254,10 @@ def pf_score_particles(states: np.ndarray, centre: np.ndarray, left: np.ndarray,
     placed = np.stack([x, y], axis=2) + states[:, None, :2]              # [P,K,2]
 
     def limits(closest, count, track):                                   # (:391-400)
-        idx = np.linspace(closest, closest + count, count, dtype=np.uint16)
+        # The reference takes np.mod(uint16 indices, len(track)).  NumPy 1 promotes that to a wide integer; NumPy 2 keeps
+        # uint16 and refuses a polyline of 65 536 points or more (OverflowError).  The statement here is NumPy 1's, which
+        # is also the kernels': the uint16 wrap first (spelt out, not left to a float -> uint16 cast), then mod m in int64.
+        idx = np.linspace(closest, closest + count, count, dtype=np.int64) & 0xFFFF
         return track[np.mod(idx, len(track)).T]
 
     expected = np.concatenate([limits(i_left, len(obs_left), left), limits(i_right, len(obs_right), right)], axis=1)
@@ -1361,3 +1364,28 @@ def pf_resample_counter_based(states, scores, score, valid, n_desired, minimum_p
     fresh = (kept_states[picked].astype(np.float64) + z * np.asarray(noise_sigma, dtype=np.float64)).astype(np.float32)
     kept_scores = np.asarray(scores, dtype=np.float32)[keep]
     return (np.concatenate([kept_states, fresh]), np.concatenate([kept_scores, kept_scores[picked]]), picked)
+
+
+def pf_control_normals(n, seed, counter):
+    """The two standard normals (float32, bit-specified) of the control noise of particles 0 ... n - 1 at filter step
+    `counter`: Philox4x32-10 at counter (p, counter, "CTRL", 0), key (seed & 0xffffffff, seed >> 32), words 0 and 1
+    through `uniform_open` into one `box_muller_spec` pair (csrc/acmpc_pf.hip pf_step_kernel)."""
+    p = np.arange(n, dtype=np.uint32)
+    ctr = np.stack([p, np.full_like(p, counter), np.full_like(p, PF_TAG_CONTROL), np.zeros_like(p)], axis=1)
+    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32)
+    r = philox4x32_10(ctr, np.broadcast_to(key, (n, 2)))
+    u = uniform_open(r)
+    return box_muller_spec(u[:, 0], u[:, 1])
+
+
+def pf_step_counter_based(states, tyre_angle, velocity, dt, sigma_yaw, sigma_v, wheel_base, seed, counter):
+    """Restates csrc/acmpc_pf.hip pf_step_kernel (Localiser.step, localiser.py:41-77, with BUILD-DEFINED counter-based
+    draws in place of NumPy's global stream): particle p steers delta = tyre_angle + sigma_yaw z0 at speed
+    |velocity + sigma_v z1| with (z0, z1) = pf_control_normals, then one kinematic step of `kinematic_x_dot`.
+    The draws are exact; the step is float64 here on the float32 states and fast float32 transcendentals on the device
+    (the tolerance of the advance: rtol 2e-6, atol 2e-5).  Returns the new states [n, 3] float64."""
+    states = np.asarray(states, dtype=np.float32).astype(np.float64)
+    z0, z1 = pf_control_normals(states.shape[0], seed, counter)
+    delta = float(tyre_angle) + float(sigma_yaw) * z0.astype(np.float64)
+    speed = np.abs(float(velocity) + float(sigma_v) * z1.astype(np.float64))
+    return states + kinematic_x_dot(delta, states, speed, float(wheel_base)) * float(dt)
