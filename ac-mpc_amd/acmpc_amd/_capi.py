@@ -160,6 +160,9 @@ SIGNATURES = {
                                         C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "acmpc_softmin_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acmpc_softmin_sampled_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                               C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_uint64,
+                                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acmpc_sync_tables": (C.c_int, [_CTX, C.c_void_p]),
     "acmpc_sample_device": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_uint64, C.c_uint32,
@@ -753,6 +756,17 @@ class Engine:
                        d_weight_sum: int = 0, stream: int = 0):
         self._check(self._lib.acmpc_softmin_device(self._ctx, d_costs, d_keys, d_U, P, N, n, layout, d_mean,
                                                    d_weight_sum or None, stream or None))
+
+    def softmin_sampled_device(self, d_costs: int, d_keys: int, d_centre: int, centre_stride: int, d_u_ref: int, P: int,
+                               N: int, n: int, index_offset: int, sigma, seed: int, round_: int, d_mean: int,
+                               d_weight_sum: int = 0, stream: int = 0):
+        """sample_device (step-major) + softmin_device without the control matrix: the candidates (global indices
+        index_offset .. index_offset + N) are re-drawn inside the softmin kernel (acmpc_softmin_sampled_device) - the same
+        mean [P][n][2] and weight sums [P] bit for bit.  Any mode."""
+        self._check(self._lib.acmpc_softmin_sampled_device(self._ctx, d_costs, d_keys, d_centre, centre_stride,
+                                                           d_u_ref or None, P, N, n, index_offset, float(sigma[0]),
+                                                           float(sigma[1]), seed, round_, d_mean, d_weight_sum or None,
+                                                           stream or None))
 
 
 def waypoint_table(coords: np.ndarray, eps: float = 1e-12) -> np.ndarray:

@@ -4,7 +4,9 @@ kept (`acmpc_optimize`: sample -> rollout -> finalize per round).  The seam is C
 obj` with `obj.x` laid out `[x_0 .. x_n ; u_0 .. u_{n-1}]` (x = (X, Y, yaw), u = (delta, pedal)) and `obj.info.status`.
 
 Optional config keys, as sampling_solver.py reads them: `n_candidates`, `sampling_rounds`, `sampling_sigma` (delta rad,
-pedal), `sampling_seed`, `w_bound`, `nn_window`, `rollout_dt`; the weights `step_cost` (e_y, e_psi, -), `r_term` (speed
+pedal), `sampling_seed`, `sampling_update` ("argmin", the default: a round recentres on its winner; or "softmin": on the
+softmin-weighted mean of its candidates, MPPI's update, with the winner kept as candidate 1), `softmin_lambda` (default
+1.0), `w_bound`, `nn_window`, `rollout_dt`; the weights `step_cost` (e_y, e_psi, -), `r_term` (speed
 error, steering against delta_ref), `final_cost`; the input box `u_min` / `u_max` (default delta +-0.3 rad, pedal +-1).
 The warm start is the previous plan shifted by one step.
 
@@ -29,6 +31,7 @@ DEFAULT_ROUNDS = 2
 DEFAULT_SIGMA = (0.05, 0.3)
 DEFAULT_U_MIN = (-0.3, -1.0)
 DEFAULT_U_MAX = (0.3, 1.0)
+SAMPLING_UPDATES = ("argmin", "softmin")
 
 
 def ensemble_vehicles(config: Dict, params: DynamicBicycleParams) -> Optional[list]:
@@ -66,6 +69,12 @@ class DynamicSamplingSolver:
         self._dt = float(config.get("rollout_dt", 0.05))
         self._params = params if params is not None else DynamicBicycleParams.reference()
         vehicles = ensemble_vehicles(config, self._params)   # (a config error raises before any handle exists)
+        self._centre_update = config.get("sampling_update", "argmin")   # or "softmin" (MPPI-style weighted mean)
+        if self._centre_update not in SAMPLING_UPDATES:
+            raise ValueError("sampling_update is 'argmin' or 'softmin', not %r" % (self._centre_update,))
+        self._lambda = float(config.get("softmin_lambda", 1.0))
+        if not self._lambda > 0.0:
+            raise ValueError("softmin_lambda must be positive, not %r" % (self._lambda,))
         nn_window = config.get("nn_window")
         self._engine = _capi.Engine(
             mode=_capi.MODE_DYNAMIC, max_problems=1, max_candidates=self._N, max_steps=self._n,
@@ -73,7 +82,8 @@ class DynamicSamplingSolver:
             final_cost=config.get("final_cost", (1.0, 1.0, 0.0)), u_min=config.get("u_min", DEFAULT_U_MIN),
             u_max=config.get("u_max", DEFAULT_U_MAX), margin=float(config.get("margin", 0.0)),
             wheelbase=self._params.lf + self._params.lr, dt=self._dt, w_bound=float(config.get("w_bound", 1.0e6)),
-            device=device, nn_window=None if nn_window is None else tuple(nn_window))
+            device=device, nn_window=None if nn_window is None else tuple(nn_window),
+            centre_update=self._centre_update, softmin_lambda=self._lambda)
         if vehicles is None:
             self._engine.set_dynamics(self._params)
         else:

@@ -74,6 +74,24 @@ def combine_softmin(payloads, n_steps: int):
     return mean.float().reshape(-1, n_steps, 2), den[:, 0].clone()
 
 
+def gather_softmin(mean: torch.Tensor, weight_sum: torch.Tensor, count: int, n_steps: int,
+                   group: Optional[dist.ProcessGroup] = None, host_collectives: bool = False):
+    """One rank's softmin (mean, weight sum) over its `count` candidates -> those over the candidates of all ranks: ONE
+    all-gather of the payloads, combined in rank order (the same bits on every rank).  `host_collectives` stages the payload
+    through the CPU (process groups whose backend cannot move GPU tensors)."""
+    mine = softmin_payload(mean, weight_sum, count)
+    world = dist.get_world_size(group)
+    if host_collectives:
+        staged = mine.cpu()                # synchronises with the stream that produced it
+        parts = [torch.empty_like(staged) for _ in range(world)]
+        dist.all_gather(parts, staged, group=group)
+        parts = [t.to(mine.device) for t in parts]
+    else:
+        parts = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(parts, mine, group=group)
+    return combine_softmin(parts, n_steps)
+
+
 class ShardedRollout:
     """Binds an `Engine` to this rank's slice of the candidates.  All tensors are torch CUDA tensors; the engine
     is handed raw pointers and the current stream, RCCL runs on the same stream through torch.distributed."""
@@ -228,17 +246,7 @@ class ShardedRollout:
                                    self.layout, mean.data_ptr(), wsum.data_ptr(), stream)
         if not self.distributed:
             return mean, wsum
-        mine = softmin_payload(mean, wsum, self.N)
-        world = dist.get_world_size(self.group)
-        if self.host_collectives:
-            staged = mine.cpu()                # synchronises with the stream that produced it
-            parts = [torch.empty_like(staged) for _ in range(world)]
-            dist.all_gather(parts, staged, group=self.group)
-            parts = [t.to(mine.device) for t in parts]
-        else:
-            parts = [torch.empty_like(mine) for _ in range(world)]
-            dist.all_gather(parts, mine, group=self.group)
-        return combine_softmin(parts, self.n)
+        return gather_softmin(mean, wsum, self.N, self.n, self.group, self.host_collectives)
 
     def _reduce_keys(self, stream: int):
         if self.rccl_comm:
@@ -344,18 +352,32 @@ class ShardedOptimizer:
     on (torch's current stream): the engine calls and the collective are ordered by stream order alone.
 
     On a mode D engine (x0 [P,6]) there is no control matrix: a round is `rollout_sampled_device` (the candidates are
-    drawn inside the rollout kernel), the all-reduce, `finalize_sampled_device`."""
+    drawn inside the rollout kernel), the all-reduce, `finalize_sampled_device`.
+
+    `centre_update="softmin"` (acmpc_optimize's centre_update = 1 across ranks): every round but the last also takes the
+    softmin mean of ALL ranks' candidates - each rank its own slice against the global minimum in the reduced keys
+    (`softmin_sampled_device` in mode D: the candidates re-drawn once more, still no matrix; `softmin_device` over U in
+    modes S and T), one all-gather of the payloads, `combine_softmin` in rank order - and the next round samples round
+    that mean with the winner as candidate 1.  A lone rank gathers nothing and its records are `Engine.optimize`'s."""
 
     def __init__(self, engine, n_problems: int, n_local: int, n_steps: int, index_offset: int, device: torch.device,
-                 group: Optional[dist.ProcessGroup] = None, host_collectives: bool = False):
+                 group: Optional[dist.ProcessGroup] = None, host_collectives: bool = False,
+                 centre_update: str = "argmin"):
         from ._capi import LAYOUT_STEP_MAJOR, MODE_DYNAMIC, REC_HEADER, record_floats
 
+        if centre_update not in ("argmin", "softmin"):
+            raise ValueError("centre_update is 'argmin' or 'softmin', not %r" % (centre_update,))
+        self.softmin = centre_update == "softmin"
         self.shard = ShardedRollout(engine, n_problems, n_local, n_steps, LAYOUT_STEP_MAJOR, index_offset, device, group,
-                                    want_costs=False, host_collectives=host_collectives)
+                                    want_costs=self.softmin, host_collectives=host_collectives, want_keys=self.softmin)
         self.shard.distributed = self.shard.distributed or host_collectives   # keys must be produced for the reduce
         self.dynamic = getattr(engine, "mode", None) == MODE_DYNAMIC
         self.U = None if self.dynamic else torch.empty(n_problems, n_steps, 2, n_local, dtype=torch.float32, device=device)
         self._rec_header, self._rec_floats = REC_HEADER, record_floats(n_steps)
+        if self.softmin:
+            self._mean = torch.empty(n_problems, n_steps, 2, dtype=torch.float32, device=device)
+            self._wsum = torch.empty(n_problems, dtype=torch.float64, device=device)
+            self._winner = torch.empty(n_problems, n_steps, 2, dtype=torch.float32, device=device)
 
     def solve(self, x0: torch.Tensor, centre: torch.Tensor, u_ref: Optional[torch.Tensor], rounds: int, sigma,
               shrink: float = 0.5, seed: int = 0, stream: int = 0) -> torch.Tensor:
@@ -363,26 +385,45 @@ class ShardedOptimizer:
         shard, n = self.shard, self.shard.n
         if stream not in (0, torch.cuda.current_stream().cuda_stream) and not shard.host_collectives:
             raise ValueError("ShardedOptimizer.solve: `stream` must be torch's current stream (the collective runs there)")
+        want_keys = shard.distributed or self.softmin
         scale = 1.0
+        mean = None
         for r in range(rounds):
+            ref_ptr = u_ref.data_ptr() if u_ref is not None else 0
             if r == 0:
                 centre_ptr, stride = centre.data_ptr(), 2 * n
+            elif self.softmin:   # the mean of the previous round, its winner as candidate 1
+                self._winner.copy_(shard.records[:, self._rec_header:self._rec_header + 2 * n].reshape(shard.P, n, 2))
+                centre_ptr, stride, ref_ptr = mean.data_ptr(), 2 * n, self._winner.data_ptr()
             else:   # the u block of the previous round's records
                 centre_ptr, stride = shard.records.data_ptr() + 4 * self._rec_header, self._rec_floats
             sig = (sigma[0] * scale, sigma[1] * scale)
-            ref_ptr = u_ref.data_ptr() if u_ref is not None else 0
             if self.dynamic:
                 shard.engine.rollout_sampled_device(x0.data_ptr(), centre_ptr, stride, ref_ptr, shard.P, shard.N, n,
-                                                    shard.offset, sig, seed, r, 0,
-                                                    shard.keys.data_ptr() if shard.distributed else 0, stream)
+                                                    shard.offset, sig, seed, r,
+                                                    shard.costs.data_ptr() if self.softmin else 0,
+                                                    shard.keys.data_ptr() if want_keys else 0, stream)
             else:
                 shard.engine.sample_device(centre_ptr, stride, ref_ptr, shard.P, shard.N, n, shard.layout, shard.offset, sig,
                                            seed, r, self.U.data_ptr(), stream)
                 shard.rollout(x0, self.U, stream)
             if shard.distributed and dist.is_initialized() and dist.get_world_size(shard.group) > 1:
                 shard._all_reduce(shard.keys, dist.ReduceOp.MIN)
-            shard.engine.finalize_sampled_device(shard.keys.data_ptr() if shard.distributed else 0, x0.data_ptr(),
+            shard.engine.finalize_sampled_device(shard.keys.data_ptr() if want_keys else 0, x0.data_ptr(),
                                                  centre_ptr, stride, ref_ptr,
                                                  shard.P, shard.N, n, sig, seed, r, shard.records.data_ptr(), stream)
+            if self.softmin and r + 1 < rounds:
+                if self.dynamic:
+                    shard.engine.softmin_sampled_device(shard.costs.data_ptr(), shard.keys.data_ptr(), centre_ptr, stride,
+                                                        ref_ptr, shard.P, shard.N, n, shard.offset, sig, seed, r,
+                                                        self._mean.data_ptr(), self._wsum.data_ptr(), stream)
+                else:
+                    shard.engine.softmin_device(shard.costs.data_ptr(), shard.keys.data_ptr(), self.U.data_ptr(), shard.P,
+                                                shard.N, n, shard.layout, self._mean.data_ptr(), self._wsum.data_ptr(),
+                                                stream)
+                mean = self._mean
+                if dist.is_available() and dist.is_initialized() and dist.get_world_size(shard.group) > 1:
+                    mean = gather_softmin(self._mean, self._wsum, shard.N, n, shard.group,
+                                          shard.host_collectives)[0].contiguous()
             scale *= shrink
         return shard.records

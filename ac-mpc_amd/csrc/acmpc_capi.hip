@@ -544,6 +544,37 @@ int rollout_sampled_dynamic(acmpc_ctx* c, const float* d_x0, const float* d_cent
   return ACMPC_OK;
 }
 
+// the softmin mean of the candidates sample() would write for these arguments, without the matrix
+// (acmpc_kernels.hip: launch_softmin_sampled) - what sample() into a matrix and launch_softmin of it compute
+int softmin_sampled(acmpc_ctx* c, const float* d_costs, const int64_t* d_keys, const float* d_centre, int centre_stride,
+                    const float* d_uref, int P, int N, int n, int64_t offset, double sigma_v, double sigma_k, uint64_t seed,
+                    uint32_t round, float* d_mean, double* d_weight_sum, hipStream_t s) {
+  const int rc = upload_segments(c, n, s);
+  if (rc != ACMPC_OK) return rc;
+  acmpc::SoftminArgs a{};
+  a.costs = d_costs;
+  a.keys = d_keys;
+  a.partial = c->d_soft_partial;
+  a.mean = d_mean;
+  a.weight_sum = d_weight_sum;
+  a.chunks = acmpc::softmin_chunks(N);
+  a.P = P;
+  a.N = N;
+  a.n = n;
+  a.lambda = static_cast<float>(c->prm.softmin_lambda);
+  acmpc::SampleArgs smp{};
+  smp.centre = d_centre;
+  smp.u_ref = d_uref;
+  smp.centre_stride = centre_stride;
+  smp.P = P;
+  smp.N = N;
+  smp.n = n;
+  smp.index_offset = offset;
+  smp.spec = make_spec(c, sigma_v, sigma_k, seed, round);
+  ACMPC_HIP(c, acmpc::launch_softmin_sampled(a, smp, s));
+  return ACMPC_OK;
+}
+
 // what the in-launch finalize of the fused rounds and of the one-launch solve needs: ticket counters (zero between
 // launches) and the workgroups' traces
 int ensure_tail_buffers(acmpc_ctx* c) {
@@ -1267,12 +1298,18 @@ int solve_dynamic_host(acmpc_ctx* c, const float* x0, const float* U, int P, int
 // from its index - two launches, no control matrix; round r samples round the u block of round r - 1's record, with the
 // spread sigma shrink^r (acmpc_optimize's own schedule).  ACMPC_DYNAMIC_MATRIX_ROUNDS keeps sample -> rollout -> finalize
 // through the matrix (three launches): the same records bit for bit.
+// centre_update = 1 (softmin): the round protocol of modes S and T (enqueue_rounds) - after every round but the last the
+// softmin mean of its candidates goes into d_centre and is the next round's centre (candidate 0), the winner's u block is
+// staged into d_uref as the next round's candidate 1.  The rollout then leaves its costs, the finalize its keys, and the
+// sampled softmin (launch_softmin_sampled) re-draws the candidates a third time: still no matrix.  With the matrix rounds the
+// mean is launch_softmin's over the matrix - the same bits.
 int optimize_dynamic(acmpc_ctx* c, const float* x0, const float* centre, const float* u_ref, int P, int N, int n,
                      int rounds, const double sigma[2], double shrink, uint64_t seed, float* records) {
   hipStream_t s = c->stream;
   const size_t path_bytes = static_cast<size_t>(P) * n * 2 * sizeof(float);
   const int layout = ACMPC_LAYOUT_STEP_MAJOR;
   const int rec_floats = acmpc_record_floats(n);
+  const bool softmin = c->prm.centre_update == 1;
   int rc = upload_tables(c, s);
   if (rc != ACMPC_OK) return rc;
   if (c->sw.dynamic_matrix_rounds) {
@@ -1285,28 +1322,55 @@ int optimize_dynamic(acmpc_ctx* c, const float* x0, const float* centre, const f
   if (u_ref != nullptr) ACMPC_HIP(c, hipMemcpyAsync(c->d_uref, u_ref, path_bytes, hipMemcpyHostToDevice, s));
   double scale = 1.0;
   for (int r = 0; r < rounds; ++r, scale *= shrink) {
-    const float* d_c = (r == 0) ? c->d_centre : c->d_records + ACMPC_REC_HEADER;
-    const int stride = (r == 0) ? 2 * n : rec_floats;
-    const float* d_ref = u_ref != nullptr ? c->d_uref : nullptr;
+    const bool mean_round = softmin && r > 0;
+    const float* d_c = (r == 0 || mean_round) ? c->d_centre : c->d_records + ACMPC_REC_HEADER;
+    const int stride = (r == 0 || mean_round) ? 2 * n : rec_floats;
+    const float* d_ref = (u_ref != nullptr || mean_round) ? c->d_uref : nullptr;
+    if (mean_round)  // candidate 1 reads its controls at a stride of 2n: stage the winner's u block contiguously
+      ACMPC_HIP(c, hipMemcpy2DAsync(c->d_uref, static_cast<size_t>(2 * n) * sizeof(float), c->d_records + ACMPC_REC_HEADER,
+                                    static_cast<size_t>(rec_floats) * sizeof(float),
+                                    static_cast<size_t>(2 * n) * sizeof(float), P, hipMemcpyDeviceToDevice, s));
+    const bool want_mean = softmin && r + 1 < rounds;
     if (!c->sw.dynamic_matrix_rounds) {
       rc = rollout_sampled_dynamic(c, c->d_x0, d_c, stride, d_ref, P, N, n, 0, sigma[0] * scale, sigma[1] * scale, seed,
-                                   static_cast<uint32_t>(r), nullptr, s);
+                                   static_cast<uint32_t>(r), softmin ? c->d_costs : nullptr, s);
       if (rc != ACMPC_OK) return rc;
       // (the centre may be the u block of c->d_records itself: the finalize reads it before it rewrites the record)
       const Regenerate regen{d_c, stride, d_ref, make_spec(c, sigma[0] * scale, sigma[1] * scale, seed, static_cast<uint32_t>(r))};
-      rc = finalize(c, nullptr, nullptr, c->d_x0, nullptr, P, N, n, layout, 0, c->d_records,
+      rc = finalize(c, nullptr, softmin ? c->d_keys : nullptr, c->d_x0, nullptr, P, N, n, layout, 0, c->d_records,
                     acmpc::dynamic_blocks_per_problem(P, N, c->vehicles.K), s, &regen);
       if (rc != ACMPC_OK) return rc;
+      if (want_mean) {   // (reads d_centre in its first launch, writes the mean there in its second)
+        rc = softmin_sampled(c, c->d_costs, c->d_keys, d_c, stride, d_ref, P, N, n, 0, sigma[0] * scale, sigma[1] * scale,
+                             seed, static_cast<uint32_t>(r), c->d_centre, nullptr, s);
+        if (rc != ACMPC_OK) return rc;
+      }
       continue;
     }
     rc = sample(c, d_c, stride, d_ref, P, N, n, layout, 0, sigma[0] * scale, sigma[1] * scale, seed,
                 static_cast<uint32_t>(r), c->d_U, s);
     if (rc != ACMPC_OK) return rc;
     acmpc::LaunchShape shape;
-    rc = rollout(c, c->d_x0, c->d_U, P, N, n, layout, 0, nullptr, s, &shape);
+    rc = rollout(c, c->d_x0, c->d_U, P, N, n, layout, 0, softmin ? c->d_costs : nullptr, s, &shape);
     if (rc != ACMPC_OK) return rc;
-    rc = finalize(c, nullptr, nullptr, c->d_x0, c->d_U, P, N, n, layout, 0, c->d_records, shape.blocks_per_problem, s);
+    rc = finalize(c, nullptr, softmin ? c->d_keys : nullptr, c->d_x0, c->d_U, P, N, n, layout, 0, c->d_records,
+                  shape.blocks_per_problem, s);
     if (rc != ACMPC_OK) return rc;
+    if (want_mean) {
+      acmpc::SoftminArgs sm{};
+      sm.costs = c->d_costs;
+      sm.keys = c->d_keys;
+      sm.U = c->d_U;
+      sm.partial = c->d_soft_partial;
+      sm.mean = c->d_centre;   // [P][n][2]: the next round's centre
+      sm.weight_sum = nullptr;
+      sm.chunks = acmpc::softmin_chunks(N);
+      sm.P = P;
+      sm.N = N;
+      sm.n = n;
+      sm.lambda = static_cast<float>(c->prm.softmin_lambda);
+      ACMPC_HIP(c, acmpc::launch_softmin(layout, sm, s));
+    }
   }
   ACMPC_HIP(c, hipMemcpyAsync(records, c->d_records, static_cast<size_t>(P) * rec_floats * sizeof(float),
                               hipMemcpyDeviceToHost, s));
@@ -1758,12 +1822,13 @@ int acmpc_optimize(acmpc_ctx* c, const float* x0, const float* centre, const flo
   const int layout = ACMPC_LAYOUT_STEP_MAJOR;
   int rc = check_shape(c, P, N, n, layout);
   if (rc != ACMPC_OK) return rc;
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC && c->prm.centre_update == 1 && !(c->prm.softmin_lambda > 0.0))
+    return fail(c, ACMPC_EINVAL, "softmin_lambda must be positive");
   rc = ensure_device(c);
   if (rc != ACMPC_OK) return rc;
   rc = ensure_staging(c);
   if (rc != ACMPC_OK) return rc;
   if (c->prm.mode == ACMPC_MODE_DYNAMIC) {
-    if (c->prm.centre_update != 0) return fail(c, ACMPC_ESTATE, "mode D: acmpc_optimize recentres on the argmin only");
     return optimize_dynamic(c, x0, centre, u_ref, P, N, n, rounds, sigma, shrink, seed, records);
   }
   hipStream_t s = c->stream;
@@ -2603,6 +2668,24 @@ int acmpc_softmin_device(acmpc_ctx* c, const float* d_costs, const int64_t* d_ke
   a.lambda = static_cast<float>(c->prm.softmin_lambda);
   ACMPC_HIP(c, acmpc::launch_softmin(layout, a, static_cast<hipStream_t>(stream)));
   return ACMPC_OK;
+}
+
+int acmpc_softmin_sampled_device(acmpc_ctx* c, const float* d_costs, const int64_t* d_keys, const float* d_centre,
+                                 int32_t centre_stride, const float* d_u_ref, int32_t P, int32_t N, int32_t n,
+                                 int64_t index_offset, double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round,
+                                 float* d_mean, double* d_weight_sum, void* stream) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (d_costs == nullptr || d_keys == nullptr || d_centre == nullptr || d_mean == nullptr)
+    return fail(c, ACMPC_EINVAL, "null device pointer");
+  if (centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
+  if (index_offset < 0 || index_offset + N > 0xffffffffLL) return fail(c, ACMPC_EINVAL, "global index exceeds 32 bits");
+  if (!(c->prm.softmin_lambda > 0.0)) return fail(c, ACMPC_EINVAL, "softmin_lambda must be positive");
+  int rc = check_shape(c, P, N, n, ACMPC_LAYOUT_STEP_MAJOR);
+  if (rc != ACMPC_OK) return rc;
+  rc = ensure_device(c);
+  if (rc != ACMPC_OK) return rc;
+  return softmin_sampled(c, d_costs, d_keys, d_centre, centre_stride, d_u_ref, P, N, n, index_offset, sigma_v, sigma_kappa,
+                         seed, round, d_mean, d_weight_sum, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

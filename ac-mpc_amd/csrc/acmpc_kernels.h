@@ -57,7 +57,7 @@ struct SoftminArgs {
   const float* costs;     // [P][N]
   const int64_t* keys;    // [P]
   const float* U;
-  double* partial;        // [P][chunks][2n + 1] workspace
+  double* partial;        // [P][chunks][4n + 1] workspace
   float* mean;            // [P][n][2]
   double* weight_sum;     // [P] or nullptr
   int chunks;
@@ -186,5 +186,9 @@ bool traced_finalize_fits(int mode, int n);
 bool fused_finalize_fits(int mode, int n);
 int softmin_chunks(int N);
 hipError_t launch_softmin(int layout, const SoftminArgs& args, hipStream_t s);
+// launch_softmin(step-major) over the matrix launch_sample(step-major, `sample`) would write, without the matrix: the
+// candidates are re-drawn inside the partial kernel (args.U is not read; sample.U neither).  The same partial sums, mean and
+// weight sum bit for bit.  sample.P / N / n must be args', u_extra and prev_keys null (hipErrorInvalidValue otherwise).
+hipError_t launch_softmin_sampled(const SoftminArgs& args, const SampleArgs& sample, hipStream_t s);
 
 }  // namespace acmpc

@@ -68,7 +68,11 @@ extern "C" {
                                  (the rollout that draws its own candidates: no control matrix) and acmpc_optimize
                                  (that rollout + the re-drawing finalize per round, two launches;
                                  ACMPC_DYNAMIC_MATRIX_ROUNDS keeps sample -> rollout -> finalize through the matrix,
-                                 the same bits).  ACMPC_ESTATE from acmpc_control_tick and acmpc_solve_stream_device.
+                                 the same bits).  With centre_update = 1 acmpc_optimize recentres on the softmin mean
+                                 as modes S and T do - the mean of a round is acmpc_softmin_sampled_device's, which
+                                 re-draws the candidates instead of reading a matrix (a third launch per round but
+                                 the last; under ACMPC_DYNAMIC_MATRIX_ROUNDS acmpc_softmin_device over the matrix, the
+                                 same bits).  ACMPC_ESTATE from acmpc_control_tick and acmpc_solve_stream_device.
                                  DESIGN.md section 2 "Mode D". */
 
 /* Memory layout of the control-sample matrix U. */
@@ -349,6 +353,20 @@ int acmpc_rollout_sampled_device(acmpc_ctx* ctx, const float* d_x0, const float*
                                  const float* d_u_ref, int32_t P, int32_t N, int32_t n, int64_t index_offset,
                                  double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round, float* d_costs,
                                  int64_t* d_keys, void* stream);
+
+/* acmpc_sample_device (step-major) into a matrix + acmpc_softmin_device of it WITHOUT the matrix: the softmin kernel re-draws
+ * candidate index_offset + c from its global index (the same candidate as acmpc_sample_device's, bit for bit; global
+ * candidate 0 = the centre, 1 = d_u_ref when given) and sums in the matrix kernel's order, so d_mean [P][n][2] and
+ * d_weight_sum [P] (or NULL) are the same bits (csrc/acmpc_kernels.hip softmin_sampled_partial_kernel).  d_costs [P][N] and
+ * d_keys [P] come from the rollout of those candidates (acmpc_rollout_sampled_device in mode D; d_keys after
+ * acmpc_reduce_across_ranks when the candidates are spread over ranks: the weights are relative to the GLOBAL minimum);
+ * d_centre / centre_stride / d_u_ref / sigma / seed / round as acmpc_sample_device takes them.  The sampler is the same in
+ * every mode: accepted on mode S, T and D handles.  ACMPC_EINVAL for a null pointer, centre_stride < 2 n, a global index
+ * beyond 32 bits or softmin_lambda <= 0, ACMPC_ECAPACITY for a shape beyond the handle's - all before any device work. */
+int acmpc_softmin_sampled_device(acmpc_ctx* ctx, const float* d_costs, const int64_t* d_keys, const float* d_centre,
+                                 int32_t centre_stride, const float* d_u_ref, int32_t P, int32_t N, int32_t n,
+                                 int64_t index_offset, double sigma_v, double sigma_kappa, uint64_t seed, uint32_t round,
+                                 float* d_mean, double* d_weight_sum, void* stream);
 
 /* A STREAM of batches on one rank: acmpc_solve_device (d_centre NULL: the winners are read from d_U) or
  * acmpc_solve_sampled_device (d_centre given: re-drawn) with the argmin and the winners' records of one call DEFERRED -

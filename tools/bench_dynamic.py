@@ -21,7 +21,14 @@ vector-issue roof (entry `dynamic_sampled` / `dynamic_sampled_ensemble`); and on
 (p50 / p99, host-synchronised) in its two-launch form and with ACMPC_DYNAMIC_MATRIX_ROUNDS=1.  `--optimize` measures that
 acmpc_optimize alone, through nothing newer than Engine.optimize - the form to run from a checkout of an earlier commit.
 
-usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--sampled | --optimize]"""
+With `--optimize --update softmin` one softmin ROUND of acmpc_optimize (centre_update = 1) is timed in its two forms, in one
+process, warm, alternating: the matrix-free round - acmpc_rollout_sampled_device with costs and keys,
+acmpc_finalize_sampled_device, acmpc_softmin_sampled_device - against the round through the control matrix -
+acmpc_sample_device, acmpc_solve_device with costs and keys, acmpc_softmin_device - at 16 384 x 49 on one problem and at
+4 096 x 4 096 x 49; the two softmin calls alone too; median, minimum and maximum of the repetitions (device events).
+`--out PATH` also writes the JSON there.
+
+usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--sampled | --optimize [--update softmin]]"""
 import argparse
 import json
 import os
@@ -56,12 +63,17 @@ def main():
     ap.add_argument("--reduce", default="mean", choices=("mean", "max"))
     ap.add_argument("--sampled", action="store_true", help="the fused sample + rollout against the matrix pair, and acmpc_optimize")
     ap.add_argument("--optimize", action="store_true", help="acmpc_optimize 16 384 x 49, 2 rounds, alone")
+    ap.add_argument("--update", default="argmin", choices=("argmin", "softmin"),
+                    help="with --optimize: softmin = one softmin round, matrix-free against through the matrix")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
+    if args.update == "softmin" and not args.optimize:
+        ap.error("--update softmin goes with --optimize")
     if args.sampled or args.optimize:
         ks = [int(k) for k in (args.vehicles or "1").split(",")]
-        run = measure_sampled if args.sampled else measure_optimize
-        print(json.dumps({"tool": "tools/bench_dynamic.py " + ("--sampled" if args.sampled else "--optimize"),
-                          "by_vehicles": {str(k): run(args, k) for k in ks}}))
+        run = measure_sampled if args.sampled else measure_softmin_round if args.update == "softmin" else measure_optimize
+        name = "--sampled" if args.sampled else "--optimize" + (" --update softmin" if args.update == "softmin" else "")
+        emit(args, {"tool": "tools/bench_dynamic.py " + name, "by_vehicles": {str(k): run(args, k) for k in ks}})
         return
     if args.vehicles is None:
         print(json.dumps(measure(args, 1)))
@@ -85,12 +97,20 @@ def main():
     print(json.dumps(out))
 
 
+def emit(args, result):
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as handle:
+            handle.write(line + "\n")
+
+
 GRIPS = (1.0, 0.9, 1.1, 0.8, 1.2, 0.7, 1.05, 0.95)
 
 
-def _engine(dp, P, N, n, K, reduce, stream):
+def _engine(dp, P, N, n, K, reduce, stream, **extra):
     from acmpc_amd import DynamicBicycleParams, Engine
-    eng = Engine(**dict(dp["kw"], max_problems=P, max_candidates=N, max_steps=n, nn_window=(2, 5)))
+    eng = Engine(**dict(dp["kw"], max_problems=P, max_candidates=N, max_steps=n, nn_window=(2, 5), **extra))
     if K == 1:
         eng.set_dynamics(DynamicBicycleParams.reference())
     else:
@@ -141,6 +161,79 @@ def measure_optimize(args, K, out=None):
         out[name] = dict(p50_ms=float(np.percentile(lat, 50)) * 1e3, p99_ms=float(np.percentile(lat, 99)) * 1e3,
                          calls=len(lat))
     eng.close()
+    return out
+
+
+def measure_softmin_round(args, K):
+    """One softmin round of acmpc_optimize built from device calls, the matrix-free form against the form through the
+    control matrix (what a library without acmpc_softmin_sampled_device has), at 16 384 x 49 on one problem and at
+    4 096 x 4 096 x 49: device-event times of the whole round and of its softmin call alone."""
+    import torch
+    import acmpc_oracle as orc
+    import dynamic_spec as ds
+    from acmpc_amd import _capi
+
+    H = 50
+    n = H - 1
+    dp = ds.make_dynamic_problem(orc, "monza", H, 8, 0)
+    dev = torch.device("cuda", 0)
+    s = torch.cuda.current_stream().cuda_stream
+    reps = 3 if args.quick else args.reps
+    out = {"horizon": H, "search": "window (2, 5)", "vehicles": K, "softmin_lambda": 1.0, "repetitions": reps}
+    for name, P, N in (("16384x1", 1, 16384), ("4096x4096", 4096, 4096)):
+        eng = _engine(dp, P, N, n, K, args.reduce, s, softmin_lambda=1.0)
+        U = torch.empty(P, n, 2, N, device=dev)
+        x0 = torch.tensor(np.repeat(dp["x0"][None], P, axis=0), device=dev)
+        centre = torch.tensor(_centre(dp, P, n), device=dev)
+        costs = torch.empty(P, N, device=dev)
+        keys = torch.empty(P, dtype=torch.int64, device=dev)
+        recs = torch.empty(P, _capi.record_floats(n), device=dev)
+        means = [torch.empty(P, n, 2, device=dev) for _ in range(2)]
+
+        def softmin_sampled():
+            eng.softmin_sampled_device(costs.data_ptr(), keys.data_ptr(), centre.data_ptr(), 2 * n, 0, P, N, n, 0, SIGMA, 7,
+                                       1, means[0].data_ptr(), 0, s)
+
+        def softmin_matrix():
+            eng.softmin_device(costs.data_ptr(), keys.data_ptr(), U.data_ptr(), P, N, n, 1, means[1].data_ptr(), 0, s)
+
+        def round_sampled():
+            eng.rollout_sampled_device(x0.data_ptr(), centre.data_ptr(), 2 * n, 0, P, N, n, 0, SIGMA, 7, 1, costs.data_ptr(),
+                                       keys.data_ptr(), s)
+            eng.finalize_sampled_device(keys.data_ptr(), x0.data_ptr(), centre.data_ptr(), 2 * n, 0, P, N, n, SIGMA, 7, 1,
+                                        recs.data_ptr(), s)
+            softmin_sampled()
+
+        def round_matrix():
+            eng.sample_device(centre.data_ptr(), 2 * n, 0, P, N, n, 1, 0, SIGMA, 7, 1, U.data_ptr(), s)
+            eng.solve_device(x0.data_ptr(), U.data_ptr(), P, N, n, 1, costs.data_ptr(), keys.data_ptr(), recs.data_ptr(), s)
+            softmin_matrix()
+
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        forms = (("round_matrix", round_matrix), ("round_sampled", round_sampled), ("softmin_matrix", softmin_matrix),
+                 ("softmin_sampled", softmin_sampled))
+        times = {label: [] for label, _ in forms}
+        for _, call in forms:   # every shape warm before anything is timed
+            call()
+        torch.cuda.synchronize()
+        for _ in range(reps):   # the forms alternate inside every repetition
+            for label, call in forms:
+                e0.record()
+                call()
+                e1.record()
+                torch.cuda.synchronize()
+                times[label].append(e0.elapsed_time(e1))
+        same = bool(torch.equal(means[0].view(torch.int32), means[1].view(torch.int32)))
+        shape = dict(P=P, N=N, matrix_bytes=P * N * n * 8, means_equal_bit_for_bit=same)
+        for label, _ in forms:
+            t = np.asarray(times[label])
+            shape[label + "_ms"] = dict(median=float(np.median(t)), min=float(t.min()), max=float(t.max()))
+        shape["round_sampled_over_matrix"] = shape["round_sampled_ms"]["median"] / shape["round_matrix_ms"]["median"]
+        shape["softmin_sampled_over_matrix"] = shape["softmin_sampled_ms"]["median"] / shape["softmin_matrix_ms"]["median"]
+        out[name] = shape
+        eng.close()
+        del U
+        torch.cuda.empty_cache()
     return out
 
 
