@@ -3,7 +3,7 @@
 `build_mpc` / `SpatialMPC` keep the reference's surface (src/acmpc/control/controller.py:19-29,
 spatial_mpc.py:20-217); `Engine` is the thin object over the C ABI (include/acmpc.h).
 """
-from ._capi import (ENSEMBLE_MAX, ENSEMBLE_MEAN, MAX_VEHICLES, Engine, EngineError, LAYOUT_CANDIDATE_MAJOR,  # noqa: F401
+from ._capi import (ENSEMBLE_MAX, ENSEMBLE_MEAN, MAX_SUBSTEPS, MAX_VEHICLES, Engine, EngineError, LAYOUT_CANDIDATE_MAJOR,  # noqa: F401
                     LAYOUT_STEP_MAJOR, MODE_DYNAMIC, MODE_SPATIAL, MODE_TEMPORAL, load_library)
 from .dynamic_model import DynamicBicycleParams  # noqa: F401
 from .dynamic_solver import DynamicSamplingSolver  # noqa: F401
@@ -13,7 +13,7 @@ from .mpc import SpatialMPC, build_mpc  # noqa: F401
 from .reference_path import ReferencePath  # noqa: F401
 
 __all__ = ["Engine", "EngineError", "load_library", "MODE_SPATIAL", "MODE_TEMPORAL", "MODE_DYNAMIC",
-           "DynamicBicycleParams", "DynamicSamplingSolver", "MAX_VEHICLES", "ENSEMBLE_MEAN", "ENSEMBLE_MAX",
+           "DynamicBicycleParams", "DynamicSamplingSolver", "MAX_VEHICLES", "MAX_SUBSTEPS", "ENSEMBLE_MEAN", "ENSEMBLE_MAX",
            "LAYOUT_CANDIDATE_MAJOR",
            "LAYOUT_STEP_MAJOR", "build_mpc", "SpatialMPC", "SpatialBicycleModel", "ReferencePath",
            "TemporalCommandSelector", "TemporalCommandInterpolator", "steer_target"]

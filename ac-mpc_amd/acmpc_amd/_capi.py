@@ -18,6 +18,7 @@ OK, EINVAL, EHIP, ENODEVICE, ECAPACITY, ESTATE = 0, -1, -2, -3, -4, -5
 MODE_SPATIAL, MODE_TEMPORAL, MODE_DYNAMIC = 0, 1, 2
 DYNAMICS_COUNT = 26   # ACMPC_DYNAMICS_COUNT: doubles in mode D's vehicle block
 MAX_VEHICLES = 8      # ACMPC_MAX_VEHICLES: vehicles in a mode D ensemble
+MAX_SUBSTEPS = 16     # ACMPC_MAX_SUBSTEPS: Euler sub-steps per control step of mode D
 ENSEMBLE_MEAN, ENSEMBLE_MAX = 0, 1
 ENSEMBLE_REDUCE = {"mean": ENSEMBLE_MEAN, "max": ENSEMBLE_MAX}
 LAYOUT_CANDIDATE_MAJOR, LAYOUT_STEP_MAJOR = 0, 1
@@ -148,6 +149,7 @@ SIGNATURES = {
     "acmpc_set_paths": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_set_dynamics": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
     "acmpc_set_dynamics_ensemble": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "acmpc_set_dynamics_integration": (C.c_int, [_CTX, C.c_int32, C.c_double, C.c_double]),
     "acmpc_get_coefficients": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_set_coefficients": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_record_floats": (C.c_int32, [C.c_int32]),
@@ -441,6 +443,22 @@ def ensemble_blocks(vehicles) -> np.ndarray:
     return np.ascontiguousarray(np.stack(blocks))
 
 
+def integration_setting(substeps=1, low_speed_blend=None):
+    """Mode D's integration setting checked as acmpc_set_dynamics_integration checks it: (M, v_lo, v_hi), with (0, 0) for
+    no blend.  ValueError for M outside 1 .. MAX_SUBSTEPS or a blend that is not 0 <= v_lo < v_hi, both finite."""
+    if isinstance(substeps, bool) or int(substeps) != substeps or not 1 <= int(substeps) <= MAX_SUBSTEPS:
+        raise ValueError("rollout_substeps is an integer in 1 .. %d, not %r" % (MAX_SUBSTEPS, substeps))
+    if low_speed_blend is None:
+        return int(substeps), 0.0, 0.0
+    try:
+        lo, hi = (float(v) for v in low_speed_blend)
+    except (TypeError, ValueError):
+        raise ValueError("low_speed_blend is None or (v_lo, v_hi), not %r" % (low_speed_blend,)) from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo < hi):
+        raise ValueError("low_speed_blend needs 0 <= v_lo < v_hi, both finite, not %r" % (low_speed_blend,))
+    return int(substeps), lo, hi
+
+
 class Engine:
     """Owns one acmpc_ctx.  Construction does no device work (fork-safe, controller.py:293-297)."""
 
@@ -539,6 +557,13 @@ class Engine:
         self._check(self._lib.acmpc_set_dynamics_ensemble(self._ctx, blocks.ctypes.data, blocks.shape[0],
                                                           None if w is None else w.ctypes.data,
                                                           ENSEMBLE_REDUCE[reduce]))
+
+    def set_dynamics_integration(self, substeps: int = 1, low_speed_blend=None):
+        """Mode D's integration setting (acmpc_set_dynamics_integration): `substeps` Euler steps per control step (1 ..
+        16) and `low_speed_blend` = (v_lo, v_hi) m/s, the speeds between which (vy, r) go over to the kinematic bicycle's,
+        or None.  The default (1, None) is the reference's single step; the setting outlives a change of vehicle."""
+        m, lo, hi = integration_setting(substeps, low_speed_blend)
+        self._check(self._lib.acmpc_set_dynamics_integration(self._ctx, m, lo, hi))
 
     def set_coefficients(self, coef: np.ndarray):
         """The packed float32 tables themselves, [P, n, 12] (mode S) / [P, n, 8] (mode T) or one [n, stride] table

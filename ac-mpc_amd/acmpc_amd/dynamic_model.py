@@ -125,11 +125,26 @@ class DynamicBicycleParams:
         ba = B * alpha
         return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0 * np.sin(C * np.arctan(ba - E * (ba - np.arctan(ba))))
 
-    def rollout(self, state, U, dt: float = 0.05) -> np.ndarray:
-        """The mirror over a control sequence U [n, 2] with vx clipped after every step: states [n + 1, 6]."""
+    def rollout(self, state, U, dt: float = 0.05, substeps: int = 1, low_speed_blend=None) -> np.ndarray:
+        """The mirror over a control sequence U [n, 2] with vx clipped after every step: states [n + 1, 6].  `substeps`
+        and `low_speed_blend` = (v_lo, v_hi) are the integration setting of acmpc_set_dynamics_integration in float64: a
+        control step is `substeps` Euler steps of dt / substeps, and after each (vy, r) are blended towards the kinematic
+        bicycle's r_k = vx tan(delta) / (lf + lr), vy_k = lr r_k by lam = clamp((vx - v_lo) / (v_hi - v_lo), 0, 1)."""
+        substeps = int(substeps)
+        if substeps < 1:
+            raise ValueError("substeps must be positive")
+        h = dt / substeps
         out = [np.asarray(state, dtype=np.float64)]
         for u in np.asarray(U, dtype=np.float64):
-            nxt = self.predict_next_state(out[-1], u, dt)[0]
-            nxt[3] = max(nxt[3], 0.0)
+            nxt = out[-1]
+            for _ in range(substeps):
+                nxt = self.predict_next_state(nxt, u, h)[0]
+                nxt[3] = max(nxt[3], 0.0)
+                if low_speed_blend is not None:
+                    v_lo, v_hi = (float(v) for v in low_speed_blend)
+                    r_k = nxt[3] * np.tan(u[0]) / (self.lf + self.lr)
+                    lam = max(min((nxt[3] - v_lo) / (v_hi - v_lo), 1.0), 0.0)
+                    nxt[4] = lam * nxt[4] + (1.0 - lam) * (r_k * self.lr)
+                    nxt[5] = lam * nxt[5] + (1.0 - lam) * r_k
             out.append(nxt)
         return np.stack(out)

@@ -14,7 +14,12 @@ Robust scoring (acmpc_set_dynamics_ensemble): `vehicle_ensemble` - a list of Dyn
 or `grip_ensemble` - grip scales, each giving `params.with_grip(scale)` - scores every candidate under each vehicle;
 `ensemble_weights` (positive, default equal) and `ensemble_reduce` ("mean", the default, or "max": the worst case) say
 how the costs combine.  The two ensemble keys are mutually exclusive; with neither, the solver scores the one vehicle
-`params` (acmpc_set_dynamics)."""
+`params` (acmpc_set_dynamics).
+
+Integration (acmpc_set_dynamics_integration): `rollout_substeps` (default 1) Euler steps per control step and
+`low_speed_blend` (default None, or (v_lo, v_hi) m/s: below v_hi the lateral velocity and the yaw rate go over to the
+kinematic bicycle's).  The single step is unstable below about 7.5 m/s and chatters up to about 12: set
+`rollout_substeps: 4, low_speed_blend: (3, 5)` whenever a plan can fall below that (a hairpin, a pit lane, a start)."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -69,6 +74,7 @@ class DynamicSamplingSolver:
         self._dt = float(config.get("rollout_dt", 0.05))
         self._params = params if params is not None else DynamicBicycleParams.reference()
         vehicles = ensemble_vehicles(config, self._params)   # (a config error raises before any handle exists)
+        integration = _capi.integration_setting(config.get("rollout_substeps", 1), config.get("low_speed_blend"))
         self._centre_update = config.get("sampling_update", "argmin")   # or "softmin" (MPPI-style weighted mean)
         if self._centre_update not in SAMPLING_UPDATES:
             raise ValueError("sampling_update is 'argmin' or 'softmin', not %r" % (self._centre_update,))
@@ -89,6 +95,8 @@ class DynamicSamplingSolver:
         else:
             self._engine.set_dynamics_ensemble(vehicles, config.get("ensemble_weights"),
                                                config.get("ensemble_reduce", "mean"))
+        if integration != (1, 0.0, 0.0):
+            self._engine.set_dynamics_integration(integration[0], integration[1:] if integration[2] > 0.0 else None)
         self._plan: Optional[np.ndarray] = None
         self._calls = 0
 

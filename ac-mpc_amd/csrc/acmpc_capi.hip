@@ -174,6 +174,10 @@ struct acmpc_ctx {
   // mode D: the vehicles' float32 constants, one (acmpc_set_dynamics) or an ensemble (acmpc_set_dynamics_ensemble)
   bool has_dynamics = false;
   acmpc::VehicleEnsemble vehicles{};
+  // mode D: the integration setting (acmpc_set_dynamics_integration), kept apart from the vehicles: (1, 0, 0) = off
+  int substeps = 1;
+  double blend_lo = 0.0, blend_hi = 0.0;
+  double vehicle_L[acmpc::kMaxVehicles] = {};   // lf + lr of each vehicle in float64: the blend's 1 / L is rounded from it
 
   mutable std::string err;
 };
@@ -346,6 +350,21 @@ int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call 
   return ACMPC_OK;
 }
 
+// mode D: the kernels' view of the handle's integration setting, for the vehicles it has now - every float derived in
+// float64 and rounded once ("Sub-steps and the low-speed blend")
+acmpc::Integration dynamics_integration(const acmpc_ctx* c) {
+  acmpc::Integration g{};
+  g.substeps = c->substeps;
+  g.h = static_cast<float>(c->prm.dt / c->substeps);
+  g.blend = (c->blend_hi > 0.0) ? 1 : 0;
+  if (g.blend != 0) {
+    g.v_lo = static_cast<float>(c->blend_lo);
+    g.inv_span = static_cast<float>(1.0 / (c->blend_hi - c->blend_lo));
+  }
+  for (int k = 0; k < c->vehicles.K; ++k) g.inv_L[k] = static_cast<float>(1.0 / c->vehicle_L[k]);
+  return g;
+}
+
 int rollout(acmpc_ctx* c, const float* d_x0, const float* d_U, int P, int N, int n, int layout, int64_t offset,
             float* d_costs, hipStream_t s, acmpc::LaunchShape* shape_out) {
   if (c->prm.mode == ACMPC_MODE_DYNAMIC) {   // mode D: its own kernel (acmpc_dynamic.hip)
@@ -361,7 +380,7 @@ int rollout(acmpc_ctx* c, const float* d_x0, const float* d_U, int P, int N, int
     a.n = n;
     a.index_offset = offset;
     a.w = c->w;
-    ACMPC_HIP(c, acmpc::launch_rollout_dynamic(layout, a, c->vehicles, s));
+    ACMPC_HIP(c, acmpc::launch_rollout_dynamic(layout, a, c->vehicles, dynamics_integration(c), s));
     *shape_out = acmpc::LaunchShape{};
     shape_out->blocks_per_problem = acmpc::dynamic_blocks_per_problem(P, N, c->vehicles.K);
     return ACMPC_OK;
@@ -439,7 +458,7 @@ int finalize(acmpc_ctx* c, const int64_t* d_keys_in, int64_t* d_keys_out, const 
   a.index_offset = offset;
   a.w = c->w;
   if (c->prm.mode == ACMPC_MODE_DYNAMIC) {
-    ACMPC_HIP(c, acmpc::launch_finalize_dynamic(layout, a, c->vehicles, s));
+    ACMPC_HIP(c, acmpc::launch_finalize_dynamic(layout, a, c->vehicles, dynamics_integration(c), s));
     return ACMPC_OK;
   }
   ACMPC_HIP(c, acmpc::launch_finalize(c->prm.mode, layout, a, s, c->opt));
@@ -540,7 +559,7 @@ int rollout_sampled_dynamic(acmpc_ctx* c, const float* d_x0, const float* d_cent
   smp.n = n;
   smp.index_offset = offset;
   smp.spec = make_spec(c, sigma_d, sigma_p, seed, round);
-  ACMPC_HIP(c, acmpc::launch_rollout_dynamic_sampled(a, smp, c->vehicles, s));
+  ACMPC_HIP(c, acmpc::launch_rollout_dynamic_sampled(a, smp, c->vehicles, dynamics_integration(c), s));
   return ACMPC_OK;
 }
 
@@ -1378,6 +1397,7 @@ int optimize_dynamic(acmpc_ctx* c, const float* x0, const float* centre, const f
   return ACMPC_OK;
 }
 
+static_assert(acmpc::kMaxSubsteps == ACMPC_MAX_SUBSTEPS, "the sub-step limit of acmpc_dynamic.h is the header's");
 static_assert(acmpc::kMaxVehicles == ACMPC_MAX_VEHICLES && acmpc::kEnsembleMean == ACMPC_ENSEMBLE_MEAN &&
                   acmpc::kEnsembleMax == ACMPC_ENSEMBLE_MAX,
               "the ensemble constants of acmpc_dynamic.h are the header's");
@@ -1440,6 +1460,7 @@ int acmpc_set_dynamics(acmpc_ctx* c, const double* coef, int32_t count) {
   e.K = 1;
   e.reduce = ACMPC_ENSEMBLE_MEAN;
   c->vehicles = e;
+  c->vehicle_L[0] = coef[14] + coef[15];
   c->has_dynamics = true;
   return ACMPC_OK;
 }
@@ -1469,7 +1490,23 @@ int acmpc_set_dynamics_ensemble(acmpc_ctx* c, const double* coef, int32_t K, con
   e.K = K;
   e.reduce = reduce;
   c->vehicles = e;
+  for (int k = 0; k < K; ++k)
+    c->vehicle_L[k] = coef[static_cast<size_t>(k) * acmpc::kDynamicsCount + 14] + coef[static_cast<size_t>(k) * acmpc::kDynamicsCount + 15];
   c->has_dynamics = true;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_integration(acmpc_ctx* c, int32_t substeps, double blend_lo, double blend_hi) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics_integration needs a mode D handle");
+  if (substeps < 1 || substeps > ACMPC_MAX_SUBSTEPS) return fail(c, ACMPC_EINVAL, "substeps is 1 .. ACMPC_MAX_SUBSTEPS = 16");
+  const bool off = blend_lo == 0.0 && blend_hi == 0.0;
+  if (!off && !(std::isfinite(blend_lo) && std::isfinite(blend_hi) && blend_lo >= 0.0 && blend_lo < blend_hi))
+    return fail(c, ACMPC_EINVAL, "the low-speed blend is 0, 0 (off) or 0 <= lo < hi, both finite");
+  // everything is checked before anything is kept: a refused setting leaves the handle's as it was
+  c->substeps = substeps;
+  c->blend_lo = off ? 0.0 : blend_lo;   // (-0.0 is 0)
+  c->blend_hi = off ? 0.0 : blend_hi;
   return ACMPC_OK;
 }
 

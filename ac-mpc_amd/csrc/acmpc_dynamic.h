@@ -125,10 +125,28 @@ __device__ __forceinline__ F pacejka(F alpha, float B, float C, float E, float P
   return P * sin_spec<F>(C * atan_spec<F>(y));
 }
 
-// One explicit Euler step of predict_next_state (dynamic_bicycle_model.py:88-160) with u = (delta, pedal), then
-// vx = max(vx, 0) (the reference's loop, :180; maxNum: a NaN vx becomes 0).
+// What a step takes from its control alone: sincos_spec(delta) and the pedal's split.  The same for every sub-step of a
+// control step (dynamic_advance_fine computes it once).
 template <typename F>
-__device__ __forceinline__ void dynamic_advance(StateD_<F>& s, F delta, F pedal, const Vehicle& k, float dt) {
+struct ControlTerms {
+  F sd, cd, p_neg, p_pos;
+};
+template <typename F>
+__device__ __forceinline__ ControlTerms<F> control_terms(F delta, F pedal) {
+  ControlTerms<F> c;
+  c.p_neg = __builtin_elementwise_min(pedal, splat<F>(0.0f));
+  c.p_pos = vmax(pedal, splat<F>(0.0f));
+  sincos_spec<F>(delta, c.sd, c.cd);
+  return c;
+}
+
+// One explicit Euler step of predict_next_state (dynamic_bicycle_model.py:88-160) with u = (delta, pedal), then
+// vx = max(vx, 0) (the reference's loop, :180; maxNum: a NaN vx becomes 0).  HOISTED: the control's terms come in
+// through `pre` (the sub-steps of dynamic_advance_fine); otherwise they are computed here, where the single step has
+// always computed them - the default setting's kernels are to stay the code they were, instruction for instruction.
+template <bool HOISTED, typename F>
+__device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, const ControlTerms<F>* pre, const Vehicle& k,
+                                              float dt) {
   const F vx = s.vx, vy = s.vy, r = s.r;
   const F den = vx + kVxEps;
   const F qf = (r * k.lf + vy) / den;
@@ -141,12 +159,23 @@ __device__ __forceinline__ void dynamic_advance(StateD_<F>& s, F delta, F pedal,
   const F F_fric = (k.fric0 - k.Cfric2 * vx) - k.Cfric3 * vx2;
   const F brake = (k.Cb1 - k.Cb2 * vx) - k.Cb3 * vx2;
   const F motor = (k.Cm1 - k.Cm2 * vx) - k.Cm3 * vx2;
-  const F p_neg = __builtin_elementwise_min(pedal, splat<F>(0.0f));
-  const F p_pos = vmax(pedal, splat<F>(0.0f));
+  F p_neg, p_pos;
+  if constexpr (HOISTED) {
+    p_neg = pre->p_neg;
+    p_pos = pre->p_pos;
+  } else {
+    p_neg = __builtin_elementwise_min(pedal, splat<F>(0.0f));
+    p_pos = vmax(pedal, splat<F>(0.0f));
+  }
   const F F_rx = (brake * k.bias_rear) * p_neg + motor * p_pos;
   const F F_fx = (brake * k.bias_front) * p_neg;
   F sd, cd, sy, cy;
-  sincos_spec<F>(delta, sd, cd);
+  if constexpr (HOISTED) {
+    sd = pre->sd;
+    cd = pre->cd;
+  } else {
+    sincos_spec<F>(delta, sd, cd);
+  }
   sincos_spec<F>(s.t.phi, sy, cy);
   const F xd0 = vx * cy - vy * sy;
   const F xd1 = vx * sy + vy * cy;
@@ -159,6 +188,58 @@ __device__ __forceinline__ void dynamic_advance(StateD_<F>& s, F delta, F pedal,
   s.vx = vmax(vx + xd3 * dt, splat<F>(0.0f));
   s.vy = vy + xd4 * dt;
   s.r = r + xd5 * dt;
+}
+
+template <typename F>
+__device__ __forceinline__ void dynamic_advance(StateD_<F>& s, F delta, F pedal, const Vehicle& k, float dt) {
+  dynamic_euler<false, F>(s, delta, pedal, nullptr, k, dt);
+}
+
+// The integration setting of a handle (acmpc_set_dynamics_integration, DESIGN.md section 2 "Mode D", "Sub-steps and the
+// low-speed blend"): a control step of dt is `substeps` Euler steps of h = float32(dt / substeps) under the same control,
+// and after each of them (vy, r) is blended towards the kinematic bicycle's r_k = vx tan(delta) / L, vy_k = lr r_k below
+// v_hi, entirely below v_lo.  The host derives every float in float64 and rounds it once.  (1, no blend) is the default
+// and runs the kernels without any of this (their FINE = false instantiations); anything else their FINE = true ones.
+constexpr int kMaxSubsteps = 16;   // ACMPC_MAX_SUBSTEPS
+struct Integration {
+  int substeps;                 // M
+  int blend;                    // 0: off
+  float h;                      // float32(dt / M)
+  float v_lo, inv_span;         // inv_span = float32(1 / (v_hi - v_lo))
+  float inv_L[kMaxVehicles];    // float32(1 / (lf + lr)) of each vehicle
+};
+__host__ __device__ inline bool is_fine(const Integration& g) { return g.substeps != 1 || g.blend != 0; }
+
+// The control step of a FINE kernel: g.substeps times dynamic_euler with step g.h, the control's terms and tan(delta)
+// computed once, and the blend after each sub-step's update and clip.  The sub-step count and the blend switch are
+// kernel arguments: a scalar loop and a scalar branch, no divergence.  lam == 1 passes the dynamic (vy, r) through bit for
+// bit (1 * a + 0 * b); two multiplies and one add each, no fused multiply-add.
+template <typename F>
+__device__ __forceinline__ void dynamic_advance_fine(StateD_<F>& s, F delta, F pedal, const Vehicle& k,
+                                                     const Integration& g, float inv_L) {
+  const ControlTerms<F> c = control_terms<F>(delta, pedal);
+  const F td = c.sd / c.cd;
+#pragma nounroll
+  for (int m = 0; m < g.substeps; ++m) {
+    dynamic_euler<true, F>(s, delta, pedal, &c, k, g.h);
+    if (g.blend != 0) {
+      const F r_k = (s.vx * td) * inv_L;
+      const F vy_k = r_k * k.lr;
+      const F lam = vmax(__builtin_elementwise_min((s.vx - g.v_lo) * g.inv_span, splat<F>(1.0f)), splat<F>(0.0f));
+      const F mu = splat<F>(1.0f) - lam;
+      s.vy = lam * s.vy + mu * vy_k;
+      s.r = lam * s.r + mu * r_k;
+    }
+  }
+}
+
+// the control step of a kernel instantiated for the default setting (FINE = false: dynamic_advance, as ever) or for
+// the others
+template <bool FINE, typename F>
+__device__ __forceinline__ void dynamic_control_step(StateD_<F>& s, F delta, F pedal, const Vehicle& k, float dt,
+                                                     const Integration& g, float inv_L) {
+  if constexpr (FINE) dynamic_advance_fine<F>(s, delta, pedal, k, g, inv_L);
+  else dynamic_advance<F>(s, delta, pedal, k, dt);
 }
 
 // mode T's temporal_cost with the input terms of this model: dv = vx - v_ref, dk = delta - delta_ref (row[7], staged
@@ -197,18 +278,22 @@ int dynamic_candidates_per_lane(int P, int N, int K = 1);
 int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // rollout: costs [P][N] (or nullptr) and one (cost, index) partial key + feasible count per workgroup, x0 [P][6].  K = 1:
 // rollout_dynamic_kernel with the one vehicle; K > 1: rollout_dynamic_ensemble_kernel.
-hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles, hipStream_t s);
+// `integration`: the handle's setting; the default launches the FINE = false instantiations, whose step loop knows nothing
+// of it.
+hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                  const Integration& integration, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          hipStream_t s);
+                                          const Integration& integration, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
-hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles, hipStream_t s);
+hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                   const Integration& integration, hipStream_t s);
 
 }  // namespace acmpc

@@ -27,6 +27,11 @@
 //   rollout_dynamic_sampled_ensemble_kernel   the ensemble rollout without a control matrix: every wave draws the
 //                                     workgroup's candidates for itself.
 //
+// Every kernel has a second instantiation, FINE = true, for a handle whose integration setting is not the default
+// (acmpc_set_dynamics_integration; acmpc_dynamic.h: Integration, dynamic_advance_fine): its control step is M Euler
+// sub-steps - a scalar loop on a kernel argument - with the low-speed blend after each.  Search, cost and record stay once
+// per control step.  FINE = false is the step loop of the default setting, untouched by the other.
+//
 // Built with -ffp-contract=off: see acmpc_device.h.
 #include "acmpc_dynamic.h"
 
@@ -108,8 +113,9 @@ __device__ __forceinline__ void dynamic_settle(StateD_<f32x2>& s, const float* w
   dynamic_cost<f32x2>(s, g, d, q, w);
 }
 
-template <int LAYOUT, int CPT>
-__global__ void __launch_bounds__(kDynBlock) rollout_dynamic_kernel(const RolloutArgs a, const Vehicle veh) {
+template <int LAYOUT, int CPT, bool FINE>
+__global__ void __launch_bounds__(kDynBlock)
+    rollout_dynamic_kernel(const RolloutArgs a, const Vehicle veh, const Integration g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // carve: [0, 32) wave keys | [32, 48) wave feasible counts | [64, ...) waypoint rows, then the search keys
   int64_t* s_key = reinterpret_cast<int64_t*>(smem);
@@ -148,7 +154,7 @@ __global__ void __launch_bounds__(kDynBlock) rollout_dynamic_kernel(const Rollou
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      dynamic_advance<F>(st, d, q, veh, w.dt);
+      dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
     }
@@ -250,9 +256,9 @@ __device__ __forceinline__ void stage_draw_tables(const DynamicDraw& d, int p, i
 // the new pair are drawn unless resident: four draws per candidate, as draw_normals() makes.  SHARED (the ensemble: the K
 // waves of a workgroup roll the same candidates): one wave draws for all, between two barriers that every wave reaches -
 // the knot changes are the same steps in every wave.
-template <int CPT, bool SHARED, typename F>
+template <int CPT, bool SHARED, bool FINE, typename F>
 __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& sp, const Vehicle& veh, const Weights& w,
-                                             const int p, const int n, const uint32_t (&gidx)[CPT], const bool has_ref,
+                                             const Integration& g, const float inv_L, const int p, const int n, const uint32_t (&gidx)[CPT], const bool has_ref,
                                              const float* s_wp, const float* s_xy, const float* s_seg,
                                              const float* s_centre, const float* s_ref, f32x2* s_z, const int row,
                                              const int zi, const bool draws) {
@@ -308,7 +314,7 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
         d = dj[0];
         q = qj[0];
       }
-      dynamic_advance<F>(st, d, q, veh, w.dt);
+      dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
     }
@@ -317,9 +323,9 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
 
 // rollout_dynamic_kernel without a control matrix: the same workgroup shape, tail rule (lanes past N repeat candidate
 // N - 1 unreported), costs, partial keys and feasible counts.
-template <int CPT>
+template <int CPT, bool FINE>
 __global__ void __launch_bounds__(kDynBlock)
-    rollout_dynamic_sampled_kernel(const RolloutArgs a, const DynamicDraw smp, const Vehicle veh) {
+    rollout_dynamic_sampled_kernel(const RolloutArgs a, const DynamicDraw smp, const Vehicle veh, const Integration g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // carve: [0, 32) wave keys | [32, 48) wave feasible counts | [64, ...) the lanes' normals [4][256][CPT] pairs, waypoint
   // rows, search keys, the draw's tables
@@ -347,8 +353,8 @@ __global__ void __launch_bounds__(kDynBlock)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) gidx[j] = static_cast<uint32_t>(a.index_offset + min(c0 + j, a.N - 1));
   StateD_<F> st = start_dynamic<F>(x0, coef);
-  roll_sampled<CPT, false, F>(st, draw_spec(smp, w), veh, w, p, n, gidx, smp.u_ref != nullptr, s_wp, s_xy, s_seg, s_centre,
-                              s_ref, s_z, kDynBlock, tid, true);
+  roll_sampled<CPT, false, FINE, F>(st, draw_spec(smp, w), veh, w, g, g.inv_L[0], p, n, gidx, smp.u_ref != nullptr, s_wp,
+                                    s_xy, s_seg, s_centre, s_ref, s_z, kDynBlock, tid, true);
   const F cost_v = finish_temporal<F>(st.t, n, w);
   float cost[CPT];
   bool feas[CPT];
@@ -423,8 +429,9 @@ __device__ __forceinline__ void regenerate_dynamic_controls(const FinalizeArgs& 
   }
 }
 
-template <int LAYOUT>
-__global__ void __launch_bounds__(kWave) finalize_dynamic_kernel(const FinalizeArgs a, const Vehicle veh) {
+template <int LAYOUT, bool FINE>
+__global__ void __launch_bounds__(kWave)
+    finalize_dynamic_kernel(const FinalizeArgs a, const Vehicle veh, const Integration g) {
   extern __shared__ __attribute__((aligned(16))) float s_rec[];   // record image, then the waypoint rows and keys
   const int p = static_cast<int>(blockIdx.x);
   const int lane = static_cast<int>(threadIdx.x);
@@ -477,7 +484,7 @@ __global__ void __launch_bounds__(kWave) finalize_dynamic_kernel(const FinalizeA
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
     const float d = su[2 * i], q = su[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
-    dynamic_advance<float>(st, d, q, veh, w.dt);
+    dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[0]);
     // the first minimum of the key over the search's waypoints, the lanes side by side; ties -> the lower index, and the
     // search's first waypoint when no key compares below +inf (as the rollout's `d < best` scans)
     const int lo = exhaustive ? 0 : max(min(j_prev - w.nn_back, n - win_w), 0);
@@ -520,9 +527,9 @@ __global__ void __launch_bounds__(kWave) finalize_dynamic_kernel(const FinalizeA
   for (int e = lane; e < rec_floats; e += kWave) rec[e] = s_rec[e];
 }
 
-template <int LAYOUT, int CPT>
+template <int LAYOUT, int CPT, bool FINE>
 __global__ void __launch_bounds__(kWave * kMaxVehicles)
-    rollout_dynamic_ensemble_kernel(const RolloutArgs a, const VehicleEnsemble e) {
+    rollout_dynamic_ensemble_kernel(const RolloutArgs a, const VehicleEnsemble e, const Integration g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // carve: [K][64 CPT] per-vehicle costs | [K][64 CPT] per-vehicle violations | waypoint rows | search keys
   constexpr int kPerGroup = kWave * CPT;
@@ -565,7 +572,7 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      dynamic_advance<F>(st, d, q, veh, w.dt);
+      dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
     }
@@ -606,9 +613,10 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
 
 // rollout_dynamic_ensemble_kernel without a control matrix: wave 0 draws the workgroup's 64 CPT candidates for the K waves
 // (roll_sampled's SHARED form)
-template <int CPT>
+template <int CPT, bool FINE>
 __global__ void __launch_bounds__(kWave * kMaxVehicles)
-    rollout_dynamic_sampled_ensemble_kernel(const RolloutArgs a, const DynamicDraw smp, const VehicleEnsemble e) {
+    rollout_dynamic_sampled_ensemble_kernel(const RolloutArgs a, const DynamicDraw smp, const VehicleEnsemble e,
+                                            const Integration g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // carve: [K][64 CPT] per-vehicle costs | [K][64 CPT] per-vehicle violations | the candidates' normals [4][64][CPT] pairs |
   // waypoint rows | search keys | draw tables
@@ -641,8 +649,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) gidx[j] = static_cast<uint32_t>(a.index_offset + min(c0 + j, a.N - 1));
   StateD_<F> st = start_dynamic<F>(x0, coef);
-  roll_sampled<CPT, true, F>(st, draw_spec(smp, w), veh, w, p, n, gidx, smp.u_ref != nullptr, s_wp, s_xy, s_seg, s_centre,
-                             s_ref, s_z, kWave, lane, k == 0);
+  roll_sampled<CPT, true, FINE, F>(st, draw_spec(smp, w), veh, w, g, g.inv_L[k], p, n, gidx, smp.u_ref != nullptr, s_wp,
+                                   s_xy, s_seg, s_centre, s_ref, s_z, kWave, lane, k == 0);
   const F cost_v = finish_temporal<F>(st.t, n, w);
   if constexpr (CPT == 2) {
     s_c[k * kPerGroup + 2 * lane] = cost_v[0];
@@ -677,9 +685,9 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   }
 }
 
-template <int LAYOUT>
+template <int LAYOUT, bool FINE>
 __global__ void __launch_bounds__(kWave * kMaxVehicles)
-    finalize_dynamic_ensemble_kernel(const FinalizeArgs a, const VehicleEnsemble e) {
+    finalize_dynamic_ensemble_kernel(const FinalizeArgs a, const VehicleEnsemble e, const Integration g) {
   // record image | [kMaxVehicles] costs, [kMaxVehicles] violations | waypoint rows | search keys
   extern __shared__ __attribute__((aligned(16))) float s_rec[];
   const int p = static_cast<int>(blockIdx.x);
@@ -740,7 +748,7 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
     const float d = su[2 * i], q = su[2 * i + 1];
-    dynamic_advance<float>(st, d, q, veh, w.dt);
+    dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[k]);
     // finalize_dynamic_kernel's search, within this wave
     const int lo = exhaustive ? 0 : max(min(j_prev - w.nn_back, n - win_w), 0);
     const int hi = exhaustive ? n - 1 : min(lo + win_w, n) - 1;
@@ -789,6 +797,15 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   for (int q = tid; q < rec_floats; q += threads) rec[q] = s_rec[q];
 }
 
+// the FINE = true instantiations for any setting but the default (acmpc_dynamic.h: Integration), FINE = false for that
+template <typename Body>
+void with_integration_kind(const Integration& g, Body&& body) {
+  if (is_fine(g)) body(std::true_type{});
+  else body(std::false_type{});
+}
+
+bool integration_valid(const Integration& g) { return g.substeps >= 1 && g.substeps <= kMaxSubsteps; }
+
 }  // namespace
 
 int dynamic_candidates_per_lane(int P, int N, int K) {
@@ -802,8 +819,10 @@ int dynamic_blocks_per_problem(int P, int N, int K) {
   return (N + per_block - 1) / per_block;
 }
 
-hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles, hipStream_t s) {
+hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                  const Integration& g, hipStream_t s) {
   (void)hipGetLastError();
+  if (!integration_valid(g)) return hipErrorInvalidValue;
   if (args.n < 1 || args.n > kDynamicMaxSteps || args.N < 1 || args.P < 1) return hipErrorInvalidValue;
   if (vehicles.K < 1 || vehicles.K > kMaxVehicles || (layout != 0 && layout != 1)) return hipErrorInvalidValue;
   const int K = vehicles.K;
@@ -814,30 +833,37 @@ hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const Veh
     const Vehicle& vehicle = vehicles.v[0];
     const dim3 block(kDynBlock);
     const size_t lds = 64 + tables;
-    if (layout == 0) {
-      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_kernel<0, 2>), grid, block, lds, s, args, vehicle);
-      else hipLaunchKernelGGL((rollout_dynamic_kernel<0, 1>), grid, block, lds, s, args, vehicle);
-    } else {
-      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_kernel<1, 2>), grid, block, lds, s, args, vehicle);
-      else hipLaunchKernelGGL((rollout_dynamic_kernel<1, 1>), grid, block, lds, s, args, vehicle);
-    }
+    with_integration_kind(g, [&](auto fine) {
+      constexpr bool kFine = decltype(fine)::value;
+      if (layout == 0) {
+        if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_kernel<0, 2, kFine>), grid, block, lds, s, args, vehicle, g);
+        else hipLaunchKernelGGL((rollout_dynamic_kernel<0, 1, kFine>), grid, block, lds, s, args, vehicle, g);
+      } else {
+        if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_kernel<1, 2, kFine>), grid, block, lds, s, args, vehicle, g);
+        else hipLaunchKernelGGL((rollout_dynamic_kernel<1, 1, kFine>), grid, block, lds, s, args, vehicle, g);
+      }
+    });
     return hipGetLastError();
   }
   const dim3 block(kWave * K);
   const size_t lds = 2 * static_cast<size_t>(K) * kWave * cpt * sizeof(float) + tables;
-  if (layout == 0) {
-    if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<0, 2>), grid, block, lds, s, args, vehicles);
-    else hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<0, 1>), grid, block, lds, s, args, vehicles);
-  } else {
-    if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<1, 2>), grid, block, lds, s, args, vehicles);
-    else hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<1, 1>), grid, block, lds, s, args, vehicles);
-  }
+  with_integration_kind(g, [&](auto fine) {
+    constexpr bool kFine = decltype(fine)::value;
+    if (layout == 0) {
+      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<0, 2, kFine>), grid, block, lds, s, args, vehicles, g);
+      else hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<0, 1, kFine>), grid, block, lds, s, args, vehicles, g);
+    } else {
+      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<1, 2, kFine>), grid, block, lds, s, args, vehicles, g);
+      else hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<1, 1, kFine>), grid, block, lds, s, args, vehicles, g);
+    }
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          hipStream_t s) {
+                                          const Integration& g, hipStream_t s) {
   (void)hipGetLastError();
+  if (!integration_valid(g)) return hipErrorInvalidValue;
   if (args.n < 1 || args.n > kDynamicMaxSteps || args.N < 1 || args.P < 1) return hipErrorInvalidValue;
   if (vehicles.K < 1 || vehicles.K > kMaxVehicles) return hipErrorInvalidValue;
   if (sample.P != args.P || sample.N != args.N || sample.n != args.n || sample.index_offset != args.index_offset)
@@ -867,20 +893,28 @@ hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleA
     const Vehicle& vehicle = vehicles.v[0];
     const dim3 block(kDynBlock);
     const size_t lds = 64 + static_cast<size_t>(kDrawSlots) * kDynBlock * cpt * sizeof(f32x2) + tables;   // <= 60 KB
-    if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<2>), grid, block, lds, s, args, d, vehicle);
-    else hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<1>), grid, block, lds, s, args, d, vehicle);
+    with_integration_kind(g, [&](auto fine) {
+      constexpr bool kFine = decltype(fine)::value;
+      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<2, kFine>), grid, block, lds, s, args, d, vehicle, g);
+      else hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<1, kFine>), grid, block, lds, s, args, d, vehicle, g);
+    });
     return hipGetLastError();
   }
   const dim3 block(kWave * K);
   const size_t lds = 2 * static_cast<size_t>(K) * kWave * cpt * sizeof(float) +
                      static_cast<size_t>(kDrawSlots) * kWave * cpt * sizeof(f32x2) + tables;
-  if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<2>), grid, block, lds, s, args, d, vehicles);
-  else hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<1>), grid, block, lds, s, args, d, vehicles);
+  with_integration_kind(g, [&](auto fine) {
+    constexpr bool kFine = decltype(fine)::value;
+    if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<2, kFine>), grid, block, lds, s, args, d, vehicles, g);
+    else hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<1, kFine>), grid, block, lds, s, args, d, vehicles, g);
+  });
   return hipGetLastError();
 }
 
-hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles, hipStream_t s) {
+hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                   const Integration& g, hipStream_t s) {
   (void)hipGetLastError();
+  if (!integration_valid(g)) return hipErrorInvalidValue;
   if (args.controls_only || args.n < 1 || args.n > kDynamicMaxSteps) return hipErrorInvalidValue;
   if (args.regenerate && (args.centre == nullptr || args.spec.segments == nullptr || args.u_extra != nullptr))
     return hipErrorInvalidValue;
@@ -891,14 +925,20 @@ hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const V
   if (vehicles.K == 1) {
     const Vehicle& vehicle = vehicles.v[0];
     const size_t lds = (rec_pad + tables) * sizeof(float);
-    if (layout == 0) hipLaunchKernelGGL((finalize_dynamic_kernel<0>), dim3(args.P), dim3(kWave), lds, s, args, vehicle);
-    else hipLaunchKernelGGL((finalize_dynamic_kernel<1>), dim3(args.P), dim3(kWave), lds, s, args, vehicle);
+    with_integration_kind(g, [&](auto fine) {
+      constexpr bool kFine = decltype(fine)::value;
+      if (layout == 0) hipLaunchKernelGGL((finalize_dynamic_kernel<0, kFine>), dim3(args.P), dim3(kWave), lds, s, args, vehicle, g);
+      else hipLaunchKernelGGL((finalize_dynamic_kernel<1, kFine>), dim3(args.P), dim3(kWave), lds, s, args, vehicle, g);
+    });
     return hipGetLastError();
   }
   const size_t lds = (rec_pad + 2 * kMaxVehicles + tables) * sizeof(float);
   const dim3 block(kWave * vehicles.K);
-  if (layout == 0) hipLaunchKernelGGL((finalize_dynamic_ensemble_kernel<0>), dim3(args.P), block, lds, s, args, vehicles);
-  else hipLaunchKernelGGL((finalize_dynamic_ensemble_kernel<1>), dim3(args.P), block, lds, s, args, vehicles);
+  with_integration_kind(g, [&](auto fine) {
+    constexpr bool kFine = decltype(fine)::value;
+    if (layout == 0) hipLaunchKernelGGL((finalize_dynamic_ensemble_kernel<0, kFine>), dim3(args.P), block, lds, s, args, vehicles, g);
+    else hipLaunchKernelGGL((finalize_dynamic_ensemble_kernel<1, kFine>), dim3(args.P), block, lds, s, args, vehicles, g);
+  });
   return hipGetLastError();
 }
 

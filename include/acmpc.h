@@ -239,6 +239,24 @@ int acmpc_set_dynamics(acmpc_ctx* ctx, const double* coef, int32_t count);
 #define ACMPC_ENSEMBLE_MAX 1
 int acmpc_set_dynamics_ensemble(acmpc_ctx* ctx, const double* coef, int32_t K, const double* weights, int32_t reduce);
 
+/* Mode D's integration setting: how a control step of dt is integrated.  Off by default - (1, 0, 0): one explicit Euler
+ * step, the reference's - and independent of the vehicle: it survives acmpc_set_dynamics and acmpc_set_dynamics_ensemble
+ * and applies to every member of an ensemble with that member's lf, lr.
+ *   substeps   M in 1 .. ACMPC_MAX_SUBSTEPS: M Euler steps of h = float32(dt / M) (the quotient in float64, rounded
+ *              once; M = 1: h == dt) under the same (delta, pedal), vx clipped at 0 after each.  Nearest waypoint, cost,
+ *              the record's x row and the terminal cost stay once per control step, on the state after the M-th.
+ *   blend      [blend_lo, blend_hi] m/s with 0 <= blend_lo < blend_hi, both finite; 0, 0 is off.  After each sub-step,
+ *              lam = clamp((vx - blend_lo) / (blend_hi - blend_lo), 0, 1) and (vy, r) become lam (vy, r) + (1 - lam)
+ *              (lr r_k, r_k) with r_k = vx tan(delta) / (lf + lr), the kinematic bicycle's: the dynamic model above
+ *              blend_hi bit for bit, the kinematic one below blend_lo.
+ * The single Euler step is linearly unstable below about 7.5 m/s for the default vehicle and chatters up to about 12:
+ * turn this on (4 sub-steps, blend 3 .. 5) for plans that can fall below that.  Every call form of mode D takes it from
+ * the handle.  No device work.  ACMPC_EINVAL for a handle whose mode is not ACMPC_MODE_DYNAMIC, substeps outside
+ * 1 .. ACMPC_MAX_SUBSTEPS, or a blend that is neither 0, 0 nor 0 <= lo < hi finite; the handle then keeps its previous
+ * setting.  DESIGN.md section 2 "Mode D", "Sub-steps and the low-speed blend". */
+#define ACMPC_MAX_SUBSTEPS 16
+int acmpc_set_dynamics_integration(acmpc_ctx* ctx, int32_t substeps, double blend_lo, double blend_hi);
+
 /* Copies the packed float32 table of problem `problem` (n rows of ACMPC_COEF_STRIDE_* floats) to `out`.
  * Host only; lets CPU tests pin the host-side arithmetic against the oracle. */
 int acmpc_get_coefficients(const acmpc_ctx* ctx, int32_t problem, float* out, int32_t capacity_floats);

@@ -28,7 +28,13 @@ acmpc_sample_device, acmpc_solve_device with costs and keys, acmpc_softmin_devic
 4 096 x 4 096 x 49; the two softmin calls alone too; median, minimum and maximum of the repetitions (device events).
 `--out PATH` also writes the JSON there.
 
-usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--sampled | --optimize [--update softmin]]"""
+With `--substeps M` and / or `--blend LO,HI` every handle is given that integration setting (acmpc_set_dynamics_integration:
+M Euler sub-steps per control step, the low-speed blend between LO and HI m/s); rates still count CONTROL steps.  The rollout's
+vector-issue roof then prices the FINE kernels' mix: the step loop's own trip (`dynamic_fine_step`) plus M trips of the
+sub-step loop (`dynamic_fine_substep`, whose static count holds the blend's block whether or not the blend is on).
+
+usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI]
+                                      [--sampled | --optimize [--update softmin]]"""
 import argparse
 import json
 import os
@@ -42,10 +48,35 @@ for _p in (ROOT, os.path.join(ROOT, "ac-mpc_amd"), os.path.join(ROOT, "oracle"),
     sys.path.insert(0, _p)
 
 
+INTEGRATION = (1, None)   # (--substeps, --blend): what every handle of this run is set to
+
+
+def integrate(eng):
+    """The run's integration setting on a new handle (a library without the entry point takes only the default)."""
+    if INTEGRATION != (1, None):
+        eng.set_dynamics_integration(*INTEGRATION)
+    return eng
+
+
+def fine_issue_roof(bench, candidates, steps, kernel_s, name):
+    """issue_roof for a FINE kernel: VALU per control step = the step loop's trip + M sub-step trips, priced with the
+    sub-step loop's mix (which is nearly all of it)."""
+    mix, mix_path = bench.newest_profile("isa_mix.json")
+    step, sub = mix["entries"][name + "_fine_step"], mix["entries"][name + "_fine_substep"]
+    per_step = (sum(step["valu"].values()) + INTEGRATION[0] * sum(sub["valu"].values())) / float(sub["candidates_per_lane"])
+    counted = (per_step, mix_path + " (static count: step trip + M sub-step trips)", {"source_sha256": mix.get("source_sha256")})
+    roof, _ = bench.valu_roofline(counted, candidates, steps, kernel_s, mix_entry=name + "_fine_substep",
+                                  cpt=sub["candidates_per_lane"])
+    roof["substep_count_holds_the_blend_block"] = True
+    return roof
+
+
 def issue_roof(bench, candidates, steps, kernel_s, name="dynamic"):
     """bench.valu_roofline for the `dynamic` entry (`dynamic_ensemble`: candidates = vehicle-candidates): the step loop's
     static VALU count per candidate-step (the isa mix, whose sources must be the loaded build's -
     `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
+    if INTEGRATION != (1, None) and name in ("dynamic", "dynamic_ensemble"):
+        return fine_issue_roof(bench, candidates, steps, kernel_s, name)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     entry = mix["entries"][name]
     per_step = sum(entry["valu"].values()) / float(entry["candidates_per_lane"])
@@ -66,7 +97,11 @@ def main():
     ap.add_argument("--update", default="argmin", choices=("argmin", "softmin"),
                     help="with --optimize: softmin = one softmin round, matrix-free against through the matrix")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--substeps", type=int, default=1, help="Euler sub-steps per control step (1 .. 16)")
+    ap.add_argument("--blend", default=None, help="LO,HI m/s: the low-speed blend")
     args = ap.parse_args()
+    global INTEGRATION
+    INTEGRATION = (args.substeps, None if args.blend is None else tuple(float(v) for v in args.blend.split(",")))
     if args.update == "softmin" and not args.optimize:
         ap.error("--update softmin goes with --optimize")
     if args.sampled or args.optimize:
@@ -117,7 +152,7 @@ def _engine(dp, P, N, n, K, reduce, stream, **extra):
         eng.set_dynamics_ensemble([DynamicBicycleParams.reference().with_grip(g) for g in GRIPS[:K]], reduce=reduce)
     eng.set_paths(np.repeat(dp["table"][None], P, axis=0))
     eng.sync_tables(stream)
-    return eng
+    return integrate(eng)
 
 
 def _centre(dp, P, n):
@@ -311,6 +346,8 @@ def measure(args, K):
     s = torch.cuda.current_stream().cuda_stream
     reps = 3 if args.quick else args.reps
     out = {"tool": "tools/bench_dynamic.py", "horizon": H, "search": "window (2, 5)"}
+    if INTEGRATION != (1, None):
+        out.update(substeps=INTEGRATION[0], low_speed_blend=INTEGRATION[1])
     if K > 1:
         out.update(vehicles=K, reduce=args.reduce, grips=list(GRIPS[:K]))
 
@@ -324,7 +361,7 @@ def measure(args, K):
                                       reduce=args.reduce)
         eng.set_paths(np.repeat(dp["table"][None], P, axis=0))
         eng.sync_tables(s)
-        return eng
+        return integrate(eng)
 
     def controls(P, N):
         g = torch.Generator(device=dev).manual_seed(7)

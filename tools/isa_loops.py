@@ -2,14 +2,16 @@
 """Development aid: opcode histogram of every innermost loop (a label that a later branch of the same kernel jumps
 back to, with no other such label in between) of one kernel in a hipcc --save-temps .s file.  With --outer: of every loop
 that HAS loops inside it, less the instructions of those - a step loop whose trip now and then runs a loop of its own.
-usage: isa_loops.py file.s <mangled-name-substring> [--json] [--outer]"""
+With --rotated: innermost loops as without it, those that close with an unconditional s_branch included (a loop with its
+exit test at its head, such as mode D's sub-step loop inside the step loop).
+usage: isa_loops.py file.s <mangled-name-substring> [--json] [--outer | --rotated]"""
 import collections
 import json
 import re
 import sys
 
 
-def loops(path, needle, outer=False):
+def loops(path, needle, outer=False, rotated=False):
     lines = open(path).read().split("\n")
     start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and needle in l and ":" in l)
     end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith("s_endpgm"))
@@ -23,7 +25,7 @@ def loops(path, needle, outer=False):
     for i, l in enumerate(body):
         t = l.strip().split()
         # (a rotated loop - exit test at its head - closes with an unconditional s_branch: the step loops that --outer is for)
-        closes = t[0].startswith("s_cbranch") or (outer and t[0] == "s_branch") if t else False
+        closes = t[0].startswith("s_cbranch") or ((outer or rotated) and t[0] == "s_branch") if t else False
         if len(t) == 2 and closes and t[1] in where and where[t[1]] < i:
             found.append((where[t[1]], i, t[1]))
     # (a backward branch between the flow blocks of a scalar if-chain - s_setprio by quarter of the horizon - is not a loop
@@ -53,7 +55,7 @@ def loops(path, needle, outer=False):
 
 
 if __name__ == "__main__":
-    result = loops(sys.argv[1], sys.argv[2], outer="--outer" in sys.argv)
+    result = loops(sys.argv[1], sys.argv[2], outer="--outer" in sys.argv, rotated="--rotated" in sys.argv)
     if "--json" in sys.argv:
         print(json.dumps({label: dict(h) for label, h in result}, indent=1))
     else:

@@ -31,17 +31,26 @@ ENTRIES = {
     "fused_round": ("acmpc_kernels.hip", "rollout_sampled_kernelILi0E", None),
     # mode D (the dynamic bicycle, two candidates per lane, step-major): the largest step loop - a windowed search's, whose
     # trip is the dynamics + an unrolled window + the cost; the exhaustive form adds its waypoint loop to the same trip
-    "dynamic": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2EE", None),
+    "dynamic": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2ELb0EE", None),
     # mode D with an ensemble of vehicles (one wavefront per vehicle): the same step loop under wave k's vehicle
-    "dynamic_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2EE", None),
+    "dynamic_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb0EE", None),
     # mode D drawing its own candidates (two per lane): the same step loop with the blend of the step's control in front.
     # The loop holds the Philox draws as loops of its own, run on at most seven of a rollout's trips: the mix is the trip
     # without them (OUTER)
-    "dynamic_sampled": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_kernelILi2EE", None),
-    "dynamic_sampled_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_ensemble_kernelILi2EE", None),
+    "dynamic_sampled": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_kernelILi2ELb0EE", None),
+    "dynamic_sampled_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_ensemble_kernelILi2ELb0EE", None),
+    # mode D with an integration setting (the FINE kernels): a control step is the step loop's own trip - the control's
+    # terms, the search, the cost (`_step`: the trip less its inner loop, OUTER) - plus M trips of the sub-step loop, the
+    # dynamics and the blend (`_substep`, the largest innermost loop, the blend's block counted): VALU per control step =
+    # step + M substep
+    "dynamic_fine_step": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2ELb1EE", None),
+    "dynamic_fine_substep": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2ELb1EE", None),
+    "dynamic_ensemble_fine_step": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EE", None),
+    "dynamic_ensemble_fine_substep": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EE", None),
 }
 CANDIDATES_PER_LANE = {"fused_round": 1}
-OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble")
+OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dynamic_ensemble_fine_step")
+ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep")   # (exit test at the head: closes with s_branch)
 
 
 def source_hash():
@@ -71,7 +80,7 @@ def main():
         for entry, (source, kernel, signature) in ENTRIES.items():
             if source not in cache:
                 cache[source] = assembly(source, scratch)
-            every = loops(cache[source], kernel, outer=entry in OUTER)
+            every = loops(cache[source], kernel, outer=entry in OUTER, rotated=entry in ROTATED)
             if signature is None:
                 found = [max(every, key=lambda lh: sum(lh[1].values()))]
             else:
