@@ -150,6 +150,8 @@ SIGNATURES = {
     "acmpc_set_dynamics": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
     "acmpc_set_dynamics_ensemble": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "acmpc_set_dynamics_integration": (C.c_int, [_CTX, C.c_int32, C.c_double, C.c_double]),
+    "acmpc_set_dynamics_terms": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
+    "acmpc_set_previous_control": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
     "acmpc_get_coefficients": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_set_coefficients": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_record_floats": (C.c_int32, [C.c_int32]),
@@ -459,6 +461,30 @@ def integration_setting(substeps=1, low_speed_blend=None):
     return int(substeps), lo, hi
 
 
+def dynamics_terms(rate_weight=(0.0, 0.0), rate_max=None, slip_weight=0.0, slip_max=None):
+    """Mode D's rate and slip terms checked as acmpc_set_dynamics_terms checks them: (rate_weight [2], rate_max [2],
+    slip_weight, slip_max) in float64, a limit of None (or None inside rate_max) as +inf.  ValueError for a weight that is
+    negative or not finite (as a float32), or a limit that is not > 0."""
+    try:
+        w = [float(v) for v in rate_weight]
+        m = [np.inf, np.inf] if rate_max is None else [np.inf if v is None else float(v) for v in rate_max]
+        sw = float(slip_weight)
+        sm = np.inf if slip_max is None else float(slip_max)
+    except (TypeError, ValueError):
+        raise ValueError("the rate and slip terms are (delta, pedal) pairs of numbers and two numbers, not %r"
+                         % ((rate_weight, rate_max, slip_weight, slip_max),)) from None
+    if len(w) != 2 or len(m) != 2:
+        raise ValueError("rate_weight and rate_max are (delta, pedal) pairs")
+    with np.errstate(over="ignore"):
+        for v in (w[0], w[1], sw):
+            if not (np.isfinite(np.float32(v)) and v >= 0.0):
+                raise ValueError("a weight of the rate and slip terms is finite and >= 0, not %r" % (v,))
+        for v in (m[0], m[1], sm):
+            if not np.float32(v) > 0.0:
+                raise ValueError("a limit of the rate and slip terms is > 0 (None: no limit), not %r" % (v,))
+    return np.array(w, dtype=np.float64), np.array(m, dtype=np.float64), sw, sm
+
+
 class Engine:
     """Owns one acmpc_ctx.  Construction does no device work (fork-safe, controller.py:293-297)."""
 
@@ -564,6 +590,27 @@ class Engine:
         or None.  The default (1, None) is the reference's single step; the setting outlives a change of vehicle."""
         m, lo, hi = integration_setting(substeps, low_speed_blend)
         self._check(self._lib.acmpc_set_dynamics_integration(self._ctx, m, lo, hi))
+
+    def set_dynamics_terms(self, rate_weight=(0.0, 0.0), rate_max=None, slip_weight: float = 0.0, slip_max=None):
+        """Mode D's rate and slip terms (acmpc_set_dynamics_terms): `rate_weight` = (delta, pedal) weights of the squared
+        control rates (1/s), `rate_max` their limits or None, `slip_weight` / `slip_max` the same for the rear slip ratio
+        (r lr - vy) / vx.  A candidate over a limit is infeasible.  The defaults switch everything off; the setting
+        outlives a change of vehicle or of the integration setting."""
+        w, m, sw, sm = dynamics_terms(rate_weight, rate_max, slip_weight, slip_max)
+        self._check(self._lib.acmpc_set_dynamics_terms(self._ctx, w.ctypes.data, m.ctypes.data, sw, sm))
+
+    def set_previous_control(self, u_prev=None):
+        """The control applied just before the plans start (acmpc_set_previous_control): [P, 2] (or [2]) = (delta, pedal),
+        what step 0's rates are taken against; None clears it.  It stays until replaced or cleared."""
+        if u_prev is None:
+            self._check(self._lib.acmpc_set_previous_control(self._ctx, None, 0))
+            return
+        u = np.ascontiguousarray(u_prev, dtype=np.float32)
+        if u.ndim == 1:
+            u = u[None]
+        if u.ndim != 2 or u.shape[1] != 2:
+            raise ValueError("u_prev must be [P, 2]")
+        self._check(self._lib.acmpc_set_previous_control(self._ctx, u.ctypes.data, u.shape[0]))
 
     def set_coefficients(self, coef: np.ndarray):
         """The packed float32 tables themselves, [P, n, 12] (mode S) / [P, n, 8] (mode T) or one [n, stride] table

@@ -148,3 +148,24 @@ class DynamicBicycleParams:
                     nxt[5] = lam * nxt[5] + (1.0 - lam) * r_k
             out.append(nxt)
         return np.stack(out)
+
+
+def stage_terms(states, U, dt: float, u_prev, params: DynamicBicycleParams, rate_weight=(0.0, 0.0), rate_max=None,
+                slip_weight: float = 0.0, slip_max=None) -> Tuple[float, float]:
+    """The rate and slip terms of acmpc_set_dynamics_terms in float64 over `states` [n + 1, 6] = params.rollout(state, U, ...)
+    and U [n, 2]: (E, extra_V) with E = 1/2 sum_i (w_d rd_i^2 + w_p rp_i^2 + w_s b_i^2) and extra_V the summed squared
+    excesses over the limits (None: no limit), rd_i = (delta_i - delta_{i-1}) / dt, rp_i likewise - step 0 against
+    `u_prev`, or a zero increment without one - and b_i = (r lr - vy) / (vx + 1e-3) on states[i + 1]."""
+    U = np.asarray(U, dtype=np.float64)
+    states = np.asarray(states, dtype=np.float64)
+    first = U[0] if u_prev is None else np.asarray(u_prev, dtype=np.float64)
+    rates = np.diff(np.concatenate([first[None], U]), axis=0) / dt
+    b = (states[1:, 5] * params.lr - states[1:, 4]) / (states[1:, 3] + 1e-3)
+    limits = [np.inf, np.inf] if rate_max is None else [np.inf if v is None else float(v) for v in rate_max]
+    limits.append(np.inf if slip_max is None else float(slip_max))
+    weights = (float(rate_weight[0]), float(rate_weight[1]), float(slip_weight))
+    E, V = 0.0, 0.0
+    for w, limit, a in zip(weights, limits, (rates[:, 0], rates[:, 1], b)):
+        E += 0.5 * w * float(np.sum(a * a))
+        V += float(np.sum(np.maximum(np.abs(a) - limit, 0.0) ** 2))
+    return E, V

@@ -19,7 +19,13 @@ how the costs combine.  The two ensemble keys are mutually exclusive; with neith
 Integration (acmpc_set_dynamics_integration): `rollout_substeps` (default 1) Euler steps per control step and
 `low_speed_blend` (default None, or (v_lo, v_hi) m/s: below v_hi the lateral velocity and the yaw rate go over to the
 kinematic bicycle's).  The single step is unstable below about 7.5 m/s and chatters up to about 12: set
-`rollout_substeps: 4, low_speed_blend: (3, 5)` whenever a plan can fall below that (a hairpin, a pit lane, a start)."""
+`rollout_substeps: 4, low_speed_blend: (3, 5)` whenever a plan can fall below that (a hairpin, a pit lane, a start).
+
+Rate and slip terms (acmpc_set_dynamics_terms): `rate_cost` = (delta, pedal) weights of the squared control rates (per
+second), `rate_limit` = their limits (None, or a pair whose members may be None), `slip_cost` / `slip_limit` the same for
+the rear slip ratio (r lr - vy) / vx.  A candidate over a limit is infeasible, as one outside the input box is.  Step 0's
+rate is taken against the control applied before the plan: `solve(..., previous_control=)`, by default the first control
+of the last accepted plan - what a caller that applies the plans has just applied; none on the first solve."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -75,6 +81,8 @@ class DynamicSamplingSolver:
         self._params = params if params is not None else DynamicBicycleParams.reference()
         vehicles = ensemble_vehicles(config, self._params)   # (a config error raises before any handle exists)
         integration = _capi.integration_setting(config.get("rollout_substeps", 1), config.get("low_speed_blend"))
+        terms = _capi.dynamics_terms(config.get("rate_cost", (0.0, 0.0)), config.get("rate_limit"),
+                                     config.get("slip_cost", 0.0), config.get("slip_limit"))
         self._centre_update = config.get("sampling_update", "argmin")   # or "softmin" (MPPI-style weighted mean)
         if self._centre_update not in SAMPLING_UPDATES:
             raise ValueError("sampling_update is 'argmin' or 'softmin', not %r" % (self._centre_update,))
@@ -97,6 +105,9 @@ class DynamicSamplingSolver:
                                                config.get("ensemble_reduce", "mean"))
         if integration != (1, 0.0, 0.0):
             self._engine.set_dynamics_integration(integration[0], integration[1:] if integration[2] > 0.0 else None)
+        self._rate_terms = bool(np.any(terms[0] != 0.0) or np.any(np.isfinite(terms[1])))
+        if self._rate_terms or terms[2] != 0.0 or np.isfinite(terms[3]):
+            self._engine.set_dynamics_terms(*terms)
         self._plan: Optional[np.ndarray] = None
         self._calls = 0
 
@@ -110,9 +121,10 @@ class DynamicSamplingSolver:
             return np.zeros((self._n, 2), dtype=np.float32)
         return np.concatenate([self._plan[1:], self._plan[-1:]]).astype(np.float32)
 
-    def solve(self, state, reference_path):
+    def solve(self, state, reference_path, previous_control=None):
         """state (X, Y, yaw, vx, vy, r); reference_path a [7, n] table (rows x, y, psi, kappa, ds, width, v) or an object
-        with `as_table()` / `_reference_path` giving one."""
+        with `as_table()` / `_reference_path` giving one.  `previous_control` = (delta, pedal) applied just before this
+        solve, for the rate terms' step 0; None: the first control of the last accepted plan (none before there is one)."""
         table = reference_path
         if hasattr(reference_path, "as_table"):
             table = reference_path.as_table()
@@ -120,6 +132,10 @@ class DynamicSamplingSolver:
             table = reference_path._reference_path
         table = np.asarray(table, dtype=np.float64)[:, : self._n]
         self._engine.set_paths(table)
+        if self._rate_terms:
+            if previous_control is None and self._plan is not None:
+                previous_control = self._plan[0]
+            self._engine.set_previous_control(previous_control)
         out = self._engine.optimize(np.asarray(state, dtype=np.float32).reshape(1, 6), self.warm_start()[None], None,
                                     self._N, self._rounds, self._sigma, seed=self._seed + self._calls)
         self._calls += 1
@@ -130,7 +146,8 @@ class DynamicSamplingSolver:
             self._plan = u.astype(np.float32)
         status = SOLVED if ok else "failed"
         return SimpleNamespace(x=np.concatenate([x.ravel(), u.ravel()]), info=SimpleNamespace(status=status),
-                               cost=float(out["cost"][0]), violation=float(out["violation"][0]))
+                               cost=float(out["cost"][0]), violation=float(out["violation"][0]),
+                               n_feasible=int(out["n_feasible"][0]))
 
     def close(self):
         self._engine.close()

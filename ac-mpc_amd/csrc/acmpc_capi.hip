@@ -178,6 +178,14 @@ struct acmpc_ctx {
   int substeps = 1;
   double blend_lo = 0.0, blend_hi = 0.0;
   double vehicle_L[acmpc::kMaxVehicles] = {};   // lf + lr of each vehicle in float64: the blend's 1 / L is rounded from it
+  // mode D: the rate and slip terms (acmpc_set_dynamics_terms), kept apart like the integration setting: weights 0 and
+  // limits +inf = off; and the previous control (acmpc_set_previous_control), staged here until the next upload_tables
+  double rate_weight[2] = {0.0, 0.0}, rate_max[2] = {HUGE_VAL, HUGE_VAL};
+  double slip_weight = 0.0, slip_max = HUGE_VAL;
+  std::vector<float> h_uprev;   // [uprev_P][2]
+  int uprev_P = 0;              // 0: none set
+  bool uprev_dirty = false;
+  float* d_uprev = nullptr;     // [max_problems][2]
 
   mutable std::string err;
 };
@@ -294,12 +302,23 @@ int ensure_device(acmpc_ctx* c) {
     ACMPC_HIP(c, alloc_once(&c->d_nn_frames, static_cast<size_t>(p.max_problems) * sizeof(float) *
                                                  acmpc::verified_frame_floats(std::max(std::min(p.max_steps, kMaxVerifiedSteps),
                                                                                        acmpc::kVerifiedWindow))));
+  if (p.mode == ACMPC_MODE_DYNAMIC) ACMPC_HIP(c, alloc_once(&c->d_uprev, static_cast<size_t>(p.max_problems) * 2 * sizeof(float)));
   c->device_ready = true;
+  return ACMPC_OK;
+}
+
+// mode D: the previous control staged by acmpc_set_previous_control goes up on the stream of the call that reads it
+int upload_previous_control(acmpc_ctx* c, hipStream_t s) {
+  if (!c->uprev_dirty || c->uprev_P == 0 || c->d_uprev == nullptr) return ACMPC_OK;
+  ACMPC_HIP(c, hipMemcpyAsync(c->d_uprev, c->h_uprev.data(), c->h_uprev.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  c->uprev_dirty = false;
   return ACMPC_OK;
 }
 
 int upload_tables(acmpc_ctx* c, hipStream_t s) {
   if (c->P_set == 0) return fail(c, ACMPC_ESTATE, "acmpc_set_paths has not been called");
+  const int rc_prev = upload_previous_control(c, s);
+  if (rc_prev != ACMPC_OK) return rc_prev;
   // pageable source: hipMemcpyAsync stages it before returning, so the host vectors may change afterwards.  (Round 4 tried
   // a page-locked staging block for small tables - a memcpy and a true asynchronous packet: 0.7 us of a 91 us
   // set_paths + solve, not worth the bookkeeping of when the block is free again.)
@@ -347,7 +366,31 @@ int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call 
                   c->n_set);
     return fail(c, ACMPC_EINVAL, buf);
   }
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC && c->uprev_P != 0 && P != c->uprev_P) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "P=%d does not match the previous controls set (P=%d): acmpc_set_previous_control", P,
+                  c->uprev_P);
+    return fail(c, ACMPC_ESTATE, buf);
+  }
   return ACMPC_OK;
+}
+
+// mode D: the kernels' view of the handle's rate and slip terms - every float derived in float64 and rounded once
+// ("Rate and slip terms").  A part whose weights are 0 and whose limits are +inf is off.
+acmpc::Terms dynamics_terms(const acmpc_ctx* c) {
+  acmpc::Terms t{};
+  t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
+            std::isfinite(c->rate_max[1])) ? 1 : 0;
+  t.slip = (c->slip_weight != 0.0 || std::isfinite(c->slip_max)) ? 1 : 0;
+  t.inv_dt = static_cast<float>(1.0 / c->prm.dt);
+  t.hwd = 0.5f * static_cast<float>(c->rate_weight[0]);
+  t.hwp = 0.5f * static_cast<float>(c->rate_weight[1]);
+  t.hws = 0.5f * static_cast<float>(c->slip_weight);
+  t.rd_max = static_cast<float>(c->rate_max[0]);
+  t.rp_max = static_cast<float>(c->rate_max[1]);
+  t.b_max = static_cast<float>(c->slip_max);
+  t.u_prev = (t.rate != 0 && c->uprev_P != 0) ? c->d_uprev : nullptr;
+  return t;
 }
 
 // mode D: the kernels' view of the handle's integration setting, for the vehicles it has now - every float derived in
@@ -380,7 +423,7 @@ int rollout(acmpc_ctx* c, const float* d_x0, const float* d_U, int P, int N, int
     a.n = n;
     a.index_offset = offset;
     a.w = c->w;
-    ACMPC_HIP(c, acmpc::launch_rollout_dynamic(layout, a, c->vehicles, dynamics_integration(c), s));
+    ACMPC_HIP(c, acmpc::launch_rollout_dynamic(layout, a, c->vehicles, dynamics_integration(c), dynamics_terms(c), s));
     *shape_out = acmpc::LaunchShape{};
     shape_out->blocks_per_problem = acmpc::dynamic_blocks_per_problem(P, N, c->vehicles.K);
     return ACMPC_OK;
@@ -458,7 +501,9 @@ int finalize(acmpc_ctx* c, const int64_t* d_keys_in, int64_t* d_keys_out, const 
   a.index_offset = offset;
   a.w = c->w;
   if (c->prm.mode == ACMPC_MODE_DYNAMIC) {
-    ACMPC_HIP(c, acmpc::launch_finalize_dynamic(layout, a, c->vehicles, dynamics_integration(c), s));
+    const int rc_prev = upload_previous_control(c, s);   // (a finalize follows a rollout that has brought it up already)
+    if (rc_prev != ACMPC_OK) return rc_prev;
+    ACMPC_HIP(c, acmpc::launch_finalize_dynamic(layout, a, c->vehicles, dynamics_integration(c), dynamics_terms(c), s));
     return ACMPC_OK;
   }
   ACMPC_HIP(c, acmpc::launch_finalize(c->prm.mode, layout, a, s, c->opt));
@@ -559,7 +604,7 @@ int rollout_sampled_dynamic(acmpc_ctx* c, const float* d_x0, const float* d_cent
   smp.n = n;
   smp.index_offset = offset;
   smp.spec = make_spec(c, sigma_d, sigma_p, seed, round);
-  ACMPC_HIP(c, acmpc::launch_rollout_dynamic_sampled(a, smp, c->vehicles, dynamics_integration(c), s));
+  ACMPC_HIP(c, acmpc::launch_rollout_dynamic_sampled(a, smp, c->vehicles, dynamics_integration(c), dynamics_terms(c), s));
   return ACMPC_OK;
 }
 
@@ -972,6 +1017,7 @@ void acmpc_destroy(acmpc_ctx* c) {
     (void)hipFree(c->d_partial_feas);
     (void)hipFree(c->d_soft_partial);
     (void)hipFree(c->d_segments);
+    (void)hipFree(c->d_uprev);
     (void)hipFree(c->d_centre);
     (void)hipFree(c->d_uref);
     (void)hipFree(c->d_U);
@@ -1507,6 +1553,45 @@ int acmpc_set_dynamics_integration(acmpc_ctx* c, int32_t substeps, double blend_
   c->substeps = substeps;
   c->blend_lo = off ? 0.0 : blend_lo;   // (-0.0 is 0)
   c->blend_hi = off ? 0.0 : blend_hi;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_terms(acmpc_ctx* c, const double rate_weight[2], const double rate_max[2], double slip_weight,
+                             double slip_max) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics_terms needs a mode D handle");
+  if (rate_weight == nullptr || rate_max == nullptr) return fail(c, ACMPC_EINVAL, "null rate_weight or rate_max");
+  const double weights[3] = {rate_weight[0], rate_weight[1], slip_weight};
+  const double limits[3] = {rate_max[0], rate_max[1], slip_max};
+  for (int q = 0; q < 3; ++q) {
+    // float32 is what the kernels get: a weight that overflows it is not finite there
+    if (!std::isfinite(static_cast<float>(weights[q])) || !(weights[q] >= 0.0))
+      return fail(c, ACMPC_EINVAL, "a weight of the rate and slip terms must be finite and >= 0");
+    if (!(static_cast<float>(limits[q]) > 0.0f)) return fail(c, ACMPC_EINVAL, "a limit of the rate and slip terms must be > 0 (INFINITY: none)");
+  }
+  // everything is checked before anything is kept: a refused setting leaves the handle's as it was
+  for (int q = 0; q < 2; ++q) {
+    c->rate_weight[q] = weights[q] + 0.0;   // (-0.0 is 0)
+    c->rate_max[q] = limits[q];
+  }
+  c->slip_weight = slip_weight + 0.0;
+  c->slip_max = slip_max;
+  return ACMPC_OK;
+}
+
+int acmpc_set_previous_control(acmpc_ctx* c, const float* u_prev, int32_t P) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_previous_control needs a mode D handle");
+  if (u_prev == nullptr) {
+    c->h_uprev.clear();
+    c->uprev_P = 0;
+    c->uprev_dirty = false;
+    return ACMPC_OK;
+  }
+  if (P < 1 || P > c->prm.max_problems) return fail(c, ACMPC_EINVAL, "P must be 1 .. max_problems");
+  c->h_uprev.assign(u_prev, u_prev + static_cast<size_t>(P) * 2);
+  c->uprev_P = P;
+  c->uprev_dirty = true;
   return ACMPC_OK;
 }
 

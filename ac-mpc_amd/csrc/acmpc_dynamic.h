@@ -199,7 +199,8 @@ __device__ __forceinline__ void dynamic_advance(StateD_<F>& s, F delta, F pedal,
 // low-speed blend"): a control step of dt is `substeps` Euler steps of h = float32(dt / substeps) under the same control,
 // and after each of them (vy, r) is blended towards the kinematic bicycle's r_k = vx tan(delta) / L, vy_k = lr r_k below
 // v_hi, entirely below v_lo.  The host derives every float in float64 and rounds it once.  (1, no blend) is the default
-// and runs the kernels without any of this (their FINE = false instantiations); anything else their FINE = true ones.
+// and runs the kernels without any of this (their FINE = false instantiations); anything else their FINE = true ones,
+// and the kernels with the rate and slip terms (Terms, below).
 constexpr int kMaxSubsteps = 16;   // ACMPC_MAX_SUBSTEPS
 struct Integration {
   int substeps;                 // M
@@ -242,6 +243,73 @@ __device__ __forceinline__ void dynamic_control_step(StateD_<F>& s, F delta, F p
   else dynamic_advance<F>(s, delta, pedal, k, dt);
 }
 
+// The rate and slip terms of a handle (acmpc_set_dynamics_terms, DESIGN.md section 2 "Mode D", "Rate and slip terms"): per
+// control step, after dynamic_cost, the squared rates of the two controls and the squared rear slip ratio
+// b = (r lr - vy) / (vx + 1e-3) join a third cost sum E, and their excesses over the limits join V.  The host derives every
+// float in float64 and rounds it once; a limit of +inf is no limit.  Two parts, each off (0) when its weights are 0 and
+// its limits +inf: a part that is off executes nothing, and with both off the handle launches the kernels it would
+// without the setting.  u_prev: the control applied before step 0, [P][2] on the device, or nullptr (step 0's own control
+// then stands for it: an increment of +0); not read while the rate part is off.  A kernel argument: SGPRs, and the
+// branches on it are scalar.  The kernels take it as a parameter pack `TM... tm` that is empty or one Terms, and touch
+// nothing of this under an empty one (`if constexpr`): those are the code they were.  The terms have kernels of their own (the general step of FINE = true plus this), launched
+// only when a part is on, and a translation unit of their own (acmpc_dynamic_terms.hip).
+struct Terms {
+  int rate, slip;
+  float inv_dt;                 // float32(1 / dt)
+  float hwd, hwp, hws;          // 0.5f * float32(weight): exact
+  float rd_max, rp_max, b_max;
+  const float* u_prev;
+};
+__host__ __device__ inline bool has_terms(const Terms& t) { return t.rate != 0 || t.slip != 0; }
+
+// what the terms carry from step to step: the previous step's control and the cost sum
+template <typename F>
+struct TermsState {
+  F pd, pp, E;
+};
+template <typename F>
+__device__ __forceinline__ TermsState<F> start_terms(int p, const Terms& t) {
+  TermsState<F> ts{splat<F>(0.0f), splat<F>(0.0f), splat<F>(0.0f)};
+  if (t.rate != 0 && t.u_prev != nullptr) {   // (a wave-uniform address: one scalar load per wave)
+    ts.pd = splat<F>(t.u_prev[2 * p]);
+    ts.pp = splat<F>(t.u_prev[2 * p + 1]);
+  }
+  return ts;
+}
+
+// `state_of(ts, tm)..., tm...` hands a function the state and the Terms where the pack holds them, nothing where it is empty
+template <typename F>
+__device__ __forceinline__ TermsState<F>& state_of(TermsState<F>& ts, const Terms&) {
+  return ts;
+}
+
+// the terms of one control step, on the state the step's dynamic_cost saw; `first`: step 0
+template <typename F>
+__device__ __forceinline__ void dynamic_terms(StateD_<F>& s, F delta, F pedal, bool first, const Vehicle& k,
+                                              TermsState<F>& ts, const Terms& t) {
+  if (t.rate != 0) {
+    const bool own = first && t.u_prev == nullptr;
+    const F pd = own ? delta : ts.pd;
+    const F pp = own ? pedal : ts.pp;
+    const F rd = (delta - pd) * t.inv_dt;
+    const F rp = (pedal - pp) * t.inv_dt;
+    ts.E = fma_(t.hwd * rd, rd, ts.E);
+    ts.E = fma_(t.hwp * rp, rp, ts.E);
+    const F hd = vmax(abs_(rd) - t.rd_max, splat<F>(0.0f));
+    s.t.V = fma_(hd, hd, s.t.V);
+    const F hp = vmax(abs_(rp) - t.rp_max, splat<F>(0.0f));
+    s.t.V = fma_(hp, hp, s.t.V);
+    ts.pd = delta;
+    ts.pp = pedal;
+  }
+  if (t.slip != 0) {
+    const F b = (s.r * k.lr - s.vy) / (s.vx + kVxEps);   // dynamic_euler's qr, on the updated state
+    ts.E = fma_(t.hws * b, b, ts.E);
+    const F hb = vmax(abs_(b) - t.b_max, splat<F>(0.0f));
+    s.t.V = fma_(hb, hb, s.t.V);
+  }
+}
+
 // mode T's temporal_cost with the input terms of this model: dv = vx - v_ref, dk = delta - delta_ref (row[7], staged
 // once per waypoint), the input box on (delta, pedal).  g = a derived waypoint row (stage_dynamic_tables).
 template <typename F>
@@ -280,20 +348,30 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // rollout_dynamic_kernel with the one vehicle; K > 1: rollout_dynamic_ensemble_kernel.
 // `integration`: the handle's setting; the default launches the FINE = false instantiations, whose step loop knows nothing
 // of it.
+// `terms`: the handle's rate and slip terms; when on, the kernels that hold them run, with the general step whatever the
+// integration setting (the default one as M = 1, no blend, h = float32(dt)).
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& integration, hipStream_t s);
+                                  const Integration& integration, const Terms& terms, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, hipStream_t s);
+                                          const Integration& integration, const Terms& terms, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& integration, hipStream_t s);
+                                   const Integration& integration, const Terms& terms, hipStream_t s);
+// what the three above call when has_terms(terms) (acmpc_dynamic_terms.hip)
+hipError_t launch_rollout_dynamic_terms(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                        const Integration& integration, const Terms& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_sampled_terms(const RolloutArgs& args, const SampleArgs& sample,
+                                                const VehicleEnsemble& vehicles, const Integration& integration,
+                                                const Terms& terms, hipStream_t s);
+hipError_t launch_finalize_dynamic_terms(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                         const Integration& integration, const Terms& terms, hipStream_t s);
 
 }  // namespace acmpc

@@ -32,6 +32,15 @@
 // sub-steps - a scalar loop on a kernel argument - with the low-speed blend after each.  Search, cost and record stay once
 // per control step.  FINE = false is the step loop of the default setting, untouched by the other.
 //
+// And a third form, for a handle with rate and slip terms (acmpc_set_dynamics_terms; acmpc_dynamic.h: Terms,
+// dynamic_terms): every kernel takes a parameter pack `TM... tm` that is empty - the two above, which compile nothing of
+// the terms - or the handle's Terms: the general step of FINE = true plus, after each step's cost, the terms - three floats
+// of state per candidate (the previous step's control and the cost sum E) behind scalar branches on the kernel argument; a
+// handle with terms and the default integration runs them with M = 1.  They are instantiated in a translation unit of their
+// own, acmpc_dynamic_terms.hip, which includes this file: this unit's code object stays what it was.  (Kernels of their own
+// because inside the FINE = true ones the terms cost the step-major two-per-lane rollouts a wave per SIMD: 82 / 83 VGPRs
+// against 76 / 74)
+//
 // Built with -ffp-contract=off: see acmpc_device.h.
 #include "acmpc_dynamic.h"
 
@@ -113,9 +122,9 @@ __device__ __forceinline__ void dynamic_settle(StateD_<f32x2>& s, const float* w
   dynamic_cost<f32x2>(s, g, d, q, w);
 }
 
-template <int LAYOUT, int CPT, bool FINE>
+template <int LAYOUT, int CPT, bool FINE, typename... TM>
 __global__ void __launch_bounds__(kDynBlock)
-    rollout_dynamic_kernel(const RolloutArgs a, const Vehicle veh, const Integration g) {
+    rollout_dynamic_kernel(const RolloutArgs a, const Vehicle veh, const Integration g, const TM... tm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // carve: [0, 32) wave keys | [32, 48) wave feasible counts | [64, ...) waypoint rows, then the search keys
   int64_t* s_key = reinterpret_cast<int64_t*>(smem);
@@ -140,6 +149,9 @@ __global__ void __launch_bounds__(kDynBlock)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) cand[j] = min(c0 + j, a.N - 1);
   StateD_<F> st = start_dynamic<F>(x0, coef);
+  constexpr bool kTerms = sizeof...(TM) != 0;
+  [[maybe_unused]] TermsState<F> ts;
+  if constexpr (kTerms) ts = start_terms<F>(p, tm...);
   I nearest = I(0);
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
@@ -157,9 +169,12 @@ __global__ void __launch_bounds__(kDynBlock)
       dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
+      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, ts, tm...);
     }
   });
-  const F cost_v = finish_temporal<F>(st.t, n, w);
+  F cost_v;
+  if constexpr (kTerms) cost_v = finish_temporal_extra<F>(st.t, ts.E, n, w);
+  else cost_v = finish_temporal<F>(st.t, n, w);
   float cost[CPT];
   bool feas[CPT];
   if constexpr (CPT == 2) {
@@ -256,13 +271,14 @@ __device__ __forceinline__ void stage_draw_tables(const DynamicDraw& d, int p, i
 // the new pair are drawn unless resident: four draws per candidate, as draw_normals() makes.  SHARED (the ensemble: the K
 // waves of a workgroup roll the same candidates): one wave draws for all, between two barriers that every wave reaches -
 // the knot changes are the same steps in every wave.
-template <int CPT, bool SHARED, bool FINE, typename F>
+template <int CPT, bool SHARED, bool FINE, typename F, typename... TT>
 __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& sp, const Vehicle& veh, const Weights& w,
                                              const Integration& g, const float inv_L, const int p, const int n, const uint32_t (&gidx)[CPT], const bool has_ref,
                                              const float* s_wp, const float* s_xy, const float* s_seg,
                                              const float* s_centre, const float* s_ref, f32x2* s_z, const int row,
-                                             const int zi, const bool draws) {
+                                             const int zi, const bool draws, TT&... tt) {
   using I = typename IndexOf<F>::type;
+  constexpr bool kTerms = sizeof...(TT) != 0;   // (tt: nothing, or the terms' state and the Terms)
   float amp[CPT];
   const float* cen[CPT];
 #pragma unroll
@@ -317,15 +333,17 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
       dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
+      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, tt...);   // (the state keeps this step's blended control)
     }
   });
 }
 
 // rollout_dynamic_kernel without a control matrix: the same workgroup shape, tail rule (lanes past N repeat candidate
 // N - 1 unreported), costs, partial keys and feasible counts.
-template <int CPT, bool FINE>
+template <int CPT, bool FINE, typename... TM>
 __global__ void __launch_bounds__(kDynBlock)
-    rollout_dynamic_sampled_kernel(const RolloutArgs a, const DynamicDraw smp, const Vehicle veh, const Integration g) {
+    rollout_dynamic_sampled_kernel(const RolloutArgs a, const DynamicDraw smp, const Vehicle veh, const Integration g,
+                                   const TM... tm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // carve: [0, 32) wave keys | [32, 48) wave feasible counts | [64, ...) the lanes' normals [4][256][CPT] pairs, waypoint
   // rows, search keys, the draw's tables
@@ -353,9 +371,14 @@ __global__ void __launch_bounds__(kDynBlock)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) gidx[j] = static_cast<uint32_t>(a.index_offset + min(c0 + j, a.N - 1));
   StateD_<F> st = start_dynamic<F>(x0, coef);
+  constexpr bool kTerms = sizeof...(TM) != 0;
+  [[maybe_unused]] TermsState<F> ts;
+  if constexpr (kTerms) ts = start_terms<F>(p, tm...);
   roll_sampled<CPT, false, FINE, F>(st, draw_spec(smp, w), veh, w, g, g.inv_L[0], p, n, gidx, smp.u_ref != nullptr, s_wp,
-                                    s_xy, s_seg, s_centre, s_ref, s_z, kDynBlock, tid, true);
-  const F cost_v = finish_temporal<F>(st.t, n, w);
+                                    s_xy, s_seg, s_centre, s_ref, s_z, kDynBlock, tid, true, state_of(ts, tm)..., tm...);
+  F cost_v;
+  if constexpr (kTerms) cost_v = finish_temporal_extra<F>(st.t, ts.E, n, w);
+  else cost_v = finish_temporal<F>(st.t, n, w);
   float cost[CPT];
   bool feas[CPT];
   if constexpr (CPT == 2) {
@@ -429,9 +452,9 @@ __device__ __forceinline__ void regenerate_dynamic_controls(const FinalizeArgs& 
   }
 }
 
-template <int LAYOUT, bool FINE>
+template <int LAYOUT, bool FINE, typename... TM>
 __global__ void __launch_bounds__(kWave)
-    finalize_dynamic_kernel(const FinalizeArgs a, const Vehicle veh, const Integration g) {
+    finalize_dynamic_kernel(const FinalizeArgs a, const Vehicle veh, const Integration g, const TM... tm) {
   extern __shared__ __attribute__((aligned(16))) float s_rec[];   // record image, then the waypoint rows and keys
   const int p = static_cast<int>(blockIdx.x);
   const int lane = static_cast<int>(threadIdx.x);
@@ -473,6 +496,9 @@ __global__ void __launch_bounds__(kWave)
     for (int i = lane; i < n; i += kWave) load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, c, su[2 * i], su[2 * i + 1]);
   }
   StateD st = start_dynamic<float>(x0, coef);
+  constexpr bool kTerms = sizeof...(TM) != 0;
+  [[maybe_unused]] TermsState<float> ts;
+  if constexpr (kTerms) ts = start_terms<float>(p, tm...);
   if (lane == 0) {
     sx[0] = st.t.X + coef[0];   // (poses leave in the caller's frame: start_temporal())
     sx[1] = st.t.Y + coef[1];
@@ -511,6 +537,7 @@ __global__ void __launch_bounds__(kWave)
     j = (j == 0x7fffffff) ? lo : j;
     j_prev = j;
     dynamic_settle(st, s_wp, j, d, q, w);
+    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i == 0, veh, ts, tm...);
     if (lane == 0) {
       sx[3 * (i + 1)] = st.t.X + coef[0];
       sx[3 * (i + 1) + 1] = st.t.Y + coef[1];
@@ -518,7 +545,8 @@ __global__ void __launch_bounds__(kWave)
     }
   }
   if (lane == 0) {
-    s_rec[0] = finish_temporal<float>(st.t, n, w);
+    if constexpr (kTerms) s_rec[0] = finish_temporal_extra<float>(st.t, ts.E, n, w);
+    else s_rec[0] = finish_temporal<float>(st.t, n, w);
     s_rec[1] = st.t.V;
     s_rec[2] = static_cast<float>(nfeas);
     s_rec[3] = 1.0f;
@@ -527,9 +555,9 @@ __global__ void __launch_bounds__(kWave)
   for (int e = lane; e < rec_floats; e += kWave) rec[e] = s_rec[e];
 }
 
-template <int LAYOUT, int CPT, bool FINE>
+template <int LAYOUT, int CPT, bool FINE, typename... TM>
 __global__ void __launch_bounds__(kWave * kMaxVehicles)
-    rollout_dynamic_ensemble_kernel(const RolloutArgs a, const VehicleEnsemble e, const Integration g) {
+    rollout_dynamic_ensemble_kernel(const RolloutArgs a, const VehicleEnsemble e, const Integration g, const TM... tm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // carve: [K][64 CPT] per-vehicle costs | [K][64 CPT] per-vehicle violations | waypoint rows | search keys
   constexpr int kPerGroup = kWave * CPT;
@@ -558,6 +586,9 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) cand[j] = min(c0 + j, a.N - 1);
   StateD_<F> st = start_dynamic<F>(x0, coef);
+  constexpr bool kTerms = sizeof...(TM) != 0;
+  [[maybe_unused]] TermsState<F> ts;
+  if constexpr (kTerms) ts = start_terms<F>(p, tm...);
   I nearest = I(0);
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
@@ -575,9 +606,12 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
+      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, ts, tm...);
     }
   });
-  const F cost_v = finish_temporal<F>(st.t, n, w);
+  F cost_v;
+  if constexpr (kTerms) cost_v = finish_temporal_extra<F>(st.t, ts.E, n, w);
+  else cost_v = finish_temporal<F>(st.t, n, w);
   if constexpr (CPT == 2) {
     s_c[k * kPerGroup + 2 * lane] = cost_v[0];
     s_c[k * kPerGroup + 2 * lane + 1] = cost_v[1];
@@ -613,10 +647,10 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
 
 // rollout_dynamic_ensemble_kernel without a control matrix: wave 0 draws the workgroup's 64 CPT candidates for the K waves
 // (roll_sampled's SHARED form)
-template <int CPT, bool FINE>
+template <int CPT, bool FINE, typename... TM>
 __global__ void __launch_bounds__(kWave * kMaxVehicles)
     rollout_dynamic_sampled_ensemble_kernel(const RolloutArgs a, const DynamicDraw smp, const VehicleEnsemble e,
-                                            const Integration g) {
+                                            const Integration g, const TM... tm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // carve: [K][64 CPT] per-vehicle costs | [K][64 CPT] per-vehicle violations | the candidates' normals [4][64][CPT] pairs |
   // waypoint rows | search keys | draw tables
@@ -649,9 +683,14 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
 #pragma unroll
   for (int j = 0; j < CPT; ++j) gidx[j] = static_cast<uint32_t>(a.index_offset + min(c0 + j, a.N - 1));
   StateD_<F> st = start_dynamic<F>(x0, coef);
+  constexpr bool kTerms = sizeof...(TM) != 0;
+  [[maybe_unused]] TermsState<F> ts;
+  if constexpr (kTerms) ts = start_terms<F>(p, tm...);
   roll_sampled<CPT, true, FINE, F>(st, draw_spec(smp, w), veh, w, g, g.inv_L[k], p, n, gidx, smp.u_ref != nullptr, s_wp,
-                                   s_xy, s_seg, s_centre, s_ref, s_z, kWave, lane, k == 0);
-  const F cost_v = finish_temporal<F>(st.t, n, w);
+                                   s_xy, s_seg, s_centre, s_ref, s_z, kWave, lane, k == 0, state_of(ts, tm)..., tm...);
+  F cost_v;
+  if constexpr (kTerms) cost_v = finish_temporal_extra<F>(st.t, ts.E, n, w);
+  else cost_v = finish_temporal<F>(st.t, n, w);
   if constexpr (CPT == 2) {
     s_c[k * kPerGroup + 2 * lane] = cost_v[0];
     s_c[k * kPerGroup + 2 * lane + 1] = cost_v[1];
@@ -685,9 +724,9 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   }
 }
 
-template <int LAYOUT, bool FINE>
+template <int LAYOUT, bool FINE, typename... TM>
 __global__ void __launch_bounds__(kWave * kMaxVehicles)
-    finalize_dynamic_ensemble_kernel(const FinalizeArgs a, const VehicleEnsemble e, const Integration g) {
+    finalize_dynamic_ensemble_kernel(const FinalizeArgs a, const VehicleEnsemble e, const Integration g, const TM... tm) {
   // record image | [kMaxVehicles] costs, [kMaxVehicles] violations | waypoint rows | search keys
   extern __shared__ __attribute__((aligned(16))) float s_rec[];
   const int p = static_cast<int>(blockIdx.x);
@@ -735,6 +774,9 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
     for (int i = tid; i < n; i += threads) load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, c, su[2 * i], su[2 * i + 1]);
   }
   StateD st = start_dynamic<float>(x0, coef);
+  constexpr bool kTerms = sizeof...(TM) != 0;
+  [[maybe_unused]] TermsState<float> ts;
+  if constexpr (kTerms) ts = start_terms<float>(p, tm...);
   const bool writer = (k == 0 && lane == 0);   // vehicle 0's trajectory is the record's
   if (writer) {
     sx[0] = st.t.X + coef[0];
@@ -774,6 +816,7 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
     j = (j == 0x7fffffff) ? lo : j;
     j_prev = j;
     dynamic_settle(st, s_wp, j, d, q, w);
+    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i == 0, veh, ts, tm...);
     if (writer) {
       sx[3 * (i + 1)] = st.t.X + coef[0];
       sx[3 * (i + 1) + 1] = st.t.Y + coef[1];
@@ -781,7 +824,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
     }
   }
   if (lane == 0) {
-    s_ck[k] = finish_temporal<float>(st.t, n, w);
+    if constexpr (kTerms) s_ck[k] = finish_temporal_extra<float>(st.t, ts.E, n, w);
+    else s_ck[k] = finish_temporal<float>(st.t, n, w);
     s_ck[kMaxVehicles + k] = st.t.V;
   }
   __syncthreads();
@@ -797,30 +841,26 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   for (int q = tid; q < rec_floats; q += threads) rec[q] = s_rec[q];
 }
 
-// the FINE = true instantiations for any setting but the default (acmpc_dynamic.h: Integration), FINE = false for that
-template <typename Body>
+// FINE = true for any integration setting but the default (acmpc_dynamic.h: Integration) and, whatever the setting, for
+// the kernels with the terms (GENERAL: they have no FINE = false form); FINE = false for the default setting
+template <bool GENERAL, typename Body>
 void with_integration_kind(const Integration& g, Body&& body) {
-  if (is_fine(g)) body(std::true_type{});
-  else body(std::false_type{});
+  if constexpr (GENERAL) {
+    body(std::true_type{});
+  } else {
+    if (is_fine(g)) body(std::true_type{});
+    else body(std::false_type{});
+  }
 }
 
 bool integration_valid(const Integration& g) { return g.substeps >= 1 && g.substeps <= kMaxSubsteps; }
 
-}  // namespace
-
-int dynamic_candidates_per_lane(int P, int N, int K) {
-  // 256 CUs x 4 SIMDs x 8 waves x 64 lanes = 524 288 lanes: two candidates per lane once every lane would get two
-  // (an ensemble's lanes are P N K: one per vehicle and candidate)
-  return (static_cast<int64_t>(P) * N * K >= (int64_t{1} << 20)) ? 2 : 1;
-}
-
-int dynamic_blocks_per_problem(int P, int N, int K) {
-  const int per_block = (K > 1 ? kWave : kDynBlock) * dynamic_candidates_per_lane(P, N, K);
-  return (N + per_block - 1) / per_block;
-}
-
-hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& g, hipStream_t s) {
+// The three launchers, written once: `tm` is nothing (the kernels without the terms, this translation unit) or the
+// handle's Terms (the kernels with them, acmpc_dynamic_terms.hip).
+template <typename... TM>
+hipError_t rollout_dynamic_launch(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles, const Integration& g,
+                                  hipStream_t s, const TM&... tm) {
+  constexpr bool kGeneral = sizeof...(TM) != 0;
   (void)hipGetLastError();
   if (!integration_valid(g)) return hipErrorInvalidValue;
   if (args.n < 1 || args.n > kDynamicMaxSteps || args.N < 1 || args.P < 1) return hipErrorInvalidValue;
@@ -833,35 +873,37 @@ hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const Veh
     const Vehicle& vehicle = vehicles.v[0];
     const dim3 block(kDynBlock);
     const size_t lds = 64 + tables;
-    with_integration_kind(g, [&](auto fine) {
+    with_integration_kind<kGeneral>(g, [&](auto fine) {
       constexpr bool kFine = decltype(fine)::value;
       if (layout == 0) {
-        if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_kernel<0, 2, kFine>), grid, block, lds, s, args, vehicle, g);
-        else hipLaunchKernelGGL((rollout_dynamic_kernel<0, 1, kFine>), grid, block, lds, s, args, vehicle, g);
+        if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_kernel<0, 2, kFine, TM...>), grid, block, lds, s, args, vehicle, g, tm...);
+        else hipLaunchKernelGGL((rollout_dynamic_kernel<0, 1, kFine, TM...>), grid, block, lds, s, args, vehicle, g, tm...);
       } else {
-        if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_kernel<1, 2, kFine>), grid, block, lds, s, args, vehicle, g);
-        else hipLaunchKernelGGL((rollout_dynamic_kernel<1, 1, kFine>), grid, block, lds, s, args, vehicle, g);
+        if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_kernel<1, 2, kFine, TM...>), grid, block, lds, s, args, vehicle, g, tm...);
+        else hipLaunchKernelGGL((rollout_dynamic_kernel<1, 1, kFine, TM...>), grid, block, lds, s, args, vehicle, g, tm...);
       }
     });
     return hipGetLastError();
   }
   const dim3 block(kWave * K);
   const size_t lds = 2 * static_cast<size_t>(K) * kWave * cpt * sizeof(float) + tables;
-  with_integration_kind(g, [&](auto fine) {
+  with_integration_kind<kGeneral>(g, [&](auto fine) {
     constexpr bool kFine = decltype(fine)::value;
     if (layout == 0) {
-      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<0, 2, kFine>), grid, block, lds, s, args, vehicles, g);
-      else hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<0, 1, kFine>), grid, block, lds, s, args, vehicles, g);
+      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<0, 2, kFine, TM...>), grid, block, lds, s, args, vehicles, g, tm...);
+      else hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<0, 1, kFine, TM...>), grid, block, lds, s, args, vehicles, g, tm...);
     } else {
-      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<1, 2, kFine>), grid, block, lds, s, args, vehicles, g);
-      else hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<1, 1, kFine>), grid, block, lds, s, args, vehicles, g);
+      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<1, 2, kFine, TM...>), grid, block, lds, s, args, vehicles, g, tm...);
+      else hipLaunchKernelGGL((rollout_dynamic_ensemble_kernel<1, 1, kFine, TM...>), grid, block, lds, s, args, vehicles, g, tm...);
     }
   });
   return hipGetLastError();
 }
 
-hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& g, hipStream_t s) {
+template <typename... TM>
+hipError_t rollout_dynamic_sampled_launch(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
+                                          const Integration& g, hipStream_t s, const TM&... tm) {
+  constexpr bool kGeneral = sizeof...(TM) != 0;
   (void)hipGetLastError();
   if (!integration_valid(g)) return hipErrorInvalidValue;
   if (args.n < 1 || args.n > kDynamicMaxSteps || args.N < 1 || args.P < 1) return hipErrorInvalidValue;
@@ -893,26 +935,28 @@ hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleA
     const Vehicle& vehicle = vehicles.v[0];
     const dim3 block(kDynBlock);
     const size_t lds = 64 + static_cast<size_t>(kDrawSlots) * kDynBlock * cpt * sizeof(f32x2) + tables;   // <= 60 KB
-    with_integration_kind(g, [&](auto fine) {
+    with_integration_kind<kGeneral>(g, [&](auto fine) {
       constexpr bool kFine = decltype(fine)::value;
-      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<2, kFine>), grid, block, lds, s, args, d, vehicle, g);
-      else hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<1, kFine>), grid, block, lds, s, args, d, vehicle, g);
+      if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<2, kFine, TM...>), grid, block, lds, s, args, d, vehicle, g, tm...);
+      else hipLaunchKernelGGL((rollout_dynamic_sampled_kernel<1, kFine, TM...>), grid, block, lds, s, args, d, vehicle, g, tm...);
     });
     return hipGetLastError();
   }
   const dim3 block(kWave * K);
   const size_t lds = 2 * static_cast<size_t>(K) * kWave * cpt * sizeof(float) +
                      static_cast<size_t>(kDrawSlots) * kWave * cpt * sizeof(f32x2) + tables;
-  with_integration_kind(g, [&](auto fine) {
+  with_integration_kind<kGeneral>(g, [&](auto fine) {
     constexpr bool kFine = decltype(fine)::value;
-    if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<2, kFine>), grid, block, lds, s, args, d, vehicles, g);
-    else hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<1, kFine>), grid, block, lds, s, args, d, vehicles, g);
+    if (cpt == 2) hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<2, kFine, TM...>), grid, block, lds, s, args, d, vehicles, g, tm...);
+    else hipLaunchKernelGGL((rollout_dynamic_sampled_ensemble_kernel<1, kFine, TM...>), grid, block, lds, s, args, d, vehicles, g, tm...);
   });
   return hipGetLastError();
 }
 
-hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& g, hipStream_t s) {
+template <typename... TM>
+hipError_t finalize_dynamic_launch(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles, const Integration& g,
+                                   hipStream_t s, const TM&... tm) {
+  constexpr bool kGeneral = sizeof...(TM) != 0;
   (void)hipGetLastError();
   if (!integration_valid(g)) return hipErrorInvalidValue;
   if (args.controls_only || args.n < 1 || args.n > kDynamicMaxSteps) return hipErrorInvalidValue;
@@ -925,21 +969,74 @@ hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const V
   if (vehicles.K == 1) {
     const Vehicle& vehicle = vehicles.v[0];
     const size_t lds = (rec_pad + tables) * sizeof(float);
-    with_integration_kind(g, [&](auto fine) {
+    with_integration_kind<kGeneral>(g, [&](auto fine) {
       constexpr bool kFine = decltype(fine)::value;
-      if (layout == 0) hipLaunchKernelGGL((finalize_dynamic_kernel<0, kFine>), dim3(args.P), dim3(kWave), lds, s, args, vehicle, g);
-      else hipLaunchKernelGGL((finalize_dynamic_kernel<1, kFine>), dim3(args.P), dim3(kWave), lds, s, args, vehicle, g);
+      if (layout == 0) hipLaunchKernelGGL((finalize_dynamic_kernel<0, kFine, TM...>), dim3(args.P), dim3(kWave), lds, s, args, vehicle, g, tm...);
+      else hipLaunchKernelGGL((finalize_dynamic_kernel<1, kFine, TM...>), dim3(args.P), dim3(kWave), lds, s, args, vehicle, g, tm...);
     });
     return hipGetLastError();
   }
   const size_t lds = (rec_pad + 2 * kMaxVehicles + tables) * sizeof(float);
   const dim3 block(kWave * vehicles.K);
-  with_integration_kind(g, [&](auto fine) {
+  with_integration_kind<kGeneral>(g, [&](auto fine) {
     constexpr bool kFine = decltype(fine)::value;
-    if (layout == 0) hipLaunchKernelGGL((finalize_dynamic_ensemble_kernel<0, kFine>), dim3(args.P), block, lds, s, args, vehicles, g);
-    else hipLaunchKernelGGL((finalize_dynamic_ensemble_kernel<1, kFine>), dim3(args.P), block, lds, s, args, vehicles, g);
+    if (layout == 0) hipLaunchKernelGGL((finalize_dynamic_ensemble_kernel<0, kFine, TM...>), dim3(args.P), block, lds, s, args, vehicles, g, tm...);
+    else hipLaunchKernelGGL((finalize_dynamic_ensemble_kernel<1, kFine, TM...>), dim3(args.P), block, lds, s, args, vehicles, g, tm...);
   });
   return hipGetLastError();
 }
+
+}  // namespace
+
+#ifdef ACMPC_DYNAMIC_TERMS_TU
+
+hipError_t launch_rollout_dynamic_terms(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                        const Integration& g, const Terms& tm, hipStream_t s) {
+  return rollout_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+hipError_t launch_rollout_dynamic_sampled_terms(const RolloutArgs& args, const SampleArgs& sample,
+                                                const VehicleEnsemble& vehicles, const Integration& g, const Terms& tm,
+                                                hipStream_t s) {
+  return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s, tm);
+}
+
+hipError_t launch_finalize_dynamic_terms(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                         const Integration& g, const Terms& tm, hipStream_t s) {
+  return finalize_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+#else  // ACMPC_DYNAMIC_TERMS_TU
+
+int dynamic_candidates_per_lane(int P, int N, int K) {
+  // 256 CUs x 4 SIMDs x 8 waves x 64 lanes = 524 288 lanes: two candidates per lane once every lane would get two
+  // (an ensemble's lanes are P N K: one per vehicle and candidate)
+  return (static_cast<int64_t>(P) * N * K >= (int64_t{1} << 20)) ? 2 : 1;
+}
+
+int dynamic_blocks_per_problem(int P, int N, int K) {
+  const int per_block = (K > 1 ? kWave : kDynBlock) * dynamic_candidates_per_lane(P, N, K);
+  return (N + per_block - 1) / per_block;
+}
+
+hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                  const Integration& g, const Terms& tm, hipStream_t s) {
+  if (has_terms(tm)) return launch_rollout_dynamic_terms(layout, args, vehicles, g, tm, s);
+  return rollout_dynamic_launch(layout, args, vehicles, g, s);
+}
+
+hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
+                                          const Integration& g, const Terms& tm, hipStream_t s) {
+  if (has_terms(tm)) return launch_rollout_dynamic_sampled_terms(args, sample, vehicles, g, tm, s);
+  return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s);
+}
+
+hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                   const Integration& g, const Terms& tm, hipStream_t s) {
+  if (has_terms(tm)) return launch_finalize_dynamic_terms(layout, args, vehicles, g, tm, s);
+  return finalize_dynamic_launch(layout, args, vehicles, g, s);
+}
+
+#endif  // ACMPC_DYNAMIC_TERMS_TU
 
 }  // namespace acmpc

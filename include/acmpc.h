@@ -257,6 +257,36 @@ int acmpc_set_dynamics_ensemble(acmpc_ctx* ctx, const double* coef, int32_t K, c
 #define ACMPC_MAX_SUBSTEPS 16
 int acmpc_set_dynamics_integration(acmpc_ctx* ctx, int32_t substeps, double blend_lo, double blend_hi);
 
+/* Mode D's rate and slip terms: what a plan pays for moving its controls quickly and for sliding.  Off by default.  Per
+ * control step i, after the stage cost of that step and on the same state:
+ *   rd = (delta_i - delta_{i-1}) / dt, rp = (pedal_i - pedal_{i-1}) / dt     the controls' rates; step 0 against the
+ *                                                                          previous control (acmpc_set_previous_control)
+ *   b  = (r lr - vy) / (vx + 1e-3)                                          the rear slip ratio, lr of the vehicle rolled
+ *   J += 1/2 (rate_weight[0] rd^2 + rate_weight[1] rp^2 + slip_weight b^2)
+ *   V += max(|rd| - rate_max[0], 0)^2 + max(|rp| - rate_max[1], 0)^2 + max(|b| - slip_max, 0)^2
+ * so a plan over a limit is infeasible (V > 0) as one outside the input box is.  Weights are finite and >= 0; limits are
+ * > 0, +inf (INFINITY) meaning none; every value is rounded to float32 once.  The rate part is on when a rate weight is
+ * not 0 or a rate limit finite, the slip part when slip_weight is not 0 or slip_max finite; a part that is off computes
+ * nothing, and with both off the handle runs exactly what it ran before the call.  The setting belongs to the handle: it
+ * survives acmpc_set_dynamics, acmpc_set_dynamics_ensemble and acmpc_set_dynamics_integration, every member of an
+ * ensemble carries it (the slip part with its own lr), and every call form of mode D takes it from the handle.  b
+ * divides by vx + 1e-3: below the speeds where the single Euler step chatters, use the slip part together with the
+ * low-speed blend of acmpc_set_dynamics_integration, which drives r lr - vy to 0 there.  No device work.  ACMPC_EINVAL for
+ * a handle whose mode is not ACMPC_MODE_DYNAMIC, a null array, a weight that is negative or not finite, a limit that is
+ * not > 0 (NaN included); the handle then keeps its previous setting.  DESIGN.md section 2 "Mode D", "Rate and slip
+ * terms". */
+int acmpc_set_dynamics_terms(acmpc_ctx* ctx, const double rate_weight[2], const double rate_max[2], double slip_weight,
+                             double slip_max);
+
+/* The control applied just before each problem's plan starts: u_prev host [P][2] = (delta, pedal), what step 0's rates
+ * are taken against; NULL clears it (P is then ignored), and step 0's own control stands for it: an increment of +0.
+ * Staged on the host; it travels to the device with the tables, on the next call's stream (acmpc_sync_tables covers it),
+ * and stays until replaced or cleared.  Every round of acmpc_optimize uses the same one.  Not read while the rate part
+ * of acmpc_set_dynamics_terms is off.  The values are not checked: a NaN makes step 0's rate NaN.  ACMPC_EINVAL for a
+ * handle whose mode is not ACMPC_MODE_DYNAMIC or P outside 1 .. max_problems; a later mode D call whose P is not the
+ * stored one returns ACMPC_ESTATE. */
+int acmpc_set_previous_control(acmpc_ctx* ctx, const float* u_prev, int32_t P);
+
 /* Copies the packed float32 table of problem `problem` (n rows of ACMPC_COEF_STRIDE_* floats) to `out`.
  * Host only; lets CPU tests pin the host-side arithmetic against the oracle. */
 int acmpc_get_coefficients(const acmpc_ctx* ctx, int32_t problem, float* out, int32_t capacity_floats);

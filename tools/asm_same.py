@@ -1,0 +1,48 @@
+#!/usr/bin/env python3
+"""Development aid: are the kernels of two hipcc --save-temps assembly files the same instructions?  Per kernel the
+instruction lines are compared in order - comments, directives and block labels' numbers apart - and the kernels are matched
+by their mangled names with the template parameter pack of mode D's kernels (`J...E`, and the pack in the argument list)
+taken out, so that a file from before the pack existed compares with one from after.  Prints what differs and how many
+kernels are identical; exit status 1 unless every kernel of OLD is in NEW and identical.
+
+usage: hipcc <the library's flags> -c csrc/acmpc_dynamic.hip -o unit.o --save-temps     (at both commits, in two directories)
+       python3 tools/asm_same.py OLD/acmpc_dynamic-hip-amdgcn-amd-amdhsa-gfx950.s NEW/acmpc_dynamic-hip-amdgcn-amd-amdhsa-gfx950.s"""
+import difflib
+import re
+import sys
+
+
+def kernels(path):
+    text = open(path).read()
+    out = {}
+    for m in re.finditer(r"^(_Z\S+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
+        body = []
+        for line in m.group(2).split("\n"):
+            line = re.sub(r";.*", "", line).strip()
+            if line.startswith(".LBB"):
+                body.append(re.sub(r"\d+_", "N_", line))
+            elif line and not line.startswith("."):
+                body.append(re.sub(r"\.LBB\d+_", ".LBBN_", line))
+        name = re.sub(r"DpK?T\d*_", "", re.sub(r"J(?:NS_\d+\w+?E)*E(E+v)", r"\1", m.group(1)))
+        out[name] = body
+    return out
+
+
+def main():
+    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    same = 0
+    for name, body in old.items():
+        if name not in new:
+            print("MISSING", name)
+        elif body == new[name]:
+            same += 1
+        else:
+            delta = [l for l in difflib.unified_diff(body, new[name], lineterm="", n=0) if not l.startswith(("---", "+++", "@@"))]
+            print("DIFFERENT %s: %d lines against %d, %d differ" % (name, len(body), len(new[name]), len(delta)))
+            print("\n".join("    " + l for l in delta[:12]))
+    print("%d of %d kernels identical (%d in the new file)" % (same, len(old), len(new)))
+    return 0 if same == len(old) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -33,7 +33,12 @@ M Euler sub-steps per control step, the low-speed blend between LO and HI m/s); 
 vector-issue roof then prices the FINE kernels' mix: the step loop's own trip (`dynamic_fine_step`) plus M trips of the
 sub-step loop (`dynamic_fine_substep`, whose static count holds the blend's block whether or not the blend is on).
 
-usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI]
+With `--terms` every handle is given rate and slip terms (acmpc_set_dynamics_terms: both parts on, weights and limits as a
+controller would set them - TERMS below) and a previous control of zeros for each of its problems: the same shapes, the
+kernels of csrc/acmpc_dynamic_terms.hip; with `--substeps` / `--blend` as well, under that integration setting.  The roof
+prices `dynamic_terms_step` + M `dynamic_terms_substep`.
+
+usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms]
                                       [--sampled | --optimize [--update softmin]]"""
 import argparse
 import json
@@ -51,10 +56,17 @@ for _p in (ROOT, os.path.join(ROOT, "ac-mpc_amd"), os.path.join(ROOT, "oracle"),
 INTEGRATION = (1, None)   # (--substeps, --blend): what every handle of this run is set to
 
 
+TERMS = None              # --terms: the rate and slip terms every handle of this run is given
+TERMS_ON = dict(rate_weight=(0.5, 0.05), rate_max=(1.0, 8.0), slip_weight=10.0, slip_max=0.1)
+
+
 def integrate(eng):
-    """The run's integration setting on a new handle (a library without the entry point takes only the default)."""
+    """The run's integration setting and terms on a new handle (a library without the entry points takes only the defaults)."""
     if INTEGRATION != (1, None):
         eng.set_dynamics_integration(*INTEGRATION)
+    if TERMS is not None:
+        eng.set_dynamics_terms(**TERMS)
+        eng.set_previous_control(np.zeros((eng.params.max_problems, 2), dtype=np.float32))   # (a handle's solves use all of them)
     return eng
 
 
@@ -62,10 +74,11 @@ def fine_issue_roof(bench, candidates, steps, kernel_s, name):
     """issue_roof for a FINE kernel: VALU per control step = the step loop's trip + M sub-step trips, priced with the
     sub-step loop's mix (which is nearly all of it)."""
     mix, mix_path = bench.newest_profile("isa_mix.json")
-    step, sub = mix["entries"][name + "_fine_step"], mix["entries"][name + "_fine_substep"]
+    kind = "_terms_" if TERMS is not None else "_fine_"
+    step, sub = mix["entries"][name + kind + "step"], mix["entries"][name + kind + "substep"]
     per_step = (sum(step["valu"].values()) + INTEGRATION[0] * sum(sub["valu"].values())) / float(sub["candidates_per_lane"])
     counted = (per_step, mix_path + " (static count: step trip + M sub-step trips)", {"source_sha256": mix.get("source_sha256")})
-    roof, _ = bench.valu_roofline(counted, candidates, steps, kernel_s, mix_entry=name + "_fine_substep",
+    roof, _ = bench.valu_roofline(counted, candidates, steps, kernel_s, mix_entry=name + kind + "substep",
                                   cpt=sub["candidates_per_lane"])
     roof["substep_count_holds_the_blend_block"] = True
     return roof
@@ -75,7 +88,7 @@ def issue_roof(bench, candidates, steps, kernel_s, name="dynamic"):
     """bench.valu_roofline for the `dynamic` entry (`dynamic_ensemble`: candidates = vehicle-candidates): the step loop's
     static VALU count per candidate-step (the isa mix, whose sources must be the loaded build's -
     `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
-    if INTEGRATION != (1, None) and name in ("dynamic", "dynamic_ensemble"):
+    if (INTEGRATION != (1, None) or TERMS is not None) and name in ("dynamic", "dynamic_ensemble"):
         return fine_issue_roof(bench, candidates, steps, kernel_s, name)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     entry = mix["entries"][name]
@@ -99,8 +112,10 @@ def main():
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--substeps", type=int, default=1, help="Euler sub-steps per control step (1 .. 16)")
     ap.add_argument("--blend", default=None, help="LO,HI m/s: the low-speed blend")
+    ap.add_argument("--terms", action="store_true", help="rate and slip terms on every handle (TERMS_ON)")
     args = ap.parse_args()
-    global INTEGRATION
+    global INTEGRATION, TERMS
+    TERMS = dict(TERMS_ON) if args.terms else None
     INTEGRATION = (args.substeps, None if args.blend is None else tuple(float(v) for v in args.blend.split(",")))
     if args.update == "softmin" and not args.optimize:
         ap.error("--update softmin goes with --optimize")
@@ -348,6 +363,8 @@ def measure(args, K):
     out = {"tool": "tools/bench_dynamic.py", "horizon": H, "search": "window (2, 5)"}
     if INTEGRATION != (1, None):
         out.update(substeps=INTEGRATION[0], low_speed_blend=INTEGRATION[1])
+    if TERMS is not None:
+        out.update(terms={k: list(v) if isinstance(v, tuple) else v for k, v in TERMS.items()})
     if K > 1:
         out.update(vehicles=K, reduce=args.reduce, grips=list(GRIPS[:K]))
 

@@ -31,26 +31,35 @@ ENTRIES = {
     "fused_round": ("acmpc_kernels.hip", "rollout_sampled_kernelILi0E", None),
     # mode D (the dynamic bicycle, two candidates per lane, step-major): the largest step loop - a windowed search's, whose
     # trip is the dynamics + an unrolled window + the cost; the exhaustive form adds its waypoint loop to the same trip
-    "dynamic": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2ELb0EE", None),
+    "dynamic": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2ELb0EJEEE", None),
     # mode D with an ensemble of vehicles (one wavefront per vehicle): the same step loop under wave k's vehicle
-    "dynamic_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb0EE", None),
+    "dynamic_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb0EJEEE", None),
     # mode D drawing its own candidates (two per lane): the same step loop with the blend of the step's control in front.
     # The loop holds the Philox draws as loops of its own, run on at most seven of a rollout's trips: the mix is the trip
     # without them (OUTER)
-    "dynamic_sampled": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_kernelILi2ELb0EE", None),
-    "dynamic_sampled_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_ensemble_kernelILi2ELb0EE", None),
+    "dynamic_sampled": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_kernelILi2ELb0EJEEE", None),
+    "dynamic_sampled_ensemble": ("acmpc_dynamic.hip", "rollout_dynamic_sampled_ensemble_kernelILi2ELb0EJEEE", None),
     # mode D with an integration setting (the FINE kernels): a control step is the step loop's own trip - the control's
     # terms, the search, the cost (`_step`: the trip less its inner loop, OUTER) - plus M trips of the sub-step loop, the
     # dynamics and the blend (`_substep`, the largest innermost loop, the blend's block counted): VALU per control step =
     # step + M substep
-    "dynamic_fine_step": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2ELb1EE", None),
-    "dynamic_fine_substep": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2ELb1EE", None),
-    "dynamic_ensemble_fine_step": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EE", None),
-    "dynamic_ensemble_fine_substep": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EE", None),
+    "dynamic_fine_step": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJEEE", None),
+    "dynamic_fine_substep": ("acmpc_dynamic.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJEEE", None),
+    "dynamic_ensemble_fine_step": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJEEE", None),
+    "dynamic_ensemble_fine_substep": ("acmpc_dynamic.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJEEE", None),
+    # mode D with rate and slip terms (acmpc_set_dynamics_terms: the kernels of acmpc_dynamic_terms.hip, the FINE step plus
+    # the terms after the cost): the same two loops.  The terms' block is in the step loop's own trip: its instructions =
+    # `dynamic_terms_step` - `dynamic_fine_step`, both parts on (the count is static: a part that is off is branched over)
+    "dynamic_terms_step": ("acmpc_dynamic_terms.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
+    "dynamic_terms_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
+    "dynamic_ensemble_terms_step": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
+    "dynamic_ensemble_terms_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
 }
 CANDIDATES_PER_LANE = {"fused_round": 1}
-OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dynamic_ensemble_fine_step")
-ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep")   # (exit test at the head: closes with s_branch)
+OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dynamic_ensemble_fine_step",
+         "dynamic_terms_step", "dynamic_ensemble_terms_step")
+# (exit test at the head: closes with s_branch)
+ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep")
 
 
 def source_hash():
