@@ -7,13 +7,14 @@ from ._capi import (ENSEMBLE_MAX, ENSEMBLE_MEAN, MAX_SUBSTEPS, MAX_VEHICLES, Eng
                     LAYOUT_STEP_MAJOR, MODE_DYNAMIC, MODE_SPATIAL, MODE_TEMPORAL, load_library)
 from .dynamic_model import DynamicBicycleParams  # noqa: F401
 from .dynamic_solver import DynamicSamplingSolver  # noqa: F401
+from .grip_estimator import GripEstimator  # noqa: F401
 from .bicycle_model import SpatialBicycleModel  # noqa: F401
 from .command_selection import TemporalCommandInterpolator, TemporalCommandSelector, steer_target  # noqa: F401
 from .mpc import SpatialMPC, build_mpc  # noqa: F401
 from .reference_path import ReferencePath  # noqa: F401
 
 __all__ = ["Engine", "EngineError", "load_library", "MODE_SPATIAL", "MODE_TEMPORAL", "MODE_DYNAMIC",
-           "DynamicBicycleParams", "DynamicSamplingSolver", "MAX_VEHICLES", "MAX_SUBSTEPS", "ENSEMBLE_MEAN", "ENSEMBLE_MAX",
+           "DynamicBicycleParams", "DynamicSamplingSolver", "GripEstimator", "MAX_VEHICLES", "MAX_SUBSTEPS", "ENSEMBLE_MEAN", "ENSEMBLE_MAX",
            "LAYOUT_CANDIDATE_MAJOR",
            "LAYOUT_STEP_MAJOR", "build_mpc", "SpatialMPC", "SpatialBicycleModel", "ReferencePath",
            "TemporalCommandSelector", "TemporalCommandInterpolator", "steer_target"]

@@ -19,6 +19,8 @@ MODE_SPATIAL, MODE_TEMPORAL, MODE_DYNAMIC = 0, 1, 2
 DYNAMICS_COUNT = 26   # ACMPC_DYNAMICS_COUNT: doubles in mode D's vehicle block
 MAX_VEHICLES = 8      # ACMPC_MAX_VEHICLES: vehicles in a mode D ensemble
 MAX_SUBSTEPS = 16     # ACMPC_MAX_SUBSTEPS: Euler sub-steps per control step of mode D
+MAX_LOG_STEPS = 512   # ACMPC_MAX_LOG_STEPS: control steps in the log of acmpc_score_grips
+MAX_GRIP_HYPOTHESES = 65536   # ACMPC_MAX_GRIP_HYPOTHESES
 ENSEMBLE_MEAN, ENSEMBLE_MAX = 0, 1
 ENSEMBLE_REDUCE = {"mean": ENSEMBLE_MEAN, "max": ENSEMBLE_MAX}
 LAYOUT_CANDIDATE_MAJOR, LAYOUT_STEP_MAJOR = 0, 1
@@ -152,6 +154,8 @@ SIGNATURES = {
     "acmpc_set_dynamics_integration": (C.c_int, [_CTX, C.c_int32, C.c_double, C.c_double]),
     "acmpc_set_dynamics_terms": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "acmpc_set_previous_control": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
+    "acmpc_score_grips": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
     "acmpc_get_coefficients": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_set_coefficients": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_record_floats": (C.c_int32, [C.c_int32]),
@@ -611,6 +615,33 @@ class Engine:
         if u.ndim != 2 or u.shape[1] != 2:
             raise ValueError("u_prev must be [P, 2]")
         self._check(self._lib.acmpc_set_previous_control(self._ctx, u.ctypes.data, u.shape[0]))
+
+    def score_grips(self, states, controls, dt: float, scales, segment: int = 1, weights=(1.0, 1.0, 1.0)):
+        """Mode D's grip identification (acmpc_score_grips): `states` [W + 1, 3] = (vx, vy, r) - or [W + 1, 6], whose last
+        three columns are taken - and `controls` [W, 2] = (delta, pedal) logged every `dt` seconds, control j between
+        states j and j + 1; `scales` [K, 2] = (front, rear) grip scales of the hypotheses (vehicle 0 with Df, Dr scaled).
+        The log is cut into segments of `segment` steps, each rolled open-loop from its logged start; a hypothesis's error
+        is the `weights`-weighted sum of its squared residuals on (vx, vy, r).  Returns (errors [K] float32, best index):
+        ties go to the lower index, non-finite errors rank last."""
+        x = np.asarray(states, dtype=np.float32)
+        if x.ndim == 2 and x.shape[1] == 6:
+            x = x[:, 3:]
+        x = np.ascontiguousarray(x)
+        u = np.ascontiguousarray(controls, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != 3 or u.ndim != 2 or u.shape[1] != 2 or x.shape[0] != u.shape[0] + 1:
+            raise ValueError("states are [W + 1, 3] (or [W + 1, 6]) and controls [W, 2]")
+        sc = np.ascontiguousarray(scales, dtype=np.float64)
+        if sc.ndim != 2 or sc.shape[1] != 2:
+            raise ValueError("scales are [K, 2] = (front, rear)")
+        w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        if w.size != 3:
+            raise ValueError("weights are three numbers, for (vx, vy, r)")
+        errors = np.empty(sc.shape[0], dtype=np.float32)
+        best = C.c_int64(0)
+        self._check(self._lib.acmpc_score_grips(self._ctx, x.ctypes.data, u.ctypes.data, u.shape[0], float(dt), int(segment),
+                                                w.ctypes.data, sc.ctypes.data, sc.shape[0], errors.ctypes.data,
+                                                C.byref(best)))
+        return errors, key_index(best.value)
 
     def set_coefficients(self, coef: np.ndarray):
         """The packed float32 tables themselves, [P, n, 12] (mode S) / [P, n, 8] (mode T) or one [n, stride] table

@@ -75,10 +75,16 @@ class DynamicBicycleParams:
         friction coefficient) scaled, nothing else.  The drive, brake and friction maps are left alone: this model has no
         friction circle, so its longitudinal forces do not depend on the tyres' grip.  An ensemble of grips
         (DynamicSamplingSolver's `grip_ensemble`) scores every candidate on several such roads."""
-        scale = float(scale)
-        if not (np.isfinite(scale) and scale > 0.0):
-            raise ValueError("a grip scale is finite and positive, not %r" % (scale,))
-        return dataclasses.replace(self, Df=self.Df * scale, Dr=self.Dr * scale)
+        return self.with_axle_grip(scale, scale)
+
+    def with_axle_grip(self, front: float, rear: float) -> "DynamicBicycleParams":
+        """`with_grip` with a scale per axle: Df times `front`, Dr times `rear` (with_grip(s) is with_axle_grip(s, s)).
+        What a hypothesis of the grip identification is (Engine.score_grips, GripEstimator)."""
+        front, rear = float(front), float(rear)
+        for scale in (front, rear):
+            if not (np.isfinite(scale) and scale > 0.0):
+                raise ValueError("a grip scale is finite and positive, not %r" % (scale,))
+        return dataclasses.replace(self, Df=self.Df * front, Dr=self.Dr * rear)
 
     def coefficients(self) -> np.ndarray:
         """The ABI block: float64 [26] in FIELDS order (acmpc_set_dynamics)."""

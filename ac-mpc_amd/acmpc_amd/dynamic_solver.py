@@ -25,7 +25,17 @@ Rate and slip terms (acmpc_set_dynamics_terms): `rate_cost` = (delta, pedal) wei
 second), `rate_limit` = their limits (None, or a pair whose members may be None), `slip_cost` / `slip_limit` the same for
 the rear slip ratio (r lr - vy) / vx.  A candidate over a limit is infeasible, as one outside the input box is.  Step 0's
 rate is taken against the control applied before the plan: `solve(..., previous_control=)`, by default the first control
-of the last accepted plan - what a caller that applies the plans has just applied; none on the first solve."""
+of the last accepted plan - what a caller that applies the plans has just applied; none on the first solve.
+
+Grip adaptation (acmpc_score_grips, GripEstimator): `grip_adapt` - a dict, off by default - lets the solver find the road's
+grip from its own driving instead of being told an ensemble.  Every solve logs (state, the control applied since the
+previous solve - `previous_control`, else the last accepted plan's first control), scores a grid of grip hypotheses
+against the last `window` transitions, and when an ACCEPTED estimate (GripEstimator's rule) has moved by at least one
+grid step, scores from then on under `set_dynamics_ensemble([params.with_axle_grip(f b, r b) for b in bracket],
+reduce="mean")`.  Keys: `grid` (default 0.3 .. 1.5 step 0.05), `axles` ("tied" or "split"), `window` (40), `min_window`
+(10), `segment` (1), `bracket` (default (0.8, 1.2)), `prior` (grip scales scored under until the first accepted estimate,
+default (1.0,): the nominal vehicle), `log_dt` (default `rollout_dt`: the period at which solve is called).  Mutually
+exclusive with `vehicle_ensemble` / `grip_ensemble`.  `solver.grip` is the current estimate."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -35,6 +45,7 @@ import numpy as np
 
 from . import _capi
 from .dynamic_model import DynamicBicycleParams
+from .grip_estimator import GripEstimator
 
 SOLVED = "solved"
 DEFAULT_CANDIDATES = 16384
@@ -43,6 +54,30 @@ DEFAULT_SIGMA = (0.05, 0.3)
 DEFAULT_U_MIN = (-0.3, -1.0)
 DEFAULT_U_MAX = (0.3, 1.0)
 SAMPLING_UPDATES = ("argmin", "softmin")
+GRIP_ADAPT_KEYS = ("grid", "axles", "window", "min_window", "segment", "bracket", "prior", "log_dt")
+DEFAULT_BRACKET = (0.8, 1.2)
+DEFAULT_PRIOR = (1.0,)
+
+
+def grip_adaptation(config: Dict) -> Optional[Dict]:
+    """The checked `grip_adapt` setting of a config (None: off): ValueError with an ensemble key beside it, for an unknown
+    key, or for a bracket / prior that is not 1 .. MAX_VEHICLES finite positive scales."""
+    adapt = config.get("grip_adapt")
+    if adapt is None:
+        return None
+    for key in ("vehicle_ensemble", "grip_ensemble", "ensemble_weights", "ensemble_reduce"):
+        if config.get(key) is not None:
+            raise ValueError("grip_adapt and %s are mutually exclusive" % key)
+    adapt = dict(adapt)
+    unknown = sorted(set(adapt) - set(GRIP_ADAPT_KEYS))
+    if unknown:
+        raise ValueError("unknown grip_adapt key(s) %s" % ", ".join(unknown))
+    for key, default in (("bracket", DEFAULT_BRACKET), ("prior", DEFAULT_PRIOR)):
+        scales = tuple(float(v) for v in adapt.get(key, default))
+        if not 1 <= len(scales) <= _capi.MAX_VEHICLES or not all(np.isfinite(v) and v > 0.0 for v in scales):
+            raise ValueError("grip_adapt %s is 1 .. %d finite, positive scales, not %r" % (key, _capi.MAX_VEHICLES, scales))
+        adapt[key] = scales
+    return adapt
 
 
 def ensemble_vehicles(config: Dict, params: DynamicBicycleParams) -> Optional[list]:
@@ -79,7 +114,10 @@ class DynamicSamplingSolver:
         self._seed = int(config.get("sampling_seed", 0))
         self._dt = float(config.get("rollout_dt", 0.05))
         self._params = params if params is not None else DynamicBicycleParams.reference()
-        vehicles = ensemble_vehicles(config, self._params)   # (a config error raises before any handle exists)
+        adapt = grip_adaptation(config)                      # (a config error raises before any handle exists)
+        vehicles = ensemble_vehicles(config, self._params)
+        if adapt is not None:
+            vehicles = [self._params.with_grip(g) for g in adapt["prior"]]
         integration = _capi.integration_setting(config.get("rollout_substeps", 1), config.get("low_speed_blend"))
         terms = _capi.dynamics_terms(config.get("rate_cost", (0.0, 0.0)), config.get("rate_limit"),
                                      config.get("slip_cost", 0.0), config.get("slip_limit"))
@@ -110,6 +148,17 @@ class DynamicSamplingSolver:
             self._engine.set_dynamics_terms(*terms)
         self._plan: Optional[np.ndarray] = None
         self._calls = 0
+        self._adapt = adapt
+        self._estimator: Optional[GripEstimator] = None
+        self._applied_grip: Optional[tuple] = None   # the estimate the current ensemble was built round
+        self.grip = SimpleNamespace(front=None, rear=None, error=float("nan"), accepted=False, errors=None)
+        if adapt is not None:
+            # the handle's vehicle 0 - what acmpc_score_grips scales - is member 0 of the current ensemble, not `params`:
+            # its own scale is divided out so that the grid stays relative to `params`
+            self._base_grip = (adapt["prior"][0], adapt["prior"][0])
+            self._estimator = GripEstimator(self._score_grips, grid=adapt.get("grid"), axles=adapt.get("axles", "tied"),
+                                            window=int(adapt.get("window", 40)), min_window=int(adapt.get("min_window", 10)),
+                                            segment=int(adapt.get("segment", 1)), dt=float(adapt.get("log_dt", self._dt)))
 
     @property
     def engine(self):
@@ -120,6 +169,30 @@ class DynamicSamplingSolver:
         if self._plan is None:
             return np.zeros((self._n, 2), dtype=np.float32)
         return np.concatenate([self._plan[1:], self._plan[-1:]]).astype(np.float32)
+
+    def _score_grips(self, states, controls, dt, scales, segment=1, weights=(1.0, 1.0, 1.0)):
+        return self._engine.score_grips(states, controls, dt, np.asarray(scales) / np.asarray(self._base_grip), segment=segment,
+                                        weights=weights)
+
+    def _adapt_grip(self, state, previous_control):
+        """grip_adapt: log this tick, estimate, and rebuild the ensemble round an accepted estimate that has moved."""
+        est = self._estimator
+        applied = previous_control if previous_control is not None else (None if self._plan is None else self._plan[0])
+        if est.transitions == 0 and applied is None:
+            est.reset()          # (nothing applied yet: this state starts the log)
+        elif applied is None:
+            return
+        est.push(state, applied)
+        self.grip = est.estimate()
+        if not self.grip.accepted:
+            return
+        now = (self.grip.front, self.grip.rear)
+        step = est.grid_step * (1.0 - 1e-9)
+        if self._applied_grip is None or any(abs(a - b) >= step for a, b in zip(now, self._applied_grip)):
+            self._engine.set_dynamics_ensemble([self._params.with_axle_grip(now[0] * b, now[1] * b)
+                                                for b in self._adapt["bracket"]], reduce="mean")
+            self._applied_grip = now
+            self._base_grip = (now[0] * self._adapt["bracket"][0], now[1] * self._adapt["bracket"][0])
 
     def solve(self, state, reference_path, previous_control=None):
         """state (X, Y, yaw, vx, vy, r); reference_path a [7, n] table (rows x, y, psi, kappa, ds, width, v) or an object
@@ -132,6 +205,8 @@ class DynamicSamplingSolver:
             table = reference_path._reference_path
         table = np.asarray(table, dtype=np.float64)[:, : self._n]
         self._engine.set_paths(table)
+        if self._estimator is not None:
+            self._adapt_grip(state, previous_control)
         if self._rate_terms:
             if previous_control is None and self._plan is not None:
                 previous_control = self._plan[0]

@@ -125,6 +125,19 @@ __device__ __forceinline__ F pacejka(F alpha, float B, float C, float E, float P
   return P * sin_spec<F>(C * atan_spec<F>(y));
 }
 
+// Where a step takes the two axles' peak factors from: the Vehicle's own (every rollout: scalars of the kernel argument,
+// read where the step has always read them) or a lane's pair (the grip identification, acmpc_identify.hip: one hypothetical
+// vehicle per lane, everything but its two peaks the base Vehicle's).
+struct VehiclePeaks {
+  __device__ __forceinline__ float front(const Vehicle& k) const { return k.Pf; }
+  __device__ __forceinline__ float rear(const Vehicle& k) const { return k.Pr; }
+};
+struct LanePeaks {
+  float Pf, Pr;
+  __device__ __forceinline__ float front(const Vehicle&) const { return Pf; }
+  __device__ __forceinline__ float rear(const Vehicle&) const { return Pr; }
+};
+
 // What a step takes from its control alone: sincos_spec(delta) and the pedal's split.  The same for every sub-step of a
 // control step (dynamic_advance_fine computes it once).
 template <typename F>
@@ -144,17 +157,18 @@ __device__ __forceinline__ ControlTerms<F> control_terms(F delta, F pedal) {
 // vx = max(vx, 0) (the reference's loop, :180; maxNum: a NaN vx becomes 0).  HOISTED: the control's terms come in
 // through `pre` (the sub-steps of dynamic_advance_fine); otherwise they are computed here, where the single step has
 // always computed them - the default setting's kernels are to stay the code they were, instruction for instruction.
-template <bool HOISTED, typename F>
+// PK: the source of the peak factors (VehiclePeaks or LanePeaks).
+template <bool HOISTED, typename F, typename PK = VehiclePeaks>
 __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, const ControlTerms<F>* pre, const Vehicle& k,
-                                              float dt) {
+                                              float dt, const PK pk = PK{}) {
   const F vx = s.vx, vy = s.vy, r = s.r;
   const F den = vx + kVxEps;
   const F qf = (r * k.lf + vy) / den;
   const F qr = (r * k.lr - vy) / den;
   const F a_f = delta - atan_spec<F>(qf);   // the reference's -atan(q) + delta: the same float
   const F a_r = atan_spec<F>(qr);
-  const F F_fy = pacejka<F>(a_f, k.Bf, k.Cf, k.Ef, k.Pf);
-  const F F_ry = pacejka<F>(a_r, k.Br, k.Cr, k.Er, k.Pr);
+  const F F_fy = pacejka<F>(a_f, k.Bf, k.Cf, k.Ef, pk.front(k));
+  const F F_ry = pacejka<F>(a_r, k.Br, k.Cr, k.Er, pk.rear(k));
   const F vx2 = vx * vx;
   const F F_fric = (k.fric0 - k.Cfric2 * vx) - k.Cfric3 * vx2;
   const F brake = (k.Cb1 - k.Cb2 * vx) - k.Cb3 * vx2;
@@ -214,15 +228,15 @@ __host__ __device__ inline bool is_fine(const Integration& g) { return g.substep
 // The control step of a FINE kernel: g.substeps times dynamic_euler with step g.h, the control's terms and tan(delta)
 // computed once, and the blend after each sub-step's update and clip.  The sub-step count and the blend switch are
 // kernel arguments: a scalar loop and a scalar branch, no divergence.  lam == 1 passes the dynamic (vy, r) through bit for
-// bit (1 * a + 0 * b); two multiplies and one add each, no fused multiply-add.
-template <typename F>
+// bit (1 * a + 0 * b); two multiplies and one add each, no fused multiply-add.  PK: as dynamic_euler's.
+template <typename F, typename PK = VehiclePeaks>
 __device__ __forceinline__ void dynamic_advance_fine(StateD_<F>& s, F delta, F pedal, const Vehicle& k,
-                                                     const Integration& g, float inv_L) {
+                                                     const Integration& g, float inv_L, const PK pk = PK{}) {
   const ControlTerms<F> c = control_terms<F>(delta, pedal);
   const F td = c.sd / c.cd;
 #pragma nounroll
   for (int m = 0; m < g.substeps; ++m) {
-    dynamic_euler<true, F>(s, delta, pedal, &c, k, g.h);
+    dynamic_euler<true, F, PK>(s, delta, pedal, &c, k, g.h, pk);
     if (g.blend != 0) {
       const F r_k = (s.vx * td) * inv_L;
       const F vy_k = r_k * k.lr;

@@ -1,0 +1,37 @@
+// Mode D's grip identification (acmpc_score_grips): the launcher of acmpc_identify.hip and its limits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "acmpc_dynamic.h"
+
+namespace acmpc {
+
+constexpr int kIdentifyMaxSteps = 512;            // ACMPC_MAX_LOG_STEPS
+constexpr int kIdentifyMaxHypotheses = 65536;     // ACMPC_MAX_GRIP_HYPOTHESES
+constexpr int64_t kIdentifyMaxValues = int64_t{1} << 22;   // S K: the per-segment values e [S][K]
+
+// Everything on the device.  states [W + 1][3] = (vx, vy, r), controls [W][2] = (delta, pedal), peaks [K][2] = the
+// hypotheses' (Pf, Pr) (8-byte aligned), w = the residual's weights; e [S][K] scratch, S = identify_segments(W, L);
+// errors [K], partial_keys [identify_blocks(K)] and best [1] are written.
+struct IdentifyArgs {
+  const float* states;
+  const float* controls;
+  const float* peaks;
+  float* e;
+  float* errors;
+  int64_t* partial_keys;
+  int64_t* best;
+  int W, L, K;
+  float w[3];
+};
+
+int identify_segments(int W, int L);   // ceil(W / L)
+int identify_blocks(int K);            // workgroups (= partial keys) of K hypotheses: <= 256
+// `vehicle`: the base vehicle (its Pf, Pr are not read); `g`: the integration setting with h of the LOG's period and
+// inv_L[0] the base vehicle's.  hipErrorInvalidValue beyond the limits above.
+hipError_t launch_identify_grip(const IdentifyArgs& args, const Vehicle& vehicle, const Integration& g, hipStream_t s);
+
+}  // namespace acmpc

@@ -287,6 +287,34 @@ int acmpc_set_dynamics_terms(acmpc_ctx* ctx, const double rate_weight[2], const 
  * stored one returns ACMPC_ESTATE. */
 int acmpc_set_previous_control(acmpc_ctx* ctx, const float* u_prev, int32_t P);
 
+/* Mode D, grip identification: which vehicle did a logged stretch of driving come from?  K hypotheses - the handle's
+ * vehicle 0 (the block of acmpc_set_dynamics, or member 0 of acmpc_set_dynamics_ensemble) with Df scales[k][0] and
+ * Dr scales[k][1], derived as every block is (the two peaks in float64, rounded once; everything else vehicle 0's own
+ * floats, so scales (1, 1) is vehicle 0 bit for bit) - are rolled over the log and scored by their prediction error.
+ *   states    host [W + 1][3] float32 (vx, vy, r); controls host [W][2] float32 (delta, pedal), 1 <= W <=
+ *             ACMPC_MAX_LOG_STEPS; control j was applied between state j and state j + 1 (no pose: the velocity rows of
+ *             the step do not read it)
+ *   dt        the LOG's period (need not be the handle's): a control step is the handle's integration setting (M, blend)
+ *             with h = float32(dt / M)
+ *   segment   L in 1 .. W: segment s covers steps [s L, min((s + 1) L, W)), starts from the LOGGED state s L, rolls
+ *             open-loop under the logged controls and adds, after every control step j,
+ *             weights[0] dvx^2 + weights[1] dvy^2 + weights[2] dr^2 of (rolled - logged state j + 1); L = 1: one-step-ahead
+ *             residuals, L = W: one open-loop roll
+ *   errors    [K] (or NULL): E_k = the segments' sums added in segment order (float32); a NaN or inf in the log makes E_k
+ *             NaN or inf
+ *   best      min_k acmpc_pack_key(E_k, k): ties go to the lower index, non-finite errors rank last
+ * Host pointers; the call blocks and makes one round trip.  It changes nothing a later solve reads.  Refused before any
+ * device work: ACMPC_EINVAL for a null pointer (errors may be), W, K < 1 or segment out of range, dt not finite and
+ * positive, a scale that is not finite and > 0, a weight that is not finite and >= 0 (as a float32), or all weights 0;
+ * ACMPC_ESTATE for a handle that is not mode D or has no vehicle, or while a batch of acmpc_solve_stream_device is
+ * pending; ACMPC_ECAPACITY for K > ACMPC_MAX_GRIP_HYPOTHESES or ceil(W / segment) K > 2^22.  DESIGN.md section 2 "Mode D,
+ * grip identification". */
+#define ACMPC_MAX_LOG_STEPS 512
+#define ACMPC_MAX_GRIP_HYPOTHESES 65536
+int acmpc_score_grips(acmpc_ctx* ctx, const float* states, const float* controls, int32_t W, double dt, int32_t segment,
+                      const double weights[3], const double* scales /* [K][2] front, rear */, int32_t K,
+                      float* errors /* [K] or NULL */, int64_t* best);
+
 /* Copies the packed float32 table of problem `problem` (n rows of ACMPC_COEF_STRIDE_* floats) to `out`.
  * Host only; lets CPU tests pin the host-side arithmetic against the oracle. */
 int acmpc_get_coefficients(const acmpc_ctx* ctx, int32_t problem, float* out, int32_t capacity_floats);

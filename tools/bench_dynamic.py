@@ -38,8 +38,15 @@ controller would set them - TERMS below) and a previous control of zeros for eac
 kernels of csrc/acmpc_dynamic_terms.hip; with `--substeps` / `--blend` as well, under that integration setting.  The roof
 prices `dynamic_terms_step` + M `dynamic_terms_substep`.
 
+With `--identify` the grip identification (acmpc_score_grips: host pointers, one blocking round trip) is timed at K = 4 096
+(the 64 x 64 split grid) and K = 65 536 (256 x 256) hypotheses over a window of W = 40 steps, in one-step (L = 1) and
+eight-step (L = 8) segments, under the run's integration setting: p50 / p99 of the call, the static VALU count per
+hypothesis and control step (profiles/*_isa_mix.json, entry `identify_grip`: M sub-step trips + the rest of the step loop),
+and the vector-issue time that count needs (bench.valu_roofline) as a fraction of the CALL - a lower bound on the step
+kernel's own fraction, which a `rocprofv3 --kernel-trace --stats` run of this command gives (kernel identify_grip_kernel).
+
 usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms]
-                                      [--sampled | --optimize [--update softmin]]"""
+                                      [--sampled | --optimize [--update softmin] | --identify]"""
 import argparse
 import json
 import os
@@ -109,6 +116,7 @@ def main():
     ap.add_argument("--optimize", action="store_true", help="acmpc_optimize 16 384 x 49, 2 rounds, alone")
     ap.add_argument("--update", default="argmin", choices=("argmin", "softmin"),
                     help="with --optimize: softmin = one softmin round, matrix-free against through the matrix")
+    ap.add_argument("--identify", action="store_true", help="acmpc_score_grips at K = 4 096 and 65 536, W = 40, L = 1 and 8")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--substeps", type=int, default=1, help="Euler sub-steps per control step (1 .. 16)")
     ap.add_argument("--blend", default=None, help="LO,HI m/s: the low-speed blend")
@@ -119,6 +127,9 @@ def main():
     INTEGRATION = (args.substeps, None if args.blend is None else tuple(float(v) for v in args.blend.split(",")))
     if args.update == "softmin" and not args.optimize:
         ap.error("--update softmin goes with --optimize")
+    if args.identify:
+        emit(args, measure_identify(args))
+        return
     if args.sampled or args.optimize:
         ks = [int(k) for k in (args.vehicles or "1").split(",")]
         run = measure_sampled if args.sampled else measure_softmin_round if args.update == "softmin" else measure_optimize
@@ -284,6 +295,51 @@ def measure_softmin_round(args, K):
         eng.close()
         del U
         torch.cuda.empty_cache()
+    return out
+
+
+def measure_identify(args):
+    """acmpc_score_grips on a log driven at grip (0.5, 0.7): the call's latency at the four shapes, and what the step
+    kernel's instructions cost at the vector-issue rate."""
+    import bench
+    import grip_spec as gs
+    from acmpc_amd import DynamicBicycleParams, Engine, _capi
+    from acmpc_amd.grip_estimator import grip_scales
+
+    base = DynamicBicycleParams.reference()
+    W = 40
+    states, controls = gs.steering_log(base.with_axle_grip(0.5, 0.7), 0.02, steps=W)
+    eng = Engine(mode=_capi.MODE_DYNAMIC, max_problems=1, max_candidates=64, max_steps=8, step_cost=(1.0, 1.0, 0.0),
+                 r_term=(0.5, 10.0), final_cost=(1.0, 1.0, 0.0), u_min=(-0.3, -1.0), u_max=(0.3, 1.0), margin=0.0,
+                 wheelbase=base.lf + base.lr, dt=0.05)
+    eng.set_dynamics(base)
+    integrate(eng)
+    mix, mix_path = bench.newest_profile("isa_mix.json")
+    M = INTEGRATION[0]
+    per_step = M * sum(mix["entries"]["identify_grip"]["valu"].values()) + sum(mix["entries"]["identify_grip_step"]["valu"].values())
+    out = {"tool": "tools/bench_dynamic.py --identify", "W": W, "substeps": M, "low_speed_blend": INTEGRATION[1],
+           "valu_per_hypothesis_step": per_step}
+    calls = 20 if args.quick else 200
+    for side in (64, 256):
+        scales = grip_scales(np.linspace(0.3, 1.5, side), "split")
+        K = scales.shape[0]
+        for L in (1, 8):
+            lat = []
+            for i in range(10 + calls):
+                t0 = time.perf_counter()
+                errors, best = eng.score_grips(states, controls, 0.05, scales, segment=L)
+                if i >= 10:
+                    lat.append(time.perf_counter() - t0)
+            p50 = float(np.percentile(lat, 50))
+            counted = (float(per_step), mix_path + " (static count: M sub-step trips + the step loop's rest)",
+                       {"source_sha256": mix.get("source_sha256")})
+            roof, _ = bench.valu_roofline(counted, K, W, p50, mix_entry="identify_grip", cpt=1)
+            out["K%d_L%d" % (K, L)] = dict(K=K, L=L, segments=(W + L - 1) // L, p50_ms=p50 * 1e3,
+                                           p99_ms=float(np.percentile(lat, 99)) * 1e3, calls=len(lat),
+                                           best=[float(v) for v in scales[best]], error_best=float(errors[best]),
+                                           vector_issue_time_over_call_p50=roof["frac"],
+                                           opcode_mix_matches_loaded_sources=roof["opcode_mix_matches_loaded_sources"])
+    eng.close()
     return out
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Development tool: the VALU opcode mix of the instruction-bound kernels' hot loops, from the compiler's own assembly.
 
-Compiles csrc/acmpc_kernels_temporal.hip and csrc/acmpc_kernels.hip with the library's flags + --save-temps in a scratch
+Compiles the sources of the named kernels (csrc/acmpc_kernels_temporal.hip, csrc/acmpc_kernels.hip, mode D's units) with the library's flags + --save-temps in a scratch
 directory, takes the innermost loops of the named kernels (tools/isa_loops.py) and writes
 profiles/<tag>_isa_mix.json: per entry the static opcode histogram of ONE trip of the loop (one wave-step), the wave's
 candidates per lane, and the sha256 of the sources it was compiled from - bench.py prices the mix with the issue costs of
@@ -54,12 +54,19 @@ ENTRIES = {
     "dynamic_terms_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
     "dynamic_ensemble_terms_step": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
     "dynamic_ensemble_terms_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
+    # mode D's grip identification (acmpc_score_grips, one hypothesis per lane): the sub-step loop of its step kernel - the
+    # dynamics and the blend's block, WITHOUT the pose (nothing reads it there: no sincos_spec(yaw), no X, Y, yaw updates).
+    # VALU per hypothesis and control step = M trips of it + `identify_grip_step`: the control's terms and the residual, the
+    # step loop's own trip (OUTER)
+    "identify_grip": ("acmpc_identify.hip", "identify_grip_kernel", None),
+    "identify_grip_step": ("acmpc_identify.hip", "identify_grip_kernel", None),
 }
-CANDIDATES_PER_LANE = {"fused_round": 1}
+CANDIDATES_PER_LANE = {"fused_round": 1, "identify_grip": 1, "identify_grip_step": 1}
 OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dynamic_ensemble_fine_step",
-         "dynamic_terms_step", "dynamic_ensemble_terms_step")
+         "dynamic_terms_step", "dynamic_ensemble_terms_step", "identify_grip_step")
 # (exit test at the head: closes with s_branch)
-ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep")
+ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep",
+           "identify_grip")
 
 
 def source_hash():
