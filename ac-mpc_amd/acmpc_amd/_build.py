@@ -10,8 +10,9 @@ CSRC_DIR = os.path.normpath(os.path.join(PKG_DIR, "..", "csrc"))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libacmpc_hip.so")
 SOURCES = ("acmpc_kernels.hip", "acmpc_kernels_temporal.hip", "acmpc_capi.hip", "acmpc_prologue.hip", "acmpc_pf.hip",
-           "acmpc_speed_profile.cpp", "acmpc_host_path.cpp", "acmpc_dynamic.hip", "acmpc_dynamic_terms.hip", "acmpc_identify.hip")
-HEADERS = ("acmpc_kernels.h", "acmpc_device.h", "acmpc_dynamic.h", "acmpc_identify.h", "acmpc_frames.h", "acmpc_admm.h", "acmpc_prologue.h", "acmpc_lq.h", "acmpc_lq_box.h",
+           "acmpc_speed_profile.cpp", "acmpc_host_path.cpp", "acmpc_dynamic.hip", "acmpc_dynamic_terms.hip", "acmpc_identify.hip",
+           "acmpc_capi_solve.hip", "acmpc_capi_optimize.hip", "acmpc_capi_tick.hip", "acmpc_capi_dynamic.hip", "acmpc_capi_rccl.hip")
+HEADERS = ("acmpc_ctx.h", "acmpc_kernels.h", "acmpc_device.h", "acmpc_dynamic.h", "acmpc_identify.h", "acmpc_frames.h", "acmpc_admm.h", "acmpc_prologue.h", "acmpc_lq.h", "acmpc_lq_box.h",
            os.path.join("..", "..", "include", "acmpc.h"))
 
 # -ffp-contract=off: no IMPLICIT fused multiply-add anywhere; the FMAs of mode T's specification are spelt out

@@ -1,0 +1,259 @@
+// C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
+// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the previous control, and the grip
+// identification (acmpc_score_grips), with the checks that the kernels' limits are the public header's.
+#include <algorithm>
+
+#include "acmpc_ctx.h"
+#include "acmpc_identify.h"
+
+using namespace acmpc::capi;
+
+namespace {
+
+static_assert(acmpc::kIdentifyMaxSteps == ACMPC_MAX_LOG_STEPS && acmpc::kIdentifyMaxHypotheses == ACMPC_MAX_GRIP_HYPOTHESES,
+              "the grip identification's limits of acmpc_identify.h are the header's");
+static_assert(acmpc::kMaxSubsteps == ACMPC_MAX_SUBSTEPS, "the sub-step limit of acmpc_dynamic.h is the header's");
+static_assert(acmpc::kMaxVehicles == ACMPC_MAX_VEHICLES && acmpc::kEnsembleMean == ACMPC_ENSEMBLE_MEAN &&
+                  acmpc::kEnsembleMax == ACMPC_ENSEMBLE_MAX,
+              "the ensemble constants of acmpc_dynamic.h are the header's");
+
+// The two axles' peak factors of a vehicle block whose Df and Dr are scaled by (sf, sr) - (1, 1): the block's own - in
+// float64, the reference's association, each rounded to float32 once (the block is checked: derive_vehicle)
+void derive_peaks(const double* coef, double sf, double sr, float* Pf, float* Pr) {
+  const double F_z0 = coef[0], Df = coef[3] * sf, epsf = coef[5], Dr = coef[8] * sr, epsr = coef[10], mass = coef[11],
+               g = coef[13], lf = coef[14], lr = coef[15];
+  const double F_zf = mass * g * lr / (lr + lf);
+  const double F_zr = mass * g * lf / (lr + lf);
+  *Pf = static_cast<float>(Df * (1 + epsf * F_zf / F_z0) * F_zf / F_z0);
+  *Pr = static_cast<float>(Dr * (1 + epsr * F_zr / F_z0) * F_zr / F_z0);
+}
+
+// mode D's float32 constants of one vehicle block (acmpc_set_dynamics): nullptr, or why the block is refused
+const char* derive_vehicle(const double* coef, double wheelbase, acmpc::Vehicle* out) {
+  for (int q = 0; q < acmpc::kDynamicsCount; ++q)
+    if (!std::isfinite(coef[q])) return "non-finite value in the vehicle block";
+  const double F_z0 = coef[0], Bf = coef[1], Cf = coef[2], Ef = coef[4], Br = coef[6], Cr = coef[7], Er = coef[9],
+               mass = coef[11], Iz = coef[12], lf = coef[14], lr = coef[15], bias = coef[16];
+  if (!(mass > 0.0) || !(Iz > 0.0)) return "mass and Iz must be positive";
+  if (F_z0 == 0.0 || lr + lf == 0.0) return "F_z0 and lf + lr must not be zero";
+  // float64, the reference's association, each constant rounded to float32 once ("Mode D")
+  acmpc::Vehicle& v = *out;
+  derive_peaks(coef, 1.0, 1.0, &v.Pf, &v.Pr);
+  v.lf = static_cast<float>(lf);
+  v.lr = static_cast<float>(lr);
+  v.Bf = static_cast<float>(Bf);
+  v.Cf = static_cast<float>(Cf);
+  v.Ef = static_cast<float>(Ef);
+  v.Br = static_cast<float>(Br);
+  v.Cr = static_cast<float>(Cr);
+  v.Er = static_cast<float>(Er);
+  v.mass = static_cast<float>(mass);
+  v.inv_mass = static_cast<float>(1.0 / mass);
+  v.inv_Iz = static_cast<float>(1.0 / Iz);
+  v.Cm1 = static_cast<float>(coef[17]);
+  v.Cm2 = static_cast<float>(coef[18]);
+  v.Cm3 = static_cast<float>(coef[19]);
+  v.Cb1 = static_cast<float>(coef[20]);
+  v.Cb2 = static_cast<float>(coef[21]);
+  v.Cb3 = static_cast<float>(coef[22]);
+  v.fric0 = static_cast<float>(-coef[23]);
+  v.Cfric2 = static_cast<float>(coef[24]);
+  v.Cfric3 = static_cast<float>(coef[25]);
+  v.bias_front = static_cast<float>(bias);
+  v.bias_rear = static_cast<float>(1 - bias);
+  v.wheelbase = static_cast<float>(wheelbase);
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int acmpc_set_dynamics(acmpc_ctx* c, const double* coef, int32_t count) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics needs a mode D handle");
+  if (coef == nullptr) return fail(c, ACMPC_EINVAL, "null vehicle block");
+  if (count != acmpc::kDynamicsCount) return fail(c, ACMPC_EINVAL, "the vehicle block has ACMPC_DYNAMICS_COUNT = 26 values");
+  // an ensemble of one (omega_0 = 1, MEAN): the single-vehicle kernels
+  acmpc::VehicleEnsemble e{};
+  const char* why = derive_vehicle(coef, c->prm.wheelbase, &e.v[0]);
+  if (why != nullptr) return fail(c, ACMPC_EINVAL, why);
+  e.omega[0] = 1.0f;
+  e.K = 1;
+  e.reduce = ACMPC_ENSEMBLE_MEAN;
+  c->vehicles = e;
+  c->vehicle_L[0] = coef[14] + coef[15];
+  std::memcpy(c->vehicle0, coef, sizeof c->vehicle0);
+  c->has_dynamics = true;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_ensemble(acmpc_ctx* c, const double* coef, int32_t K, const double* weights, int32_t reduce) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics_ensemble needs a mode D handle");
+  if (coef == nullptr) return fail(c, ACMPC_EINVAL, "null vehicle blocks");
+  if (K < 1 || K > ACMPC_MAX_VEHICLES) return fail(c, ACMPC_EINVAL, "an ensemble has 1 .. ACMPC_MAX_VEHICLES = 8 vehicles");
+  if (reduce != ACMPC_ENSEMBLE_MEAN && reduce != ACMPC_ENSEMBLE_MAX) return fail(c, ACMPC_EINVAL, "unknown reduce");
+  // everything is checked before anything is kept: a refused ensemble leaves the handle's vehicle(s) as they were
+  acmpc::VehicleEnsemble e{};
+  double total = 0.0;
+  for (int k = 0; k < K; ++k) {
+    if (weights != nullptr) {
+      if (!std::isfinite(weights[k]) || !(weights[k] > 0.0))
+        return fail(c, ACMPC_EINVAL, "vehicle " + std::to_string(k) + ": a weight must be finite and positive");
+      total += weights[k];
+    }
+    const char* why = derive_vehicle(coef + static_cast<size_t>(k) * acmpc::kDynamicsCount, c->prm.wheelbase, &e.v[k]);
+    if (why != nullptr) return fail(c, ACMPC_EINVAL, "vehicle " + std::to_string(k) + ": " + why);
+  }
+  if (weights != nullptr && !std::isfinite(total)) return fail(c, ACMPC_EINVAL, "the weights' sum is not finite");
+  // omega_k = w_k / sum_j w_j in float64 (the sum in k order), each rounded once; no weights: float32(1 / K)
+  for (int k = 0; k < K; ++k)
+    e.omega[k] = static_cast<float>(weights != nullptr ? weights[k] / total : 1.0 / K);
+  e.K = K;
+  e.reduce = reduce;
+  c->vehicles = e;
+  for (int k = 0; k < K; ++k)
+    c->vehicle_L[k] = coef[static_cast<size_t>(k) * acmpc::kDynamicsCount + 14] + coef[static_cast<size_t>(k) * acmpc::kDynamicsCount + 15];
+  std::memcpy(c->vehicle0, coef, sizeof c->vehicle0);
+  c->has_dynamics = true;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_integration(acmpc_ctx* c, int32_t substeps, double blend_lo, double blend_hi) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics_integration needs a mode D handle");
+  if (substeps < 1 || substeps > ACMPC_MAX_SUBSTEPS) return fail(c, ACMPC_EINVAL, "substeps is 1 .. ACMPC_MAX_SUBSTEPS = 16");
+  const bool off = blend_lo == 0.0 && blend_hi == 0.0;
+  if (!off && !(std::isfinite(blend_lo) && std::isfinite(blend_hi) && blend_lo >= 0.0 && blend_lo < blend_hi))
+    return fail(c, ACMPC_EINVAL, "the low-speed blend is 0, 0 (off) or 0 <= lo < hi, both finite");
+  // everything is checked before anything is kept: a refused setting leaves the handle's as it was
+  c->substeps = substeps;
+  c->blend_lo = off ? 0.0 : blend_lo;   // (-0.0 is 0)
+  c->blend_hi = off ? 0.0 : blend_hi;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_terms(acmpc_ctx* c, const double rate_weight[2], const double rate_max[2], double slip_weight,
+                             double slip_max) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_dynamics_terms needs a mode D handle");
+  if (rate_weight == nullptr || rate_max == nullptr) return fail(c, ACMPC_EINVAL, "null rate_weight or rate_max");
+  const double weights[3] = {rate_weight[0], rate_weight[1], slip_weight};
+  const double limits[3] = {rate_max[0], rate_max[1], slip_max};
+  for (int q = 0; q < 3; ++q) {
+    // float32 is what the kernels get: a weight that overflows it is not finite there
+    if (!std::isfinite(static_cast<float>(weights[q])) || !(weights[q] >= 0.0))
+      return fail(c, ACMPC_EINVAL, "a weight of the rate and slip terms must be finite and >= 0");
+    if (!(static_cast<float>(limits[q]) > 0.0f)) return fail(c, ACMPC_EINVAL, "a limit of the rate and slip terms must be > 0 (INFINITY: none)");
+  }
+  // everything is checked before anything is kept: a refused setting leaves the handle's as it was
+  for (int q = 0; q < 2; ++q) {
+    c->rate_weight[q] = weights[q] + 0.0;   // (-0.0 is 0)
+    c->rate_max[q] = limits[q];
+  }
+  c->slip_weight = slip_weight + 0.0;
+  c->slip_max = slip_max;
+  return ACMPC_OK;
+}
+
+int acmpc_set_previous_control(acmpc_ctx* c, const float* u_prev, int32_t P) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_EINVAL, "acmpc_set_previous_control needs a mode D handle");
+  if (u_prev == nullptr) {
+    c->h_uprev.clear();
+    c->uprev_P = 0;
+    c->uprev_dirty = false;
+    return ACMPC_OK;
+  }
+  if (P < 1 || P > c->prm.max_problems) return fail(c, ACMPC_EINVAL, "P must be 1 .. max_problems");
+  c->h_uprev.assign(u_prev, u_prev + static_cast<size_t>(P) * 2);
+  c->uprev_P = P;
+  c->uprev_dirty = true;
+  return ACMPC_OK;
+}
+
+int acmpc_score_grips(acmpc_ctx* c, const float* states, const float* controls, int32_t W, double dt, int32_t segment,
+                      const double weights[3], const double* scales, int32_t K, float* errors, int64_t* best) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  // every refusal comes before any device work
+  if (states == nullptr || controls == nullptr || weights == nullptr || scales == nullptr || best == nullptr)
+    return fail(c, ACMPC_EINVAL, "acmpc_score_grips: null pointer");
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_score_grips needs a mode D handle");
+  if (!c->has_dynamics) return fail(c, ACMPC_ESTATE, "mode D: acmpc_set_dynamics has not been called");
+  if (c->stream_pending)
+    return fail(c, ACMPC_ESTATE, "a batch of acmpc_solve_stream_device is pending: acmpc_solve_stream_flush first");
+  if (W < 1 || W > ACMPC_MAX_LOG_STEPS) return fail(c, ACMPC_EINVAL, "the log has 1 .. ACMPC_MAX_LOG_STEPS = 512 steps");
+  if (segment < 1 || segment > W) return fail(c, ACMPC_EINVAL, "segment is 1 .. W");
+  if (K < 1) return fail(c, ACMPC_EINVAL, "K must be positive");
+  if (!std::isfinite(dt) || !(dt > 0.0)) return fail(c, ACMPC_EINVAL, "dt must be finite and positive");
+  bool any_weight = false;
+  for (int q = 0; q < 3; ++q) {
+    // float32 is what the kernel gets: a weight that overflows it is not finite there
+    if (!std::isfinite(static_cast<float>(weights[q])) || !(weights[q] >= 0.0))
+      return fail(c, ACMPC_EINVAL, "a weight of the residual must be finite and >= 0");
+    any_weight = any_weight || static_cast<float>(weights[q]) != 0.0f;
+  }
+  if (!any_weight) return fail(c, ACMPC_EINVAL, "the residual's weights are all zero");
+  if (K > ACMPC_MAX_GRIP_HYPOTHESES) return fail(c, ACMPC_ECAPACITY, "at most ACMPC_MAX_GRIP_HYPOTHESES = 65536 hypotheses");
+  const int S = acmpc::identify_segments(W, segment);
+  if (static_cast<int64_t>(S) * K > acmpc::kIdentifyMaxValues)
+    return fail(c, ACMPC_ECAPACITY, "segments x hypotheses exceeds 2^22");
+  for (int64_t q = 0; q < 2 * static_cast<int64_t>(K); ++q)
+    if (!std::isfinite(scales[q]) || !(scales[q] > 0.0))
+      return fail(c, ACMPC_EINVAL, "hypothesis " + std::to_string(q / 2) + ": a grip scale must be finite and positive");
+
+  // device block: [256] partial keys | best key | [max K] errors | [max K][2] peaks | [513][3] states | [512][2] controls
+  constexpr size_t kMaxK = ACMPC_MAX_GRIP_HYPOTHESES, kMaxW = ACMPC_MAX_LOG_STEPS;
+  constexpr size_t kBestAt = 256 * sizeof(int64_t), kErrorsAt = kBestAt + sizeof(int64_t);
+  constexpr size_t kUpAt = kErrorsAt + kMaxK * sizeof(float);   // (a multiple of 8: the peaks are read in pairs)
+  constexpr size_t kBlockBytes = kUpAt + (2 * kMaxK + 3 * (kMaxW + 1) + 2 * kMaxW) * sizeof(float);
+  static_assert(kUpAt % 8 == 0, "the peaks' pairs are 8-byte aligned");
+  ACMPC_TRY(ensure_device(c));
+  if (c->stream == nullptr) ACMPC_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  hipStream_t s = c->stream;
+  ACMPC_HIP(c, alloc_once(&c->d_identify, kBlockBytes));
+  const size_t e_floats = static_cast<size_t>(S) * K;
+  if (c->identify_e_floats < e_floats) {   // (nothing of an earlier call is in flight: the call blocks)
+    (void)hipFree(c->d_identify_e);
+    c->d_identify_e = nullptr;
+    c->identify_e_floats = 0;
+    ACMPC_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_identify_e), e_floats * sizeof(float)));
+    c->identify_e_floats = e_floats;
+  }
+  // one copy up: peaks | states | controls
+  const size_t peak_floats = 2 * static_cast<size_t>(K), state_floats = 3 * (static_cast<size_t>(W) + 1),
+               control_floats = 2 * static_cast<size_t>(W);
+  const size_t up_bytes = (peak_floats + state_floats + control_floats) * sizeof(float);
+  const size_t down_bytes = sizeof(int64_t) + (errors != nullptr ? static_cast<size_t>(K) * sizeof(float) : 0);
+  c->h_identify.resize(std::max(up_bytes, down_bytes));
+  float* up = reinterpret_cast<float*>(c->h_identify.data());
+  for (int k = 0; k < K; ++k) derive_peaks(c->vehicle0, scales[2 * k], scales[2 * k + 1], &up[2 * k], &up[2 * k + 1]);
+  std::memcpy(up + peak_floats, states, state_floats * sizeof(float));
+  std::memcpy(up + peak_floats + state_floats, controls, control_floats * sizeof(float));
+  ACMPC_HIP(c, hipMemcpyAsync(c->d_identify + kUpAt, up, up_bytes, hipMemcpyHostToDevice, s));
+  acmpc::IdentifyArgs a{};
+  a.peaks = reinterpret_cast<const float*>(c->d_identify + kUpAt);
+  a.states = a.peaks + peak_floats;
+  a.controls = a.states + state_floats;
+  a.e = c->d_identify_e;
+  a.errors = reinterpret_cast<float*>(c->d_identify + kErrorsAt);
+  a.partial_keys = reinterpret_cast<int64_t*>(c->d_identify);
+  a.best = reinterpret_cast<int64_t*>(c->d_identify + kBestAt);
+  a.W = W;
+  a.L = segment;
+  a.K = K;
+  for (int q = 0; q < 3; ++q) a.w[q] = static_cast<float>(weights[q]);
+  // the handle's integration setting with the step of THIS log, under vehicle 0
+  acmpc::Integration g = dynamics_integration(c);
+  g.h = static_cast<float>(dt / c->substeps);
+  ACMPC_HIP(c, acmpc::launch_identify_grip(a, c->vehicles.v[0], g, s));
+  // one copy down: best key | errors
+  ACMPC_HIP(c, hipMemcpyAsync(c->h_identify.data(), c->d_identify + kBestAt, down_bytes, hipMemcpyDeviceToHost, s));
+  ACMPC_HIP(c, hipStreamSynchronize(s));
+  std::memcpy(best, c->h_identify.data(), sizeof(int64_t));
+  if (errors != nullptr) std::memcpy(errors, c->h_identify.data() + sizeof(int64_t), static_cast<size_t>(K) * sizeof(float));
+  return ACMPC_OK;
+}
+
+}  // extern "C"

@@ -4,7 +4,7 @@ keeps it at any problem count); from 256 problems up sixteen lanes per problem, 
 problem takes the argmin and re-rolls the winner while other problems are still streaming); and - a stream of batches -
 inside the NEXT batch's rollout launch (rollout_chained_kernel).  The records must be
 the two-launch form's (rollout_kernel + finalize_kernel, the default: it is the faster of the two on the headline's batch,
-csrc/acmpc_capi.hip solve_batched; ACMPC_TAILED_ROLLOUT=1 selects the one launch) bit for bit, and the oracle's."""
+csrc/acmpc_capi_solve.hip solve_batched; ACMPC_TAILED_ROLLOUT=1 selects the one launch) bit for bit, and the oracle's."""
 import numpy as np
 import pytest
 
