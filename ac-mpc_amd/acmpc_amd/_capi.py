@@ -27,6 +27,9 @@ LAYOUT_CANDIDATE_MAJOR, LAYOUT_STEP_MAJOR = 0, 1
 COEF_STRIDE = {MODE_SPATIAL: 12, MODE_TEMPORAL: 8, MODE_DYNAMIC: 8}
 STATE_FLOATS = {MODE_SPATIAL: 3, MODE_TEMPORAL: 3, MODE_DYNAMIC: 6}   # a start state x0
 REC_COST, REC_VIOLATION, REC_NFEASIBLE, REC_OWNER, REC_HEADER = 0, 1, 2, 3, 4
+ROUND_SINGLE, ROUND_PAIR, ROUND_QUAD, ROUND_TRIO = 0, 1, 2, 3   # ACMPC_ROUND_*: the kernel of a sampled round
+ROUND_FIELDS = ("kernel", "fused_finalize", "traced", "chained", "frames_in_lds", "frames_tabulated", "tick_accepted",
+                "tick_frames")   # acmpc_describe_rounds' out[8]
 
 
 class EngineError(RuntimeError):
@@ -199,6 +202,7 @@ SIGNATURES = {
                                            C.c_void_p, _I32P]),
     "acmpc_tick_read_device_tables": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acmpc_tick_read_device_frames": (C.c_int, [_CTX, C.c_void_p, C.c_int64]),
+    "acmpc_describe_rounds": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, _I32P]),
     "acmpc_speed_profile_qp_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double,
                                                 C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p,
                                                 C.c_void_p, C.c_int32, _I32P]),
@@ -795,6 +799,15 @@ class Engine:
         out = np.empty(self._lib.acmpc_search_frame_floats(n), dtype=np.float32)
         self._check(self._lib.acmpc_tick_read_device_frames(self._ctx, out.ctypes.data, out.size))
         return out
+
+    def describe_rounds(self, P: int, N: int, n: int) -> dict:
+        """Which form the sampled rounds of `optimize` with P problems, N candidates and n steps - and of a tick of n + 1
+        points - take on this handle (acmpc_describe_rounds; test hook, no device work): dict(kernel = ROUND_*, or -1 for
+        rounds through the control matrix; fused_finalize, traced, chained, frames_in_lds, frames_tabulated, tick_accepted,
+        tick_frames as bools)."""
+        out = np.zeros(8, dtype=np.int32)
+        self._check(self._lib.acmpc_describe_rounds(self._ctx, int(P), int(N), int(n), out.ctypes.data_as(_I32P)))
+        return dict(kernel=int(out[0]), **{name: bool(v) for name, v in zip(ROUND_FIELDS[1:], out[1:])})
 
     def speed_profile_qp_device(self, v_hi, ds, a_min, a_max, v_min, max_iter=4000, eps_abs=1e-3, eps_rel=1e-3,
                                 warm=None, check_every=10):

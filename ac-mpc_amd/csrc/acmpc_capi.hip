@@ -86,6 +86,11 @@ static void verified_frames(const float* coef, int P, int n, std::vector<float>*
   }
 }
 
+// mode T with the exhaustive search, from the verified window's width up to the cap above
+bool paths_tabulate_frames(const acmpc_ctx* c, int n) {
+  return c->prm.mode == ACMPC_MODE_TEMPORAL && c->prm.nn_ahead < 0 && n >= acmpc::kVerifiedWindow && n <= kMaxVerifiedSteps;
+}
+
 int ensure_device(acmpc_ctx* c) {
   if (c->device_ready) return ACMPC_OK;
   c->touched_device = true;
@@ -524,7 +529,7 @@ int acmpc_set_paths(acmpc_ctx* c, const double* tables, int32_t P, int32_t n) {
   }
   if (c->prm.lq_candidate != 0) c->h_tables.assign(tables, tables + static_cast<size_t>(P) * 7 * n);
   c->h_nn_frames.clear();
-  if (c->prm.mode == ACMPC_MODE_TEMPORAL && c->prm.nn_ahead < 0 && n >= acmpc::kVerifiedWindow && n <= kMaxVerifiedSteps)
+  if (paths_tabulate_frames(c, n))
     verified_frames(c->h_coef.data(), P, n, &c->h_nn_frames);
   c->P_set = P;
   c->n_set = n;
@@ -541,7 +546,7 @@ int acmpc_set_coefficients(acmpc_ctx* c, const float* coef, int32_t P, int32_t n
   c->h_coef.assign(coef, coef + static_cast<size_t>(P) * n * c->coef_stride);
   if (c->h_tables.size() != static_cast<size_t>(P) * 7 * n) c->h_tables.clear();   // (no float64 tables for these paths)
   c->h_nn_frames.clear();
-  if (c->prm.mode == ACMPC_MODE_TEMPORAL && c->prm.nn_ahead < 0 && n >= acmpc::kVerifiedWindow && n <= kMaxVerifiedSteps)
+  if (paths_tabulate_frames(c, n))
     verified_frames(c->h_coef.data(), P, n, &c->h_nn_frames);
   c->P_set = P;
   c->n_set = n;

@@ -18,11 +18,20 @@ bool use_fused_finalize(const acmpc_ctx* c, int n) {
   return !c->sw.no_fused_finalize && acmpc::fused_finalize_fits(c->prm.mode, n);
 }
 
-// The fused finalize copies the record out of the winning workgroup's trace when the launch is small enough for the
-// trace buffer (closed-loop rounds are: 256 workgroups) and the trace fits the LDS; else it re-draws and re-rolls.
-static bool use_traced_finalize(const acmpc_ctx* c, int P, int N, int n) {
-  return !c->sw.no_traced_finalize && acmpc::traced_finalize_fits(c->prm.mode, n) &&
-         static_cast<long long>(P) * ((N + 63) / 64) <= kTraceBlocks;
+// How the fused rounds of a (P, N, n) optimisation run: THE place where that is decided - enqueue_rounds takes it from
+// here, and so does acmpc_describe_rounds.
+// Traced: the fused finalize copies the record out of the winning workgroup's trace when the launch is small enough for
+// the trace buffer (closed-loop rounds are: 256 workgroups) and the trace fits the LDS; else it re-draws and re-rolls.
+// Chained: a traced round that is not the last ends without a finalize and the next launch finds its winner itself,
+// while a problem has no more workgroups than a wave's lanes hold keys for.
+RoundPlan plan_rounds(const acmpc_ctx* c, int P, int N, int n) {
+  const int blocks = (N + 63) / 64;
+  RoundPlan plan{};
+  plan.fused_finalize = use_fused_finalize(c, n);
+  plan.traced = plan.fused_finalize && !c->sw.no_traced_finalize && acmpc::traced_finalize_fits(c->prm.mode, n) &&
+                static_cast<long long>(P) * blocks <= kTraceBlocks;
+  plan.chained = plan.traced && blocks <= acmpc::kChainBlocks && !c->sw.no_chained_rounds;
+  return plan;
 }
 
 // One LQ plan (csrc/acmpc_lq.h) into `out` [n][2]: the path's 7 x n float64 table, the start state as the rollouts take it
@@ -61,7 +70,8 @@ int enqueue_rounds(acmpc_ctx* c, const OptInputs& in, int P, int N, int n, int r
                    double shrink, uint64_t seed, const uint32_t* d_seed, hipStream_t s, bool fused, float* final_records,
                    unsigned* done, unsigned done_value) {
   const bool has_uref = in.uref != nullptr;
-  const bool fused_finalize = use_fused_finalize(c, n);
+  const RoundPlan plan = plan_rounds(c, P, N, n);
+  const bool fused_finalize = plan.fused_finalize;
   const int layout = ACMPC_LAYOUT_STEP_MAJOR;
   const int rec_floats = acmpc_record_floats(n);
   double scale = 1.0;
@@ -85,8 +95,7 @@ int enqueue_rounds(acmpc_ctx* c, const OptInputs& in, int P, int N, int n, int r
     // last-workgroup tail (six dependent device-scope round trips, ~10 us).  Keys, counts and traces alternate between
     // two sets, since a round reads its predecessor's while it writes its own.
     const int blocks = (N + 63) / 64;
-    const bool traced = fused_finalize && use_traced_finalize(c, P, N, n);
-    const bool chain = traced && blocks <= acmpc::kChainBlocks && !c->sw.no_chained_rounds;
+    const bool traced = plan.traced, chain = plan.chained;
     const size_t set = (chain && (r & 1)) ? 1 : 0;
     const size_t trace_set_floats = static_cast<size_t>(kTraceBlocks) * acmpc::trace_floats(c->prm.max_steps);
     float* d_trace = c->d_trace + set * trace_set_floats;
@@ -188,6 +197,33 @@ static int optimize_dynamic(acmpc_ctx* c, const float* x0, const float* centre, 
 }  // namespace acmpc
 
 extern "C" {
+
+static_assert(acmpc::kSampledSingle == ACMPC_ROUND_SINGLE && acmpc::kSampledPair == ACMPC_ROUND_PAIR &&
+              acmpc::kSampledQuad == ACMPC_ROUND_QUAD && acmpc::kSampledTrio == ACMPC_ROUND_TRIO, "include/acmpc.h");
+
+int acmpc_describe_rounds(const acmpc_ctx* c, int32_t P, int32_t N, int32_t n, int32_t out[8]) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (out == nullptr) return fail(c, ACMPC_EINVAL, "null output");
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "mode D has no sampled rounds of these forms");
+  if (P < 1 || N < 1 || n < 1) return fail(c, ACMPC_EINVAL, "P, N and n must be positive");
+  if (P > c->prm.max_problems || N > c->prm.max_candidates || n > c->prm.max_steps)
+    return fail(c, ACMPC_ECAPACITY, "shape exceeds the handle's capacity");
+  const bool tabulated = paths_tabulate_frames(c, n);
+  const bool fused = !c->sw.no_fused_sampling && c->prm.centre_update == 0;   // (else: rounds through the control matrix)
+  const RoundPlan plan = fused ? plan_rounds(c, P, N, n) : RoundPlan{};
+  const acmpc::SampledForm form = acmpc::choose_sampled_form(c->prm.mode, n, plan.traced, plan.fused_finalize,
+                                                             tabulated && !c->sw.no_verified_search, c->opt);
+  const char* why = nullptr;
+  out[0] = fused ? form.kernel : -1;
+  out[1] = plan.fused_finalize ? 1 : 0;
+  out[2] = plan.traced ? 1 : 0;
+  out[3] = plan.chained ? 1 : 0;
+  out[4] = (fused && form.frames) ? 1 : 0;
+  out[5] = tabulated ? 1 : 0;
+  out[6] = tick_check(c, n + 1, 1, N, &why) == ACMPC_OK ? 1 : 0;
+  out[7] = (out[6] != 0 && tick_tabulates_frames(c, n)) ? 1 : 0;
+  return ACMPC_OK;
+}
 
 int acmpc_optimize(acmpc_ctx* c, const float* x0, const float* centre, const float* u_ref, int32_t P, int32_t N,
                    int32_t n, int32_t rounds, const double sigma[2], double shrink, uint64_t seed, float* records) {

@@ -127,17 +127,11 @@ int tick_validate(acmpc_ctx* c, const acmpc_tick* t, const double* coords, const
   if (t->struct_size != sizeof(acmpc_tick)) return fail(c, ACMPC_EINVAL, "acmpc_tick size mismatch");
   if (c->stream_pending)
     return fail(c, ACMPC_ESTATE, "a batch of acmpc_solve_stream_device is pending: acmpc_solve_stream_flush first");
-  if (c->prm.mode == ACMPC_MODE_DYNAMIC)
-    return fail(c, ACMPC_ESTATE, "mode D has no control tick: use acmpc_set_paths + acmpc_optimize");
-  if (c->prm.centre_update != 0) return fail(c, ACMPC_ESTATE, "acmpc_control_tick needs a handle with centre_update = 0");
-  if (c->prm.mode == ACMPC_MODE_TEMPORAL && !(c->prm.dt > 0.0)) return fail(c, ACMPC_ESTATE, "mode T needs a positive dt");
-  const int H = t->horizon, n = H - 1, N = t->n_candidates;
-  if (H < 3 || t->rounds < 1 || N < 1) return fail(c, ACMPC_EINVAL, "need horizon >= 3, rounds >= 1, n_candidates >= 1");
-  if (n > c->prm.max_steps || N > c->prm.max_candidates) return fail(c, ACMPC_ECAPACITY, "horizon or candidates exceed capacity");
-  if (n > acmpc::kPrologueMaxSteps) return fail(c, ACMPC_ESTATE, "the device prologue holds at most 128 steps");
+  const char* why = nullptr;
+  const int rc = tick_check(c, t->horizon, t->rounds, t->n_candidates, &why);
+  if (rc != ACMPC_OK) return fail(c, rc, why);
   if (centre == nullptr && t->centre_is_reference == 0) return fail(c, ACMPC_EINVAL, "null centre");
   if (coords == nullptr && c->h_map.empty()) return fail(c, ACMPC_EINVAL, "null coords and no map bound");
-  if (!acmpc::fused_finalize_fits(c->prm.mode, n)) return fail(c, ACMPC_ESTATE, "fused finalize does not fit");
   return ACMPC_OK;
 }
 
@@ -170,12 +164,7 @@ int tick_arguments(Tick& k, hipStream_t s) {
   pa.x0 = reinterpret_cast<float*>(c->d_tick + k.in.x0);
   pa.u_ref = reinterpret_cast<float*>(c->d_tick + k.in.uref);
   pa.coef = reinterpret_cast<float*>(c->d_tick + k.in.coef);
-  // the frames of the verified search: tabulated (by the prologue's second workgroup) only when the rounds can take them
-  // - beyond 106 steps they no longer fit the three-wave round's LDS and the search wave scans every waypoint
-  pa.frames = (k.temporal && c->prm.nn_ahead < 0 && k.n >= acmpc::kVerifiedWindow && acmpc::trio_frames_fit(k.n) &&
-               !c->opt.no_trio_rounds && !c->sw.no_verified_search)
-                  ? reinterpret_cast<float*>(c->d_tick + k.in.frames)
-                  : nullptr;
+  pa.frames = tick_tabulates_frames(c, k.n) ? reinterpret_cast<float*>(c->d_tick + k.in.frames) : nullptr;
   pa.centre = reinterpret_cast<float*>(c->d_tick + k.in.centre);
   pa.seed = reinterpret_cast<uint32_t*>(c->d_tick + k.in.seed);
   pa.table_out = reinterpret_cast<double*>(c->h_tick_out + k.out.table);
@@ -432,6 +421,32 @@ int unpack_result(const Tick& k, double* table, float* record, double* decision,
 
 }  // namespace
 
+namespace acmpc {
+namespace capi __attribute__((visibility("hidden"))) {
+
+int tick_check(const acmpc_ctx* c, int H, int rounds, int N, const char** why) {
+  auto no = [why](int code, const char* text) { *why = text; return code; };
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC) return no(ACMPC_ESTATE, "mode D has no control tick: use acmpc_set_paths + acmpc_optimize");
+  if (c->prm.centre_update != 0) return no(ACMPC_ESTATE, "acmpc_control_tick needs a handle with centre_update = 0");
+  if (c->prm.mode == ACMPC_MODE_TEMPORAL && !(c->prm.dt > 0.0)) return no(ACMPC_ESTATE, "mode T needs a positive dt");
+  const int n = H - 1;
+  if (H < 3 || rounds < 1 || N < 1) return no(ACMPC_EINVAL, "need horizon >= 3, rounds >= 1, n_candidates >= 1");
+  if (n > c->prm.max_steps || N > c->prm.max_candidates) return no(ACMPC_ECAPACITY, "horizon or candidates exceed capacity");
+  if (n > acmpc::kPrologueMaxSteps) return no(ACMPC_ESTATE, "the device prologue holds at most 128 steps");
+  if (!acmpc::fused_finalize_fits(c->prm.mode, n)) return no(ACMPC_ESTATE, "fused finalize does not fit");
+  return ACMPC_OK;
+}
+
+// the frames of the verified search: tabulated (by the prologue's second workgroup) only when the rounds can take them -
+// beyond 106 steps they no longer fit the three-wave round's LDS and the search wave scans every waypoint
+bool tick_tabulates_frames(const acmpc_ctx* c, int n) {
+  return c->prm.mode == ACMPC_MODE_TEMPORAL && c->prm.nn_ahead < 0 && n >= acmpc::kVerifiedWindow && acmpc::trio_frames_fit(n) &&
+         !c->opt.no_trio_rounds && !c->sw.no_verified_search;
+}
+
+}  // namespace capi
+}  // namespace acmpc
+
 extern "C" {
 
 int acmpc_control_tick(acmpc_ctx* c, const acmpc_tick* t, const double* coords, const float* centre, double* table,
@@ -527,8 +542,7 @@ int acmpc_tick_read_device_frames(acmpc_ctx* c, float* out, int64_t capacity_flo
   if (out == nullptr) return fail(c, ACMPC_EINVAL, "null output");
   if (!c->tick_ready || c->tick_last_n == 0) return fail(c, ACMPC_ESTATE, "acmpc_control_tick has not run");
   const int n = c->tick_last_n;
-  if (c->prm.mode != ACMPC_MODE_TEMPORAL || c->prm.nn_ahead >= 0 || n < acmpc::kVerifiedWindow || !acmpc::trio_frames_fit(n) ||
-      c->opt.no_trio_rounds || c->sw.no_verified_search)
+  if (!tick_tabulates_frames(c, n))
     return fail(c, ACMPC_ESTATE, "the last tick tabulated no frames (mode T with the exhaustive search, window <= n <= 106 steps)");
   const int floats = acmpc::verified_frame_floats(n);
   if (capacity_floats < floats) return fail(c, ACMPC_ECAPACITY, "output buffer too small");

@@ -291,6 +291,7 @@ int upload_previous_control(acmpc_ctx* c, hipStream_t s);
 int upload_tables(acmpc_ctx* c, hipStream_t s);
 int upload_frames(acmpc_ctx* c, hipStream_t s);
 int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call = false);
+bool paths_tabulate_frames(const acmpc_ctx* c, int n);   // acmpc_set_paths leaves the verified search's frames at this horizon
 
 // ---- acmpc_capi_solve.hip: the kernels' argument blocks from the handle, and one launch each
 struct Regenerate {
@@ -344,11 +345,22 @@ struct OptInputs {
   std::function<bool()> before_last;
 };
 bool use_fused_finalize(const acmpc_ctx* c, int n);
+struct RoundPlan {
+  bool fused_finalize;   // the last workgroup of a problem writes its record inside the round's launch
+  bool traced;           // ... copied from the winning workgroup's trace
+  bool chained;          // ... and only in the last round: the others hand their keys and traces to the next launch
+};
+RoundPlan plan_rounds(const acmpc_ctx* c, int P, int N, int n);
 bool lq_plan_into(acmpc_ctx* c, const double* table, int n, const double start[3], float* out, bool start_is_pose = false,
                   int problem = 0);
 int enqueue_rounds(acmpc_ctx* c, const OptInputs& in, int P, int N, int n, int rounds, double sigma_v, double sigma_k,
                    double shrink, uint64_t seed, const uint32_t* d_seed, hipStream_t s, bool fused,
                    float* final_records = nullptr, unsigned* done = nullptr, unsigned done_value = 0);
+
+// ---- acmpc_capi_tick.hip: what a tick of H points asks of the handle (the code acmpc_control_tick fails with, and why),
+// and whether its prologue tabulates the verified search's frames
+int tick_check(const acmpc_ctx* c, int H, int rounds, int N, const char** why);
+bool tick_tabulates_frames(const acmpc_ctx* c, int n);
 
 }  // namespace capi
 }  // namespace acmpc

@@ -165,6 +165,19 @@ struct FusedFinalize {
   int ticket_groups = 0;         // power of two <= kTicketGroupsMax (set by the launcher)
 };
 
+// The kernel one sampled round runs - one wave per workgroup, or (traced rounds only) mode S's two and four waves and mode
+// T's three - and its LDS image.  choose_sampled_form is the only place that decides it, from the CU's 160 KiB and the
+// switches: launch_rollout_sampled launches what it returns, acmpc_describe_rounds reports it.
+enum SampledKernel { kSampledSingle = 0, kSampledPair = 1, kSampledQuad = 2, kSampledTrio = 3 };
+struct SampledForm {
+  int kernel;      // SampledKernel
+  bool frames;     // three waves only: the verified search's frames are staged in LDS with the tables
+  size_t lds;      // bytes of dynamic LDS; more than 160 KiB: not even the single wave fits, nothing is launched
+  int offset[3];   // the kernel's LDS offsets in floats, in the order of its arguments
+};
+// `traced`: the workgroups leave traces (FusedFinalize::trace); `tail`: the last workgroup finalizes (::tickets); `frames`:
+// the caller has frames for these paths (RolloutArgs::nn_frames)
+SampledForm choose_sampled_form(int mode, int n, bool traced, bool tail, bool frames, const LaunchOptions& opt = LaunchOptions());
 // sample + rollout + cost (+ finalize) fused: candidates are drawn inside the rollout kernel and never touch memory
 // (the closed-loop solve, where every launch is ~10 us of latency-bound work)
 hipError_t launch_rollout_sampled(int mode, const RolloutArgs& rollout, const SampleArgs& sample,

@@ -3245,18 +3245,6 @@ bool fused_finalize_fits(int mode, int n) {
 
 int trace_floats(int n) { return 5 * n + 2; }
 
-// whether the frames of the verified search fit beside the three-wave mode T round's tables, trace, operands and indices
-// (launch_rollout_sampled drops them otherwise and the search wave scans every waypoint): they do up to n = 106
-bool trio_frames_fit(int n) {
-  if (n < kVerifiedWindow) return false;
-  const size_t tables = ((static_cast<size_t>(n) * (kCoefT + kKeyStride) + 3) & ~static_cast<size_t>(3)) +
-                        static_cast<size_t>(verified_frame_floats(n));
-  const size_t trace = static_cast<size_t>(trace_floats(n)) * kWave;
-  const size_t uniform = (static_cast<size_t>(n) * 7 + 4 + 3) & ~static_cast<size_t>(3);
-  const size_t index = (static_cast<size_t>(n) * kWave / 2 + 3) & ~static_cast<size_t>(3);
-  return (tables + trace + uniform + index) * sizeof(float) <= 160u * 1024u;
-}
-
 // The traced form keeps [5n + 2][64] floats in LDS per workgroup (63 kB at H = 50): up to the CU's 160 kB.
 bool traced_finalize_fits(int mode, int n) {
   return (sampled_rollout_floats(mode, n) + static_cast<size_t>(trace_floats(n)) * kWave +
@@ -3279,107 +3267,142 @@ static hipError_t raise_lds_limit(const void* kernel, int which, size_t lds) {
   return hipSuccess;
 }
 
+// Which kernel one sampled round runs and how its LDS is laid out: THE place where that is decided - the launch below
+// takes what this returns, and so does acmpc_describe_rounds.
+SampledForm choose_sampled_form(int mode, int n, bool traced, bool tail, bool frames, const LaunchOptions& opt) {
+  constexpr size_t kBudget = 160u * 1024u;
+  SampledForm form{};
+  // one wave per workgroup: mode T tables | trace, or the record image of the re-rolling tail | uniform operands
+  const size_t rollout_floats = sampled_rollout_floats(mode, n);
+  const size_t trace = static_cast<size_t>(trace_floats(n)) * kWave;
+  const size_t finalize_floats = traced ? trace : tail ? sampled_finalize_floats(mode, n) : 0;
+  const size_t uniform_floats = sampled_uniform_floats(mode, n);
+  form.kernel = kSampledSingle;
+  form.lds = (rollout_floats + finalize_floats + uniform_floats) * sizeof(float);
+  form.offset[0] = static_cast<int>(rollout_floats);
+  form.offset[1] = static_cast<int>(rollout_floats + finalize_floats);
+  if (form.lds > kBudget) return form;  // no form fits (callers check *_fits() first)
+  if (mode == 1 && traced && !opt.no_trio_rounds) {
+    // three waves per workgroup: tables | trace | uniform operands (centre, reference, weights) | nearest indices
+    const size_t plain_tables = (static_cast<size_t>(n) * (kCoefT + kKeyStride) + 3) & ~static_cast<size_t>(3);
+    const size_t uniform = (static_cast<size_t>(n) * 7 + 4 + 3) & ~static_cast<size_t>(3);
+    const size_t index = (static_cast<size_t>(n) * kWave / 2 + 3) & ~static_cast<size_t>(3);   // 16-bit entries
+    // the frames of the verified search ride along when they fit beside the rest (they do up to n = 106); a longer
+    // horizon keeps the three waves and scans every waypoint, as it did before there were frames
+    bool with_frames = frames && n >= kVerifiedWindow;
+    size_t tables = plain_tables + (with_frames ? static_cast<size_t>(verified_frame_floats(n)) : 0);
+    if ((tables + trace + uniform + index) * sizeof(float) > kBudget) {
+      with_frames = false;
+      tables = plain_tables;
+    }
+    const size_t trio_lds = (tables + trace + uniform + index) * sizeof(float);
+    if (trio_lds <= kBudget) {
+      form.kernel = kSampledTrio;
+      form.frames = with_frames;
+      form.lds = trio_lds;
+      form.offset[0] = static_cast<int>(tables);
+      form.offset[1] = static_cast<int>(tables + trace);
+      form.offset[2] = static_cast<int>(tables + trace + uniform);
+      return form;
+    }
+  }
+  if (mode == 0 && traced && !opt.no_quad_rounds && !opt.no_pair_rounds) {
+    // four waves per workgroup: trace | uniform operands (table rows, centre, reference, weights) | normals | J
+    const size_t uniform = (uniform_floats + 3) & ~static_cast<size_t>(3);
+    const size_t quad_lds = (trace + uniform + static_cast<size_t>(2 * kKnots + 1) * kWave) * sizeof(float);
+    if (quad_lds <= kBudget) {
+      form.kernel = kSampledQuad;
+      form.lds = quad_lds;
+      form.offset[0] = static_cast<int>(trace);
+      form.offset[1] = static_cast<int>(trace + uniform);
+      return form;
+    }
+  }
+  if (mode == 0 && traced && !opt.no_pair_rounds) {
+    // two waves per workgroup: trace | uniform operands | exchange buffers (no mode T tables, no record image)
+    const size_t exchange = static_cast<size_t>(2) * kPairChunk * kPairValues * kWave;
+    const size_t pair_lds = (trace + uniform_floats + exchange) * sizeof(float);
+    if (pair_lds <= kBudget) {
+      form.kernel = kSampledPair;
+      form.lds = pair_lds;
+      form.offset[0] = static_cast<int>(trace);
+      form.offset[1] = static_cast<int>(trace + uniform_floats);
+      return form;
+    }
+  }
+  return form;
+}
+
+// whether the frames of the verified search fit beside the three-wave mode T round's tables, trace, operands and indices
+// (the round drops them otherwise and the search wave scans every waypoint): they do up to n = 106
+bool trio_frames_fit(int n) { return choose_sampled_form(1, n, true, true, true, LaunchOptions()).frames; }
+
 hipError_t launch_rollout_sampled(int mode, const RolloutArgs& rollout, const SampleArgs& sample,
                                   const FusedFinalize& fused, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
                                   const LaunchOptions& opt) {
   clear_stale_error();
   const int n = rollout.n;
   const dim3 grid((rollout.N + kWave - 1) / kWave, rollout.P);
-  const size_t rollout_floats = sampled_rollout_floats(mode, n);
   const bool traced = fused.trace != nullptr;
-  const size_t finalize_floats = traced                     ? static_cast<size_t>(trace_floats(n)) * kWave
-                                 : fused.tickets != nullptr ? sampled_finalize_floats(mode, n)
-                                                            : 0;
-  const size_t uniform_floats = sampled_uniform_floats(mode, n);
-  const size_t lds = (rollout_floats + finalize_floats + uniform_floats) * sizeof(float);
-  if (lds > 160u * 1024u) return hipErrorInvalidValue;  // callers check *_fits() first
-  const int uniform_offset = static_cast<int>(rollout_floats + finalize_floats);
-  if (traced && fused.trace_pitch < trace_floats(n)) return hipErrorInvalidValue;
-  const int offset = static_cast<int>(rollout_floats);
   if (mode != 0 && mode != 1) return hipErrorInvalidValue;
+  const SampledForm form = choose_sampled_form(mode, n, traced, fused.tickets != nullptr, rollout.nn_frames != nullptr, opt);
+  if (form.lds > 160u * 1024u) return hipErrorInvalidValue;  // callers check *_fits() first
+  if (traced && fused.trace_pitch < trace_floats(n)) return hipErrorInvalidValue;
+  const bool timed = e0 != nullptr && e1 != nullptr;
+  const std::uint32_t lds32 = static_cast<std::uint32_t>(form.lds);
+  if (form.kernel == kSampledTrio) {
+    RolloutArgs rollout_trio = rollout;
+    if (!form.frames) rollout_trio.nn_frames = nullptr;
+    hipError_t e = raise_lds_limit(reinterpret_cast<const void*>(&rollout_sampled_trio_kernel), 11, form.lds);
+    if (e != hipSuccess) return e;
+    if (timed) {
+      hipExtLaunchKernelGGL(rollout_sampled_trio_kernel, grid, dim3(3 * kWave), lds32, s, e0, e1, 0, rollout_trio, sample,
+                            fused, form.offset[0], form.offset[1], form.offset[2]);
+    } else {
+      hipLaunchKernelGGL(rollout_sampled_trio_kernel, grid, dim3(3 * kWave), form.lds, s, rollout_trio, sample, fused,
+                         form.offset[0], form.offset[1], form.offset[2]);
+    }
+    return hipGetLastError();
+  }
+  if (form.kernel == kSampledQuad) {
+    hipError_t e = raise_lds_limit(reinterpret_cast<const void*>(&rollout_sampled_quad_kernel), 12, form.lds);
+    if (e != hipSuccess) return e;
+    if (timed) {
+      hipExtLaunchKernelGGL(rollout_sampled_quad_kernel, grid, dim3(kQuadWaves * kWave), lds32, s, e0, e1, 0, rollout, sample,
+                            fused, form.offset[0], form.offset[1]);
+    } else {
+      hipLaunchKernelGGL(rollout_sampled_quad_kernel, grid, dim3(kQuadWaves * kWave), form.lds, s, rollout, sample, fused,
+                         form.offset[0], form.offset[1]);
+    }
+    return hipGetLastError();
+  }
+  if (form.kernel == kSampledPair) {
+    hipError_t e = raise_lds_limit(reinterpret_cast<const void*>(&rollout_sampled_pair_kernel), 2, form.lds);
+    if (e != hipSuccess) return e;
+    if (timed) {
+      hipExtLaunchKernelGGL(rollout_sampled_pair_kernel, grid, dim3(2 * kWave), lds32, s, e0, e1, 0, rollout, sample, fused,
+                            form.offset[0], form.offset[1]);
+    } else {
+      hipLaunchKernelGGL(rollout_sampled_pair_kernel, grid, dim3(2 * kWave), form.lds, s, rollout, sample, fused,
+                         form.offset[0], form.offset[1]);
+    }
+    return hipGetLastError();
+  }
   {
     const hipError_t e = raise_lds_limit(mode == 0 ? reinterpret_cast<const void*>(&rollout_sampled_kernel<0>)
                                                    : reinterpret_cast<const void*>(&rollout_sampled_kernel<1>),
-                                         mode, lds);
+                                         mode, form.lds);
     if (e != hipSuccess) return e;
   }
-  if (mode == 1 && traced && !opt.no_trio_rounds) {
-    // three waves per workgroup: tables | trace | uniform operands (centre, reference, weights) | nearest indices
-    const size_t plain_tables = (static_cast<size_t>(n) * (kCoefT + kKeyStride) + 3) & ~static_cast<size_t>(3);
-    const size_t trace = static_cast<size_t>(trace_floats(n)) * kWave;
-    const size_t uniform = (static_cast<size_t>(n) * 7 + 4 + 3) & ~static_cast<size_t>(3);
-    const size_t index = (static_cast<size_t>(n) * kWave / 2 + 3) & ~static_cast<size_t>(3);   // 16-bit entries
-    // the frames of the verified search ride along when they fit beside the rest (they do up to n = 106); a longer
-    // horizon keeps the three waves and scans every waypoint, as it did before there were frames
-    RolloutArgs rollout_trio = rollout;
-    size_t tables = plain_tables + (rollout.nn_frames != nullptr ? static_cast<size_t>(verified_frame_floats(n)) : 0);
-    if ((tables + trace + uniform + index) * sizeof(float) > 160u * 1024u) {
-      rollout_trio.nn_frames = nullptr;
-      tables = plain_tables;
-    }
-    const size_t trio_lds = (tables + trace + uniform + index) * sizeof(float);
-    if (trio_lds <= 160u * 1024u) {
-      hipError_t e = raise_lds_limit(reinterpret_cast<const void*>(&rollout_sampled_trio_kernel), 11, trio_lds);
-      if (e != hipSuccess) return e;
-      if (e0 != nullptr && e1 != nullptr) {
-        hipExtLaunchKernelGGL(rollout_sampled_trio_kernel, grid, dim3(3 * kWave), static_cast<std::uint32_t>(trio_lds), s, e0,
-                              e1, 0, rollout_trio, sample, fused, static_cast<int>(tables), static_cast<int>(tables + trace),
-                              static_cast<int>(tables + trace + uniform));
-      } else {
-        hipLaunchKernelGGL(rollout_sampled_trio_kernel, grid, dim3(3 * kWave), trio_lds, s, rollout_trio, sample, fused,
-                           static_cast<int>(tables), static_cast<int>(tables + trace),
-                           static_cast<int>(tables + trace + uniform));
-      }
-      return hipGetLastError();
-    }
-  }
-  if (mode == 0 && traced && !opt.no_quad_rounds && !opt.no_pair_rounds) {
-    // four waves per workgroup: trace | uniform operands (table rows, centre, reference, weights) | normals | J
-    const size_t trace = static_cast<size_t>(trace_floats(n)) * kWave;
-    const size_t uniform = (uniform_floats + 3) & ~static_cast<size_t>(3);
-    const size_t quad_lds = (trace + uniform + static_cast<size_t>(2 * kKnots + 1) * kWave) * sizeof(float);
-    if (quad_lds <= 160u * 1024u) {
-      hipError_t e = raise_lds_limit(reinterpret_cast<const void*>(&rollout_sampled_quad_kernel), 12, quad_lds);
-      if (e != hipSuccess) return e;
-      if (e0 != nullptr && e1 != nullptr) {
-        hipExtLaunchKernelGGL(rollout_sampled_quad_kernel, grid, dim3(kQuadWaves * kWave), static_cast<std::uint32_t>(quad_lds), s, e0,
-                              e1, 0, rollout, sample, fused, static_cast<int>(trace), static_cast<int>(trace + uniform));
-      } else {
-        hipLaunchKernelGGL(rollout_sampled_quad_kernel, grid, dim3(kQuadWaves * kWave), quad_lds, s, rollout, sample, fused,
-                           static_cast<int>(trace), static_cast<int>(trace + uniform));
-      }
-      return hipGetLastError();
-    }
-  }
-  if (mode == 0 && traced && !opt.no_pair_rounds) {
-    // two waves per workgroup: trace | uniform operands | exchange buffers (no mode T tables, no record image)
-    const size_t trace = static_cast<size_t>(trace_floats(n)) * kWave;
-    const size_t exchange = static_cast<size_t>(2) * kPairChunk * kPairValues * kWave;
-    const size_t pair_lds = (trace + uniform_floats + exchange) * sizeof(float);
-    if (pair_lds <= 160u * 1024u) {
-      hipError_t e = raise_lds_limit(reinterpret_cast<const void*>(&rollout_sampled_pair_kernel), 2, pair_lds);
-      if (e != hipSuccess) return e;
-      if (e0 != nullptr && e1 != nullptr) {
-        hipExtLaunchKernelGGL(rollout_sampled_pair_kernel, grid, dim3(2 * kWave), static_cast<std::uint32_t>(pair_lds), s,
-                              e0, e1, 0, rollout, sample, fused, static_cast<int>(trace),
-                              static_cast<int>(trace + uniform_floats));
-      } else {
-        hipLaunchKernelGGL(rollout_sampled_pair_kernel, grid, dim3(2 * kWave), pair_lds, s, rollout, sample, fused,
-                           static_cast<int>(trace), static_cast<int>(trace + uniform_floats));
-      }
-      return hipGetLastError();
-    }
-  }
-  const bool timed = e0 != nullptr && e1 != nullptr;
-  const std::uint32_t lds32 = static_cast<std::uint32_t>(lds);
+  const int offset = form.offset[0], uniform_offset = form.offset[1];
   if (mode == 0 && timed) {
     hipExtLaunchKernelGGL((rollout_sampled_kernel<0>), grid, dim3(kWave), lds32, s, e0, e1, 0, rollout, sample, fused, offset, uniform_offset);
   } else if (mode == 0) {
-    hipLaunchKernelGGL((rollout_sampled_kernel<0>), grid, dim3(kWave), lds, s, rollout, sample, fused, offset, uniform_offset);
+    hipLaunchKernelGGL((rollout_sampled_kernel<0>), grid, dim3(kWave), form.lds, s, rollout, sample, fused, offset, uniform_offset);
   } else if (timed) {
     hipExtLaunchKernelGGL((rollout_sampled_kernel<1>), grid, dim3(kWave), lds32, s, e0, e1, 0, rollout, sample, fused, offset, uniform_offset);
   } else {
-    hipLaunchKernelGGL((rollout_sampled_kernel<1>), grid, dim3(kWave), lds, s, rollout, sample, fused, offset, uniform_offset);
+    hipLaunchKernelGGL((rollout_sampled_kernel<1>), grid, dim3(kWave), form.lds, s, rollout, sample, fused, offset, uniform_offset);
   }
   return hipGetLastError();
 }

@@ -566,6 +566,25 @@ int acmpc_speed_profile_qp_device(acmpc_ctx* ctx, const double* v_hi, const doub
                                   double a_max, double v_min, int32_t max_iter, int32_t check_every, double eps_abs,
                                   double eps_rel, double* v, double* y, int32_t warm_start, int32_t* iterations);
 
+/* Test hook of the sampled rounds (modes S and T): which form the rounds of acmpc_optimize(P, N, n) - and of a tick of
+ * n + 1 points with N candidates - take on this handle, with its mode, search window and switches.  The answer comes
+ * from the functions the launches themselves ask; no device work, the GPU is not initialised.  out[8] =
+ *   [0] ACMPC_ROUND_* below: the kernel of a round; -1 when the rounds go through the control matrix (centre_update = 1,
+ *       ACMPC_NO_FUSED_SAMPLING)
+ *   [1] the last workgroup of a problem finalizes inside the round's launch (else a finalize launch follows)
+ *   [2] ... by copying the record out of the winning workgroup's trace (else it re-draws and re-rolls the winner)
+ *   [3] rounds before the last are chained: no finalize, the next launch finds the winner
+ *   [4] the verified search's frames ride in the round's LDS (acmpc_optimize; a tick's do whenever [7] is set)
+ *   [5] acmpc_set_paths tabulates those frames at this n
+ *   [6] acmpc_control_tick accepts this n and N
+ *   [7] ... and its prologue tabulates the frames
+ * ACMPC_ECAPACITY beyond the handle's capacities, ACMPC_ESTATE in mode D. */
+#define ACMPC_ROUND_SINGLE 0 /* one wave per workgroup */
+#define ACMPC_ROUND_PAIR 1   /* mode S, two waves */
+#define ACMPC_ROUND_QUAD 2   /* mode S, four waves */
+#define ACMPC_ROUND_TRIO 3   /* mode T, three waves */
+int acmpc_describe_rounds(const acmpc_ctx* ctx, int32_t P, int32_t N, int32_t n, int32_t out[8]);
+
 /* Host-side float64 helpers round one solve (csrc/acmpc_host_path.cpp; no GPU work, no handle).
  * Replaces: SpatialMPC.construct_waypoints (spatial_mpc.py:125-154).  coords [H][3] = (x, y, width) ->
  * table [7][n], n = H - 1, rows [x, y, psi, kappa, ds, width, v = 0]. */

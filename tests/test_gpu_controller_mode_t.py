@@ -41,7 +41,9 @@ def _tick(H, cons, n_candidates, rounds, offset, seed):
 @pytest.mark.parametrize("nn_window", [(2, 5), (1, 2), None])
 @pytest.mark.parametrize("H,N,rounds", [(50, 4096, 3), (20, 1000, 2), (81, 2048, 2),
                                         (101, 1024, 2),    # the mapping controller's horizon: the frames still fit the LDS
-                                        (105, 1024, 2)])   # ... and no longer do: three waves without them
+                                        (105, 1024, 2),    # ... and still do here (they fit up to 106 steps, H = 107)
+                                        (108, 1024, 2),    # 107 steps: they no longer do - three waves without them
+                                        (110, 1024, 2)])   # 109 steps: nor do three waves - one wave, the record from its trace
 def test_tick_equals_set_paths_plus_optimize_in_mode_t(nn_window, H, N, rounds):
     """tick(T) == set_paths + optimize(T), bit for bit: the prologue's pose and waypoint rows handed to the two-call
     path (same seed, same spread) give the same winner's record; and the record is what the oracle rolls."""
