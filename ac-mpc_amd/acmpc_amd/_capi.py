@@ -157,6 +157,8 @@ SIGNATURES = {
     "acmpc_set_dynamics_integration": (C.c_int, [_CTX, C.c_int32, C.c_double, C.c_double]),
     "acmpc_set_dynamics_terms": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "acmpc_set_previous_control": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
+    "acmpc_set_dynamics_objective": (C.c_int, [_CTX, C.c_double, C.c_void_p]),
+    "acmpc_get_progress_table": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_score_grips": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
     "acmpc_get_coefficients": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
@@ -493,6 +495,34 @@ def dynamics_terms(rate_weight=(0.0, 0.0), rate_max=None, slip_weight=0.0, slip_
     return np.array(w, dtype=np.float64), np.array(m, dtype=np.float64), sw, sm
 
 
+def dynamics_objective(progress_weight=0.0, speed_ceiling=None):
+    """Mode D's objective checked as acmpc_set_dynamics_objective checks it: (progress_weight, ceiling) with ceiling None or
+    a float64 pair (scale, offset); a scalar `speed_ceiling` is the scale with offset 0.  ValueError for a weight or a scale
+    that is negative or not finite (as a float32), or an offset that is not finite."""
+    try:
+        weight = float(progress_weight)
+        if speed_ceiling is None:
+            ceiling = None
+        elif np.ndim(speed_ceiling) == 0:
+            ceiling = (float(speed_ceiling), 0.0)
+        else:
+            ceiling = tuple(float(v) for v in speed_ceiling)
+    except (TypeError, ValueError):
+        raise ValueError("the objective is a number and None, a number or a (scale, offset) pair, not %r"
+                         % ((progress_weight, speed_ceiling),)) from None
+    if ceiling is not None and len(ceiling) != 2:
+        raise ValueError("speed_ceiling is a scale or a (scale, offset) pair, not %r" % (speed_ceiling,))
+    with np.errstate(over="ignore"):
+        if not (np.isfinite(np.float32(weight)) and weight >= 0.0):
+            raise ValueError("progress_weight is finite and >= 0, not %r" % (weight,))
+        if ceiling is not None:
+            if not (np.isfinite(np.float32(ceiling[0])) and ceiling[0] >= 0.0):
+                raise ValueError("the speed ceiling's scale is finite and >= 0, not %r" % (ceiling[0],))
+            if not np.isfinite(np.float32(ceiling[1])):
+                raise ValueError("the speed ceiling's offset is finite, not %r" % (ceiling[1],))
+    return weight, (None if ceiling is None else np.array(ceiling, dtype=np.float64))
+
+
 class Engine:
     """Owns one acmpc_ctx.  Construction does no device work (fork-safe, controller.py:293-297)."""
 
@@ -606,6 +636,20 @@ class Engine:
         outlives a change of vehicle or of the integration setting."""
         w, m, sw, sm = dynamics_terms(rate_weight, rate_max, slip_weight, slip_max)
         self._check(self._lib.acmpc_set_dynamics_terms(self._ctx, w.ctypes.data, m.ctypes.data, sw, sm))
+
+    def set_dynamics_objective(self, progress_weight: float = 0.0, speed_ceiling=None):
+        """Mode D's objective (acmpc_set_dynamics_objective): `progress_weight` (cost units per metre) rewards the arc
+        length made good at the end of the plan - costs may then be negative; `speed_ceiling` = a scale, or (scale, offset),
+        makes a candidate infeasible wherever vx > scale * v_ref + offset; None: no ceiling.  The defaults switch both off;
+        the setting outlives a change of vehicle, of the integration setting or of the rate and slip terms."""
+        weight, ceiling = dynamics_objective(progress_weight, speed_ceiling)
+        self._check(self._lib.acmpc_set_dynamics_objective(self._ctx, weight, None if ceiling is None else ceiling.ctypes.data))
+
+    def progress_table(self, problem: int = 0) -> np.ndarray:
+        """Mode D's progress table q [n] of a problem (acmpc_get_progress_table), host only."""
+        out = np.empty(self.n, dtype=np.float32)
+        self._check(self._lib.acmpc_get_progress_table(self._ctx, problem, _f32(out), out.size))
+        return out
 
     def set_previous_control(self, u_prev=None):
         """The control applied just before the plans start (acmpc_set_previous_control): [P, 2] (or [2]) = (delta, pedal),

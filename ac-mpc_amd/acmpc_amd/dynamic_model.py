@@ -6,7 +6,11 @@ The reference's fitted drive, brake and friction maps are in newtons while its t
 1.160 t, F_z0 = 3): taken literally, 20 m/s at pedal 0.5 becomes 145 m/s after one 50 ms step.  The coefficients are
 therefore data ("Mode D"): `DynamicBicycleParams.reference(literal=True)` is the reference's block bit
 for bit (the parity tests use it), `reference()` - the default vehicle - the same block with the nine longitudinal
-coefficients in kilonewtons."""
+coefficients in kilonewtons.
+
+`stage_terms` and `objective_terms` are float64 mirrors of what acmpc_set_dynamics_terms and acmpc_set_dynamics_objective add
+to a candidate's cost and violation - rates, rear slip; the progress made good and the excess over a speed ceiling - over
+one trajectory of `DynamicBicycleParams.rollout`: what the float32 specification is measured against."""
 from __future__ import annotations
 
 import dataclasses
@@ -175,3 +179,36 @@ def stage_terms(states, U, dt: float, u_prev, params: DynamicBicycleParams, rate
         E += 0.5 * w * float(np.sum(a * a))
         V += float(np.sum(np.maximum(np.abs(a) - limit, 0.0) ** 2))
     return E, V
+
+
+def objective_terms(states, U, table, progress_weight: float = 0.0, speed_ceiling=None, nn_window=None) -> Tuple[float, float]:
+    """The progress and ceiling parts of acmpc_set_dynamics_objective in float64 over `states` [n + 1, 6] =
+    params.rollout(state, U, ...) and the path `table` [7, n] (rows x, y, psi, kappa, ds, width, v): (s, extra_V).  s is the
+    arc length made good at the last state - the polyline length up to its nearest waypoint j plus the along-track offset
+    cos psi_j (X - x_j) + sin psi_j (Y - y_j); the cost's term is -progress_weight s, which the caller applies (`U` and
+    `progress_weight` only say what the call is about: s does not depend on them).  extra_V is the summed squared excess
+    of vx over scale * v_j + offset at every step's nearest waypoint (`speed_ceiling` a scale, a (scale, offset) pair or
+    None: 0).  `nn_window` = (back, ahead) searches as the handle's window does, from waypoint 0; None: all waypoints."""
+    states = np.asarray(states, dtype=np.float64)
+    table = np.asarray(table, dtype=np.float64)
+    x, y, psi, v = table[0], table[1], table[2], table[6]
+    n = table.shape[1]
+    arc = np.concatenate([[0.0], np.cumsum(np.hypot(np.diff(x), np.diff(y)))])
+    d2 = (states[1:, 0, None] - x[None, :]) ** 2 + (states[1:, 1, None] - y[None, :]) ** 2
+    if nn_window is None:
+        j = np.argmin(d2, axis=1)
+    else:
+        back, ahead = nn_window
+        width = back + ahead + 1
+        j = np.empty(len(d2), dtype=np.int64)
+        prev = 0
+        for i, row in enumerate(d2):
+            first = min(max(prev - back, 0), max(n - width, 0))
+            prev = j[i] = first + int(np.argmin(row[first:first + width]))
+    last = j[-1]
+    s = arc[last] + np.cos(psi[last]) * (states[-1, 0] - x[last]) + np.sin(psi[last]) * (states[-1, 1] - y[last])
+    extra_V = 0.0
+    if speed_ceiling is not None:
+        scale, offset = (float(speed_ceiling), 0.0) if np.ndim(speed_ceiling) == 0 else (float(c) for c in speed_ceiling)
+        extra_V = float(np.sum(np.maximum(states[1:, 3] - (scale * v[j] + offset), 0.0) ** 2))
+    return float(s), extra_V

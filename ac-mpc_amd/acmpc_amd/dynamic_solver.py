@@ -27,6 +27,12 @@ the rear slip ratio (r lr - vy) / vx.  A candidate over a limit is infeasible, a
 rate is taken against the control applied before the plan: `solve(..., previous_control=)`, by default the first control
 of the last accepted plan - what a caller that applies the plans has just applied; none on the first solve.
 
+Objective (acmpc_set_dynamics_objective): `progress_cost` (cost units per metre, default 0) rewards the arc length made
+good at the end of the plan, the minimum-time objective, and `speed_ceiling` - a scale, or (scale, offset), default None -
+makes a candidate infeasible wherever vx > scale * v_ref + offset.  To drive at the grip limit instead of tracking the
+kinematic profile: `r_term` = (0, .), a `progress_cost`, the profile as the ceiling (scale = sqrt(tyre a_y / profile a_y))
+and a `slip_limit`.  Costs may then be negative; a solve fails only on a non-finite one, as before.
+
 Grip adaptation (acmpc_score_grips, GripEstimator): `grip_adapt` - a dict, off by default - lets the solver find the road's
 grip from its own driving instead of being told an ensemble.  Every solve logs (state, the control applied since the
 previous solve - `previous_control`, else the last accepted plan's first control), scores a grid of grip hypotheses
@@ -121,6 +127,7 @@ class DynamicSamplingSolver:
         integration = _capi.integration_setting(config.get("rollout_substeps", 1), config.get("low_speed_blend"))
         terms = _capi.dynamics_terms(config.get("rate_cost", (0.0, 0.0)), config.get("rate_limit"),
                                      config.get("slip_cost", 0.0), config.get("slip_limit"))
+        objective = _capi.dynamics_objective(config.get("progress_cost", 0.0), config.get("speed_ceiling"))
         self._centre_update = config.get("sampling_update", "argmin")   # or "softmin" (MPPI-style weighted mean)
         if self._centre_update not in SAMPLING_UPDATES:
             raise ValueError("sampling_update is 'argmin' or 'softmin', not %r" % (self._centre_update,))
@@ -146,6 +153,8 @@ class DynamicSamplingSolver:
         self._rate_terms = bool(np.any(terms[0] != 0.0) or np.any(np.isfinite(terms[1])))
         if self._rate_terms or terms[2] != 0.0 or np.isfinite(terms[3]):
             self._engine.set_dynamics_terms(*terms)
+        if objective[0] != 0.0 or objective[1] is not None:
+            self._engine.set_dynamics_objective(*objective)
         self._plan: Optional[np.ndarray] = None
         self._calls = 0
         self._adapt = adapt

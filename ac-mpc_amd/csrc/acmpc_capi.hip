@@ -119,6 +119,8 @@ int ensure_device(acmpc_ctx* c) {
                                                  acmpc::verified_frame_floats(std::max(std::min(p.max_steps, kMaxVerifiedSteps),
                                                                                        acmpc::kVerifiedWindow))));
   if (p.mode == ACMPC_MODE_DYNAMIC) ACMPC_HIP(c, alloc_once(&c->d_uprev, static_cast<size_t>(p.max_problems) * 2 * sizeof(float)));
+  if (p.mode == ACMPC_MODE_DYNAMIC)
+    ACMPC_HIP(c, alloc_once(&c->d_progress, static_cast<size_t>(p.max_problems) * p.max_steps * sizeof(float)));
   c->device_ready = true;
   return ACMPC_OK;
 }
@@ -141,8 +143,36 @@ int upload_tables(acmpc_ctx* c, hipStream_t s) {
   if (!c->tables_dirty) return ACMPC_OK;
   const size_t bytes = static_cast<size_t>(c->P_set) * c->n_set * c->coef_stride * sizeof(float);
   ACMPC_HIP(c, hipMemcpyAsync(c->d_coef, c->h_coef.data(), bytes, hipMemcpyHostToDevice, s));
+  if (c->d_progress != nullptr)   // mode D: the progress table of these rows, [P][n]
+    ACMPC_HIP(c, hipMemcpyAsync(c->d_progress, c->h_progress.data(), c->h_progress.size() * sizeof(float), hipMemcpyHostToDevice, s));
   c->tables_dirty = false;
   return ACMPC_OK;
+}
+
+// Mode D's progress table ("Progress and ceiling") from the packed float32 rows, whoever put them
+// there: in float64, in the order written, no fused multiply-add (the unit is built with -ffp-contract=off)
+//   S_0 = 0, S_m = S_{m-1} + sqrt(dx dx + dy dy);  q_m = float32(S_m - (c_m (x_m - x_0) + s_m (y_m - y_0)))
+// so that with positions relative to the first waypoint fma(s_j, Y, fma(c_j, X, q_j)) is the arc length of waypoint j plus
+// the along-track offset from it.
+void derive_progress_table(acmpc_ctx* c) {
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return;
+  const int P = c->P_set, n = c->n_set, stride = c->coef_stride;
+  c->h_progress.resize(static_cast<size_t>(P) * n);
+  for (int p = 0; p < P; ++p) {
+    const float* rows = c->h_coef.data() + static_cast<size_t>(p) * n * stride;
+    float* q = c->h_progress.data() + static_cast<size_t>(p) * n;
+    const double x0 = rows[0], y0 = rows[1];
+    double S = 0.0;
+    for (int m = 0; m < n; ++m) {
+      const float* r = rows + static_cast<size_t>(m) * stride;
+      const double x = r[0], y = r[1], cm = r[2], sm = r[3];
+      if (m > 0) {
+        const double dx = x - static_cast<double>(r[0 - stride]), dy = y - static_cast<double>(r[1 - stride]);
+        S = S + std::sqrt(dx * dx + dy * dy);
+      }
+      q[m] = static_cast<float>(S - (cm * (x - x0) + sm * (y - y0)));
+    }
+  }
 }
 
 // The captured optimisation carries the coefficient table in its staging block but not the frames of mode T's
@@ -455,6 +485,7 @@ void acmpc_destroy(acmpc_ctx* c) {
     (void)hipFree(c->d_soft_partial);
     (void)hipFree(c->d_segments);
     (void)hipFree(c->d_uprev);
+    (void)hipFree(c->d_progress);
     (void)hipFree(c->d_identify);
     (void)hipFree(c->d_identify_e);
     (void)hipFree(c->d_centre);
@@ -533,6 +564,7 @@ int acmpc_set_paths(acmpc_ctx* c, const double* tables, int32_t P, int32_t n) {
     verified_frames(c->h_coef.data(), P, n, &c->h_nn_frames);
   c->P_set = P;
   c->n_set = n;
+  derive_progress_table(c);
   c->tables_dirty = true;
   c->frames_dirty = !c->h_nn_frames.empty();
   return ACMPC_OK;
@@ -550,6 +582,7 @@ int acmpc_set_coefficients(acmpc_ctx* c, const float* coef, int32_t P, int32_t n
     verified_frames(c->h_coef.data(), P, n, &c->h_nn_frames);
   c->P_set = P;
   c->n_set = n;
+  derive_progress_table(c);
   c->tables_dirty = true;
   c->frames_dirty = !c->h_nn_frames.empty();
   return ACMPC_OK;
@@ -581,6 +614,18 @@ int acmpc_get_coefficients(const acmpc_ctx* c, int32_t problem, float* out, int3
   const size_t count = static_cast<size_t>(c->n_set) * c->coef_stride;
   if (capacity_floats < static_cast<int64_t>(count)) return fail(c, ACMPC_ECAPACITY, "output buffer too small");
   std::memcpy(out, c->h_coef.data() + static_cast<size_t>(problem) * count, count * sizeof(float));
+  return ACMPC_OK;
+}
+
+int acmpc_get_progress_table(const acmpc_ctx* c, int32_t problem, float* out, int32_t capacity_floats) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (out == nullptr) return fail(c, ACMPC_EINVAL, "null output");
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_get_progress_table needs a mode D handle");
+  if (c->P_set == 0) return fail(c, ACMPC_ESTATE, "acmpc_set_paths has not been called");
+  if (problem < 0 || problem >= c->P_set) return fail(c, ACMPC_EINVAL, "problem index out of range");
+  const size_t count = static_cast<size_t>(c->n_set);
+  if (capacity_floats < static_cast<int64_t>(count)) return fail(c, ACMPC_ECAPACITY, "output buffer too small");
+  std::memcpy(out, c->h_progress.data() + static_cast<size_t>(problem) * count, count * sizeof(float));
   return ACMPC_OK;
 }
 

@@ -1,5 +1,5 @@
 // C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
-// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the previous control, and the grip
+// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the previous control, and the grip
 // identification (acmpc_score_grips), with the checks that the kernels' limits are the public header's.
 #include <algorithm>
 
@@ -154,6 +154,25 @@ int acmpc_set_dynamics_terms(acmpc_ctx* c, const double rate_weight[2], const do
   }
   c->slip_weight = slip_weight + 0.0;
   c->slip_max = slip_max;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_objective(acmpc_ctx* c, double progress_weight, const double speed_ceiling[2]) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_dynamics_objective needs a mode D handle");
+  // float32 is what the kernels get: a value that overflows it is not finite there
+  if (!std::isfinite(static_cast<float>(progress_weight)) || !(progress_weight >= 0.0))
+    return fail(c, ACMPC_EINVAL, "progress_weight must be finite and >= 0");
+  if (speed_ceiling != nullptr) {
+    if (!std::isfinite(static_cast<float>(speed_ceiling[0])) || !(speed_ceiling[0] >= 0.0))
+      return fail(c, ACMPC_EINVAL, "the speed ceiling's scale must be finite and >= 0");
+    if (!std::isfinite(static_cast<float>(speed_ceiling[1]))) return fail(c, ACMPC_EINVAL, "the speed ceiling's offset must be finite");
+  }
+  // everything is checked before anything is kept: a refused setting leaves the handle's as it was
+  c->progress_weight = progress_weight + 0.0;   // (-0.0 is 0)
+  c->has_ceiling = speed_ceiling != nullptr;
+  c->speed_ceiling[0] = c->has_ceiling ? speed_ceiling[0] + 0.0 : 0.0;
+  c->speed_ceiling[1] = c->has_ceiling ? speed_ceiling[1] : 0.0;
   return ACMPC_OK;
 }
 

@@ -12,9 +12,10 @@ namespace acmpc {
 namespace capi __attribute__((visibility("hidden"))) {
 
 // mode D: the kernels' view of the handle's rate and slip terms - every float derived in float64 and rounded once
-// ("Rate and slip terms").  A part whose weights are 0 and whose limits are +inf is off.
-static acmpc::Terms dynamics_terms(const acmpc_ctx* c) {
-  acmpc::Terms t{};
+// ("Rate and slip terms").  A part whose weights are 0 and whose limits are +inf is off.  And of its
+// objective ("Progress and ceiling"): the progress part is on with a weight that is not 0, the ceiling part when one is set.
+static acmpc::TermsObjective dynamics_terms(const acmpc_ctx* c) {
+  acmpc::TermsObjective t{};
   t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
             std::isfinite(c->rate_max[1])) ? 1 : 0;
   t.slip = (c->slip_weight != 0.0 || std::isfinite(c->slip_max)) ? 1 : 0;
@@ -26,6 +27,12 @@ static acmpc::Terms dynamics_terms(const acmpc_ctx* c) {
   t.rp_max = static_cast<float>(c->rate_max[1]);
   t.b_max = static_cast<float>(c->slip_max);
   t.u_prev = (t.rate != 0 && c->uprev_P != 0) ? c->d_uprev : nullptr;
+  t.progress = (c->progress_weight != 0.0) ? 1 : 0;
+  t.ceiling = c->has_ceiling ? 1 : 0;
+  t.nwp = -static_cast<float>(c->progress_weight);
+  t.cs = static_cast<float>(c->speed_ceiling[0]);
+  t.co = static_cast<float>(c->speed_ceiling[1]);
+  t.q = c->d_progress;
   return t;
 }
 

@@ -275,6 +275,13 @@ struct acmpc_ctx {
   int uprev_P = 0;              // 0: none set
   bool uprev_dirty = false;
   float* d_uprev = nullptr;     // [max_problems][2]
+  // mode D: the objective (acmpc_set_dynamics_objective), kept apart like the terms: weight 0 and no ceiling = off; and the
+  // progress table q [P_set][n_set], derived from the packed rows whenever they change and uploaded with them
+  double progress_weight = 0.0;
+  bool has_ceiling = false;
+  double speed_ceiling[2] = {0.0, 0.0};   // (scale, offset)
+  std::vector<float> h_progress;
+  float* d_progress = nullptr;  // [max_problems][max_steps]
 
   mutable std::string err;
 };
@@ -288,6 +295,7 @@ int ensure_staging(acmpc_ctx* c);
 int ensure_matrix(acmpc_ctx* c);
 int ensure_tail_buffers(acmpc_ctx* c);
 int upload_previous_control(acmpc_ctx* c, hipStream_t s);
+void derive_progress_table(acmpc_ctx* c);   // mode D: h_progress from h_coef (no-op in the other modes)
 int upload_tables(acmpc_ctx* c, hipStream_t s);
 int upload_frames(acmpc_ctx* c, hipStream_t s);
 int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call = false);

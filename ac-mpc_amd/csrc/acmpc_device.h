@@ -781,23 +781,6 @@ __device__ __forceinline__ F finish_temporal(const StateT_<F>& s, int n, const W
   return fma_(splat<F>(w.wbound), s.V, J);
 }
 
-// finish_temporal with one more stage sum, E, whose weights are already in it (mode D's rate and slip terms,
-// acmpc_dynamic.h): the same lines, and stage = stage + E after the last weighted sum
-template <typename F>
-__device__ __forceinline__ F finish_temporal_extra(const StateT_<F>& s, F E, int n, const Weights& w) {
-  const float tN = static_cast<float>(n) * w.dt;
-  F stage = splat<F>(w.hq0) * s.S0;
-  stage = fma_(splat<F>(w.hq1), s.S1, stage);
-  stage = fma_(splat<F>(w.hr0), s.S2, stage);
-  stage = fma_(splat<F>(w.hr1), s.S3, stage);
-  stage = stage + E;
-  F a = (w.hqn0 * s.ey) * s.ey;
-  a = fma_(w.hqn1 * s.ep, s.ep, a);
-  a = fma_(splat<F>(w.hqn2 * tN), splat<F>(tN), a);
-  const F J = stage + a;
-  return fma_(splat<F>(w.wbound), s.V, J);
-}
-
 // ---- candidate sampling ------------------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter-based, so candidate c
 // of problem p in round r is the same numbers on every rank and in every launch shape.

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "acmpc_device.h"
 #include "acmpc_kernels.h"
 
@@ -276,14 +278,29 @@ struct Terms {
 };
 __host__ __device__ inline bool has_terms(const Terms& t) { return t.rate != 0 || t.slip != 0; }
 
+// The Terms plus the objective of a handle (acmpc_set_dynamics_objective, DESIGN.md section 2 "Mode D", "Progress and ceiling"): a third
+// and a fourth part, off (0) by default like the two above.  A pack type of its own: the kernels instantiated for it hold all
+// four parts and run only while the progress or the ceiling part is on; the kernels of a plain Terms stay the code they were
+// (inside them the two new parts cost the one-per-lane sampled rollouts a wave per SIMD).  progress: the cost ends with J = fma(nwp, s, J), s the arc
+// length made good at the last control step - fma(s_j, Y, fma(c_j, X, q_j)) on the nearest waypoint j that step's
+// dynamic_cost used - and nwp = -float32(progress_weight): the only cost term that is not a square, so J may be negative.
+// ceiling: per control step the excess of vx over cap = fma(cs, v_ref_j, co) joins V, after the rate and slip lines.
+struct TermsObjective : Terms {
+  int progress, ceiling;
+  float nwp, cs, co;
+  const float* q;               // the progress table [P][n] on the device (the host derives it from the packed rows)
+};
+__host__ __device__ inline bool has_objective(const TermsObjective& t) { return t.progress != 0 || t.ceiling != 0; }
+
 // what the terms carry from step to step: the previous step's control and the cost sum
 template <typename F>
 struct TermsState {
   F pd, pp, E;
+  typename IndexOf<F>::type j;   // the last control step's nearest waypoint, where the step loop is not the kernel's own
 };
 template <typename F>
 __device__ __forceinline__ TermsState<F> start_terms(int p, const Terms& t) {
-  TermsState<F> ts{splat<F>(0.0f), splat<F>(0.0f), splat<F>(0.0f)};
+  TermsState<F> ts{splat<F>(0.0f), splat<F>(0.0f), splat<F>(0.0f), typename IndexOf<F>::type(0)};
   if (t.rate != 0 && t.u_prev != nullptr) {   // (a wave-uniform address: one scalar load per wave)
     ts.pd = splat<F>(t.u_prev[2 * p]);
     ts.pp = splat<F>(t.u_prev[2 * p + 1]);
@@ -297,10 +314,23 @@ __device__ __forceinline__ TermsState<F>& state_of(TermsState<F>& ts, const Term
   return ts;
 }
 
-// the terms of one control step, on the state the step's dynamic_cost saw; `first`: step 0
+// one float of the staged waypoint row(s) j, or of a table of one float per waypoint (stride 1)
+__device__ __forceinline__ float gather_float(const float* t, int j, int stride, int e) { return t[j * stride + e]; }
+__device__ __forceinline__ f32x2 gather_float(const float* t, i32x2 j, int stride, int e) {
+  return f32x2{t[j[0] * stride + e], t[j[1] * stride + e]};
+}
+
 template <typename F>
+__device__ __forceinline__ void keep_nearest(typename IndexOf<F>::type j, TermsState<F>& ts, const Terms&) {
+  ts.j = j;
+}
+
+// the terms of one control step, on the state the step's dynamic_cost saw; `first`: step 0; wp, j: the staged rows and the
+// nearest waypoint(s) that dynamic_cost used (the ceiling reads v_ref_j, float 5 of the row, again)
+template <typename F, typename TT>
 __device__ __forceinline__ void dynamic_terms(StateD_<F>& s, F delta, F pedal, bool first, const Vehicle& k,
-                                              TermsState<F>& ts, const Terms& t) {
+                                              [[maybe_unused]] const float* wp, [[maybe_unused]] typename IndexOf<F>::type j,
+                                              TermsState<F>& ts, const TT& t) {
   if (t.rate != 0) {
     const bool own = first && t.u_prev == nullptr;
     const F pd = own ? delta : ts.pd;
@@ -322,6 +352,43 @@ __device__ __forceinline__ void dynamic_terms(StateD_<F>& s, F delta, F pedal, b
     const F hb = vmax(abs_(b) - t.b_max, splat<F>(0.0f));
     s.t.V = fma_(hb, hb, s.t.V);
   }
+  if constexpr (std::is_same<TT, TermsObjective>::value) {
+    if (t.ceiling == 0) return;
+    const F cap = fma_(splat<F>(t.cs), gather_float(wp, j, kCoefT, 5), splat<F>(t.co));
+    const F h = vmax(s.vx - cap, splat<F>(0.0f));   // (maxNum: a NaN v_ref is no ceiling)
+    s.t.V = fma_(h, h, s.t.V);
+  }
+}
+
+// finish_temporal (acmpc_device.h) with the terms: stage = stage + E after the last weighted sum when the rate or the slip
+// part is on (under a plain Terms one of them is), and J = fma(nwp, s, J) between J = stage + a and the violations' fma when the progress part is on.  wp, j: the
+// staged rows and the nearest waypoint(s) of the last control step; p: the problem, whose row of the progress table is read
+// from global memory (one gather per candidate).
+template <typename F, typename TT>
+__device__ __forceinline__ F finish_dynamic_terms(const StateD_<F>& s, const TermsState<F>& ts, [[maybe_unused]] const float* wp,
+                                                  [[maybe_unused]] typename IndexOf<F>::type j, [[maybe_unused]] int p, int n,
+                                                  const Weights& w, const TT& t) {
+  constexpr bool kObjective = std::is_same<TT, TermsObjective>::value;
+  const StateT_<F>& st = s.t;
+  const float tN = static_cast<float>(n) * w.dt;
+  F stage = splat<F>(w.hq0) * st.S0;
+  stage = fma_(splat<F>(w.hq1), st.S1, stage);
+  stage = fma_(splat<F>(w.hr0), st.S2, stage);
+  stage = fma_(splat<F>(w.hr1), st.S3, stage);
+  if (!kObjective || t.rate != 0 || t.slip != 0) stage = stage + ts.E;
+  F a = (w.hqn0 * st.ey) * st.ey;
+  a = fma_(w.hqn1 * st.ep, st.ep, a);
+  a = fma_(splat<F>(w.hqn2 * tN), splat<F>(tN), a);
+  F J = stage + a;
+  if constexpr (kObjective) {
+    if (t.progress == 0) return fma_(splat<F>(w.wbound), st.V, J);
+    const F sj = -gather_float(wp, j, kCoefT, 1);   // the row holds -sin psi_j: the negation is exact
+    const F cj = gather_float(wp, j, kCoefT, 2);
+    const F qj = gather_float(t.q + static_cast<size_t>(p) * n, j, 1, 0);
+    const F prog = fma_(sj, st.Y, fma_(cj, st.X, qj));
+    J = fma_(splat<F>(t.nwp), prog, J);
+  }
+  return fma_(splat<F>(w.wbound), st.V, J);
 }
 
 // mode T's temporal_cost with the input terms of this model: dv = vx - v_ref, dk = delta - delta_ref (row[7], staged
@@ -362,30 +429,31 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // rollout_dynamic_kernel with the one vehicle; K > 1: rollout_dynamic_ensemble_kernel.
 // `integration`: the handle's setting; the default launches the FINE = false instantiations, whose step loop knows nothing
 // of it.
-// `terms`: the handle's rate and slip terms; when on, the kernels that hold them run, with the general step whatever the
+// `terms`: the handle's rate and slip terms and its objective; when any part is on, the kernels that hold them run, with the general step whatever the
 // integration setting (the default one as M = 1, no blend, h = float32(dt)).
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& integration, const Terms& terms, hipStream_t s);
+                                  const Integration& integration, const TermsObjective& terms, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const Terms& terms, hipStream_t s);
+                                          const Integration& integration, const TermsObjective& terms, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& integration, const Terms& terms, hipStream_t s);
-// what the three above call when has_terms(terms) (acmpc_dynamic_terms.hip)
+                                   const Integration& integration, const TermsObjective& terms, hipStream_t s);
+// what the three above call when has_terms(terms) or has_objective(terms) (acmpc_dynamic_terms.hip: the kernels of a plain
+// Terms in the first case alone, those of a TermsObjective otherwise)
 hipError_t launch_rollout_dynamic_terms(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                        const Integration& integration, const Terms& terms, hipStream_t s);
+                                        const Integration& integration, const TermsObjective& terms, hipStream_t s);
 hipError_t launch_rollout_dynamic_sampled_terms(const RolloutArgs& args, const SampleArgs& sample,
                                                 const VehicleEnsemble& vehicles, const Integration& integration,
-                                                const Terms& terms, hipStream_t s);
+                                                const TermsObjective& terms, hipStream_t s);
 hipError_t launch_finalize_dynamic_terms(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                         const Integration& integration, const Terms& terms, hipStream_t s);
+                                         const Integration& integration, const TermsObjective& terms, hipStream_t s);
 
 }  // namespace acmpc

@@ -41,6 +41,13 @@
 // because inside the FINE = true ones the terms cost the step-major two-per-lane rollouts a wave per SIMD: 82 / 83 VGPRs
 // against 76 / 74)
 //
+// And a fourth, for a handle with the objective (acmpc_set_dynamics_objective; acmpc_dynamic.h: TermsObjective): the pack is
+// one TermsObjective - the Terms plus a speed ceiling among the step's hinges (dynamic_terms) and a progress reward in the
+// finish (finish_dynamic_terms), which reads the last step's nearest waypoint: live in every kernel at that point, handed back
+// through the terms' state by roll_sampled.  Sixteen more instantiations of acmpc_dynamic_terms.hip, launched only while the
+// progress or the ceiling part is on: the kernels of a plain Terms stay the code they were (inside them the two parts cost the
+// one-per-lane sampled rollouts a wave per SIMD: 74 VGPRs against 69 / 70).
+//
 // Built with -ffp-contract=off: see acmpc_device.h.
 #include "acmpc_dynamic.h"
 
@@ -169,11 +176,11 @@ __global__ void __launch_bounds__(kDynBlock)
       dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
-      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, ts, tm...);
+      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, s_wp, nearest, ts, tm...);
     }
   });
   F cost_v;
-  if constexpr (kTerms) cost_v = finish_temporal_extra<F>(st.t, ts.E, n, w);
+  if constexpr (kTerms) cost_v = finish_dynamic_terms<F>(st, ts, s_wp, nearest, p, n, w, tm...);
   else cost_v = finish_temporal<F>(st.t, n, w);
   float cost[CPT];
   bool feas[CPT];
@@ -333,9 +340,10 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
       dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
-      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, tt...);   // (the state keeps this step's blended control)
+      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, s_wp, nearest, tt...);   // (the state keeps this step's blended control)
     }
   });
+  if constexpr (kTerms) keep_nearest<F>(nearest, tt...);   // (the progress part reads the last step's at the finish)
 }
 
 // rollout_dynamic_kernel without a control matrix: the same workgroup shape, tail rule (lanes past N repeat candidate
@@ -377,7 +385,7 @@ __global__ void __launch_bounds__(kDynBlock)
   roll_sampled<CPT, false, FINE, F>(st, draw_spec(smp, w), veh, w, g, g.inv_L[0], p, n, gidx, smp.u_ref != nullptr, s_wp,
                                     s_xy, s_seg, s_centre, s_ref, s_z, kDynBlock, tid, true, state_of(ts, tm)..., tm...);
   F cost_v;
-  if constexpr (kTerms) cost_v = finish_temporal_extra<F>(st.t, ts.E, n, w);
+  if constexpr (kTerms) cost_v = finish_dynamic_terms<F>(st, ts, s_wp, ts.j, p, n, w, tm...);
   else cost_v = finish_temporal<F>(st.t, n, w);
   float cost[CPT];
   bool feas[CPT];
@@ -537,7 +545,7 @@ __global__ void __launch_bounds__(kWave)
     j = (j == 0x7fffffff) ? lo : j;
     j_prev = j;
     dynamic_settle(st, s_wp, j, d, q, w);
-    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i == 0, veh, ts, tm...);
+    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i == 0, veh, s_wp, j, ts, tm...);
     if (lane == 0) {
       sx[3 * (i + 1)] = st.t.X + coef[0];
       sx[3 * (i + 1) + 1] = st.t.Y + coef[1];
@@ -545,7 +553,7 @@ __global__ void __launch_bounds__(kWave)
     }
   }
   if (lane == 0) {
-    if constexpr (kTerms) s_rec[0] = finish_temporal_extra<float>(st.t, ts.E, n, w);
+    if constexpr (kTerms) s_rec[0] = finish_dynamic_terms<float>(st, ts, s_wp, j_prev, p, n, w, tm...);
     else s_rec[0] = finish_temporal<float>(st.t, n, w);
     s_rec[1] = st.t.V;
     s_rec[2] = static_cast<float>(nfeas);
@@ -606,11 +614,11 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
-      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, ts, tm...);
+      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, s_wp, nearest, ts, tm...);
     }
   });
   F cost_v;
-  if constexpr (kTerms) cost_v = finish_temporal_extra<F>(st.t, ts.E, n, w);
+  if constexpr (kTerms) cost_v = finish_dynamic_terms<F>(st, ts, s_wp, nearest, p, n, w, tm...);
   else cost_v = finish_temporal<F>(st.t, n, w);
   if constexpr (CPT == 2) {
     s_c[k * kPerGroup + 2 * lane] = cost_v[0];
@@ -689,7 +697,7 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   roll_sampled<CPT, true, FINE, F>(st, draw_spec(smp, w), veh, w, g, g.inv_L[k], p, n, gidx, smp.u_ref != nullptr, s_wp,
                                    s_xy, s_seg, s_centre, s_ref, s_z, kWave, lane, k == 0, state_of(ts, tm)..., tm...);
   F cost_v;
-  if constexpr (kTerms) cost_v = finish_temporal_extra<F>(st.t, ts.E, n, w);
+  if constexpr (kTerms) cost_v = finish_dynamic_terms<F>(st, ts, s_wp, ts.j, p, n, w, tm...);
   else cost_v = finish_temporal<F>(st.t, n, w);
   if constexpr (CPT == 2) {
     s_c[k * kPerGroup + 2 * lane] = cost_v[0];
@@ -816,7 +824,7 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
     j = (j == 0x7fffffff) ? lo : j;
     j_prev = j;
     dynamic_settle(st, s_wp, j, d, q, w);
-    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i == 0, veh, ts, tm...);
+    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i == 0, veh, s_wp, j, ts, tm...);
     if (writer) {
       sx[3 * (i + 1)] = st.t.X + coef[0];
       sx[3 * (i + 1) + 1] = st.t.Y + coef[1];
@@ -824,7 +832,7 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
     }
   }
   if (lane == 0) {
-    if constexpr (kTerms) s_ck[k] = finish_temporal_extra<float>(st.t, ts.E, n, w);
+    if constexpr (kTerms) s_ck[k] = finish_dynamic_terms<float>(st, ts, s_wp, j_prev, p, n, w, tm...);
     else s_ck[k] = finish_temporal<float>(st.t, n, w);
     s_ck[kMaxVehicles + k] = st.t.V;
   }
@@ -856,7 +864,7 @@ void with_integration_kind(const Integration& g, Body&& body) {
 bool integration_valid(const Integration& g) { return g.substeps >= 1 && g.substeps <= kMaxSubsteps; }
 
 // The three launchers, written once: `tm` is nothing (the kernels without the terms, this translation unit) or the
-// handle's Terms (the kernels with them, acmpc_dynamic_terms.hip).
+// handle's Terms or TermsObjective (the kernels with them, acmpc_dynamic_terms.hip).
 template <typename... TM>
 hipError_t rollout_dynamic_launch(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles, const Integration& g,
                                   hipStream_t s, const TM&... tm) {
@@ -990,20 +998,24 @@ hipError_t finalize_dynamic_launch(int layout, const FinalizeArgs& args, const V
 
 #ifdef ACMPC_DYNAMIC_TERMS_TU
 
+// (a handle without the objective runs the kernels of a plain Terms)
 hipError_t launch_rollout_dynamic_terms(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                        const Integration& g, const Terms& tm, hipStream_t s) {
-  return rollout_dynamic_launch(layout, args, vehicles, g, s, tm);
+                                        const Integration& g, const TermsObjective& tm, hipStream_t s) {
+  if (has_objective(tm)) return rollout_dynamic_launch(layout, args, vehicles, g, s, tm);
+  return rollout_dynamic_launch(layout, args, vehicles, g, s, static_cast<const Terms&>(tm));
 }
 
 hipError_t launch_rollout_dynamic_sampled_terms(const RolloutArgs& args, const SampleArgs& sample,
-                                                const VehicleEnsemble& vehicles, const Integration& g, const Terms& tm,
-                                                hipStream_t s) {
-  return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s, tm);
+                                                const VehicleEnsemble& vehicles, const Integration& g,
+                                                const TermsObjective& tm, hipStream_t s) {
+  if (has_objective(tm)) return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s, tm);
+  return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s, static_cast<const Terms&>(tm));
 }
 
 hipError_t launch_finalize_dynamic_terms(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                         const Integration& g, const Terms& tm, hipStream_t s) {
-  return finalize_dynamic_launch(layout, args, vehicles, g, s, tm);
+                                         const Integration& g, const TermsObjective& tm, hipStream_t s) {
+  if (has_objective(tm)) return finalize_dynamic_launch(layout, args, vehicles, g, s, tm);
+  return finalize_dynamic_launch(layout, args, vehicles, g, s, static_cast<const Terms&>(tm));
 }
 
 #else  // ACMPC_DYNAMIC_TERMS_TU
@@ -1020,20 +1032,20 @@ int dynamic_blocks_per_problem(int P, int N, int K) {
 }
 
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& g, const Terms& tm, hipStream_t s) {
-  if (has_terms(tm)) return launch_rollout_dynamic_terms(layout, args, vehicles, g, tm, s);
+                                  const Integration& g, const TermsObjective& tm, hipStream_t s) {
+  if (has_terms(tm) || has_objective(tm)) return launch_rollout_dynamic_terms(layout, args, vehicles, g, tm, s);
   return rollout_dynamic_launch(layout, args, vehicles, g, s);
 }
 
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& g, const Terms& tm, hipStream_t s) {
-  if (has_terms(tm)) return launch_rollout_dynamic_sampled_terms(args, sample, vehicles, g, tm, s);
+                                          const Integration& g, const TermsObjective& tm, hipStream_t s) {
+  if (has_terms(tm) || has_objective(tm)) return launch_rollout_dynamic_sampled_terms(args, sample, vehicles, g, tm, s);
   return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s);
 }
 
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& g, const Terms& tm, hipStream_t s) {
-  if (has_terms(tm)) return launch_finalize_dynamic_terms(layout, args, vehicles, g, tm, s);
+                                   const Integration& g, const TermsObjective& tm, hipStream_t s) {
+  if (has_terms(tm) || has_objective(tm)) return launch_finalize_dynamic_terms(layout, args, vehicles, g, tm, s);
   return finalize_dynamic_launch(layout, args, vehicles, g, s);
 }
 

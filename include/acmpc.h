@@ -278,6 +278,28 @@ int acmpc_set_dynamics_integration(acmpc_ctx* ctx, int32_t substeps, double blen
 int acmpc_set_dynamics_terms(acmpc_ctx* ctx, const double rate_weight[2], const double rate_max[2], double slip_weight,
                              double slip_max);
 
+/* Mode D's objective: a terminal progress reward and a per-step speed ceiling, a third and a fourth part of the terms
+ * above, both off by default.
+ *   progress: with s the arc length made good at the last control step - the arc length of the nearest waypoint j that
+ *   step's cost used plus the along-track offset from it, s = fma(sin psi_j, Y, fma(cos psi_j, X, q_j)) with the progress
+ *   table q of acmpc_get_progress_table - the cost ends with J = fma(-float32(progress_weight), s, J), between the stage and
+ *   terminal sums and the violations' term.  The distance made good over the horizon is the minimum-time objective; it is
+ *   the one term that is not a square: COSTS MAY BE NEGATIVE.  Keys, argmin and softmin order negative costs as floats;
+ *   -inf, like every non-finite cost, ranks last.  Past the last waypoint j stays n - 1 and s keeps growing linearly.
+ *   ceiling: speed_ceiling = (scale, offset), or NULL for none; per control step, after the rate and slip lines,
+ *   cap = fma(float32(scale), v_ref_j, float32(offset)); V += max(vx - cap, 0)^2: a plan faster than the ceiling is
+ *   infeasible.  A NaN v_ref is no ceiling at that step.  The ceiling is what stops a finite-horizon progress reward from
+ *   ending flat out before a corner: give it the speed profile (whose backward pass knows the corner) scaled by what the
+ *   tyres allow over what the profile assumed, with weights.r_term[0] = 0 and a slip_max.
+ * The progress part is on when progress_weight is not 0, the ceiling part when speed_ceiling is not NULL; a part that is
+ * off computes nothing, and with all four parts off the handle runs exactly what it ran before the call.  The setting
+ * belongs to the handle: it survives acmpc_set_dynamics, _ensemble, _integration and _terms, every member of an ensemble
+ * carries it with its own end state, and every call form of mode D takes it from the handle.  No device work.
+ * ACMPC_ESTATE for a handle whose mode is not ACMPC_MODE_DYNAMIC; ACMPC_EINVAL for a weight that is negative or not finite,
+ * a scale that is negative or not finite, an offset that is not finite (each as a float32); the handle then keeps its
+ * previous setting.  DESIGN.md section 2 "Mode D, progress and ceiling". */
+int acmpc_set_dynamics_objective(acmpc_ctx* ctx, double progress_weight, const double speed_ceiling[2] /* NULL: none */);
+
 /* The control applied just before each problem's plan starts: u_prev host [P][2] = (delta, pedal), what step 0's rates
  * are taken against; NULL clears it (P is then ignored), and step 0's own control stands for it: an increment of +0.
  * Staged on the host; it travels to the device with the tables, on the next call's stream (acmpc_sync_tables covers it),
@@ -318,6 +340,13 @@ int acmpc_score_grips(acmpc_ctx* ctx, const float* states, const float* controls
 /* Copies the packed float32 table of problem `problem` (n rows of ACMPC_COEF_STRIDE_* floats) to `out`.
  * Host only; lets CPU tests pin the host-side arithmetic against the oracle. */
 int acmpc_get_coefficients(const acmpc_ctx* ctx, int32_t problem, float* out, int32_t capacity_floats);
+
+/* Mode D: copies the progress table of problem `problem` (n floats) to `out`.  Derived from the packed float32 rows
+ * (x_m, y_m, c_m = cos psi_m, s_m = sin psi_m) whenever acmpc_set_paths or acmpc_set_coefficients change them, in float64
+ * in the order written, no fused multiply-add:
+ *   S_0 = 0,  S_m = S_{m-1} + sqrt(dx dx + dy dy),  q_m = float32(S_m - (c_m (x_m - x_0) + s_m (y_m - y_0))).
+ * Host only, like acmpc_get_coefficients.  ACMPC_ESTATE for a handle that is not mode D or has no paths. */
+int acmpc_get_progress_table(const acmpc_ctx* ctx, int32_t problem, float* out, int32_t capacity_floats);
 
 /* Floats in one winner record: ACMPC_REC_HEADER + 2 n + 3 (n + 1) =
  *   [cost, violation, n_feasible, owner, u_0 .. u_{n-1} (2 each), x_0 .. x_n (3 each)]

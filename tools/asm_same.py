@@ -2,7 +2,8 @@
 """Development aid: are the kernels of two hipcc --save-temps assembly files the same instructions?  Per kernel the
 instruction lines are compared in order - comments, directives and block labels' numbers apart - and the kernels are matched
 by their mangled names with the template parameter pack of mode D's kernels (`J...E`, and the pack in the argument list)
-taken out, so that a file from before the pack existed compares with one from after.  Prints what differs and how many
+taken out where it is empty or one Terms, so that a file from before the pack existed compares with one from after; a kernel
+of any other pack (TermsObjective) keeps its name and is counted among the new file's only.  Prints what differs and how many
 kernels are identical; exit status 1 unless every kernel of OLD is in NEW and identical.
 
 usage: hipcc <the library's flags> -c csrc/acmpc_dynamic.hip -o unit.o --save-temps     (at both commits, in two directories)
@@ -23,7 +24,7 @@ def kernels(path):
                 body.append(re.sub(r"\d+_", "N_", line))
             elif line and not line.startswith("."):
                 body.append(re.sub(r"\.LBB\d+_", ".LBBN_", line))
-        name = re.sub(r"DpK?T\d*_", "", re.sub(r"J(?:NS_\d+\w+?E)*E(E+v)", r"\1", m.group(1)))
+        name = re.sub(r"DpK?T\d*_", "", re.sub(r"J(?:NS_5TermsE)?E(E+v)", r"\1", m.group(1)))
         out[name] = body
     return out
 

@@ -36,7 +36,9 @@ sub-step loop (`dynamic_fine_substep`, whose static count holds the blend's bloc
 With `--terms` every handle is given rate and slip terms (acmpc_set_dynamics_terms: both parts on, weights and limits as a
 controller would set them - TERMS below) and a previous control of zeros for each of its problems: the same shapes, the
 kernels of csrc/acmpc_dynamic_terms.hip; with `--substeps` / `--blend` as well, under that integration setting.  The roof
-prices `dynamic_terms_step` + M `dynamic_terms_substep`.
+prices `dynamic_terms_step` + M `dynamic_terms_substep`.  With `--objective` (beside `--terms` or alone) every handle is also
+given the progress reward and a speed ceiling (acmpc_set_dynamics_objective: both parts on, OBJECTIVE_ON below): the
+TermsObjective kernels of the same unit, priced with `dynamic_objective_step` + M `dynamic_objective_substep`.
 
 With `--identify` the grip identification (acmpc_score_grips: host pointers, one blocking round trip) is timed at K = 4 096
 (the 64 x 64 split grid) and K = 65 536 (256 x 256) hypotheses over a window of W = 40 steps, in one-step (L = 1) and
@@ -45,7 +47,7 @@ hypothesis and control step (profiles/*_isa_mix.json, entry `identify_grip`: M s
 and the vector-issue time that count needs (bench.valu_roofline) as a fraction of the CALL - a lower bound on the step
 kernel's own fraction, which a `rocprofv3 --kernel-trace --stats` run of this command gives (kernel identify_grip_kernel).
 
-usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms]
+usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms] [--objective]
                                       [--sampled | --optimize [--update softmin] | --identify]"""
 import argparse
 import json
@@ -67,6 +69,10 @@ TERMS = None              # --terms: the rate and slip terms every handle of thi
 TERMS_ON = dict(rate_weight=(0.5, 0.05), rate_max=(1.0, 8.0), slip_weight=10.0, slip_max=0.1)
 
 
+OBJECTIVE = None          # --objective: the progress reward and the speed ceiling every handle of this run is given
+OBJECTIVE_ON = dict(progress_weight=1.0, speed_ceiling=(1.1, 0.0))
+
+
 def integrate(eng):
     """The run's integration setting and terms on a new handle (a library without the entry points takes only the defaults)."""
     if INTEGRATION != (1, None):
@@ -74,6 +80,8 @@ def integrate(eng):
     if TERMS is not None:
         eng.set_dynamics_terms(**TERMS)
         eng.set_previous_control(np.zeros((eng.params.max_problems, 2), dtype=np.float32))   # (a handle's solves use all of them)
+    if OBJECTIVE is not None:
+        eng.set_dynamics_objective(**OBJECTIVE)
     return eng
 
 
@@ -81,7 +89,7 @@ def fine_issue_roof(bench, candidates, steps, kernel_s, name):
     """issue_roof for a FINE kernel: VALU per control step = the step loop's trip + M sub-step trips, priced with the
     sub-step loop's mix (which is nearly all of it)."""
     mix, mix_path = bench.newest_profile("isa_mix.json")
-    kind = "_terms_" if TERMS is not None else "_fine_"
+    kind = "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
     step, sub = mix["entries"][name + kind + "step"], mix["entries"][name + kind + "substep"]
     per_step = (sum(step["valu"].values()) + INTEGRATION[0] * sum(sub["valu"].values())) / float(sub["candidates_per_lane"])
     counted = (per_step, mix_path + " (static count: step trip + M sub-step trips)", {"source_sha256": mix.get("source_sha256")})
@@ -95,7 +103,7 @@ def issue_roof(bench, candidates, steps, kernel_s, name="dynamic"):
     """bench.valu_roofline for the `dynamic` entry (`dynamic_ensemble`: candidates = vehicle-candidates): the step loop's
     static VALU count per candidate-step (the isa mix, whose sources must be the loaded build's -
     `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
-    if (INTEGRATION != (1, None) or TERMS is not None) and name in ("dynamic", "dynamic_ensemble"):
+    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None) and name in ("dynamic", "dynamic_ensemble"):
         return fine_issue_roof(bench, candidates, steps, kernel_s, name)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     entry = mix["entries"][name]
@@ -121,9 +129,11 @@ def main():
     ap.add_argument("--substeps", type=int, default=1, help="Euler sub-steps per control step (1 .. 16)")
     ap.add_argument("--blend", default=None, help="LO,HI m/s: the low-speed blend")
     ap.add_argument("--terms", action="store_true", help="rate and slip terms on every handle (TERMS_ON)")
+    ap.add_argument("--objective", action="store_true", help="the progress reward and a speed ceiling on every handle (OBJECTIVE_ON)")
     args = ap.parse_args()
-    global INTEGRATION, TERMS
+    global INTEGRATION, TERMS, OBJECTIVE
     TERMS = dict(TERMS_ON) if args.terms else None
+    OBJECTIVE = dict(OBJECTIVE_ON) if args.objective else None
     INTEGRATION = (args.substeps, None if args.blend is None else tuple(float(v) for v in args.blend.split(",")))
     if args.update == "softmin" and not args.optimize:
         ap.error("--update softmin goes with --optimize")
@@ -419,6 +429,8 @@ def measure(args, K):
     out = {"tool": "tools/bench_dynamic.py", "horizon": H, "search": "window (2, 5)"}
     if INTEGRATION != (1, None):
         out.update(substeps=INTEGRATION[0], low_speed_blend=INTEGRATION[1])
+    if OBJECTIVE is not None:
+        out.update(objective={k: list(v) if isinstance(v, tuple) else v for k, v in OBJECTIVE.items()})
     if TERMS is not None:
         out.update(terms={k: list(v) if isinstance(v, tuple) else v for k, v in TERMS.items()})
     if K > 1:

@@ -54,6 +54,13 @@ ENTRIES = {
     "dynamic_terms_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
     "dynamic_ensemble_terms_step": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
     "dynamic_ensemble_terms_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_5TermsEEE", None),
+    # mode D with the objective (acmpc_set_dynamics_objective: the TermsObjective kernels of the same unit, all four parts):
+    # the ceiling's block is in the step loop's own trip - `dynamic_objective_step` - `dynamic_terms_step` - and the progress
+    # part is outside both loops, once per candidate
+    "dynamic_objective_step": ("acmpc_dynamic_terms.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_14TermsObjectiveEEE", None),
+    "dynamic_objective_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_14TermsObjectiveEEE", None),
+    "dynamic_ensemble_objective_step": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_14TermsObjectiveEEE", None),
+    "dynamic_ensemble_objective_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_14TermsObjectiveEEE", None),
     # mode D's grip identification (acmpc_score_grips, one hypothesis per lane): the sub-step loop of its step kernel - the
     # dynamics and the blend's block, WITHOUT the pose (nothing reads it there: no sincos_spec(yaw), no X, Y, yaw updates).
     # VALU per hypothesis and control step = M trips of it + `identify_grip_step`: the control's terms and the residual, the
@@ -63,10 +70,11 @@ ENTRIES = {
 }
 CANDIDATES_PER_LANE = {"fused_round": 1, "identify_grip": 1, "identify_grip_step": 1}
 OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dynamic_ensemble_fine_step",
-         "dynamic_terms_step", "dynamic_ensemble_terms_step", "identify_grip_step")
+         "dynamic_terms_step", "dynamic_ensemble_terms_step", "dynamic_objective_step", "dynamic_ensemble_objective_step",
+         "identify_grip_step")
 # (exit test at the head: closes with s_branch)
 ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep",
-           "identify_grip")
+           "dynamic_objective_substep", "dynamic_ensemble_objective_substep", "identify_grip")
 
 
 def source_hash():
