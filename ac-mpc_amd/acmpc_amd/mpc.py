@@ -88,7 +88,7 @@ class SpatialMPC:
         self._device_prologue = bool(config.get("device_prologue", True))
         self._qp_check_every = int(config.get("speed_profile_check_every", 5))
         # `speed_profile_method`: "exact" (default) = the QP's optimum in two passes, the OSQP-style splitting only for a
-        # problem the passes do not solve (infeasible: the reference's status then); "admm" = always the splitting
+        # problem the passes do not take (never "solved" where it has no optimum: a ceiling below v_min); "admm" = always the splitting
         self._speed_profile_method = profile_config["method"]
 
     # -- speed profiles -----------------------------------------------------------------------------------

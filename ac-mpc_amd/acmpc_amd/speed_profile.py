@@ -10,7 +10,8 @@ last entry forced to the end velocity (speed_profile.py:26-43).  It is solved on
 1/2 |v - v_hi|^2 and v_hi is the upper bound, so the optimum is the pointwise largest feasible profile - config key
 `method: "exact"`, the default), and by the native tridiagonal ADMM that restates OSQP's iteration
 (`acmpc_speed_profile_qp`, O(n) per iteration - also for the 10^4-waypoint lap profile) otherwise or with
-`method: "admm"`.  The tick's device prologue makes the same choice with the same arithmetic (acmpc_tick.qp_method).  `constraints` is held by reference: the control process rewrites its "v_max"
+`method: "admm"`.  A problem without an optimum - a ceiling below v_min (the end velocity, or the localised v_max), a spacing
+that is not positive and finite - is never "solved": the splitting runs to its cap and the kept iterate stays as it was.  The tick's device prologue makes the same choice with the same arithmetic (acmpc_tick.qp_method).  `constraints` is held by reference: the control process rewrites its "v_max"
 every tick (controller.py:241-243) and the next solve must see it.
 """
 from __future__ import annotations

@@ -109,6 +109,17 @@ struct HostTeam {
 constexpr double kSigma = 1e-6;
 constexpr double kAlpha = 1.6;
 
+// What makes a problem one without an optimum, element by element: an empty box (the ceiling below v_min: a row with
+// l > u - false for the equality row v_hi == v_min and for a NaN ceiling, on which nothing converges anyway) or a spacing
+// that is not positive and finite (exact_profile's "not a path": a negative one flips its rate row, an infinite one cuts
+// the chain in two - QPs of their own that would converge to a profile of something else).  1.0 / 0.0: combined by
+// the team's max-reduction.
+ACMPC_HD double no_optimum(double ceiling, double v_min, double spacing) {
+  const double empty = ceiling < v_min ? 1.0 : 0.0;
+  const double broken = (spacing > 0.0 && spacing < __builtin_huge_val()) ? 0.0 : 1.0;
+  return dmax(empty, broken);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // n <= kPcrMaxN: cyclic reduction, worker-local state
 // ---------------------------------------------------------------------------------------------------------------------
@@ -203,11 +214,13 @@ ACMPC_HD int solve_small(const Team& team, const Workspace& w, const double* v_h
   const int m = n - 1;  // acceleration rows; then n box rows
   Small<Team, K> st;
   double rho = 0.1;
+  double hopeless = 0.0;   // (a slot without an element looks at element n - 1 and row m - 1 again)
 ACMPC_SLOTS
   for (int k = 0; k < K; ++k) {
     const int i = team.rank() + k * Team::size;
     if (Team::size == 1 && i >= n) break;
     const int ic = clamp_index(i, n);
+    hopeless = dmax(hopeless, no_optimum(v_hi[ic], s.v_min, ds[clamp_index(i, m)]));
     // a slot without an element copies element n - 1 and never stores; the last element has no row (g = 0), the first
     // no row behind it (gm = 0)
     st.g[k] = (i < m) ? 1.0 / (2.0 * ds[clamp_index(i, m)]) : 0.0;
@@ -218,6 +231,7 @@ ACMPC_SLOTS
     st.ya[k] = (warm != 0 && i < m) ? y[clamp_index(i, m)] : 0.0;
     st.za[k] = st.zb[k] = 0.0;
   }
+  hopeless = team.max(hopeless, w.red);
   factor_small(team, w, st, n, rho, s);
   // z = clamp(A x): the rows need x_{i+1}
 ACMPC_SLOTS
@@ -339,7 +353,7 @@ ACMPC_SLOTS
     r_dual = team.max(r_dual, w.red);
     const double s_prim = team.max(dmax(s_ax, s_z), w.red);
     const double s_dual = team.max(dmax(dmax(s_px, s_aty), s_q), w.red);
-    if (r_prim <= s.eps_abs + s.eps_rel * s_prim && r_dual <= s.eps_abs + s.eps_rel * s_dual) {
+    if (hopeless == 0.0 && r_prim <= s.eps_abs + s.eps_rel * s_prim && r_dual <= s.eps_abs + s.eps_rel * s_dual) {
       status = 0;
       break;
     }
@@ -432,9 +446,14 @@ ACMPC_HD void refactor(const Team& team, const Workspace& w, int n, double rho, 
 // device a wavefront holds an element per lane and a pass is six exchanges (n <= 64; through the workspace for more);
 // as two serial sweeps - 2 n dependent steps - the same profile took a lone wavefront 5.3 us at n = 49.
 // Returns true with v = the optimum and y = 0 (no dual iterate: nothing iterates), on every worker alike; false - v and y
-// untouched or partly written - when the problem is not of this shape (a_min > 0, a_max < 0, a non-finite or non-positive
-// spacing, a non-finite ceiling) or infeasible: the caller then runs the splitting, whose status is the reference's own
-// for such a problem.  `scratch`: 4 n doubles (not needed by a 64-wide team with n <= 64).  v must not overlap v_hi or ds.
+// UNTOUCHED: the verdict is taken on the scan's own result before anything is stored, so a caller's warm iterate in v, y
+// is still there for the splitting - when the problem is not of this shape (a_min > 0, a_max < 0, a non-finite or
+// non-positive spacing, a non-finite ceiling) or infeasible.  The caller then runs the splitting (solve, below).  With a
+// rate bound of the wrong sign the problem is still a QP with an optimum, which the splitting finds ("solved"); the
+// other problems have none - a ceiling below v_min is a box row with l > u, which OSQP refuses as data; a spacing that is
+// not positive and finite is not a path - and the splitting never reports them solved: it runs to its cap (status 1),
+// the controller keeps the path's zero velocities (spatial_mpc.py:115-122).
+// `scratch`: 4 n doubles (not needed by a 64-wide team with n <= 64).  v must not overlap v_hi or ds.
 template <class Team>
 ACMPC_HD bool exact_profile(const Team& team, const Workspace& w, const double* v_hi, const double* ds, int n,
                             const Settings& s, double* v, double* y, double* scratch) {
@@ -467,6 +486,12 @@ ACMPC_HD bool exact_profile(const Team& team, const Workspace& w, const double* 
           gap = gap + other_gap;
         }
       }
+      // accepted or handed back on the scan's own result, before anything is stored
+      double bad = 0.0;
+      if (mine && (!(val >= s.v_min) || !(val <= v_hi[i]) || !(v_hi[i] < inf))) bad = 1.0;   // infeasible, or a non-finite ceiling
+      if (i + 1 < n && !(ds[i] > 0.0 && ds[i] < inf)) bad = 1.0;                              // not a path
+      bad = team.max(bad, w.red);
+      if (bad != 0.0) return false;
       if (mine) v[i] = val;
       done = true;
     }
@@ -514,23 +539,25 @@ ACMPC_HD bool exact_profile(const Team& team, const Workspace& w, const double* 
       double* t = cur_v; cur_v = nxt_v; nxt_v = t;
       t = cur_g; cur_g = nxt_g; nxt_g = t;
     }
+    double bad = 0.0;
+    for (int i = team.rank(); i < n; i += Team::size) {
+      if (!(cur_v[i] >= s.v_min) || !(cur_v[i] <= v_hi[i]) || !(v_hi[i] < inf)) bad = 1.0;   // infeasible, or a non-finite ceiling
+      if (i + 1 < n && !(ds[i] > 0.0 && ds[i] < inf)) bad = 1.0;                              // not a path
+    }
+    bad = team.max(bad, w.red);
+    if (bad != 0.0) return false;   // (the same on every worker; nothing of v or y has been written)
     for (int i = team.rank(); i < n; i += Team::size) v[i] = cur_v[i];
   }
-  team.sync();
-  double bad = 0.0;
-  for (int i = team.rank(); i < n; i += Team::size) {
-    if (!(v[i] >= s.v_min) || !(v[i] <= v_hi[i])) bad = 1.0;                       // infeasible, or a non-finite ceiling
-    if (i + 1 < n && !(ds[i] > 0.0 && ds[i] < __builtin_huge_val())) bad = 1.0;   // not a path
-  }
-  bad = team.max(bad, w.red);
-  if (bad != 0.0) return false;
   for (int i = team.rank(); i < 2 * n - 1; i += Team::size) y[i] = 0.0;
   team.sync();
   return true;
 }
 
 // `v` [n] and `y` [2n - 1] hold the primal / dual iterate: read when warm != 0, always written.  Returns 0 = solved,
-// 1 = maximum iterations reached; *iterations = iterations run.
+// 1 = maximum iterations reached; *iterations = iterations run.  A problem without an optimum (no_optimum) is never
+// "solved": its stopping test is not allowed to accept, so the solve runs to max_iter in every form - left to
+// itself the iteration settles between the two sides of an empty box and passes the 1e-3 test there (n = 49, v_min 8, end
+// velocity 2: "solved" after 150 iterations with v[n - 1] = 2.003, 6 m/s under v_min).
 template <class Team>
 ACMPC_HD int solve(const Team& team, const Workspace& w, const double* v_hi, const double* ds, int n,
                    const Settings& s, double* v, double* y, int warm, int* iterations) {
@@ -543,7 +570,12 @@ ACMPC_HD int solve(const Team& team, const Workspace& w, const double* v_hi, con
   }
   const int m = n - 1;  // acceleration rows; then n box rows
   double rho = 0.1;
-  for (int i = team.rank(); i < m; i += Team::size) w.g[i] = 1.0 / (2.0 * ds[i]);
+  double hopeless = 0.0;
+  for (int i = team.rank(); i < n; i += Team::size) {
+    if (i < m) w.g[i] = 1.0 / (2.0 * ds[i]);
+    hopeless = dmax(hopeless, no_optimum(v_hi[i], s.v_min, ds[i < m ? i : m - 1]));
+  }
+  hopeless = team.max(hopeless, w.red);
   team.sync();
   refactor(team, w, n, rho, v_hi, s);
   for (int i = team.rank(); i < n; i += Team::size) {
@@ -637,7 +669,7 @@ ACMPC_HD int solve(const Team& team, const Workspace& w, const double* v_hi, con
     r_dual = team.max(r_dual, w.red);
     const double s_prim = team.max(dmax(s_ax, s_z), w.red);
     const double s_dual = team.max(dmax(dmax(s_px, s_aty), s_q), w.red);
-    if (r_prim <= s.eps_abs + s.eps_rel * s_prim && r_dual <= s.eps_abs + s.eps_rel * s_dual) {
+    if (hopeless == 0.0 && r_prim <= s.eps_abs + s.eps_rel * s_prim && r_dual <= s.eps_abs + s.eps_rel * s_dual) {
       status = 0;
       break;
     }

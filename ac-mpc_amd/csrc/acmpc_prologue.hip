@@ -383,7 +383,9 @@ __global__ void __launch_bounds__(64) prologue_kernel(const PrologueArgs a) {
                                 h.qp_eps_abs, h.qp_eps_rel};
   int iterations = 0;
   // the QP's exact optimum in two sweeps where it has that shape (every tick of a feasible profile: no iteration count to
-  // depend on the approach of a braking zone); the splitting - with the iterate kept from the last tick it ran - otherwise
+  // depend on the approach of a braking zone); the splitting otherwise, from the iterate the last solved tick kept (the
+  // sweeps leave qv, qy alone when they reject): it solves a problem whose rate bound has the wrong sign and runs to its cap,
+  // status 1, on one without an optimum (a ceiling below v_min, coincident waypoints, a non-finite ceiling)
   const bool swept = h.qp_method == 0 && admm::exact_profile(team, ws, v_hi, tds, n, settings, qv, qy, ws.ex[0]);
   const int status = swept ? 0 : admm::solve(team, ws, v_hi, tds, n, settings, qv, qy, warm ? 1 : 0, &iterations);
   ACMPC_PSTAMP(4);

@@ -542,7 +542,8 @@ typedef struct acmpc_tick {
   int32_t qp_max_iter;         /* speed-profile QP: iteration cap (the reference passes 4000, spatial_mpc.py:17) */
   int32_t qp_check_every;      /* stopping test every this many iterations (<= 0: 10)                           */
   int32_t qp_method;           /* speed-profile QP: 0 = its exact optimum in two passes (acmpc_speed_profile_exact), the
-                                  splitting below only where that does not apply (an infeasible or misshapen problem);
+                                  splitting below only where that does not apply (a rate bound of the wrong sign: solved
+                                  there; an infeasible or misshapen problem: status 1 after qp_max_iter iterations);
                                   1 = always the OSQP splitting (acmpc_speed_profile_qp), warm-started between ticks    */
   double offset;               /* lateral displacement of the car: pose (offset, 0, pi/2), spatial_mpc.py:187   */
   double v_min, v_max, a_min, a_max, ay_max, ki_min, end_velocity; /* speed_profile_constraints, read every tick */
@@ -659,7 +660,9 @@ void acmpc_philox4x32(const uint32_t counter[4], const uint32_t key[2], uint32_t
  * whole-lap profile (n ~ 1e4, spatial_mpc.py:60-87) is as cheap per iteration as the horizon's.  `v` [n] and `y`
  * [2n - 1] hold the primal/dual iterate: read when warm_start != 0, always written.  The stopping test (OSQP's, at
  * eps_abs / eps_rel) runs every `check_every` iterations (<= 0: 10).  Returns 0 = solved, 1 = maximum iterations
- * reached, ACMPC_EINVAL on bad arguments.  No GPU work.  The device prologue of acmpc_control_tick runs the same
+ * reached, ACMPC_EINVAL on bad arguments.  A problem without an optimum - some v_hi[i] < v_min (a box row with l > u), a
+ * spacing that is not positive and finite - is never reported solved: the iteration runs to max_iter (returns 1,
+ * *iterations = max_iter).  No GPU work.  The device prologue of acmpc_control_tick runs the same
  * statement of the algorithm (csrc/acmpc_admm.h) on one wavefront: same float64 operations in the same order. */
 int acmpc_speed_profile_qp(const double* v_hi, const double* ds, int32_t n, double a_min, double a_max, double v_min,
                            int32_t max_iter, int32_t check_every, double eps_abs, double eps_rel, double* v, double* y,
@@ -669,8 +672,9 @@ int acmpc_speed_profile_qp(const double* v_hi, const double* ds, int32_t n, doub
  * constant and v_hi is also the upper bound, so the optimum is the pointwise largest feasible profile - v_hi cut down by a
  * forward sweep (a_max) and a backward sweep (a_min).  Returns 0 with v [n] = the optimum and y [2n - 1] = 0; 1 when the
  * problem is not of that shape (a_min > 0, a_max < 0, a spacing that is not positive and finite, a non-finite ceiling) or
- * infeasible (some v below v_min): solve it with acmpc_speed_profile_qp then, whose status is the reference's for such a
- * problem; ACMPC_EINVAL on bad arguments.  acmpc_control_tick's prologue does exactly this on the device (qp_method 0).
+ * infeasible (some v below v_min) - v and y are then left exactly as they were, so a warm iterate in them is still there
+ * for acmpc_speed_profile_qp, which solves the problems with a rate bound of the wrong sign and reports the others as not
+ * solved; ACMPC_EINVAL on bad arguments.  acmpc_control_tick's prologue does exactly this on the device (qp_method 0).
  * No GPU work. */
 int acmpc_speed_profile_exact(const double* v_hi, const double* ds, int32_t n, double a_min, double a_max, double v_min,
                               double* v, double* y);

@@ -253,7 +253,8 @@ def speed_profile_exact(v_hi: np.ndarray, ds: np.ndarray, a_min: float, a_max: f
             new_gap[:-d] = gap[:-d] + gap[d:]
             v, gap = new_v, new_gap
             d *= 2
-        if not (np.all(v >= v_min) and np.all(v <= v_hi)) or not np.all((ds[:n - 1] > 0.0) & np.isfinite(ds[:n - 1])):
+        if not (np.all(v >= v_min) and np.all(v <= v_hi) and np.all(v_hi < np.inf)) or \
+                not np.all((ds[:n - 1] > 0.0) & np.isfinite(ds[:n - 1])):
             return None
     return v
 
