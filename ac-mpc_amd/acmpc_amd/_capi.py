@@ -158,6 +158,7 @@ SIGNATURES = {
     "acmpc_set_dynamics_terms": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "acmpc_set_previous_control": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
     "acmpc_set_dynamics_objective": (C.c_int, [_CTX, C.c_double, C.c_void_p]),
+    "acmpc_set_dynamics_coupling": (C.c_int, [_CTX, C.c_void_p]),
     "acmpc_get_progress_table": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_score_grips": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
@@ -523,6 +524,25 @@ def dynamics_objective(progress_weight=0.0, speed_ceiling=None):
     return weight, (None if ceiling is None else np.array(ceiling, dtype=np.float64))
 
 
+def dynamics_coupling(value=None):
+    """Mode D's tyre coupling checked as acmpc_set_dynamics_coupling checks it: None (off), or the float64 pair (rho_f,
+    rho_r) of a pair or of a scalar for both axles.  ValueError for a ratio that is not > 0 as a float32 (NaN included);
+    +inf is no coupling on that axle."""
+    if value is None:
+        return None
+    try:
+        ratio = (float(value),) * 2 if np.ndim(value) == 0 else tuple(float(v) for v in value)
+    except (TypeError, ValueError):
+        raise ValueError("the tyre coupling is None, a ratio or a (front, rear) pair of ratios, not %r" % (value,)) from None
+    if len(ratio) != 2:
+        raise ValueError("the tyre coupling is a ratio or a (front, rear) pair, not %r" % (value,))
+    with np.errstate(over="ignore", under="ignore"):
+        for v in ratio:
+            if not np.float32(v) > 0.0:
+                raise ValueError("a coupling ratio is > 0 (inf: no coupling on that axle), not %r" % (v,))
+    return np.array(ratio, dtype=np.float64)
+
+
 class Engine:
     """Owns one acmpc_ctx.  Construction does no device work (fork-safe, controller.py:293-297)."""
 
@@ -644,6 +664,15 @@ class Engine:
         the setting outlives a change of vehicle, of the integration setting or of the rate and slip terms."""
         weight, ceiling = dynamics_objective(progress_weight, speed_ceiling)
         self._check(self._lib.acmpc_set_dynamics_objective(self._ctx, weight, None if ceiling is None else ceiling.ctypes.data))
+
+    def set_dynamics_coupling(self, ratio=None):
+        """Mode D's tyre coupling (acmpc_set_dynamics_coupling): `ratio` = rho, or (rho_f, rho_r) - each axle's drive and
+        brake force is clipped at rho times that axle's lateral peak, and its side force scaled by what the friction ellipse
+        leaves, so a grip scale reaches braking and traction too.  None switches it off; inf is no coupling on that axle.
+        While it is on every vehicle needs positive peaks.  The setting outlives a change of vehicle or of any other
+        setting."""
+        pair = dynamics_coupling(ratio)
+        self._check(self._lib.acmpc_set_dynamics_coupling(self._ctx, None if pair is None else pair.ctypes.data))
 
     def progress_table(self, problem: int = 0) -> np.ndarray:
         """Mode D's progress table q [n] of a problem (acmpc_get_progress_table), host only."""

@@ -76,9 +76,12 @@ class DynamicBicycleParams:
 
     def with_grip(self, scale: float) -> "DynamicBicycleParams":
         """A copy on a road with `scale` times the grip: the Pacejka peak factors Df and Dr (proportional to the road's
-        friction coefficient) scaled, nothing else.  The drive, brake and friction maps are left alone: this model has no
-        friction circle, so its longitudinal forces do not depend on the tyres' grip.  An ensemble of grips
-        (DynamicSamplingSolver's `grip_ensemble`) scores every candidate on several such roads."""
+        friction coefficient) scaled, nothing else.  The drive, brake and friction maps are left alone: without the tyre
+        coupling (acmpc_set_dynamics_coupling, `coupling=` below) the longitudinal forces do not depend on the tyres' grip.
+        With it each axle's drive and brake force is capped at rho times that axle's peak factor, which carries Df / Dr: the
+        scale then limits braking and traction as well as cornering, and a saturated axle has no side force left.  The
+        friction map is drag and stays as it is.  An ensemble of grips (DynamicSamplingSolver's `grip_ensemble`) scores every
+        candidate on several such roads."""
         return self.with_axle_grip(scale, scale)
 
     def with_axle_grip(self, front: float, rear: float) -> "DynamicBicycleParams":
@@ -102,10 +105,22 @@ class DynamicBicycleParams:
     def F_zr(self) -> float:
         return self.mass * self.g * self.lf / (self.lr + self.lf)
 
-    def predict_next_state(self, state, u, dt: float = 0.05) -> Tuple[np.ndarray, np.ndarray, list]:
+    @property
+    def peak_front(self) -> float:
+        """The front axle's peak factor Pf = Df (1 + epsf F_zf / F_z0) F_zf / F_z0: the most side force it gives."""
+        return self.Df * (1 + self.epsf * self.F_zf / self.F_z0) * self.F_zf / self.F_z0
+
+    @property
+    def peak_rear(self) -> float:
+        return self.Dr * (1 + self.epsr * self.F_zr / self.F_z0) * self.F_zr / self.F_z0
+
+    def predict_next_state(self, state, u, dt: float = 0.05, coupling=None) -> Tuple[np.ndarray, np.ndarray, list]:
         """One explicit Euler step in float64: state (X, Y, yaw, vx, vy, r), u = (delta, pedal) with the pedal in
         [-1, 1].  Returns (next_state, x_dot, [F_fy, F_ry, F_fx, F_rx]) like the reference; the caller clips vx >= 0
-        (the reference's loop does, dynamic_bicycle_model.py:180; so do the kernels, inside the step)."""
+        (the reference's loop does, dynamic_bicycle_model.py:180; so do the kernels, inside the step).  `coupling` = rho
+        or (rho_f, rho_r) is the tyre coupling of acmpc_set_dynamics_coupling in float64 (None: off; inf: none on that
+        axle): per axle F_x is clipped at +-rho P and F_y scaled by sqrt(1 - (F_x / (rho P))^2); the returned forces are
+        the coupled ones."""
         delta, pedal = float(u[0]), float(u[1])
         X, Y, yaw, vx, vy, r = (float(s) for s in state)
         den = vx + 1e-3
@@ -119,6 +134,10 @@ class DynamicBicycleParams:
         braking = min(0.0, pedal)
         F_rx = brake * (1 - self.brake_bias) * braking + motor * max(0.0, pedal)
         F_fx = brake * self.brake_bias * braking
+        if coupling is not None:
+            rho_f, rho_r = (float(coupling),) * 2 if np.ndim(coupling) == 0 else (float(v) for v in coupling)
+            F_fx, F_fy = _couple(F_fx, F_fy, rho_f * self.peak_front)
+            F_rx, F_ry = _couple(F_rx, F_ry, rho_r * self.peak_rear)
         sd, cd = np.sin(delta), np.cos(delta)
         x_dot = np.array([
             vx * np.cos(yaw) - vy * np.sin(yaw),
@@ -135,11 +154,12 @@ class DynamicBicycleParams:
         ba = B * alpha
         return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0 * np.sin(C * np.arctan(ba - E * (ba - np.arctan(ba))))
 
-    def rollout(self, state, U, dt: float = 0.05, substeps: int = 1, low_speed_blend=None) -> np.ndarray:
+    def rollout(self, state, U, dt: float = 0.05, substeps: int = 1, low_speed_blend=None, coupling=None) -> np.ndarray:
         """The mirror over a control sequence U [n, 2] with vx clipped after every step: states [n + 1, 6].  `substeps`
         and `low_speed_blend` = (v_lo, v_hi) are the integration setting of acmpc_set_dynamics_integration in float64: a
         control step is `substeps` Euler steps of dt / substeps, and after each (vy, r) are blended towards the kinematic
-        bicycle's r_k = vx tan(delta) / (lf + lr), vy_k = lr r_k by lam = clamp((vx - v_lo) / (v_hi - v_lo), 0, 1)."""
+        bicycle's r_k = vx tan(delta) / (lf + lr), vy_k = lr r_k by lam = clamp((vx - v_lo) / (v_hi - v_lo), 0, 1).
+        `coupling`: predict_next_state's, in every sub-step."""
         substeps = int(substeps)
         if substeps < 1:
             raise ValueError("substeps must be positive")
@@ -148,7 +168,7 @@ class DynamicBicycleParams:
         for u in np.asarray(U, dtype=np.float64):
             nxt = out[-1]
             for _ in range(substeps):
-                nxt = self.predict_next_state(nxt, u, h)[0]
+                nxt = self.predict_next_state(nxt, u, h, coupling=coupling)[0]
                 nxt[3] = max(nxt[3], 0.0)
                 if low_speed_blend is not None:
                     v_lo, v_hi = (float(v) for v in low_speed_blend)
@@ -158,6 +178,13 @@ class DynamicBicycleParams:
                     nxt[5] = lam * nxt[5] + (1.0 - lam) * r_k
             out.append(nxt)
         return np.stack(out)
+
+
+def _couple(F_x: float, F_y: float, cap: float) -> Tuple[float, float]:
+    """One axle on the friction ellipse: F_x clipped at +-cap, F_y scaled by what is left."""
+    F_x = max(min(F_x, cap), -cap)
+    u = F_x / cap
+    return F_x, F_y * float(np.sqrt(1.0 - u * u))
 
 
 def stage_terms(states, U, dt: float, u_prev, params: DynamicBicycleParams, rate_weight=(0.0, 0.0), rate_max=None,

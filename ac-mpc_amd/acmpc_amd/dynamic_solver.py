@@ -33,6 +33,11 @@ makes a candidate infeasible wherever vx > scale * v_ref + offset.  To drive at 
 kinematic profile: `r_term` = (0, .), a `progress_cost`, the profile as the ceiling (scale = sqrt(tyre a_y / profile a_y))
 and a `slip_limit`.  Costs may then be negative; a solve fails only on a non-finite one, as before.
 
+Tyre coupling (acmpc_set_dynamics_coupling): `tyre_coupling` - a ratio rho, or (rho_f, rho_r), default None - clips each
+axle's drive and brake force at rho times that axle's lateral peak and scales its side force by what the friction ellipse
+leaves.  Without it the brake map asks the tyres for more than they have and grip scales do not reach braking; with it
+`grip_ensemble` members and `grip_adapt` hypotheses brake and accelerate as their grip allows.  rho near 1.
+
 Grip adaptation (acmpc_score_grips, GripEstimator): `grip_adapt` - a dict, off by default - lets the solver find the road's
 grip from its own driving instead of being told an ensemble.  Every solve logs (state, the control applied since the
 previous solve - `previous_control`, else the last accepted plan's first control), scores a grid of grip hypotheses
@@ -128,6 +133,7 @@ class DynamicSamplingSolver:
         terms = _capi.dynamics_terms(config.get("rate_cost", (0.0, 0.0)), config.get("rate_limit"),
                                      config.get("slip_cost", 0.0), config.get("slip_limit"))
         objective = _capi.dynamics_objective(config.get("progress_cost", 0.0), config.get("speed_ceiling"))
+        coupling = _capi.dynamics_coupling(config.get("tyre_coupling"))
         self._centre_update = config.get("sampling_update", "argmin")   # or "softmin" (MPPI-style weighted mean)
         if self._centre_update not in SAMPLING_UPDATES:
             raise ValueError("sampling_update is 'argmin' or 'softmin', not %r" % (self._centre_update,))
@@ -155,6 +161,8 @@ class DynamicSamplingSolver:
             self._engine.set_dynamics_terms(*terms)
         if objective[0] != 0.0 or objective[1] is not None:
             self._engine.set_dynamics_objective(*objective)
+        if coupling is not None:
+            self._engine.set_dynamics_coupling(coupling)
         self._plan: Optional[np.ndarray] = None
         self._calls = 0
         self._adapt = adapt

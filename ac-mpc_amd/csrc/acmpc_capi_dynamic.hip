@@ -1,5 +1,5 @@
 // C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
-// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the previous control, and the grip
+// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the previous control, and the grip
 // identification (acmpc_score_grips), with the checks that the kernels' limits are the public header's.
 #include <algorithm>
 
@@ -65,6 +65,15 @@ const char* derive_vehicle(const double* coef, double wheelbase, acmpc::Vehicle*
   return nullptr;
 }
 
+// the tyre coupling divides by rho P: while it is on, every vehicle's two peaks are finite and positive as float32
+bool peaks_couple(const acmpc::VehicleEnsemble& e) {
+  for (int k = 0; k < e.K; ++k)
+    for (float P : {e.v[k].Pf, e.v[k].Pr})
+      if (!std::isfinite(P) || !(P > 0.0f)) return false;
+  return true;
+}
+constexpr const char* kPeaksRefused = "the tyre coupling is on: every vehicle's axle peaks Pf, Pr must be finite and > 0 (as float32)";
+
 }  // namespace
 
 extern "C" {
@@ -81,6 +90,7 @@ int acmpc_set_dynamics(acmpc_ctx* c, const double* coef, int32_t count) {
   e.omega[0] = 1.0f;
   e.K = 1;
   e.reduce = ACMPC_ENSEMBLE_MEAN;
+  if (c->has_coupling && !peaks_couple(e)) return fail(c, ACMPC_EINVAL, kPeaksRefused);
   c->vehicles = e;
   c->vehicle_L[0] = coef[14] + coef[15];
   std::memcpy(c->vehicle0, coef, sizeof c->vehicle0);
@@ -112,6 +122,7 @@ int acmpc_set_dynamics_ensemble(acmpc_ctx* c, const double* coef, int32_t K, con
     e.omega[k] = static_cast<float>(weights != nullptr ? weights[k] / total : 1.0 / K);
   e.K = K;
   e.reduce = reduce;
+  if (c->has_coupling && !peaks_couple(e)) return fail(c, ACMPC_EINVAL, kPeaksRefused);
   c->vehicles = e;
   for (int k = 0; k < K; ++k)
     c->vehicle_L[k] = coef[static_cast<size_t>(k) * acmpc::kDynamicsCount + 14] + coef[static_cast<size_t>(k) * acmpc::kDynamicsCount + 15];
@@ -173,6 +184,26 @@ int acmpc_set_dynamics_objective(acmpc_ctx* c, double progress_weight, const dou
   c->has_ceiling = speed_ceiling != nullptr;
   c->speed_ceiling[0] = c->has_ceiling ? speed_ceiling[0] + 0.0 : 0.0;
   c->speed_ceiling[1] = c->has_ceiling ? speed_ceiling[1] : 0.0;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_coupling(acmpc_ctx* c, const double ratio[2]) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_dynamics_coupling needs a mode D handle");
+  if (ratio == nullptr) {
+    c->has_coupling = false;
+    c->coupling[0] = c->coupling[1] = HUGE_VALF;
+    return ACMPC_OK;
+  }
+  // float32 is what the kernels get: each ratio is rounded once, and must then be > 0 (+inf: no coupling on that axle)
+  const float rho[2] = {static_cast<float>(ratio[0]), static_cast<float>(ratio[1])};
+  for (int q = 0; q < 2; ++q)   // (a NaN compares false)
+    if (!(rho[q] > 0.0f)) return fail(c, ACMPC_EINVAL, "a coupling ratio must be > 0 and finite, or INFINITY (none)");
+  if (c->has_dynamics && !peaks_couple(c->vehicles)) return fail(c, ACMPC_EINVAL, kPeaksRefused);
+  // everything is checked before anything is kept: a refused setting leaves the handle's as it was
+  c->has_coupling = true;
+  c->coupling[0] = rho[0];
+  c->coupling[1] = rho[1];
   return ACMPC_OK;
 }
 
@@ -266,7 +297,8 @@ int acmpc_score_grips(acmpc_ctx* c, const float* states, const float* controls, 
   // the handle's integration setting with the step of THIS log, under vehicle 0
   acmpc::Integration g = dynamics_integration(c);
   g.h = static_cast<float>(dt / c->substeps);
-  ACMPC_HIP(c, acmpc::launch_identify_grip(a, c->vehicles.v[0], g, s));
+  // and its tyre coupling, each hypothesis capped by its own peaks
+  ACMPC_HIP(c, acmpc::launch_identify_grip(a, c->vehicles.v[0], g, c->has_coupling ? c->coupling : nullptr, s));
   // one copy down: best key | errors
   ACMPC_HIP(c, hipMemcpyAsync(c->h_identify.data(), c->d_identify + kBestAt, down_bytes, hipMemcpyDeviceToHost, s));
   ACMPC_HIP(c, hipStreamSynchronize(s));

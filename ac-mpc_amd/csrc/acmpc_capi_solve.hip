@@ -14,8 +14,9 @@ namespace capi __attribute__((visibility("hidden"))) {
 // mode D: the kernels' view of the handle's rate and slip terms - every float derived in float64 and rounded once
 // ("Rate and slip terms").  A part whose weights are 0 and whose limits are +inf is off.  And of its
 // objective ("Progress and ceiling"): the progress part is on with a weight that is not 0, the ceiling part when one is set.
-static acmpc::TermsObjective dynamics_terms(const acmpc_ctx* c) {
-  acmpc::TermsObjective t{};
+// And of its tyre coupling ("Tyre coupling"): the two ratios.
+static acmpc::TermsCoupled dynamics_terms(const acmpc_ctx* c) {
+  acmpc::TermsCoupled t{};
   t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
             std::isfinite(c->rate_max[1])) ? 1 : 0;
   t.slip = (c->slip_weight != 0.0 || std::isfinite(c->slip_max)) ? 1 : 0;
@@ -33,6 +34,9 @@ static acmpc::TermsObjective dynamics_terms(const acmpc_ctx* c) {
   t.cs = static_cast<float>(c->speed_ceiling[0]);
   t.co = static_cast<float>(c->speed_ceiling[1]);
   t.q = c->d_progress;
+  t.coupled = c->has_coupling ? 1 : 0;
+  t.rho_f = c->coupling[0];
+  t.rho_r = c->coupling[1];
   return t;
 }
 

@@ -282,6 +282,10 @@ struct acmpc_ctx {
   double speed_ceiling[2] = {0.0, 0.0};   // (scale, offset)
   std::vector<float> h_progress;
   float* d_progress = nullptr;  // [max_problems][max_steps]
+  // mode D: the tyre coupling (acmpc_set_dynamics_coupling), kept apart like the others: the two ratios as the float32 the
+  // kernels get (+inf: no coupling on that axle).  While it is on every vehicle of the handle has finite, positive peaks.
+  bool has_coupling = false;
+  float coupling[2] = {HUGE_VALF, HUGE_VALF};
 
   mutable std::string err;
 };

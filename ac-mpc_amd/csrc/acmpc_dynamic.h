@@ -140,6 +140,37 @@ struct LanePeaks {
   __device__ __forceinline__ float rear(const Vehicle&) const { return Pr; }
 };
 
+// The tyre coupling of a handle (acmpc_set_dynamics_coupling, DESIGN.md section 2 "Mode D, tyre coupling"): each axle's
+// longitudinal force is clipped at rho times that axle's peak factor, and its Pacejka side force scaled by what the friction
+// ellipse leaves.  It reaches the step with the peaks, whose multiples its caps are: a peak source (above) with the two ratios
+// beside it, each rounded to float32 once (+inf: no coupling on that axle).  Under a plain source the step compiles nothing of
+// this (every kernel without the coupling: the code it was).
+template <typename PK>
+struct CoupledPeaks : PK {
+  float rho_f, rho_r;
+};
+template <typename PK>
+struct IsCoupled : std::false_type {};
+template <typename PK>
+struct IsCoupled<CoupledPeaks<PK>> : std::true_type {};
+
+// correctly rounded float32 square root (what hipcc emits for the builtin under the library's flags: a v_sqrt_f32 seed and an
+// FMA fix-up)
+__device__ __forceinline__ float sqrt_(float a) { return __builtin_sqrtf(a); }
+__device__ __forceinline__ f32x2 sqrt_(f32x2 a) { return __builtin_elementwise_sqrt(a); }
+
+// One axle under the coupling, in spec order: cap = rho P; F_x = max(min(F_x, cap), -cap); u = F_x / cap (IEEE division);
+// g = sqrt(1 - u u); F_y = F_y g.  After the clip |u| <= 1: the square root is never a NaN of its own making; a saturated axle
+// has u = +-1 exactly, g = 0; F_x = +-0 (pedal 0) and cap = +inf give g = 1 and F_y back bit for bit.
+template <typename F>
+__device__ __forceinline__ void couple_axle(F& F_x, F& F_y, float rho, float P) {
+  const float cap = rho * P;
+  F_x = vmax(__builtin_elementwise_min(F_x, splat<F>(cap)), splat<F>(-cap));
+  const F u = F_x / splat<F>(cap);
+  const F g = sqrt_(splat<F>(1.0f) - u * u);
+  F_y = F_y * g;
+}
+
 // What a step takes from its control alone: sincos_spec(delta) and the pedal's split.  The same for every sub-step of a
 // control step (dynamic_advance_fine computes it once).
 template <typename F>
@@ -159,7 +190,7 @@ __device__ __forceinline__ ControlTerms<F> control_terms(F delta, F pedal) {
 // vx = max(vx, 0) (the reference's loop, :180; maxNum: a NaN vx becomes 0).  HOISTED: the control's terms come in
 // through `pre` (the sub-steps of dynamic_advance_fine); otherwise they are computed here, where the single step has
 // always computed them - the default setting's kernels are to stay the code they were, instruction for instruction.
-// PK: the source of the peak factors (VehiclePeaks or LanePeaks).
+// PK: the source of the peak factors (VehiclePeaks or LanePeaks), or a CoupledPeaks of one: the tyre coupling.
 template <bool HOISTED, typename F, typename PK = VehiclePeaks>
 __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, const ControlTerms<F>* pre, const Vehicle& k,
                                               float dt, const PK pk = PK{}) {
@@ -169,8 +200,8 @@ __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, c
   const F qr = (r * k.lr - vy) / den;
   const F a_f = delta - atan_spec<F>(qf);   // the reference's -atan(q) + delta: the same float
   const F a_r = atan_spec<F>(qr);
-  const F F_fy = pacejka<F>(a_f, k.Bf, k.Cf, k.Ef, pk.front(k));
-  const F F_ry = pacejka<F>(a_r, k.Br, k.Cr, k.Er, pk.rear(k));
+  F F_fy = pacejka<F>(a_f, k.Bf, k.Cf, k.Ef, pk.front(k));
+  F F_ry = pacejka<F>(a_r, k.Br, k.Cr, k.Er, pk.rear(k));
   const F vx2 = vx * vx;
   const F F_fric = (k.fric0 - k.Cfric2 * vx) - k.Cfric3 * vx2;
   const F brake = (k.Cb1 - k.Cb2 * vx) - k.Cb3 * vx2;
@@ -183,8 +214,12 @@ __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, c
     p_neg = __builtin_elementwise_min(pedal, splat<F>(0.0f));
     p_pos = vmax(pedal, splat<F>(0.0f));
   }
-  const F F_rx = (brake * k.bias_rear) * p_neg + motor * p_pos;
-  const F F_fx = (brake * k.bias_front) * p_neg;
+  F F_rx = (brake * k.bias_rear) * p_neg + motor * p_pos;
+  F F_fx = (brake * k.bias_front) * p_neg;
+  if constexpr (IsCoupled<PK>::value) {
+    couple_axle<F>(F_fx, F_fy, pk.rho_f, pk.front(k));
+    couple_axle<F>(F_rx, F_ry, pk.rho_r, pk.rear(k));
+  }
   F sd, cd, sy, cy;
   if constexpr (HOISTED) {
     sd = pre->sd;
@@ -292,6 +327,16 @@ struct TermsObjective : Terms {
 };
 __host__ __device__ inline bool has_objective(const TermsObjective& t) { return t.progress != 0 || t.ceiling != 0; }
 
+// The TermsObjective plus the tyre coupling of a handle (acmpc_set_dynamics_coupling, DESIGN.md section 2 "Mode D, tyre
+// coupling"): a pack type of its own again.  The kernels instantiated for it hold the general step with the coupling block in
+// every sub-step and all four term parts behind their scalar switches (any of them may be off), and run only while `coupled`
+// is set; every other kernel stays the code it was.  The launchers take the handle's settings as one of these.
+struct TermsCoupled : TermsObjective {
+  float rho_f, rho_r;
+  int coupled;                  // 0: off (rho_f, rho_r not read); the kernels do not read it
+};
+__host__ __device__ inline bool has_coupling(const TermsCoupled& t) { return t.coupled != 0; }
+
 // what the terms carry from step to step: the previous step's control and the cost sum
 template <typename F>
 struct TermsState {
@@ -312,6 +357,18 @@ __device__ __forceinline__ TermsState<F> start_terms(int p, const Terms& t) {
 template <typename F>
 __device__ __forceinline__ TermsState<F>& state_of(TermsState<F>& ts, const Terms&) {
   return ts;
+}
+
+// Whether a kernel's pack (`TM...`, or roll_sampled's `TT...` with the terms' state first) holds a TermsCoupled, and the peak
+// source its control step then takes: dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(..., coupled_peaks(tm...))
+template <typename... TM>
+constexpr bool kCoupledPack = (std::is_same<typename std::remove_cv<TM>::type, TermsCoupled>::value || ...);
+__device__ __forceinline__ CoupledPeaks<VehiclePeaks> coupled_peaks(const TermsCoupled& t) {
+  return CoupledPeaks<VehiclePeaks>{{}, t.rho_f, t.rho_r};
+}
+template <typename F>
+__device__ __forceinline__ CoupledPeaks<VehiclePeaks> coupled_peaks(const TermsState<F>&, const TermsCoupled& t) {
+  return coupled_peaks(t);
 }
 
 // one float of the staged waypoint row(s) j, or of a table of one float per waypoint (stride 1)
@@ -352,7 +409,7 @@ __device__ __forceinline__ void dynamic_terms(StateD_<F>& s, F delta, F pedal, b
     const F hb = vmax(abs_(b) - t.b_max, splat<F>(0.0f));
     s.t.V = fma_(hb, hb, s.t.V);
   }
-  if constexpr (std::is_same<TT, TermsObjective>::value) {
+  if constexpr (std::is_base_of<TermsObjective, TT>::value) {
     if (t.ceiling == 0) return;
     const F cap = fma_(splat<F>(t.cs), gather_float(wp, j, kCoefT, 5), splat<F>(t.co));
     const F h = vmax(s.vx - cap, splat<F>(0.0f));   // (maxNum: a NaN v_ref is no ceiling)
@@ -368,7 +425,7 @@ template <typename F, typename TT>
 __device__ __forceinline__ F finish_dynamic_terms(const StateD_<F>& s, const TermsState<F>& ts, [[maybe_unused]] const float* wp,
                                                   [[maybe_unused]] typename IndexOf<F>::type j, [[maybe_unused]] int p, int n,
                                                   const Weights& w, const TT& t) {
-  constexpr bool kObjective = std::is_same<TT, TermsObjective>::value;
+  constexpr bool kObjective = std::is_base_of<TermsObjective, TT>::value;
   const StateT_<F>& st = s.t;
   const float tN = static_cast<float>(n) * w.dt;
   F stage = splat<F>(w.hq0) * st.S0;
@@ -430,22 +487,23 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // `integration`: the handle's setting; the default launches the FINE = false instantiations, whose step loop knows nothing
 // of it.
 // `terms`: the handle's rate and slip terms and its objective; when any part is on, the kernels that hold them run, with the general step whatever the
-// integration setting (the default one as M = 1, no blend, h = float32(dt)).
+// integration setting (the default one as M = 1, no blend, h = float32(dt)).  And its tyre coupling: while that is on, the
+// coupled kernels run, whatever the parts.
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& integration, const TermsObjective& terms, hipStream_t s);
+                                  const Integration& integration, const TermsCoupled& terms, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const TermsObjective& terms, hipStream_t s);
+                                          const Integration& integration, const TermsCoupled& terms, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& integration, const TermsObjective& terms, hipStream_t s);
+                                   const Integration& integration, const TermsCoupled& terms, hipStream_t s);
 // what the three above call when has_terms(terms) or has_objective(terms) (acmpc_dynamic_terms.hip: the kernels of a plain
 // Terms in the first case alone, those of a TermsObjective otherwise)
 hipError_t launch_rollout_dynamic_terms(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
@@ -455,5 +513,13 @@ hipError_t launch_rollout_dynamic_sampled_terms(const RolloutArgs& args, const S
                                                 const TermsObjective& terms, hipStream_t s);
 hipError_t launch_finalize_dynamic_terms(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
                                          const Integration& integration, const TermsObjective& terms, hipStream_t s);
+// and while has_coupling(terms) (acmpc_dynamic_coupled.hip: the kernels of a TermsCoupled, whichever term parts are on)
+hipError_t launch_rollout_dynamic_coupled(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                          const Integration& integration, const TermsCoupled& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_sampled_coupled(const RolloutArgs& args, const SampleArgs& sample,
+                                                  const VehicleEnsemble& vehicles, const Integration& integration,
+                                                  const TermsCoupled& terms, hipStream_t s);
+hipError_t launch_finalize_dynamic_coupled(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                           const Integration& integration, const TermsCoupled& terms, hipStream_t s);
 
 }  // namespace acmpc

@@ -48,6 +48,11 @@
 // progress or the ceiling part is on: the kernels of a plain Terms stay the code they were (inside them the two parts cost the
 // one-per-lane sampled rollouts a wave per SIMD: 74 VGPRs against 69 / 70).
 //
+// And a fifth, for a handle with the tyre coupling (acmpc_set_dynamics_coupling; acmpc_dynamic.h: TermsCoupled, couple_axle):
+// the pack is one TermsCoupled - the TermsObjective plus the two ratios, which coupled_peaks() hands to the general step with the peaks: the
+// friction-ellipse block in every sub-step.  All four term parts sit behind their scalar switches, any of them off.  Sixteen
+// instantiations of a third translation unit, acmpc_dynamic_coupled.hip, launched only while the coupling is on.
+//
 // Built with -ffp-contract=off: see acmpc_device.h.
 #include "acmpc_dynamic.h"
 
@@ -173,7 +178,8 @@ __global__ void __launch_bounds__(kDynBlock)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
+      if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
+      else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
       if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, s_wp, nearest, ts, tm...);
@@ -337,7 +343,8 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
         d = dj[0];
         q = qj[0];
       }
-      dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
+      if constexpr (kCoupledPack<TT...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, coupled_peaks(tt...));
+      else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
       if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, s_wp, nearest, tt...);   // (the state keeps this step's blended control)
@@ -518,7 +525,8 @@ __global__ void __launch_bounds__(kWave)
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
     const float d = su[2 * i], q = su[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
-    dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[0]);
+    if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
+    else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[0]);
     // the first minimum of the key over the search's waypoints, the lanes side by side; ties -> the lower index, and the
     // search's first waypoint when no key compares below +inf (as the rollout's `d < best` scans)
     const int lo = exhaustive ? 0 : max(min(j_prev - w.nn_back, n - win_w), 0);
@@ -611,7 +619,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
+      if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
+      else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
       if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, s_wp, nearest, ts, tm...);
@@ -798,7 +807,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
     const float d = su[2 * i], q = su[2 * i + 1];
-    dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[k]);
+    if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
+    else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[k]);
     // finalize_dynamic_kernel's search, within this wave
     const int lo = exhaustive ? 0 : max(min(j_prev - w.nn_back, n - win_w), 0);
     const int hi = exhaustive ? n - 1 : min(lo + win_w, n) - 1;
@@ -996,7 +1006,25 @@ hipError_t finalize_dynamic_launch(int layout, const FinalizeArgs& args, const V
 
 }  // namespace
 
-#ifdef ACMPC_DYNAMIC_TERMS_TU
+#if defined(ACMPC_DYNAMIC_COUPLED_TU)
+
+hipError_t launch_rollout_dynamic_coupled(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                          const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+  return rollout_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+hipError_t launch_rollout_dynamic_sampled_coupled(const RolloutArgs& args, const SampleArgs& sample,
+                                                  const VehicleEnsemble& vehicles, const Integration& g,
+                                                  const TermsCoupled& tm, hipStream_t s) {
+  return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s, tm);
+}
+
+hipError_t launch_finalize_dynamic_coupled(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                           const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+  return finalize_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+#elif defined(ACMPC_DYNAMIC_TERMS_TU)
 
 // (a handle without the objective runs the kernels of a plain Terms)
 hipError_t launch_rollout_dynamic_terms(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
@@ -1018,7 +1046,7 @@ hipError_t launch_finalize_dynamic_terms(int layout, const FinalizeArgs& args, c
   return finalize_dynamic_launch(layout, args, vehicles, g, s, static_cast<const Terms&>(tm));
 }
 
-#else  // ACMPC_DYNAMIC_TERMS_TU
+#else  // neither: the kernels without the terms
 
 int dynamic_candidates_per_lane(int P, int N, int K) {
   // 256 CUs x 4 SIMDs x 8 waves x 64 lanes = 524 288 lanes: two candidates per lane once every lane would get two
@@ -1032,23 +1060,26 @@ int dynamic_blocks_per_problem(int P, int N, int K) {
 }
 
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& g, const TermsObjective& tm, hipStream_t s) {
+                                  const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+  if (has_coupling(tm)) return launch_rollout_dynamic_coupled(layout, args, vehicles, g, tm, s);
   if (has_terms(tm) || has_objective(tm)) return launch_rollout_dynamic_terms(layout, args, vehicles, g, tm, s);
   return rollout_dynamic_launch(layout, args, vehicles, g, s);
 }
 
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& g, const TermsObjective& tm, hipStream_t s) {
+                                          const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+  if (has_coupling(tm)) return launch_rollout_dynamic_sampled_coupled(args, sample, vehicles, g, tm, s);
   if (has_terms(tm) || has_objective(tm)) return launch_rollout_dynamic_sampled_terms(args, sample, vehicles, g, tm, s);
   return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s);
 }
 
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& g, const TermsObjective& tm, hipStream_t s) {
+                                   const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+  if (has_coupling(tm)) return launch_finalize_dynamic_coupled(layout, args, vehicles, g, tm, s);
   if (has_terms(tm) || has_objective(tm)) return launch_finalize_dynamic_terms(layout, args, vehicles, g, tm, s);
   return finalize_dynamic_launch(layout, args, vehicles, g, s);
 }
 
-#endif  // ACMPC_DYNAMIC_TERMS_TU
+#endif  // ACMPC_DYNAMIC_COUPLED_TU, ACMPC_DYNAMIC_TERMS_TU
 
 }  // namespace acmpc

@@ -31,7 +31,9 @@ struct IdentifyArgs {
 int identify_segments(int W, int L);   // ceil(W / L)
 int identify_blocks(int K);            // workgroups (= partial keys) of K hypotheses: <= 256
 // `vehicle`: the base vehicle (its Pf, Pr are not read); `g`: the integration setting with h of the LOG's period and
-// inv_L[0] the base vehicle's.  hipErrorInvalidValue beyond the limits above.
-hipError_t launch_identify_grip(const IdentifyArgs& args, const Vehicle& vehicle, const Integration& g, hipStream_t s);
+// inv_L[0] the base vehicle's; `coupling`: the two ratios of the handle's tyre coupling, or nullptr while it is off.  hipErrorInvalidValue
+// beyond the limits above.
+hipError_t launch_identify_grip(const IdentifyArgs& args, const Vehicle& vehicle, const Integration& g, const float* coupling,
+                                hipStream_t s);
 
 }  // namespace acmpc

@@ -300,6 +300,25 @@ int acmpc_set_dynamics_terms(acmpc_ctx* ctx, const double rate_weight[2], const 
  * previous setting.  DESIGN.md section 2 "Mode D, progress and ceiling". */
 int acmpc_set_dynamics_objective(acmpc_ctx* ctx, double progress_weight, const double speed_ceiling[2] /* NULL: none */);
 
+/* Mode D's tyre coupling: a friction ellipse between each axle's longitudinal and lateral force.  Off by default, when the
+ * drive and brake maps do not know the tyres' grip and the Pacejka side force does not know the pedal.  ratio = (rho_f,
+ * rho_r), each > 0 and finite, or +inf (INFINITY) for no coupling on that axle, each rounded to float32 once; NULL turns the
+ * setting off.  In every Euler step (every sub-step of acmpc_set_dynamics_integration), after the two longitudinal forces and
+ * before the accelerations, per axle with P that axle's peak factor (Pf or Pr of the vehicle rolled), all float32, nothing
+ * fused:
+ *   cap = rho P;  F_x = max(min(F_x, cap), -cap);  u = F_x / cap;  g = sqrt(1 - u u);  F_y = F_y g
+ * so an axle cannot push or brake harder than rho times its lateral peak, a saturated axle (|u| = 1) has no side force left,
+ * and because P carries Df / Dr a grip scale (DynamicBicycleParams.with_grip, an ensemble's members, the hypotheses of
+ * acmpc_score_grips, each with its OWN peaks) now shortens braking and traction too.  pedal == 0 and rho = +inf give the
+ * uncoupled step bit for bit.  The friction map is drag, not tyre force, and is left alone.  rho near 1 is a tyre as good
+ * along as across.  The setting belongs to the handle: it survives acmpc_set_dynamics, _ensemble, _integration, _terms and
+ * _objective, and every call form of mode D takes it from the handle.  While it is on every vehicle of the handle must have
+ * Pf, Pr finite and > 0 as float32: whichever call would break that - this one, acmpc_set_dynamics or
+ * acmpc_set_dynamics_ensemble - returns ACMPC_EINVAL and leaves the handle as it was.  No device work.  ACMPC_ESTATE for a
+ * handle whose mode is not ACMPC_MODE_DYNAMIC; ACMPC_EINVAL for a ratio that is 0, negative or NaN (as a float32).
+ * DESIGN.md section 2 "Mode D, tyre coupling". */
+int acmpc_set_dynamics_coupling(acmpc_ctx* ctx, const double ratio[2] /* NULL: off */);
+
 /* The control applied just before each problem's plan starts: u_prev host [P][2] = (delta, pedal), what step 0's rates
  * are taken against; NULL clears it (P is then ignored), and step 0's own control stands for it: an increment of +0.
  * Staged on the host; it travels to the device with the tables, on the next call's stream (acmpc_sync_tables covers it),

@@ -40,6 +40,12 @@ prices `dynamic_terms_step` + M `dynamic_terms_substep`.  With `--objective` (be
 given the progress reward and a speed ceiling (acmpc_set_dynamics_objective: both parts on, OBJECTIVE_ON below): the
 TermsObjective kernels of the same unit, priced with `dynamic_objective_step` + M `dynamic_objective_substep`.
 
+With `--coupling RF,RR` every handle is given the tyre coupling (acmpc_set_dynamics_coupling: the ratios of the front and the
+rear axle; a single number is both): the TermsCoupled kernels of csrc/acmpc_dynamic_coupled.hip, with whatever `--terms` /
+`--objective` / `--substeps` / `--blend` set beside it, priced with `dynamic_coupled_step` + M `dynamic_coupled_substep`; and
+with `--identify`, identify_grip_coupled_kernel (`identify_grip_coupled`).  To price the coupling, alternate the command with
+and without the flag in one job on one card.
+
 With `--identify` the grip identification (acmpc_score_grips: host pointers, one blocking round trip) is timed at K = 4 096
 (the 64 x 64 split grid) and K = 65 536 (256 x 256) hypotheses over a window of W = 40 steps, in one-step (L = 1) and
 eight-step (L = 8) segments, under the run's integration setting: p50 / p99 of the call, the static VALU count per
@@ -47,7 +53,7 @@ hypothesis and control step (profiles/*_isa_mix.json, entry `identify_grip`: M s
 and the vector-issue time that count needs (bench.valu_roofline) as a fraction of the CALL - a lower bound on the step
 kernel's own fraction, which a `rocprofv3 --kernel-trace --stats` run of this command gives (kernel identify_grip_kernel).
 
-usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms] [--objective]
+usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms] [--objective] [--coupling RF,RR]
                                       [--sampled | --optimize [--update softmin] | --identify]"""
 import argparse
 import json
@@ -73,6 +79,9 @@ OBJECTIVE = None          # --objective: the progress reward and the speed ceili
 OBJECTIVE_ON = dict(progress_weight=1.0, speed_ceiling=(1.1, 0.0))
 
 
+COUPLING = None           # --coupling: the tyre coupling (rho_f, rho_r) every handle of this run is given
+
+
 def integrate(eng):
     """The run's integration setting and terms on a new handle (a library without the entry points takes only the defaults)."""
     if INTEGRATION != (1, None):
@@ -82,6 +91,8 @@ def integrate(eng):
         eng.set_previous_control(np.zeros((eng.params.max_problems, 2), dtype=np.float32))   # (a handle's solves use all of them)
     if OBJECTIVE is not None:
         eng.set_dynamics_objective(**OBJECTIVE)
+    if COUPLING is not None:
+        eng.set_dynamics_coupling(COUPLING)
     return eng
 
 
@@ -89,7 +100,7 @@ def fine_issue_roof(bench, candidates, steps, kernel_s, name):
     """issue_roof for a FINE kernel: VALU per control step = the step loop's trip + M sub-step trips, priced with the
     sub-step loop's mix (which is nearly all of it)."""
     mix, mix_path = bench.newest_profile("isa_mix.json")
-    kind = "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
+    kind = "_coupled_" if COUPLING is not None else "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
     step, sub = mix["entries"][name + kind + "step"], mix["entries"][name + kind + "substep"]
     per_step = (sum(step["valu"].values()) + INTEGRATION[0] * sum(sub["valu"].values())) / float(sub["candidates_per_lane"])
     counted = (per_step, mix_path + " (static count: step trip + M sub-step trips)", {"source_sha256": mix.get("source_sha256")})
@@ -103,7 +114,7 @@ def issue_roof(bench, candidates, steps, kernel_s, name="dynamic"):
     """bench.valu_roofline for the `dynamic` entry (`dynamic_ensemble`: candidates = vehicle-candidates): the step loop's
     static VALU count per candidate-step (the isa mix, whose sources must be the loaded build's -
     `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
-    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None) and name in ("dynamic", "dynamic_ensemble"):
+    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None or COUPLING is not None) and name in ("dynamic", "dynamic_ensemble"):
         return fine_issue_roof(bench, candidates, steps, kernel_s, name)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     entry = mix["entries"][name]
@@ -130,8 +141,14 @@ def main():
     ap.add_argument("--blend", default=None, help="LO,HI m/s: the low-speed blend")
     ap.add_argument("--terms", action="store_true", help="rate and slip terms on every handle (TERMS_ON)")
     ap.add_argument("--objective", action="store_true", help="the progress reward and a speed ceiling on every handle (OBJECTIVE_ON)")
+    ap.add_argument("--coupling", default=None, help="RF,RR (or one ratio for both axles): the tyre coupling on every handle")
     args = ap.parse_args()
-    global INTEGRATION, TERMS, OBJECTIVE
+    global INTEGRATION, TERMS, OBJECTIVE, COUPLING
+    if args.coupling is not None:
+        ratios = tuple(float(v) for v in args.coupling.split(","))
+        if len(ratios) not in (1, 2):
+            ap.error("--coupling takes RF,RR or one ratio")
+        COUPLING = ratios * 2 if len(ratios) == 1 else ratios
     TERMS = dict(TERMS_ON) if args.terms else None
     OBJECTIVE = dict(OBJECTIVE_ON) if args.objective else None
     INTEGRATION = (args.substeps, None if args.blend is None else tuple(float(v) for v in args.blend.split(",")))
@@ -326,9 +343,12 @@ def measure_identify(args):
     integrate(eng)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     M = INTEGRATION[0]
-    per_step = M * sum(mix["entries"]["identify_grip"]["valu"].values()) + sum(mix["entries"]["identify_grip_step"]["valu"].values())
+    entry = "identify_grip_coupled" if COUPLING is not None else "identify_grip"
+    per_step = M * sum(mix["entries"][entry]["valu"].values()) + sum(mix["entries"][entry + "_step"]["valu"].values())
     out = {"tool": "tools/bench_dynamic.py --identify", "W": W, "substeps": M, "low_speed_blend": INTEGRATION[1],
            "valu_per_hypothesis_step": per_step}
+    if COUPLING is not None:
+        out["coupling"] = list(COUPLING)
     calls = 20 if args.quick else 200
     for side in (64, 256):
         scales = grip_scales(np.linspace(0.3, 1.5, side), "split")
@@ -343,7 +363,7 @@ def measure_identify(args):
             p50 = float(np.percentile(lat, 50))
             counted = (float(per_step), mix_path + " (static count: M sub-step trips + the step loop's rest)",
                        {"source_sha256": mix.get("source_sha256")})
-            roof, _ = bench.valu_roofline(counted, K, W, p50, mix_entry="identify_grip", cpt=1)
+            roof, _ = bench.valu_roofline(counted, K, W, p50, mix_entry=entry, cpt=1)
             out["K%d_L%d" % (K, L)] = dict(K=K, L=L, segments=(W + L - 1) // L, p50_ms=p50 * 1e3,
                                            p99_ms=float(np.percentile(lat, 99)) * 1e3, calls=len(lat),
                                            best=[float(v) for v in scales[best]], error_best=float(errors[best]),
@@ -433,6 +453,8 @@ def measure(args, K):
         out.update(objective={k: list(v) if isinstance(v, tuple) else v for k, v in OBJECTIVE.items()})
     if TERMS is not None:
         out.update(terms={k: list(v) if isinstance(v, tuple) else v for k, v in TERMS.items()})
+    if COUPLING is not None:
+        out.update(coupling=list(COUPLING))
     if K > 1:
         out.update(vehicles=K, reduce=args.reduce, grips=list(GRIPS[:K]))
 

@@ -61,20 +61,33 @@ ENTRIES = {
     "dynamic_objective_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_14TermsObjectiveEEE", None),
     "dynamic_ensemble_objective_step": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_14TermsObjectiveEEE", None),
     "dynamic_ensemble_objective_substep": ("acmpc_dynamic_terms.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_14TermsObjectiveEEE", None),
+    # mode D with the tyre coupling (acmpc_set_dynamics_coupling: the TermsCoupled kernels of acmpc_dynamic_coupled.hip, the
+    # general step with the friction-ellipse block in every sub-step and all four term parts): the block's instructions =
+    # `dynamic_coupled_substep` - `dynamic_objective_substep` - per axle the clip, an IEEE division and a correctly rounded
+    # square root
+    "dynamic_coupled_step": ("acmpc_dynamic_coupled.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12TermsCoupledEEE", None),
+    "dynamic_coupled_substep": ("acmpc_dynamic_coupled.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12TermsCoupledEEE", None),
+    "dynamic_ensemble_coupled_step": ("acmpc_dynamic_coupled.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12TermsCoupledEEE", None),
+    "dynamic_ensemble_coupled_substep": ("acmpc_dynamic_coupled.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12TermsCoupledEEE", None),
     # mode D's grip identification (acmpc_score_grips, one hypothesis per lane): the sub-step loop of its step kernel - the
     # dynamics and the blend's block, WITHOUT the pose (nothing reads it there: no sincos_spec(yaw), no X, Y, yaw updates).
     # VALU per hypothesis and control step = M trips of it + `identify_grip_step`: the control's terms and the residual, the
     # step loop's own trip (OUTER)
     "identify_grip": ("acmpc_identify.hip", "identify_grip_kernel", None),
     "identify_grip_step": ("acmpc_identify.hip", "identify_grip_kernel", None),
+    # the same under the tyre coupling (each lane's caps from its own two peaks): the block = the difference of the sub-steps
+    "identify_grip_coupled": ("acmpc_identify.hip", "identify_grip_coupled_kernel", None),
+    "identify_grip_coupled_step": ("acmpc_identify.hip", "identify_grip_coupled_kernel", None),
 }
-CANDIDATES_PER_LANE = {"fused_round": 1, "identify_grip": 1, "identify_grip_step": 1}
+CANDIDATES_PER_LANE = {"fused_round": 1, "identify_grip": 1, "identify_grip_step": 1, "identify_grip_coupled": 1,
+                       "identify_grip_coupled_step": 1}
 OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dynamic_ensemble_fine_step",
          "dynamic_terms_step", "dynamic_ensemble_terms_step", "dynamic_objective_step", "dynamic_ensemble_objective_step",
-         "identify_grip_step")
+         "dynamic_coupled_step", "dynamic_ensemble_coupled_step", "identify_grip_step", "identify_grip_coupled_step")
 # (exit test at the head: closes with s_branch)
 ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep",
-           "dynamic_objective_substep", "dynamic_ensemble_objective_substep", "identify_grip")
+           "dynamic_objective_substep", "dynamic_ensemble_objective_substep", "dynamic_coupled_substep",
+           "dynamic_ensemble_coupled_substep", "identify_grip", "identify_grip_coupled")
 
 
 def source_hash():
