@@ -807,7 +807,9 @@ __device__ __host__ __forceinline__ void philox4x32_10(const uint32_t ctr[4], co
   out[3] = c3;
 }
 
-// 32 random bits -> uniform in (0, 1): 24 bits, centred, never 0 or 1
+// 32 random bits -> uniform in (0, 1]: the float32 nearest (k + 1/2) 2^-24 for the top 24 bits k.  Never 0 (the smallest is
+// 2^-25, so a normal is at most sqrt(50 ln 2) = 5.887); 1 for k = 2^24 - 1 alone (1 - 2^-25 is a tie that rounds up), where
+// box_muller gives ln = +0, a radius of -0 and normals of +-0
 __device__ __forceinline__ float uniform_open(uint32_t bits) {
   return static_cast<float>(bits >> 8) * 5.9604644775390625e-8f + 2.98023223876953125e-8f;
 }

@@ -762,9 +762,11 @@ def philox4x32_10(counter: np.ndarray, key: np.ndarray) -> np.ndarray:
 
 
 def sample_segments(n: int) -> np.ndarray:
-    """Per step: (left knot, weight of the left knot); the next knot gets 1 - weight (raised cosine)."""
+    """Per step: (left knot, weight of the left knot); the next knot gets 1 - weight (raised cosine).  The knots are
+    spread over steps 0 .. n - 1; a horizon of one step sits on knot 0 with weight 1 (csrc/acmpc_capi_solve.hip:
+    upload_segments)."""
     width = (n - 1) / (SAMPLE_KNOTS - 1)
-    pos = np.arange(n) / width
+    pos = np.arange(n) / width if n > 1 else np.zeros(n)
     k0 = np.minimum(np.floor(pos), SAMPLE_KNOTS - 2)
     w0 = 0.5 * (1.0 + np.cos(np.pi * (pos - k0)))
     return np.stack([k0, w0], axis=1).astype(np.float32)
@@ -841,6 +843,13 @@ def candidate_normals(n_candidates, index_offset, problem, round_, seed):
     return gidx, z
 
 
+def candidate_amplitude(gidx):
+    """The amplitude level of global candidate `gidx`: ((gidx & 7) + 1) / 8, and 0 for candidate 0 - the centre
+    (csrc/acmpc_device.h: candidate_amplitude).  float32, exact."""
+    gidx = np.asarray(gidx, dtype=np.uint32)
+    return np.where(gidx == 0, np.float32(0.0), ((gidx & 7) + 1).astype(np.float32) * np.float32(0.125))
+
+
 def sample_candidates(centre, u_ref, n_candidates, index_offset, problem, round_, seed, sigma, u_lo, u_hi, u_extra=None):
     """Restates csrc sample_kernel / the fused rounds' candidate generation for ONE problem, bit for bit (round 4: the
     device's normals are specified - box_muller_spec - and the blend is float32 with one fixed association, no FMA):
@@ -855,8 +864,7 @@ def sample_candidates(centre, u_ref, n_candidates, index_offset, problem, round_
     k0 = seg[:, 0].astype(int)
     w0 = seg[:, 1].astype(T)
     w1 = T(1.0) - w0
-    amp = ((gidx & 7) + 1).astype(T) * T(0.125)
-    amp[gidx == 0] = T(0.0)
+    amp = candidate_amplitude(gidx)
     base = np.broadcast_to(centre, (n_candidates, n, 2)).copy()
     if u_ref is not None:
         base[gidx == 1] = np.asarray(u_ref, dtype=T)
