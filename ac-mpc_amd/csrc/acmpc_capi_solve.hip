@@ -263,7 +263,7 @@ int rollout_sampled_dynamic(acmpc_ctx* c, const float* d_x0, const float* d_cent
 }
 
 // the softmin mean of the candidates sample() would write for these arguments, without the matrix
-// (acmpc_kernels.hip: launch_softmin_sampled) - what sample() into a matrix and launch_softmin of it compute
+// (acmpc_softmin.hip: launch_softmin_sampled) - what sample() into a matrix and launch_softmin of it compute
 int softmin_sampled(acmpc_ctx* c, const float* d_costs, const int64_t* d_keys, const float* d_centre, int centre_stride,
                     const float* d_uref, int P, int N, int n, int64_t offset, double sigma_v, double sigma_k, uint64_t seed,
                     uint32_t round, float* d_mean, double* d_weight_sum, hipStream_t s) {

@@ -1,4 +1,4 @@
-// Host-callable launchers of the gfx950 kernels (definitions in acmpc_kernels.hip).
+// Host-callable launchers of the gfx950 kernels (definitions in acmpc_kernels.hip, acmpc_rollout.hip, acmpc_kernels_temporal.hip, acmpc_solo.hip and acmpc_softmin.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -156,7 +156,7 @@ void acmpc_destroy(acmpc_ctx* ctx);
  * environment.  ACMPC_EINVAL for an unknown name. */
 int acmpc_set_option(acmpc_ctx* ctx, const char* name, const char* value);
 /* One of them is for deployment rather than for A/B runs: "ACMPC_CONFORMANT_SYNC" = "1".  The default forms of the latency
- * paths lean on what gfx950 does rather than on what HIP and the HSA memory model promise (csrc/acmpc_kernels.hip, top):
+ * paths lean on what gfx950 does rather than on what HIP and the HSA memory model promise (csrc/acmpc_kernels_impl.h, top):
  * values cross workgroups inside a launch as relaxed agent-scope atomics ordered by s_waitcnt vmcnt(0), waves of a
  * workgroup end while the others still meet at s_barrier, and acmpc_control_tick learns of completion from a flag the
  * last kernel writes into page-locked memory.  With the option on, every solve / round / batch is separate launches
@@ -481,7 +481,7 @@ int acmpc_rollout_sampled_device(acmpc_ctx* ctx, const float* d_x0, const float*
 /* acmpc_sample_device (step-major) into a matrix + acmpc_softmin_device of it WITHOUT the matrix: the softmin kernel re-draws
  * candidate index_offset + c from its global index (the same candidate as acmpc_sample_device's, bit for bit; global
  * candidate 0 = the centre, 1 = d_u_ref when given) and sums in the matrix kernel's order, so d_mean [P][n][2] and
- * d_weight_sum [P] (or NULL) are the same bits (csrc/acmpc_kernels.hip softmin_sampled_partial_kernel).  d_costs [P][N] and
+ * d_weight_sum [P] (or NULL) are the same bits (csrc/acmpc_softmin.hip softmin_sampled_partial_kernel).  d_costs [P][N] and
  * d_keys [P] come from the rollout of those candidates (acmpc_rollout_sampled_device in mode D; d_keys after
  * acmpc_reduce_across_ranks when the candidates are spread over ranks: the weights are relative to the GLOBAL minimum);
  * d_centre / centre_stride / d_u_ref / sigma / seed / round as acmpc_sample_device takes them.  The sampler is the same in

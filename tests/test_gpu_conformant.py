@@ -1,7 +1,7 @@
 """`acmpc_set_option(ctx, "ACMPC_CONFORMANT_SYNC", "1")` (control config key `conformant_sync`): ONE switch for the forms of
 the latency paths that stay inside the HSA memory model and HIP's barrier rule - every solve, round and batch as separate
 launches ordered by the stream, rounds on one wave per workgroup, completion by hipStreamSynchronize - instead of the
-gfx950-specific ones (csrc/acmpc_kernels.hip, top: values published between workgroups of one launch with relaxed
+gfx950-specific ones (csrc/acmpc_kernels_impl.h, top: values published between workgroups of one launch with relaxed
 agent-scope atomics + s_waitcnt vmcnt(0), waves that end while their workgroup still meets at s_barrier, the tick's
 completion flag).  The results are the same bits: one solve per call, the closed-loop tick in both rollout modes, a stream
 of batches (the headline's step), and the drop-in controller."""

@@ -1,9 +1,9 @@
 // Development probe: where one launch of rollout_solo_kernel spends its time.  A standalone build of the library's
-// kernel source with -DACMPC_STAMPS: lane 0 of every wave stamps the 100 MHz wall clock at the phase boundaries.
+// one-launch solve unit (csrc/acmpc_solo.hip) with -DACMPC_STAMPS: lane 0 of every wave stamps the 100 MHz wall clock at the phase boundaries.
 // Build & run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DACMPC_STAMPS tools/solo_probe.hip -o /tmp/solo_probe
 //   /tmp/solo_probe <N> <n> <layout> [split 0|1]
-#include "../ac-mpc_amd/csrc/acmpc_kernels.hip"
+#include "../ac-mpc_amd/csrc/acmpc_solo.hip"
 
 #include <algorithm>
 #include <random>

@@ -7,7 +7,9 @@ of any other pack (TermsObjective) keeps its name and is counted among the new f
 kernels are identical; exit status 1 unless every kernel of OLD is in NEW and identical.
 
 usage: hipcc <the library's flags> -c csrc/acmpc_dynamic.hip -o unit.o --save-temps     (at both commits, in two directories)
-       python3 tools/asm_same.py OLD/acmpc_dynamic-hip-amdgcn-amd-amdhsa-gfx950.s NEW/acmpc_dynamic-hip-amdgcn-amd-amdhsa-gfx950.s"""
+       python3 tools/asm_same.py OLD/acmpc_dynamic-hip-amdgcn-amd-amdhsa-gfx950.s NEW/acmpc_dynamic-hip-amdgcn-amd-amdhsa-gfx950.s
+       python3 tools/asm_same.py OLD/unit.s NEW/part_a.s NEW/part_b.s ...     (a unit split into several, ONE flag set: the same
+                                                                               mangled name under other flags is another kernel)"""
 import difflib
 import re
 import sys
@@ -30,8 +32,13 @@ def kernels(path):
 
 
 def main():
-    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    old, new = kernels(sys.argv[1]), {}
     same = 0
+    for path in sys.argv[2:]:   # one unit split into several: the kernels of all NEW files together
+        for name, body in kernels(path).items():
+            if new.setdefault(name, body) != body:
+                print("TWICE, and not the same, among the new files:", name)
+                same -= 1
     for name, body in old.items():
         if name not in new:
             print("MISSING", name)
@@ -41,7 +48,7 @@ def main():
             delta = [l for l in difflib.unified_diff(body, new[name], lineterm="", n=0) if not l.startswith(("---", "+++", "@@"))]
             print("DIFFERENT %s: %d lines against %d, %d differ" % (name, len(body), len(new[name]), len(delta)))
             print("\n".join("    " + l for l in delta[:12]))
-    print("%d of %d kernels identical (%d in the new file)" % (same, len(old), len(new)))
+    print("%d of %d kernels identical (%d in the new file%s)" % (same, len(old), len(new), "s" if len(sys.argv) > 3 else ""))
     return 0 if same == len(old) else 1
 
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Development aid (GPU box): A/B builds of the mode T rollout (flags of csrc/acmpc_kernels.hip) timed in turn on one box.
+# Development aid (GPU box): A/B builds of the mode T rollout (flags of csrc/acmpc_rollout.h, through the units that instantiate it) timed in turn on one box.
 # usage: tools/modeT_ab.sh <P> name1="<flags>" name2="<flags>" ...     (name "tree" = the tree's library)
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
