@@ -159,6 +159,7 @@ SIGNATURES = {
     "acmpc_set_previous_control": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
     "acmpc_set_dynamics_objective": (C.c_int, [_CTX, C.c_double, C.c_void_p]),
     "acmpc_set_dynamics_coupling": (C.c_int, [_CTX, C.c_void_p]),
+    "acmpc_set_dynamics_load_transfer": (C.c_int, [_CTX, C.c_void_p]),
     "acmpc_get_progress_table": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_score_grips": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
@@ -543,6 +544,25 @@ def dynamics_coupling(value=None):
     return np.array(ratio, dtype=np.float64)
 
 
+def dynamics_load_transfer(value=None, w_frac=0.9):
+    """Mode D's load transfer checked as acmpc_set_dynamics_load_transfer checks it: None (off), or the float64 pair (h_cg,
+    w_frac) of a pair or of a height (with `w_frac`).  ValueError for a height that is negative or not finite, or a w_frac
+    outside (0, 1)."""
+    if value is None:
+        return None
+    try:
+        pair = (float(value), float(w_frac)) if np.ndim(value) == 0 else tuple(float(v) for v in value)
+    except (TypeError, ValueError):
+        raise ValueError("the load transfer is None, a CG height or a (h_cg, w_frac) pair, not %r" % (value,)) from None
+    if len(pair) != 2:
+        raise ValueError("the load transfer is a CG height or a (h_cg, w_frac) pair, not %r" % (value,))
+    if not (np.isfinite(pair[0]) and pair[0] >= 0.0):
+        raise ValueError("the CG height h_cg is finite and >= 0, not %r" % (pair[0],))
+    if not 0.0 < pair[1] < 1.0:
+        raise ValueError("w_frac lies inside (0, 1), not %r" % (pair[1],))
+    return np.array(pair, dtype=np.float64)
+
+
 class Engine:
     """Owns one acmpc_ctx.  Construction does no device work (fork-safe, controller.py:293-297)."""
 
@@ -673,6 +693,15 @@ class Engine:
         setting."""
         pair = dynamics_coupling(ratio)
         self._check(self._lib.acmpc_set_dynamics_coupling(self._ctx, None if pair is None else pair.ctypes.data))
+
+    def set_dynamics_load_transfer(self, h_cg=None, w_frac=0.9):
+        """Mode D's longitudinal load transfer (acmpc_set_dynamics_load_transfer): `h_cg` = the height of the centre of
+        gravity (or a (h_cg, w_frac) pair) - each axle's load, and with it its Pacejka peak and its coupling cap, follows the
+        longitudinal tyre force in every Euler sub-step; at most `w_frac` of the lighter axle's static load moves.  None
+        switches it off.  While it is on every vehicle needs positive peaks and peak factors that stay positive over the
+        load that may move.  The setting outlives a change of vehicle or of any other setting."""
+        pair = dynamics_load_transfer(h_cg, w_frac)
+        self._check(self._lib.acmpc_set_dynamics_load_transfer(self._ctx, None if pair is None else pair.ctypes.data))
 
     def progress_table(self, problem: int = 0) -> np.ndarray:
         """Mode D's progress table q [n] of a problem (acmpc_get_progress_table), host only."""

@@ -114,30 +114,55 @@ class DynamicBicycleParams:
     def peak_rear(self) -> float:
         return self.Dr * (1 + self.epsr * self.F_zr / self.F_z0) * self.F_zr / self.F_z0
 
-    def predict_next_state(self, state, u, dt: float = 0.05, coupling=None) -> Tuple[np.ndarray, np.ndarray, list]:
+    def peak(self, axle: str, F_z: float) -> float:
+        """The peak factor D (1 + eps F_z / F_z0) F_z / F_z0 of the axle 'f' or 'r' under the load F_z."""
+        D, eps = (self.Df, self.epsf) if axle == "f" else (self.Dr, self.epsr)
+        return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0
+
+    def loaded_axles(self, F_fx: float, F_rx: float, coupling, load_transfer) -> Tuple[float, float, float]:
+        """(w, F_zf', F_zr') of the load transfer `load_transfer` = h_cg or (h_cg, w_frac = 0.9) for the longitudinal demands
+        F_fx, F_rx (acmpc_set_dynamics_load_transfer, one explicit pass): the demands clipped at the STATIC caps of
+        `coupling`, w = h_cg / (lf + lr) times their sum clipped at +-w_frac min(F_zf, F_zr) - the load moved to the rear,
+        negative under braking - and the loads F_zf - w, F_zr + w."""
+        h_cg, w_frac = (float(load_transfer), 0.9) if np.ndim(load_transfer) == 0 else (float(v) for v in load_transfer)
+        rho_f, rho_r = _ratios(coupling)
+        cap_f, cap_r = rho_f * self.peak_front, rho_r * self.peak_rear
+        e_f = max(min(F_fx, cap_f), -cap_f)
+        e_r = max(min(F_rx, cap_r), -cap_r)
+        w_max = w_frac * min(self.F_zf, self.F_zr)
+        w = max(min(h_cg / (self.lf + self.lr) * (e_f + e_r), w_max), -w_max)
+        return w, self.F_zf - w, self.F_zr + w
+
+    def predict_next_state(self, state, u, dt: float = 0.05, coupling=None, load_transfer=None) -> Tuple[np.ndarray, np.ndarray, list]:
         """One explicit Euler step in float64: state (X, Y, yaw, vx, vy, r), u = (delta, pedal) with the pedal in
         [-1, 1].  Returns (next_state, x_dot, [F_fy, F_ry, F_fx, F_rx]) like the reference; the caller clips vx >= 0
         (the reference's loop does, dynamic_bicycle_model.py:180; so do the kernels, inside the step).  `coupling` = rho
         or (rho_f, rho_r) is the tyre coupling of acmpc_set_dynamics_coupling in float64 (None: off; inf: none on that
         axle): per axle F_x is clipped at +-rho P and F_y scaled by sqrt(1 - (F_x / (rho P))^2); the returned forces are
-        the coupled ones."""
+        the coupled ones.  `load_transfer` = h_cg or (h_cg, w_frac) is the load transfer of
+        acmpc_set_dynamics_load_transfer in float64 (None: off), the same one-pass formulation with the exact
+        load-dependent peak: loaded_axles() gives each axle's load, which both the side force and the coupling's cap then
+        take; the returned forces are the final ones."""
         delta, pedal = float(u[0]), float(u[1])
         X, Y, yaw, vx, vy, r = (float(s) for s in state)
         den = vx + 1e-3
         alpha_f = delta - np.arctan((r * self.lf + vy) / den)
         alpha_r = np.arctan((r * self.lr - vy) / den)
-        F_fy = self._lateral(alpha_f, self.Bf, self.Cf, self.Df, self.Ef, self.epsf, self.F_zf)
-        F_ry = self._lateral(alpha_r, self.Br, self.Cr, self.Dr, self.Er, self.epsr, self.F_zr)
         brake = self.Cb1 - self.Cb2 * vx - self.Cb3 * vx ** 2
         motor = self.Cm1 - self.Cm2 * vx - self.Cm3 * vx ** 2
         F_fric = -self.Cfric1 - self.Cfric2 * vx - self.Cfric3 * vx ** 2
         braking = min(0.0, pedal)
         F_rx = brake * (1 - self.brake_bias) * braking + motor * max(0.0, pedal)
         F_fx = brake * self.brake_bias * braking
+        F_zf, F_zr = self.F_zf, self.F_zr
+        if load_transfer is not None:
+            _, F_zf, F_zr = self.loaded_axles(F_fx, F_rx, coupling, load_transfer)
+        F_fy = self._lateral(alpha_f, self.Bf, self.Cf, self.Df, self.Ef, self.epsf, F_zf)
+        F_ry = self._lateral(alpha_r, self.Br, self.Cr, self.Dr, self.Er, self.epsr, F_zr)
         if coupling is not None:
-            rho_f, rho_r = (float(coupling),) * 2 if np.ndim(coupling) == 0 else (float(v) for v in coupling)
-            F_fx, F_fy = _couple(F_fx, F_fy, rho_f * self.peak_front)
-            F_rx, F_ry = _couple(F_rx, F_ry, rho_r * self.peak_rear)
+            rho_f, rho_r = _ratios(coupling)
+            F_fx, F_fy = _couple(F_fx, F_fy, rho_f * self.peak("f", F_zf))
+            F_rx, F_ry = _couple(F_rx, F_ry, rho_r * self.peak("r", F_zr))
         sd, cd = np.sin(delta), np.cos(delta)
         x_dot = np.array([
             vx * np.cos(yaw) - vy * np.sin(yaw),
@@ -154,12 +179,13 @@ class DynamicBicycleParams:
         ba = B * alpha
         return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0 * np.sin(C * np.arctan(ba - E * (ba - np.arctan(ba))))
 
-    def rollout(self, state, U, dt: float = 0.05, substeps: int = 1, low_speed_blend=None, coupling=None) -> np.ndarray:
+    def rollout(self, state, U, dt: float = 0.05, substeps: int = 1, low_speed_blend=None, coupling=None,
+                load_transfer=None) -> np.ndarray:
         """The mirror over a control sequence U [n, 2] with vx clipped after every step: states [n + 1, 6].  `substeps`
         and `low_speed_blend` = (v_lo, v_hi) are the integration setting of acmpc_set_dynamics_integration in float64: a
         control step is `substeps` Euler steps of dt / substeps, and after each (vy, r) are blended towards the kinematic
         bicycle's r_k = vx tan(delta) / (lf + lr), vy_k = lr r_k by lam = clamp((vx - v_lo) / (v_hi - v_lo), 0, 1).
-        `coupling`: predict_next_state's, in every sub-step."""
+        `coupling`, `load_transfer`: predict_next_state's, in every sub-step."""
         substeps = int(substeps)
         if substeps < 1:
             raise ValueError("substeps must be positive")
@@ -168,7 +194,7 @@ class DynamicBicycleParams:
         for u in np.asarray(U, dtype=np.float64):
             nxt = out[-1]
             for _ in range(substeps):
-                nxt = self.predict_next_state(nxt, u, h, coupling=coupling)[0]
+                nxt = self.predict_next_state(nxt, u, h, coupling=coupling, load_transfer=load_transfer)[0]
                 nxt[3] = max(nxt[3], 0.0)
                 if low_speed_blend is not None:
                     v_lo, v_hi = (float(v) for v in low_speed_blend)
@@ -178,6 +204,14 @@ class DynamicBicycleParams:
                     nxt[5] = lam * nxt[5] + (1.0 - lam) * r_k
             out.append(nxt)
         return np.stack(out)
+
+
+def _ratios(coupling) -> Tuple[float, float]:
+    """(rho_f, rho_r) of a coupling setting: None is +inf on both axles, a scalar both axles'."""
+    if coupling is None:
+        return float("inf"), float("inf")
+    rho_f, rho_r = (float(coupling),) * 2 if np.ndim(coupling) == 0 else (float(v) for v in coupling)
+    return rho_f, rho_r
 
 
 def _couple(F_x: float, F_y: float, cap: float) -> Tuple[float, float]:

@@ -38,6 +38,11 @@ axle's drive and brake force at rho times that axle's lateral peak and scales it
 leaves.  Without it the brake map asks the tyres for more than they have and grip scales do not reach braking; with it
 `grip_ensemble` members and `grip_adapt` hypotheses brake and accelerate as their grip allows.  rho near 1.
 
+Load transfer (acmpc_set_dynamics_load_transfer): `load_transfer` - the height of the centre of gravity, or (h_cg, w_frac),
+default None - lets each axle's load, and with it its Pacejka peak and its coupling cap, follow the longitudinal tyre force:
+under braking the front axle gains grip and the rear loses it.  Beside `tyre_coupling` it moves the braking limit (about 10 %
+more deceleration on the reference vehicle at h_cg = 0.35) and takes rear side force from a plan that turns in on the brakes.
+
 Grip adaptation (acmpc_score_grips, GripEstimator): `grip_adapt` - a dict, off by default - lets the solver find the road's
 grip from its own driving instead of being told an ensemble.  Every solve logs (state, the control applied since the
 previous solve - `previous_control`, else the last accepted plan's first control), scores a grid of grip hypotheses
@@ -134,6 +139,7 @@ class DynamicSamplingSolver:
                                      config.get("slip_cost", 0.0), config.get("slip_limit"))
         objective = _capi.dynamics_objective(config.get("progress_cost", 0.0), config.get("speed_ceiling"))
         coupling = _capi.dynamics_coupling(config.get("tyre_coupling"))
+        load_transfer = _capi.dynamics_load_transfer(config.get("load_transfer"))
         self._centre_update = config.get("sampling_update", "argmin")   # or "softmin" (MPPI-style weighted mean)
         if self._centre_update not in SAMPLING_UPDATES:
             raise ValueError("sampling_update is 'argmin' or 'softmin', not %r" % (self._centre_update,))
@@ -163,6 +169,8 @@ class DynamicSamplingSolver:
             self._engine.set_dynamics_objective(*objective)
         if coupling is not None:
             self._engine.set_dynamics_coupling(coupling)
+        if load_transfer is not None:
+            self._engine.set_dynamics_load_transfer(load_transfer)
         self._plan: Optional[np.ndarray] = None
         self._calls = 0
         self._adapt = adapt

@@ -1,5 +1,5 @@
 // C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
-// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the previous control, and the grip
+// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the previous control, and the grip
 // identification (acmpc_score_grips), with the checks that the kernels' limits are the public header's.
 #include <algorithm>
 
@@ -74,6 +74,55 @@ bool peaks_couple(const acmpc::VehicleEnsemble& e) {
 }
 constexpr const char* kPeaksRefused = "the tyre coupling is on: every vehicle's axle peaks Pf, Pr must be finite and > 0 (as float32)";
 
+
+// What the load transfer reads of a vehicle block in float64: the static axle loads and e_a = eps_a / F_z0
+void derive_axles(const double* coef, double* axle) {
+  const double F_z0 = coef[0], epsf = coef[5], epsr = coef[10], mass = coef[11], g = coef[13], lf = coef[14], lr = coef[15];
+  axle[0] = mass * g * lr / (lr + lf);
+  axle[1] = mass * g * lf / (lr + lf);
+  axle[2] = epsf / F_z0;
+  axle[3] = epsr / F_z0;
+}
+
+// The six float32 scalars of one vehicle under the setting (h_cg, w_frac), derived in float64 and rounded once each (include/
+// acmpc.h, acmpc_set_dynamics_load_transfer): nullptr, or why the vehicle is refused - N_a = 0, or a factor phi_a that is not
+// > 0 (in float64) at x = +-w_max or at its vertex inside
+const char* derive_load(const double* setting, double L, const double* axle, float* out) {
+  const double c_h = setting[0] / L;
+  const double w_max = setting[1] * std::min(axle[0], axle[1]);
+  if (!std::isfinite(c_h) || !std::isfinite(w_max)) return "the load transfer's c_h or w_max is not finite";
+  out[0] = static_cast<float>(c_h);
+  out[1] = static_cast<float>(w_max);
+  for (int a = 0; a < 2; ++a) {
+    const double F = axle[a], e = axle[2 + a];
+    const double N = F + e * F * F;
+    if (N == 0.0 || !std::isfinite(N)) return "the load transfer divides by N = F_z + e F_z^2, which is 0 or not finite";
+    const double a1 = (1 + 2 * e * F) / N, a2 = e / N;
+    double probe[3] = {-w_max, w_max, 0.0};
+    int probes = 2;
+    if (a2 > 0.0) {
+      const double vertex = -a1 / (2 * a2);
+      if (vertex > -w_max && vertex < w_max) probe[probes++] = vertex;
+    }
+    for (int q = 0; q < probes; ++q)
+      if (!(1 + probe[q] * (a1 + a2 * probe[q]) > 0.0)) return "the load transfer's peak factor phi is not > 0 over +-w_max";
+    out[2 + 2 * a] = static_cast<float>(a1);
+    out[3 + 2 * a] = static_cast<float>(a2);
+  }
+  return nullptr;
+}
+
+// every vehicle of an ensemble under a setting: the scalars into out[k], or why one is refused
+const char* derive_loads(const double* setting, const acmpc::VehicleEnsemble& e, const double* L, const double (*axle)[4],
+                         float (*out)[6]) {
+  if (!peaks_couple(e)) return "the load transfer is on: every vehicle's axle peaks Pf, Pr must be finite and > 0 (as float32)";
+  for (int k = 0; k < e.K; ++k) {
+    const char* why = derive_load(setting, L[k], axle[k], out[k]);
+    if (why != nullptr) return why;
+  }
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -91,7 +140,17 @@ int acmpc_set_dynamics(acmpc_ctx* c, const double* coef, int32_t count) {
   e.K = 1;
   e.reduce = ACMPC_ENSEMBLE_MEAN;
   if (c->has_coupling && !peaks_couple(e)) return fail(c, ACMPC_EINVAL, kPeaksRefused);
+  const double L[1] = {coef[14] + coef[15]};
+  double axle[1][4];
+  float load[1][6] = {};
+  derive_axles(coef, axle[0]);
+  if (c->has_load) {
+    const char* refused = derive_loads(c->load_setting, e, L, axle, load);
+    if (refused != nullptr) return fail(c, ACMPC_EINVAL, refused);
+  }
   c->vehicles = e;
+  std::memcpy(c->vehicle_axle[0], axle[0], sizeof axle[0]);
+  std::memcpy(c->load_const[0], load[0], sizeof load[0]);
   c->vehicle_L[0] = coef[14] + coef[15];
   std::memcpy(c->vehicle0, coef, sizeof c->vehicle0);
   c->has_dynamics = true;
@@ -123,7 +182,20 @@ int acmpc_set_dynamics_ensemble(acmpc_ctx* c, const double* coef, int32_t K, con
   e.K = K;
   e.reduce = reduce;
   if (c->has_coupling && !peaks_couple(e)) return fail(c, ACMPC_EINVAL, kPeaksRefused);
+  double L[acmpc::kMaxVehicles], axle[acmpc::kMaxVehicles][4];
+  float load[acmpc::kMaxVehicles][6] = {};
+  for (int k = 0; k < K; ++k) {
+    const double* ck = coef + static_cast<size_t>(k) * acmpc::kDynamicsCount;
+    L[k] = ck[14] + ck[15];
+    derive_axles(ck, axle[k]);
+  }
+  if (c->has_load) {
+    const char* refused = derive_loads(c->load_setting, e, L, axle, load);
+    if (refused != nullptr) return fail(c, ACMPC_EINVAL, refused);
+  }
   c->vehicles = e;
+  std::memcpy(c->vehicle_axle, axle, sizeof(double) * 4 * K);
+  std::memcpy(c->load_const, load, sizeof(float) * 6 * K);
   for (int k = 0; k < K; ++k)
     c->vehicle_L[k] = coef[static_cast<size_t>(k) * acmpc::kDynamicsCount + 14] + coef[static_cast<size_t>(k) * acmpc::kDynamicsCount + 15];
   std::memcpy(c->vehicle0, coef, sizeof c->vehicle0);
@@ -204,6 +276,30 @@ int acmpc_set_dynamics_coupling(acmpc_ctx* c, const double ratio[2]) {
   c->has_coupling = true;
   c->coupling[0] = rho[0];
   c->coupling[1] = rho[1];
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_load_transfer(acmpc_ctx* c, const double setting[2]) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_dynamics_load_transfer needs a mode D handle");
+  if (setting == nullptr) {
+    c->has_load = false;
+    c->load_setting[0] = c->load_setting[1] = 0.0;
+    return ACMPC_OK;
+  }
+  if (!std::isfinite(setting[0]) || !(setting[0] >= 0.0)) return fail(c, ACMPC_EINVAL, "h_cg must be finite and >= 0");
+  if (!(setting[1] > 0.0 && setting[1] < 1.0)) return fail(c, ACMPC_EINVAL, "w_frac must lie inside (0, 1)");
+  const double kept[2] = {setting[0] + 0.0, setting[1]};   // (-0.0 is 0)
+  float load[acmpc::kMaxVehicles][6] = {};
+  if (c->has_dynamics) {
+    const char* refused = derive_loads(kept, c->vehicles, c->vehicle_L, c->vehicle_axle, load);
+    if (refused != nullptr) return fail(c, ACMPC_EINVAL, refused);
+  }
+  // everything is checked before anything is kept: a refused setting leaves the handle's as it was
+  c->has_load = true;
+  c->load_setting[0] = kept[0];
+  c->load_setting[1] = kept[1];
+  std::memcpy(c->load_const, load, sizeof load);
   return ACMPC_OK;
 }
 
@@ -298,7 +394,11 @@ int acmpc_score_grips(acmpc_ctx* c, const float* states, const float* controls, 
   acmpc::Integration g = dynamics_integration(c);
   g.h = static_cast<float>(dt / c->substeps);
   // and its tyre coupling, each hypothesis capped by its own peaks
-  ACMPC_HIP(c, acmpc::launch_identify_grip(a, c->vehicles.v[0], g, c->has_coupling ? c->coupling : nullptr, s));
+  // and its load transfer: the base vehicle's factors on each hypothesis' own peaks
+  const float* lc = c->load_const[0];
+  const acmpc::IdentifyLoad load{lc[0], lc[1], lc[2], lc[3], lc[4], lc[5]};
+  ACMPC_HIP(c, acmpc::launch_identify_grip(a, c->vehicles.v[0], g, c->has_coupling ? c->coupling : nullptr,
+                                           c->has_load ? &load : nullptr, s));
   // one copy down: best key | errors
   ACMPC_HIP(c, hipMemcpyAsync(c->h_identify.data(), c->d_identify + kBestAt, down_bytes, hipMemcpyDeviceToHost, s));
   ACMPC_HIP(c, hipStreamSynchronize(s));

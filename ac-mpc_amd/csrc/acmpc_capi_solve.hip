@@ -15,8 +15,9 @@ namespace capi __attribute__((visibility("hidden"))) {
 // ("Rate and slip terms").  A part whose weights are 0 and whose limits are +inf is off.  And of its
 // objective ("Progress and ceiling"): the progress part is on with a weight that is not 0, the ceiling part when one is set.
 // And of its tyre coupling ("Tyre coupling"): the two ratios.
-static acmpc::TermsCoupled dynamics_terms(const acmpc_ctx* c) {
-  acmpc::TermsCoupled t{};
+// And of its load transfer ("Load transfer"): the six scalars of each vehicle, and the ratios +inf while the coupling is off.
+static acmpc::TermsLoaded dynamics_terms(const acmpc_ctx* c) {
+  acmpc::TermsLoaded t{};
   t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
             std::isfinite(c->rate_max[1])) ? 1 : 0;
   t.slip = (c->slip_weight != 0.0 || std::isfinite(c->slip_max)) ? 1 : 0;
@@ -37,6 +38,16 @@ static acmpc::TermsCoupled dynamics_terms(const acmpc_ctx* c) {
   t.coupled = c->has_coupling ? 1 : 0;
   t.rho_f = c->coupling[0];
   t.rho_r = c->coupling[1];
+  t.loaded = c->has_load ? 1 : 0;
+  for (int k = 0; k < c->vehicles.K && t.loaded != 0; ++k) {
+    const float* lc = c->load_const[k];
+    t.c_h[k] = lc[0];
+    t.w_max[k] = lc[1];
+    t.a1_f[k] = lc[2];
+    t.a2_f[k] = lc[3];
+    t.a1_r[k] = lc[4];
+    t.a2_r[k] = lc[5];
+  }
   return t;
 }
 

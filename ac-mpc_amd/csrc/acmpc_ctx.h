@@ -286,6 +286,14 @@ struct acmpc_ctx {
   // kernels get (+inf: no coupling on that axle).  While it is on every vehicle of the handle has finite, positive peaks.
   bool has_coupling = false;
   float coupling[2] = {HUGE_VALF, HUGE_VALF};
+  // mode D: the load transfer (acmpc_set_dynamics_load_transfer), kept apart like the others: the setting (h_cg, w_frac), what
+  // each vehicle block gives it in float64 - (F_zf, F_zr, e_f, e_r) - and the six float32 scalars the kernels get per vehicle
+  // (c_h, w_max, a1_f, a2_f, a1_r, a2_r), derived whenever the setting or the vehicles change.  While it is on every vehicle
+  // of the handle has finite, positive peaks and factors phi > 0 over +-w_max.
+  bool has_load = false;
+  double load_setting[2] = {0.0, 0.0};
+  double vehicle_axle[acmpc::kMaxVehicles][4] = {};
+  float load_const[acmpc::kMaxVehicles][6] = {};
 
   mutable std::string err;
 };

@@ -127,6 +127,14 @@ __device__ __forceinline__ F pacejka(F alpha, float B, float C, float E, float P
   return P * sin_spec<F>(C * atan_spec<F>(y));
 }
 
+// The same with a peak of the lane's own (the load transfer: the loaded peak P' in front of the unchanged shape)
+template <typename F>
+__device__ __forceinline__ F pacejka_loaded(F alpha, float B, float C, float E, F P) {
+  const F ba = B * alpha;
+  const F y = ba - E * (ba - atan_spec<F>(ba));
+  return P * sin_spec<F>(C * atan_spec<F>(y));
+}
+
 // Where a step takes the two axles' peak factors from: the Vehicle's own (every rollout: scalars of the kernel argument,
 // read where the step has always read them) or a lane's pair (the grip identification, acmpc_identify.hip: one hypothetical
 // vehicle per lane, everything but its two peaks the base Vehicle's).
@@ -171,6 +179,49 @@ __device__ __forceinline__ void couple_axle(F& F_x, F& F_y, float rho, float P) 
   F_y = F_y * g;
 }
 
+// The longitudinal load transfer of a handle (acmpc_set_dynamics_load_transfer, DESIGN.md section 2 "Mode D, load transfer"):
+// each axle's load, and with it its peak factor and its coupling cap, follows the longitudinal tyre force inside every Euler
+// sub-step.  A CoupledPeaks with the six scalars of the vehicle rolled beside it, each derived by the host in float64 and
+// rounded once: c_h = h_cg / (lf + lr), w_max = w_frac min(F_zf, F_zr), and per axle (a1, a2) with
+// P(F_z + x) / P(F_z) = 1 + x (a1 + a2 x).  rho = +inf on both axles while the coupling is off.  Not an IsCoupled: the step
+// has a block of its own for it.
+template <typename PK>
+struct LoadedPeaks : CoupledPeaks<PK> {
+  float c_h, w_max, a1_f, a2_f, a1_r, a2_r;
+};
+template <typename PK>
+struct IsLoaded : std::false_type {};
+template <typename PK>
+struct IsLoaded<LoadedPeaks<PK>> : std::true_type {};
+
+// couple_axle with the lane's loaded peak: cap = rho P' per lane, the rest as it is
+template <typename F>
+__device__ __forceinline__ void couple_axle_loaded(F& F_x, F& F_y, float rho, F P) {
+  const F cap = rho * P;
+  F_x = vmax(__builtin_elementwise_min(F_x, cap), -cap);
+  const F u = F_x / cap;
+  const F g = sqrt_(splat<F>(1.0f) - u * u);
+  F_y = F_y * g;
+}
+
+// The two loaded peaks of a sub-step, in spec order: the demands clipped at the STATIC caps, w = c_h (e_f + e_r) clipped at
+// +-w_max (the load moved to the rear; negative: braking), x_f = -w, x_r = w, phi = 1 + x (a1 + a2 x) - multiply, add,
+// multiply, add - and P' = P phi.  min / max are minNum / maxNum.  h_cg = 0 or pedal 0 give w = +-0, phi = 1, P' = P.
+template <typename F, typename PK>
+__device__ __forceinline__ void loaded_peaks_of(F F_fx, F F_rx, const Vehicle& k, const LoadedPeaks<PK>& pk, F& Pf, F& Pr) {
+  const float cap_f = pk.rho_f * pk.front(k);
+  const float cap_r = pk.rho_r * pk.rear(k);
+  const F e_f = vmax(__builtin_elementwise_min(F_fx, splat<F>(cap_f)), splat<F>(-cap_f));
+  const F e_r = vmax(__builtin_elementwise_min(F_rx, splat<F>(cap_r)), splat<F>(-cap_r));
+  F w = pk.c_h * (e_f + e_r);
+  w = vmax(__builtin_elementwise_min(w, splat<F>(pk.w_max)), splat<F>(-pk.w_max));
+  const F x_f = -w, x_r = w;
+  const F phi_f = splat<F>(1.0f) + x_f * (pk.a1_f + pk.a2_f * x_f);
+  const F phi_r = splat<F>(1.0f) + x_r * (pk.a1_r + pk.a2_r * x_r);
+  Pf = pk.front(k) * phi_f;
+  Pr = pk.rear(k) * phi_r;
+}
+
 // What a step takes from its control alone: sincos_spec(delta) and the pedal's split.  The same for every sub-step of a
 // control step (dynamic_advance_fine computes it once).
 template <typename F>
@@ -190,7 +241,8 @@ __device__ __forceinline__ ControlTerms<F> control_terms(F delta, F pedal) {
 // vx = max(vx, 0) (the reference's loop, :180; maxNum: a NaN vx becomes 0).  HOISTED: the control's terms come in
 // through `pre` (the sub-steps of dynamic_advance_fine); otherwise they are computed here, where the single step has
 // always computed them - the default setting's kernels are to stay the code they were, instruction for instruction.
-// PK: the source of the peak factors (VehiclePeaks or LanePeaks), or a CoupledPeaks of one: the tyre coupling.
+// PK: the source of the peak factors (VehiclePeaks or LanePeaks), or a CoupledPeaks of one: the tyre coupling; or a LoadedPeaks
+// of one: the coupling with the load transfer in front of it (the side forces then wait for the loaded peaks).
 template <bool HOISTED, typename F, typename PK = VehiclePeaks>
 __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, const ControlTerms<F>* pre, const Vehicle& k,
                                               float dt, const PK pk = PK{}) {
@@ -200,8 +252,11 @@ __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, c
   const F qr = (r * k.lr - vy) / den;
   const F a_f = delta - atan_spec<F>(qf);   // the reference's -atan(q) + delta: the same float
   const F a_r = atan_spec<F>(qr);
-  F F_fy = pacejka<F>(a_f, k.Bf, k.Cf, k.Ef, pk.front(k));
-  F F_ry = pacejka<F>(a_r, k.Br, k.Cr, k.Er, pk.rear(k));
+  F F_fy, F_ry;
+  if constexpr (!IsLoaded<PK>::value) {
+    F_fy = pacejka<F>(a_f, k.Bf, k.Cf, k.Ef, pk.front(k));
+    F_ry = pacejka<F>(a_r, k.Br, k.Cr, k.Er, pk.rear(k));
+  }
   const F vx2 = vx * vx;
   const F F_fric = (k.fric0 - k.Cfric2 * vx) - k.Cfric3 * vx2;
   const F brake = (k.Cb1 - k.Cb2 * vx) - k.Cb3 * vx2;
@@ -219,6 +274,14 @@ __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, c
   if constexpr (IsCoupled<PK>::value) {
     couple_axle<F>(F_fx, F_fy, pk.rho_f, pk.front(k));
     couple_axle<F>(F_rx, F_ry, pk.rho_r, pk.rear(k));
+  }
+  if constexpr (IsLoaded<PK>::value) {
+    F Pf, Pr;
+    loaded_peaks_of<F>(F_fx, F_rx, k, pk, Pf, Pr);
+    F_fy = pacejka_loaded<F>(a_f, k.Bf, k.Cf, k.Ef, Pf);
+    F_ry = pacejka_loaded<F>(a_r, k.Br, k.Cr, k.Er, Pr);
+    couple_axle_loaded<F>(F_fx, F_fy, pk.rho_f, Pf);
+    couple_axle_loaded<F>(F_rx, F_ry, pk.rho_r, Pr);
   }
   F sd, cd, sy, cy;
   if constexpr (HOISTED) {
@@ -337,6 +400,18 @@ struct TermsCoupled : TermsObjective {
 };
 __host__ __device__ inline bool has_coupling(const TermsCoupled& t) { return t.coupled != 0; }
 
+// The TermsCoupled plus the load transfer of a handle (acmpc_set_dynamics_load_transfer, DESIGN.md section 2 "Mode D, load
+// transfer"): a fourth pack type.  The six scalars of LoadedPeaks per vehicle, indexed by the wave-uniform vehicle index as
+// Integration::inv_L is.  The kernels instantiated for it (acmpc_dynamic_loaded.hip) run only while `loaded` is set, with
+// rho = +inf on both axles while the coupling is off; every other kernel stays the code it was.  The launchers take the
+// handle's settings as one of these.
+struct TermsLoaded : TermsCoupled {
+  float c_h[kMaxVehicles], w_max[kMaxVehicles];
+  float a1_f[kMaxVehicles], a2_f[kMaxVehicles], a1_r[kMaxVehicles], a2_r[kMaxVehicles];
+  int loaded;                   // 0: off (the arrays not read); the kernels do not read it
+};
+__host__ __device__ inline bool has_load_transfer(const TermsLoaded& t) { return t.loaded != 0; }
+
 // what the terms carry from step to step: the previous step's control and the cost sum
 template <typename F>
 struct TermsState {
@@ -369,6 +444,18 @@ __device__ __forceinline__ CoupledPeaks<VehiclePeaks> coupled_peaks(const TermsC
 template <typename F>
 __device__ __forceinline__ CoupledPeaks<VehiclePeaks> coupled_peaks(const TermsState<F>&, const TermsCoupled& t) {
   return coupled_peaks(t);
+}
+
+// The same for a TermsLoaded: dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(..., loaded_peaks(vk, tm...)), vk the
+// wave-uniform index of the vehicle rolled
+template <typename... TM>
+constexpr bool kLoadedPack = (std::is_same<typename std::remove_cv<TM>::type, TermsLoaded>::value || ...);
+__device__ __forceinline__ LoadedPeaks<VehiclePeaks> loaded_peaks(int vk, const TermsLoaded& t) {
+  return LoadedPeaks<VehiclePeaks>{{{}, t.rho_f, t.rho_r}, t.c_h[vk], t.w_max[vk], t.a1_f[vk], t.a2_f[vk], t.a1_r[vk], t.a2_r[vk]};
+}
+template <typename F>
+__device__ __forceinline__ LoadedPeaks<VehiclePeaks> loaded_peaks(int vk, const TermsState<F>&, const TermsLoaded& t) {
+  return loaded_peaks(vk, t);
 }
 
 // one float of the staged waypoint row(s) j, or of a table of one float per waypoint (stride 1)
@@ -488,22 +575,23 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // of it.
 // `terms`: the handle's rate and slip terms and its objective; when any part is on, the kernels that hold them run, with the general step whatever the
 // integration setting (the default one as M = 1, no blend, h = float32(dt)).  And its tyre coupling: while that is on, the
-// coupled kernels run, whatever the parts.
+// coupled kernels run, whatever the parts.  And its load transfer: while that is on, the loaded kernels run, whatever the
+// coupling and the parts.
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& integration, const TermsCoupled& terms, hipStream_t s);
+                                  const Integration& integration, const TermsLoaded& terms, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const TermsCoupled& terms, hipStream_t s);
+                                          const Integration& integration, const TermsLoaded& terms, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& integration, const TermsCoupled& terms, hipStream_t s);
+                                   const Integration& integration, const TermsLoaded& terms, hipStream_t s);
 // what the three above call when has_terms(terms) or has_objective(terms) (acmpc_dynamic_terms.hip: the kernels of a plain
 // Terms in the first case alone, those of a TermsObjective otherwise)
 hipError_t launch_rollout_dynamic_terms(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
@@ -521,5 +609,13 @@ hipError_t launch_rollout_dynamic_sampled_coupled(const RolloutArgs& args, const
                                                   const TermsCoupled& terms, hipStream_t s);
 hipError_t launch_finalize_dynamic_coupled(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
                                            const Integration& integration, const TermsCoupled& terms, hipStream_t s);
+// and while has_load_transfer(terms), before the coupling is looked at (acmpc_dynamic_loaded.hip: the kernels of a TermsLoaded)
+hipError_t launch_rollout_dynamic_loaded(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                         const Integration& integration, const TermsLoaded& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_sampled_loaded(const RolloutArgs& args, const SampleArgs& sample,
+                                                 const VehicleEnsemble& vehicles, const Integration& integration,
+                                                 const TermsLoaded& terms, hipStream_t s);
+hipError_t launch_finalize_dynamic_loaded(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                          const Integration& integration, const TermsLoaded& terms, hipStream_t s);
 
 }  // namespace acmpc

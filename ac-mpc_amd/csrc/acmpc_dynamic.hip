@@ -53,6 +53,11 @@
 // friction-ellipse block in every sub-step.  All four term parts sit behind their scalar switches, any of them off.  Sixteen
 // instantiations of a third translation unit, acmpc_dynamic_coupled.hip, launched only while the coupling is on.
 //
+// And a sixth, for a handle with the load transfer (acmpc_set_dynamics_load_transfer; acmpc_dynamic.h: TermsLoaded,
+// loaded_peaks_of): the pack is one TermsLoaded - the TermsCoupled plus six scalars per vehicle, which loaded_peaks() hands to
+// the general step with the peaks and the ratios (+inf while the coupling is off).  Sixteen instantiations of a fourth
+// translation unit, acmpc_dynamic_loaded.hip, launched only while the load transfer is on.
+//
 // Built with -ffp-contract=off: see acmpc_device.h.
 #include "acmpc_dynamic.h"
 
@@ -178,7 +183,8 @@ __global__ void __launch_bounds__(kDynBlock)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
+      if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
+      else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
@@ -289,7 +295,7 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
                                              const Integration& g, const float inv_L, const int p, const int n, const uint32_t (&gidx)[CPT], const bool has_ref,
                                              const float* s_wp, const float* s_xy, const float* s_seg,
                                              const float* s_centre, const float* s_ref, f32x2* s_z, const int row,
-                                             const int zi, const bool draws, TT&... tt) {
+                                             const int zi, const bool draws, [[maybe_unused]] const int vk, TT&... tt) {
   using I = typename IndexOf<F>::type;
   constexpr bool kTerms = sizeof...(TT) != 0;   // (tt: nothing, or the terms' state and the Terms)
   float amp[CPT];
@@ -300,6 +306,8 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
     amp[j] = use_ref ? 0.0f : candidate_amplitude(gidx[j]);
     cen[j] = use_ref ? s_ref : s_centre;
   }
+  [[maybe_unused]] LoadedPeaks<VehiclePeaks> loaded{};   // (the scalars of vehicle vk: read once, ahead of the step loop)
+  if constexpr (kLoadedPack<TT...>) loaded = loaded_peaks(vk, tt...);
   int resident[2] = {-1, -1};   // the Philox block in slots 0, 1 and in slots 2, 3
   int knot = -1;
   I nearest = I(0);
@@ -343,7 +351,8 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
         d = dj[0];
         q = qj[0];
       }
-      if constexpr (kCoupledPack<TT...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, coupled_peaks(tt...));
+      if constexpr (kLoadedPack<TT...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, loaded);
+      else if constexpr (kCoupledPack<TT...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, coupled_peaks(tt...));
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
@@ -390,7 +399,7 @@ __global__ void __launch_bounds__(kDynBlock)
   [[maybe_unused]] TermsState<F> ts;
   if constexpr (kTerms) ts = start_terms<F>(p, tm...);
   roll_sampled<CPT, false, FINE, F>(st, draw_spec(smp, w), veh, w, g, g.inv_L[0], p, n, gidx, smp.u_ref != nullptr, s_wp,
-                                    s_xy, s_seg, s_centre, s_ref, s_z, kDynBlock, tid, true, state_of(ts, tm)..., tm...);
+                                    s_xy, s_seg, s_centre, s_ref, s_z, kDynBlock, tid, true, 0, state_of(ts, tm)..., tm...);
   F cost_v;
   if constexpr (kTerms) cost_v = finish_dynamic_terms<F>(st, ts, s_wp, ts.j, p, n, w, tm...);
   else cost_v = finish_temporal<F>(st.t, n, w);
@@ -525,7 +534,8 @@ __global__ void __launch_bounds__(kWave)
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
     const float d = su[2 * i], q = su[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
-    if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
+    if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
+    else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
     else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[0]);
     // the first minimum of the key over the search's waypoints, the lanes side by side; ties -> the lower index, and the
     // search's first waypoint when no key compares below +inf (as the rollout's `d < best` scans)
@@ -619,7 +629,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
+      if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
+      else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
@@ -704,7 +715,7 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   [[maybe_unused]] TermsState<F> ts;
   if constexpr (kTerms) ts = start_terms<F>(p, tm...);
   roll_sampled<CPT, true, FINE, F>(st, draw_spec(smp, w), veh, w, g, g.inv_L[k], p, n, gidx, smp.u_ref != nullptr, s_wp,
-                                   s_xy, s_seg, s_centre, s_ref, s_z, kWave, lane, k == 0, state_of(ts, tm)..., tm...);
+                                   s_xy, s_seg, s_centre, s_ref, s_z, kWave, lane, k == 0, k, state_of(ts, tm)..., tm...);
   F cost_v;
   if constexpr (kTerms) cost_v = finish_dynamic_terms<F>(st, ts, s_wp, ts.j, p, n, w, tm...);
   else cost_v = finish_temporal<F>(st.t, n, w);
@@ -807,7 +818,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
     const float d = su[2 * i], q = su[2 * i + 1];
-    if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
+    if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
+    else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
     else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[k]);
     // finalize_dynamic_kernel's search, within this wave
     const int lo = exhaustive ? 0 : max(min(j_prev - w.nn_back, n - win_w), 0);
@@ -1006,7 +1018,25 @@ hipError_t finalize_dynamic_launch(int layout, const FinalizeArgs& args, const V
 
 }  // namespace
 
-#if defined(ACMPC_DYNAMIC_COUPLED_TU)
+#if defined(ACMPC_DYNAMIC_LOADED_TU)
+
+hipError_t launch_rollout_dynamic_loaded(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                         const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+  return rollout_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+hipError_t launch_rollout_dynamic_sampled_loaded(const RolloutArgs& args, const SampleArgs& sample,
+                                                 const VehicleEnsemble& vehicles, const Integration& g,
+                                                 const TermsLoaded& tm, hipStream_t s) {
+  return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s, tm);
+}
+
+hipError_t launch_finalize_dynamic_loaded(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                          const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+  return finalize_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+#elif defined(ACMPC_DYNAMIC_COUPLED_TU)
 
 hipError_t launch_rollout_dynamic_coupled(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
                                           const Integration& g, const TermsCoupled& tm, hipStream_t s) {
@@ -1060,26 +1090,29 @@ int dynamic_blocks_per_problem(int P, int N, int K) {
 }
 
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+                                  const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+  if (has_load_transfer(tm)) return launch_rollout_dynamic_loaded(layout, args, vehicles, g, tm, s);
   if (has_coupling(tm)) return launch_rollout_dynamic_coupled(layout, args, vehicles, g, tm, s);
   if (has_terms(tm) || has_objective(tm)) return launch_rollout_dynamic_terms(layout, args, vehicles, g, tm, s);
   return rollout_dynamic_launch(layout, args, vehicles, g, s);
 }
 
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+                                          const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+  if (has_load_transfer(tm)) return launch_rollout_dynamic_sampled_loaded(args, sample, vehicles, g, tm, s);
   if (has_coupling(tm)) return launch_rollout_dynamic_sampled_coupled(args, sample, vehicles, g, tm, s);
   if (has_terms(tm) || has_objective(tm)) return launch_rollout_dynamic_sampled_terms(args, sample, vehicles, g, tm, s);
   return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s);
 }
 
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+                                   const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+  if (has_load_transfer(tm)) return launch_finalize_dynamic_loaded(layout, args, vehicles, g, tm, s);
   if (has_coupling(tm)) return launch_finalize_dynamic_coupled(layout, args, vehicles, g, tm, s);
   if (has_terms(tm) || has_objective(tm)) return launch_finalize_dynamic_terms(layout, args, vehicles, g, tm, s);
   return finalize_dynamic_launch(layout, args, vehicles, g, s);
 }
 
-#endif  // ACMPC_DYNAMIC_COUPLED_TU, ACMPC_DYNAMIC_TERMS_TU
+#endif  // ACMPC_DYNAMIC_LOADED_TU, ACMPC_DYNAMIC_COUPLED_TU, ACMPC_DYNAMIC_TERMS_TU
 
 }  // namespace acmpc

@@ -33,7 +33,12 @@ int identify_blocks(int K);            // workgroups (= partial keys) of K hypot
 // `vehicle`: the base vehicle (its Pf, Pr are not read); `g`: the integration setting with h of the LOG's period and
 // inv_L[0] the base vehicle's; `coupling`: the two ratios of the handle's tyre coupling, or nullptr while it is off.  hipErrorInvalidValue
 // beyond the limits above.
+// `load`: the six scalars of the handle's load transfer for the base vehicle (acmpc_dynamic.h: LoadedPeaks), or nullptr while
+// it is off.
+struct IdentifyLoad {
+  float c_h, w_max, a1_f, a2_f, a1_r, a2_r;
+};
 hipError_t launch_identify_grip(const IdentifyArgs& args, const Vehicle& vehicle, const Integration& g, const float* coupling,
-                                hipStream_t s);
+                                const IdentifyLoad* load, hipStream_t s);
 
 }  // namespace acmpc

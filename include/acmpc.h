@@ -319,6 +319,32 @@ int acmpc_set_dynamics_objective(acmpc_ctx* ctx, double progress_weight, const d
  * DESIGN.md section 2 "Mode D, tyre coupling". */
 int acmpc_set_dynamics_coupling(acmpc_ctx* ctx, const double ratio[2] /* NULL: off */);
 
+/* Mode D's longitudinal load transfer: each axle's load, and with it its Pacejka peak factor and its coupling cap, follows
+ * the longitudinal tyre force.  Off by default, when the peaks are those of the static axle loads.  setting = (h_cg, w_frac):
+ * h_cg >= 0 and finite, the height of the centre of gravity in the vehicle block's length unit; 0 < w_frac < 1, the most load
+ * that may move as a fraction of the lighter axle's static load; NULL turns the setting off.  Per vehicle of the handle the
+ * host derives in float64, each rounded to float32 once:
+ *   c_h = h_cg / (lf + lr);  w_max = w_frac min(F_zf, F_zr);  e_a = eps_a / F_z0;  N_a = F_za + e_a F_za^2;
+ *   a1_a = (1 + 2 e_a F_za) / N_a;  a2_a = e_a / N_a                                   (a = f, r)
+ * so that P_a(F_za + x) / P_a(F_za) = 1 + x (a1_a + a2_a x) exactly, whatever D_a (a grip scale).  In every Euler step (every
+ * sub-step of acmpc_set_dynamics_integration), after the two longitudinal forces and before anything uses a peak, all
+ * float32, nothing fused, min / max the IEEE minNum / maxNum, Pf, Pr the peaks the step would otherwise use and rho the
+ * coupling's ratios (+inf on both axles while it is off):
+ *   e_f = max(min(F_fx, rho_f Pf), -(rho_f Pf));  e_r likewise         the demands clipped at the STATIC caps
+ *   w = c_h (e_f + e_r);  w = max(min(w, w_max), -w_max)               the load moved to the rear (negative: braking)
+ *   x_f = -w;  x_r = w;  phi_a = 1 + x_a (a1_a + a2_a x_a);  Pf' = Pf phi_f;  Pr' = Pr phi_r
+ * then the side forces with Pf', Pr' in front of the unchanged Pacejka shape, and the coupling block on the original F_fx,
+ * F_rx with Pf', Pr' in place of Pf, Pr.  One explicit pass at the algebraic loop between force and load: no carried state.
+ * h_cg = 0 and pedal == 0 give the step without the setting bit for bit (for finite forces).  The friction map is left out
+ * of w.  acmpc_score_grips applies vehicle 0's factors to each hypothesis' own peaks.  The setting belongs to the handle: it
+ * survives every other acmpc_set_dynamics* call, and every call form of mode D takes it from the handle.  While it is on,
+ * every vehicle of the handle must have N_a != 0, phi_a > 0 (in float64) at x = +-w_max and at the vertex -a1_a / (2 a2_a)
+ * where a2_a > 0 and the vertex lies inside, and Pf, Pr finite and > 0 as float32: whichever call would break that - this
+ * one, acmpc_set_dynamics or acmpc_set_dynamics_ensemble - returns ACMPC_EINVAL and leaves the handle as it was.  No device
+ * work.  ACMPC_ESTATE for a handle whose mode is not ACMPC_MODE_DYNAMIC; ACMPC_EINVAL for an h_cg that is negative or not
+ * finite, or a w_frac outside (0, 1).  DESIGN.md section 2 "Mode D, load transfer". */
+int acmpc_set_dynamics_load_transfer(acmpc_ctx* ctx, const double setting[2] /* NULL: off */);
+
 /* The control applied just before each problem's plan starts: u_prev host [P][2] = (delta, pedal), what step 0's rates
  * are taken against; NULL clears it (P is then ignored), and step 0's own control stands for it: an increment of +0.
  * Staged on the host; it travels to the device with the tables, on the next call's stream (acmpc_sync_tables covers it),

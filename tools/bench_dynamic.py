@@ -46,6 +46,12 @@ rear axle; a single number is both): the TermsCoupled kernels of csrc/acmpc_dyna
 with `--identify`, identify_grip_coupled_kernel (`identify_grip_coupled`).  To price the coupling, alternate the command with
 and without the flag in one job on one card.
 
+With `--load-transfer H[,FRAC]` every handle is given the load transfer (acmpc_set_dynamics_load_transfer: the CG height and
+w_frac, 0.9 when left out): the TermsLoaded kernels of csrc/acmpc_dynamic_loaded.hip, with whatever `--coupling` / `--terms` /
+`--objective` / `--substeps` / `--blend` set beside it, priced with `dynamic_loaded_step` + M `dynamic_loaded_substep`; and with
+`--identify`, identify_grip_loaded_kernel (`identify_grip_loaded`).  To price it, alternate `--coupling 1,1` with
+`--coupling 1,1 --load-transfer 0.35` in one job on one card.
+
 With `--identify` the grip identification (acmpc_score_grips: host pointers, one blocking round trip) is timed at K = 4 096
 (the 64 x 64 split grid) and K = 65 536 (256 x 256) hypotheses over a window of W = 40 steps, in one-step (L = 1) and
 eight-step (L = 8) segments, under the run's integration setting: p50 / p99 of the call, the static VALU count per
@@ -54,6 +60,7 @@ and the vector-issue time that count needs (bench.valu_roofline) as a fraction o
 kernel's own fraction, which a `rocprofv3 --kernel-trace --stats` run of this command gives (kernel identify_grip_kernel).
 
 usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms] [--objective] [--coupling RF,RR]
+                                      [--load-transfer H[,FRAC]]
                                       [--sampled | --optimize [--update softmin] | --identify]"""
 import argparse
 import json
@@ -80,6 +87,7 @@ OBJECTIVE_ON = dict(progress_weight=1.0, speed_ceiling=(1.1, 0.0))
 
 
 COUPLING = None           # --coupling: the tyre coupling (rho_f, rho_r) every handle of this run is given
+LOAD_TRANSFER = None      # --load-transfer: the load transfer (h_cg, w_frac) every handle of this run is given
 
 
 def integrate(eng):
@@ -93,6 +101,8 @@ def integrate(eng):
         eng.set_dynamics_objective(**OBJECTIVE)
     if COUPLING is not None:
         eng.set_dynamics_coupling(COUPLING)
+    if LOAD_TRANSFER is not None:
+        eng.set_dynamics_load_transfer(LOAD_TRANSFER)
     return eng
 
 
@@ -100,7 +110,7 @@ def fine_issue_roof(bench, candidates, steps, kernel_s, name):
     """issue_roof for a FINE kernel: VALU per control step = the step loop's trip + M sub-step trips, priced with the
     sub-step loop's mix (which is nearly all of it)."""
     mix, mix_path = bench.newest_profile("isa_mix.json")
-    kind = "_coupled_" if COUPLING is not None else "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
+    kind = "_loaded_" if LOAD_TRANSFER is not None else "_coupled_" if COUPLING is not None else "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
     step, sub = mix["entries"][name + kind + "step"], mix["entries"][name + kind + "substep"]
     per_step = (sum(step["valu"].values()) + INTEGRATION[0] * sum(sub["valu"].values())) / float(sub["candidates_per_lane"])
     counted = (per_step, mix_path + " (static count: step trip + M sub-step trips)", {"source_sha256": mix.get("source_sha256")})
@@ -114,7 +124,7 @@ def issue_roof(bench, candidates, steps, kernel_s, name="dynamic"):
     """bench.valu_roofline for the `dynamic` entry (`dynamic_ensemble`: candidates = vehicle-candidates): the step loop's
     static VALU count per candidate-step (the isa mix, whose sources must be the loaded build's -
     `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
-    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None or COUPLING is not None) and name in ("dynamic", "dynamic_ensemble"):
+    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None or COUPLING is not None or LOAD_TRANSFER is not None) and name in ("dynamic", "dynamic_ensemble"):
         return fine_issue_roof(bench, candidates, steps, kernel_s, name)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     entry = mix["entries"][name]
@@ -142,8 +152,14 @@ def main():
     ap.add_argument("--terms", action="store_true", help="rate and slip terms on every handle (TERMS_ON)")
     ap.add_argument("--objective", action="store_true", help="the progress reward and a speed ceiling on every handle (OBJECTIVE_ON)")
     ap.add_argument("--coupling", default=None, help="RF,RR (or one ratio for both axles): the tyre coupling on every handle")
+    ap.add_argument("--load-transfer", default=None, help="H[,FRAC]: the load transfer (CG height, w_frac = 0.9) on every handle")
     args = ap.parse_args()
-    global INTEGRATION, TERMS, OBJECTIVE, COUPLING
+    global INTEGRATION, TERMS, OBJECTIVE, COUPLING, LOAD_TRANSFER
+    if args.load_transfer is not None:
+        load = tuple(float(v) for v in args.load_transfer.split(","))
+        if len(load) not in (1, 2):
+            ap.error("--load-transfer takes H or H,FRAC")
+        LOAD_TRANSFER = load + (0.9,) if len(load) == 1 else load
     if args.coupling is not None:
         ratios = tuple(float(v) for v in args.coupling.split(","))
         if len(ratios) not in (1, 2):
@@ -343,12 +359,14 @@ def measure_identify(args):
     integrate(eng)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     M = INTEGRATION[0]
-    entry = "identify_grip_coupled" if COUPLING is not None else "identify_grip"
+    entry = "identify_grip_loaded" if LOAD_TRANSFER is not None else "identify_grip_coupled" if COUPLING is not None else "identify_grip"
     per_step = M * sum(mix["entries"][entry]["valu"].values()) + sum(mix["entries"][entry + "_step"]["valu"].values())
     out = {"tool": "tools/bench_dynamic.py --identify", "W": W, "substeps": M, "low_speed_blend": INTEGRATION[1],
            "valu_per_hypothesis_step": per_step}
     if COUPLING is not None:
         out["coupling"] = list(COUPLING)
+    if LOAD_TRANSFER is not None:
+        out["load_transfer"] = list(LOAD_TRANSFER)
     calls = 20 if args.quick else 200
     for side in (64, 256):
         scales = grip_scales(np.linspace(0.3, 1.5, side), "split")
@@ -455,6 +473,8 @@ def measure(args, K):
         out.update(terms={k: list(v) if isinstance(v, tuple) else v for k, v in TERMS.items()})
     if COUPLING is not None:
         out.update(coupling=list(COUPLING))
+    if LOAD_TRANSFER is not None:
+        out.update(load_transfer=list(LOAD_TRANSFER))
     if K > 1:
         out.update(vehicles=K, reduce=args.reduce, grips=list(GRIPS[:K]))
 

@@ -69,6 +69,14 @@ ENTRIES = {
     "dynamic_coupled_substep": ("acmpc_dynamic_coupled.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12TermsCoupledEEE", None),
     "dynamic_ensemble_coupled_step": ("acmpc_dynamic_coupled.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12TermsCoupledEEE", None),
     "dynamic_ensemble_coupled_substep": ("acmpc_dynamic_coupled.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12TermsCoupledEEE", None),
+    # mode D with the load transfer (acmpc_set_dynamics_load_transfer: the TermsLoaded kernels of acmpc_dynamic_loaded.hip, the
+    # coupled step with the loaded peaks in front of it): the block's instructions = `dynamic_loaded_substep` -
+    # `dynamic_coupled_substep` - two clips at the static caps, the transfer and its clip, two quadratics, two products, and
+    # the caps per lane instead of per wave
+    "dynamic_loaded_step": ("acmpc_dynamic_loaded.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_11TermsLoadedEEE", None),
+    "dynamic_loaded_substep": ("acmpc_dynamic_loaded.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_11TermsLoadedEEE", None),
+    "dynamic_ensemble_loaded_step": ("acmpc_dynamic_loaded.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_11TermsLoadedEEE", None),
+    "dynamic_ensemble_loaded_substep": ("acmpc_dynamic_loaded.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_11TermsLoadedEEE", None),
     # mode D's grip identification (acmpc_score_grips, one hypothesis per lane): the sub-step loop of its step kernel - the
     # dynamics and the blend's block, WITHOUT the pose (nothing reads it there: no sincos_spec(yaw), no X, Y, yaw updates).
     # VALU per hypothesis and control step = M trips of it + `identify_grip_step`: the control's terms and the residual, the
@@ -78,16 +86,21 @@ ENTRIES = {
     # the same under the tyre coupling (each lane's caps from its own two peaks): the block = the difference of the sub-steps
     "identify_grip_coupled": ("acmpc_identify.hip", "identify_grip_coupled_kernel", None),
     "identify_grip_coupled_step": ("acmpc_identify.hip", "identify_grip_coupled_kernel", None),
+    # and under the load transfer (the base vehicle's factors on each lane's own two peaks)
+    "identify_grip_loaded": ("acmpc_identify.hip", "identify_grip_loaded_kernel", None),
+    "identify_grip_loaded_step": ("acmpc_identify.hip", "identify_grip_loaded_kernel", None),
 }
 CANDIDATES_PER_LANE = {"fused_round": 1, "identify_grip": 1, "identify_grip_step": 1, "identify_grip_coupled": 1,
-                       "identify_grip_coupled_step": 1}
+                       "identify_grip_coupled_step": 1, "identify_grip_loaded": 1, "identify_grip_loaded_step": 1}
 OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dynamic_ensemble_fine_step",
          "dynamic_terms_step", "dynamic_ensemble_terms_step", "dynamic_objective_step", "dynamic_ensemble_objective_step",
-         "dynamic_coupled_step", "dynamic_ensemble_coupled_step", "identify_grip_step", "identify_grip_coupled_step")
+         "dynamic_coupled_step", "dynamic_ensemble_coupled_step", "dynamic_loaded_step", "dynamic_ensemble_loaded_step",
+         "identify_grip_step", "identify_grip_coupled_step", "identify_grip_loaded_step")
 # (exit test at the head: closes with s_branch)
 ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep",
            "dynamic_objective_substep", "dynamic_ensemble_objective_substep", "dynamic_coupled_substep",
-           "dynamic_ensemble_coupled_substep", "identify_grip", "identify_grip_coupled")
+           "dynamic_ensemble_coupled_substep", "dynamic_loaded_substep", "dynamic_ensemble_loaded_substep", "identify_grip",
+           "identify_grip_coupled", "identify_grip_loaded")
 
 
 def source_hash():
