@@ -3,7 +3,9 @@ count, search window, path family, problem kind, ensemble size, reduce and weigh
 per-candidate cost, the argmin, the feasible count and the winner's record must equal the float32 specification
 (tests/dynamic_spec.py, tests/dynamic_ensemble_spec.py) bit for bit.  In front of the random cases, the longest horizon
 the kernels accept (kDynamicMaxSteps = 512 steps) with both searches, one vehicle and three, both layouts.
-ACMPC_FUZZ_CASES sets the number of random cases (default 40).
+ACMPC_FUZZ_CASES sets the number of random cases (default 40).  Every handle here keeps its default settings: the plain
+kernels.  tests/test_gpu_fuzz_dynamic_settings.py draws the settings (integration, terms, objective, coupling, load transfer) and
+the sampled call forms beside these shapes.
 
 The specification is NumPy: a case costs about P K (3.3 ms n + 80 ns N n W) seconds of it (W waypoints searched per
 step).  A case drawn above BUDGET_S gives up problems first, then vehicles, then candidates - never its horizon, window
