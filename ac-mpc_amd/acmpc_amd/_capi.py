@@ -32,6 +32,10 @@ ROUND_FIELDS = ("kernel", "fused_finalize", "traced", "chained", "frames_in_lds"
                 "tick_frames")   # acmpc_describe_rounds' out[8]
 
 
+# acmpc_describe_rollout's out[4] (ACMPC_ROLLOUT_*): the kernel family and the rows kernel's table choice
+ROLLOUT_KERNELS = (("step", None), ("tile", None), ("rows", "lds"), ("rows", "scalar"))
+
+
 class EngineError(RuntimeError):
     """A call into libacmpc_hip failed; `.code` is the ACMPC_E* value."""
 
@@ -207,6 +211,7 @@ SIGNATURES = {
     "acmpc_tick_read_device_tables": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acmpc_tick_read_device_frames": (C.c_int, [_CTX, C.c_void_p, C.c_int64]),
     "acmpc_describe_rounds": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, _I32P]),
+    "acmpc_describe_rollout": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I32P]),
     "acmpc_speed_profile_qp_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double,
                                                 C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p,
                                                 C.c_void_p, C.c_int32, _I32P]),
@@ -910,6 +915,18 @@ class Engine:
         out = np.zeros(8, dtype=np.int32)
         self._check(self._lib.acmpc_describe_rounds(self._ctx, int(P), int(N), int(n), out.ctypes.data_as(_I32P)))
         return dict(kernel=int(out[0]), **{name: bool(v) for name, v in zip(ROUND_FIELDS[1:], out[1:])})
+
+    def describe_rollout(self, P: int, N: int, n: int, layout: int) -> dict:
+        """The launch a rollout over a control matrix of this shape makes on this handle (acmpc_describe_rollout; test hook,
+        no device work): dict(block, cpt, pack, workgroups as ints; kernel = "step", "tile" or "rows"; table = "lds" or
+        "scalar" for the rows kernel, else None; tailed_fits, chained_fits, solo as bools).  `solo`: `solve` and
+        `solve_device` take the one-launch solve instead at this size.  The rows kernel needs the matrix on a 16-byte
+        boundary, which only the launch sees: any other start takes the tile kernel."""
+        out = np.zeros(8, dtype=np.int32)
+        self._check(self._lib.acmpc_describe_rollout(self._ctx, int(P), int(N), int(n), int(layout), out.ctypes.data_as(_I32P)))
+        return dict(block=int(out[0]), cpt=int(out[1]), pack=int(out[2]), workgroups=int(out[3]),
+                    kernel=ROLLOUT_KERNELS[int(out[4])][0], table=ROLLOUT_KERNELS[int(out[4])][1],
+                    tailed_fits=bool(out[5]), chained_fits=bool(out[6]), solo=bool(out[7]))
 
     def speed_profile_qp_device(self, v_hi, ds, a_min, a_max, v_min, max_iter=4000, eps_abs=1e-3, eps_rel=1e-3,
                                 warm=None, check_every=10):

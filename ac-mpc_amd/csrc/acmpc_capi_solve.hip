@@ -285,6 +285,24 @@ int softmin_sampled(acmpc_ctx* c, const float* d_costs, const int64_t* d_keys, c
   return ACMPC_OK;
 }
 
+// Step-major launches with two or four candidates per lane read their controls and write their costs as ONE 8- or 16-byte
+// vector per lane (load_controls, rollout_block: a vector type's natural alignment is what the compiler may assume of the
+// address), so the matrix and the cost buffer must start on that boundary; every row then does (N is a multiple of the
+// lane's candidates).  Checked from the shape the launch will take, before any device work (include/acmpc.h).
+static int check_vector_alignment(const acmpc_ctx* c, int P, int N, int n, int layout, const float* d_U, const float* d_costs) {
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC) return ACMPC_OK;
+  const acmpc::LaunchShape shape = acmpc::choose_shape(P, N, layout, c->prm.mode, n, c->opt);
+  if (shape.tile || shape.cpt < 2) return ACMPC_OK;
+  const uintptr_t mask = static_cast<uintptr_t>(shape.cpt) * sizeof(float) - 1;
+  if ((reinterpret_cast<uintptr_t>(d_U) & mask) != 0 || (reinterpret_cast<uintptr_t>(d_costs) & mask) != 0) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "a step-major launch with %d candidates per lane needs d_U and d_costs on a %d-byte boundary",
+                  shape.cpt, static_cast<int>(mask + 1));
+    return fail(c, ACMPC_EINVAL, buf);
+  }
+  return ACMPC_OK;
+}
+
 // acmpc_solve_device / acmpc_solve in ONE launch (rollout_solo_kernel) when the problem is small enough for it: rollout,
 // argmin and the winner's record without rolling the winner a second time.  ACMPC_NO_SOLO keeps the two launches.
 static bool use_solo(const acmpc_ctx* c, int P, int N, int n, int layout) {
@@ -402,6 +420,7 @@ int acmpc_rollout_device(acmpc_ctx* c, const float* d_x0, const float* d_U, int3
   if (d_x0 == nullptr || d_U == nullptr) return fail(c, ACMPC_EINVAL, "null device pointer");
   if (index_offset < 0 || index_offset + N > 0xffffffffLL) return fail(c, ACMPC_EINVAL, "global index exceeds 32 bits");
   ACMPC_TRY(check_shape(c, P, N, n, layout));
+  ACMPC_TRY(check_vector_alignment(c, P, N, n, layout, d_U, d_costs));
   ACMPC_TRY(ensure_device(c));
   hipStream_t s = static_cast<hipStream_t>(stream);
   ACMPC_TRY(upload_tables(c, s));
@@ -431,6 +450,7 @@ int acmpc_solve_device(acmpc_ctx* c, const float* d_x0, const float* d_U, int32_
   if (d_x0 == nullptr || d_U == nullptr) return fail(c, ACMPC_EINVAL, "null device pointer");
   if (d_keys == nullptr && d_records == nullptr) return fail(c, ACMPC_EINVAL, "need d_keys and/or d_records");
   ACMPC_TRY(check_shape(c, P, N, n, layout));
+  if (!use_solo(c, P, N, n, layout)) ACMPC_TRY(check_vector_alignment(c, P, N, n, layout, d_U, d_costs));
   ACMPC_TRY(ensure_device(c));
   hipStream_t s = static_cast<hipStream_t>(stream);
   ACMPC_TRY(upload_tables(c, s));
@@ -447,6 +467,7 @@ int acmpc_solve_sampled_device(acmpc_ctx* c, const float* d_x0, const float* d_U
     return fail(c, ACMPC_EINVAL, "null device pointer");
   if (centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
   ACMPC_TRY(check_shape(c, P, N, n, layout));
+  ACMPC_TRY(check_vector_alignment(c, P, N, n, layout, d_U, d_costs));
   ACMPC_TRY(ensure_device(c));
   hipStream_t s = static_cast<hipStream_t>(stream);
   ACMPC_TRY(upload_tables(c, s));
@@ -458,6 +479,41 @@ int acmpc_solve_sampled_device(acmpc_ctx* c, const float* d_x0, const float* d_U
     return finalize(c, nullptr, d_keys, d_x0, nullptr, P, N, n, layout, 0, d_records, used.blocks_per_problem, s, &regen);
   }
   return solve_batched(c, d_x0, d_U, P, N, n, layout, d_costs, d_keys, d_records, s, &regen);
+}
+
+static_assert(ACMPC_ROLLOUT_STEP == 0 && ACMPC_ROLLOUT_TILE == 1 && ACMPC_ROLLOUT_ROWS_LDS == 2 && ACMPC_ROLLOUT_ROWS_SCALAR == 3,
+              "include/acmpc.h");
+
+int acmpc_describe_rollout(const acmpc_ctx* c, int32_t P, int32_t N, int32_t n, int32_t layout, int32_t out[8]) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (out == nullptr) return fail(c, ACMPC_EINVAL, "null output");
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "mode D has its own rollout: no launch shapes of these forms");
+  if (P < 1 || N < 1 || n < 1) return fail(c, ACMPC_EINVAL, "P, N and n must be positive");
+  if (layout != ACMPC_LAYOUT_CANDIDATE_MAJOR && layout != ACMPC_LAYOUT_STEP_MAJOR) return fail(c, ACMPC_EINVAL, "unknown layout");
+  if (P > c->prm.max_problems || N > c->prm.max_candidates || n > c->prm.max_steps)
+    return fail(c, ACMPC_ECAPACITY, "shape exceeds the handle's capacity");
+  const int mode = c->prm.mode;
+  const acmpc::LaunchShape shape = acmpc::choose_shape(P, N, layout, mode, n, c->opt);
+  // the finalize a batch of this shape leaves pending for the next call of a stream (acmpc_solve_stream_device: records
+  // wanted, the partial keys its own, the winners re-drawn or read from the same layout); only whether a pointer is null counts
+  static float some_records;
+  acmpc::FinalizeArgs pending{};
+  pending.records = &some_records;
+  pending.P = P;
+  pending.N = N;
+  pending.n = n;
+  pending.blocks_per_problem = shape.blocks_per_problem;
+  const bool rows = shape.tile && shape.tile_waves == 4;   // (launch_rollout_ml; there also: the matrix on a 16-byte boundary)
+  out[0] = shape.block;
+  out[1] = shape.cpt;
+  out[2] = shape.cpt >= 2 ? shape.pack : 1;
+  out[3] = shape.blocks_per_problem;
+  out[4] = rows ? (acmpc::tile_rows_table_in_lds(shape, P, n) ? ACMPC_ROLLOUT_ROWS_LDS : ACMPC_ROLLOUT_ROWS_SCALAR)
+                : shape.tile ? ACMPC_ROLLOUT_TILE : ACMPC_ROLLOUT_STEP;
+  out[5] = acmpc::tailed_rollout_fits(mode, layout, shape, n) ? 1 : 0;
+  out[6] = acmpc::chained_rollout_fits(mode, layout, shape, P, pending, layout) ? 1 : 0;
+  out[7] = use_solo(c, P, N, n, layout) ? 1 : 0;
+  return ACMPC_OK;
 }
 
 int acmpc_solve_stream_flush(acmpc_ctx* c, void* stream) {
@@ -478,6 +534,7 @@ int acmpc_solve_stream_device(acmpc_ctx* c, const float* d_x0, const float* d_U,
   if (d_x0 == nullptr || d_U == nullptr || d_records == nullptr) return fail(c, ACMPC_EINVAL, "null device pointer");
   if (d_centre != nullptr && centre_stride < 2 * n) return fail(c, ACMPC_EINVAL, "centre_stride must be at least 2 n");
   ACMPC_TRY(check_shape(c, P, N, n, layout, true));
+  ACMPC_TRY(check_vector_alignment(c, P, N, n, layout, d_U, d_costs));
   ACMPC_TRY(ensure_device(c));
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the pending finalize reads the tables its batch was rolled with: new ones go up behind it
@@ -562,6 +619,7 @@ int acmpc_solve(acmpc_ctx* c, const float* x0, const float* U, int32_t P, int32_
     ACMPC_TRY(solve_solo(c, d_x0, d_U, P, N, n, layout, costs != nullptr ? c->d_costs : nullptr, d_keys, d_records, s));
   } else {
     acmpc::LaunchShape shape;
+    ACMPC_TRY(check_vector_alignment(c, P, N, n, layout, d_U, nullptr));   // (a matrix read in place may be a view)
     ACMPC_TRY(rollout(c, d_x0, d_U, P, N, n, layout, 0, costs != nullptr ? c->d_costs : nullptr, s, &shape));
     ACMPC_TRY(finalize(c, nullptr, d_keys, d_x0, d_U, P, N, n, layout, 0, d_records, shape.blocks_per_problem, s));
   }

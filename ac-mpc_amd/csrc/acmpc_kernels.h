@@ -126,6 +126,9 @@ hipError_t launch_rollout_temporal_plain(const LaunchShape& shape, const Rollout
                                          hipEvent_t start, hipEvent_t stop);
 hipError_t launch_rollout_tile_rows_plain(const LaunchShape& shape, const RolloutArgs& args, hipStream_t s,
                                           hipEvent_t start, hipEvent_t stop);
+// the rows kernel's table rows: from LDS (true) or by scalar loads - what launch_rollout_tile_rows_plain launches, and what
+// acmpc_describe_rollout reports
+bool tile_rows_table_in_lds(const LaunchShape& shape, int P, int n);
 hipError_t launch_finalize(int mode, int layout, const FinalizeArgs& args, hipStream_t s,
                            const LaunchOptions& opt = LaunchOptions());
 // rollout + finalize in ONE launch for the batched solve (mode S, step-major, 256-thread shapes): the last workgroup of

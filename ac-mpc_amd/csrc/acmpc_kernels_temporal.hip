@@ -11,13 +11,17 @@ namespace acmpc {
 // and the packing adds moves - so this translation unit is compiled with -fno-slp-vectorize (ac-mpc_amd/acmpc_amd/_build.py).
 // (the candidate-major rows kernel gains the same way: its walk is one candidate per lane, and the SLP vectoriser's
 // ten packed instructions + five moves per step cost more than the twenty plain ones they replace)
-hipError_t launch_rollout_tile_rows_plain(const LaunchShape& shape, const RolloutArgs& args, hipStream_t s,
-                                          hipEvent_t e0, hipEvent_t e1) {
+bool tile_rows_table_in_lds(const LaunchShape& shape, int P, int n) {
   // Table rows from LDS (one copy per workgroup) or by scalar loads - measured, 4 096 candidates per problem, LDS / scalar:
   //   H = 50:  256 problems 92 / 92 us, 1 024: 335 / 389, 4 096: 1 258 / 1 457   (more tables in flight, more scalar misses)
   //   H = 30:  256: 51.5 / 47.8, 1 024: 212 / 216;   H = 20, 2 048 problems: 297 / 280
   //   H = 65:  256: 183 / 173, 1 024: 654 / 685;     H = 80: 256: 221 / 220, 1 024: 799 / 1 094
-  const bool lds = shape.tile_table != 0 ? shape.tile_table == 1 : (args.n > 32 && (args.n <= 50 || args.P >= 512));   // (A/B: LaunchOptions::tile_table)
+  return shape.tile_table != 0 ? shape.tile_table == 1 : (n > 32 && (n <= 50 || P >= 512));   // (A/B: LaunchOptions::tile_table)
+}
+
+hipError_t launch_rollout_tile_rows_plain(const LaunchShape& shape, const RolloutArgs& args, hipStream_t s,
+                                          hipEvent_t e0, hipEvent_t e1) {
+  const bool lds = tile_rows_table_in_lds(shape, args.P, args.n);
   if (lds) {
     if (args.n <= 32) return launch_rollout_tile_rows<32, 4, true>(shape, args, s, e0, e1);
     if (args.n <= 50) return launch_rollout_tile_rows<50, 4, true>(shape, args, s, e0, e1);

@@ -138,7 +138,7 @@ LaunchShape choose_shape(int P, int N, int layout, int mode, int n, const Launch
   s.tile = false;
   s.tile_waves = 0;
   s.pack = (mode == 1) ? 1 : 2;  // mode T: plain float32 states (see launch_rollout_temporal_plain)
-  if (opt.temporal_pack != 0) s.pack = opt.temporal_pack;
+  if (mode == 1 && opt.temporal_pack != 0) s.pack = opt.temporal_pack;   // (mode S's launches are packed pairs whatever it says)
   s.tile_table = opt.tile_table;
   const long long total = static_cast<long long>(P) * N;
   if (layout == 0 && tile_lds_bytes(mode, n) <= 64 * 1024 && !opt.no_tile) {

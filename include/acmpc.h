@@ -427,7 +427,13 @@ int acmpc_host_free(void* memory);
  * acmpc_rollout_device - and `d_records` [P][acmpc_record_floats(n)] the winner records.
  * Device buffers are what hipMalloc returns, or views into it on their element type's boundary (gfx950 serves a
  * 16-byte load on any 4-byte boundary); buffers that start 16-byte aligned are served fastest - e.g. a candidate-major
- * `d_U` then takes the faster of the two tile kernels, any other start the slower one, with the same results. */
+ * `d_U` then takes the faster of the two tile kernels, any other start the slower one, with the same results.
+ * One exception, refused with ACMPC_EINVAL before any device work: a step-major launch that gives a lane two or four
+ * adjacent candidates (modes S and T; acmpc_describe_rollout out[1]) reads their controls and writes their costs as one
+ * 8- or 16-byte vector, so there `d_U` and `d_costs` must start on an 8- / 16-byte boundary (N is then a multiple of two /
+ * four, so every row of the matrix does too).  This holds for every call that takes a step-major `d_U`:
+ * acmpc_solve_device, acmpc_rollout_device, acmpc_solve_sampled_device, acmpc_solve_stream_device, and acmpc_solve on a
+ * matrix it reads in place.  What hipMalloc returns always qualifies. */
 int acmpc_solve_device(acmpc_ctx* ctx, const float* d_x0, const float* d_U, int32_t P, int32_t N, int32_t n,
                        int32_t layout, float* d_costs, int64_t* d_keys, float* d_records, void* stream);
 
@@ -659,6 +665,32 @@ int acmpc_speed_profile_qp_device(acmpc_ctx* ctx, const double* v_hi, const doub
 #define ACMPC_ROUND_QUAD 2   /* mode S, four waves */
 #define ACMPC_ROUND_TRIO 3   /* mode T, three waves */
 int acmpc_describe_rounds(const acmpc_ctx* ctx, int32_t P, int32_t N, int32_t n, int32_t out[8]);
+
+/* Test hook of the rollouts over a caller's control matrix (modes S and T): the launch acmpc_rollout_device,
+ * acmpc_solve_device, acmpc_solve_sampled_device, acmpc_solve_stream_device and acmpc_solve make for (P, N, n, layout) on
+ * this handle, with its mode and switches (ACMPC_SHAPE, ACMPC_T_PACK, ACMPC_NO_TILE, ACMPC_TILE_ROWS, ACMPC_TILE_TABLE,
+ * ACMPC_NO_SOLO).  The answer comes from the functions the launches themselves ask (csrc: choose_shape,
+ * tailed_rollout_fits, chained_rollout_fits, tile_rows_table_in_lds, solo_fits); no device work, the GPU is not
+ * initialised.  out[8] =
+ *   [0] threads per workgroup
+ *   [1] candidates per lane (1; step-major also 2 or 4: adjacent candidates, 8- / 16-byte loads and stores)
+ *   [2] candidates per arithmetic state: 2 = packed pairs, 1 = plain float32 (always 1 with one candidate per lane)
+ *   [3] workgroups per problem = partial keys per problem (what acmpc_finalize_device / acmpc_finalize_sampled_device
+ *       expect of the rollout before them; the rows kernel launches a quarter as many workgroups, of four waves)
+ *   [4] ACMPC_ROLLOUT_* below: the kernel family
+ *   [5] the one-launch rollout + finalize (ACMPC_TAILED_ROLLOUT) takes this shape
+ *   [6] a stream of batches of this shape chains: batch k's finalize inside batch k + 1's rollout launch
+ *       (unless ACMPC_NO_CHAINED_STREAM)
+ *   [7] acmpc_solve_device and acmpc_solve do NOT make this launch here: they take the one-launch solve
+ *       (rollout_solo_kernel) at this size
+ * One thing the hook cannot see: the rows kernel moves 16-byte pieces, so a launch whose `d_U` does not start on a
+ * 16-byte boundary takes the LDS-tile kernel instead, whatever [4] says - that is decided at the launch, from the pointer.
+ * ACMPC_ECAPACITY beyond the handle's capacities, ACMPC_ESTATE in mode D. */
+#define ACMPC_ROLLOUT_STEP 0         /* rollout_kernel: a lane walks its candidates' steps, controls straight from memory */
+#define ACMPC_ROLLOUT_TILE 1         /* candidate-major: one wave per workgroup, its 64 rows staged in LDS */
+#define ACMPC_ROLLOUT_ROWS_LDS 2     /* candidate-major, mode S: rows in registers, the table's rows from LDS */
+#define ACMPC_ROLLOUT_ROWS_SCALAR 3  /* ... the table's rows by scalar loads */
+int acmpc_describe_rollout(const acmpc_ctx* ctx, int32_t P, int32_t N, int32_t n, int32_t layout, int32_t out[8]);
 
 /* Host-side float64 helpers round one solve (csrc/acmpc_host_path.cpp; no GPU work, no handle).
  * Replaces: SpatialMPC.construct_waypoints (spatial_mpc.py:125-154).  coords [H][3] = (x, y, width) ->

@@ -71,8 +71,10 @@ def test_costs_argmin_and_winner_record(mode, layout, track, H, N, P):
 
 @pytest.mark.parametrize("mode", [0, 1])
 def test_large_step_major_batch_uses_vector_loads(mode):
-    """P*N large enough for the 4-candidates-per-lane kernel; properties that need no O(N) oracle run:
-    the winner's cost equals min(costs), the record re-rolls to the same cost, and a sampled subset matches."""
+    """Lanes of several candidates, which load their controls and store their costs as vectors: four per lane in mode S -
+    forced on the handle, the default rule takes them from 1 M candidates (tests/test_gpu_rollout_shapes.py runs that) - and
+    mode T's two by its default rule.  Properties that need no O(N) oracle run: the winner's cost equals min(costs), the
+    record re-rolls to the same cost, and a sampled subset matches."""
     H, N, P = 50, 8192, 40
     n = H - 1
     problems = [make_problem(orc, "monza", H, 8, seed=77 + p) for p in range(P)]
@@ -80,6 +82,10 @@ def test_large_step_major_batch_uses_vector_loads(mode):
     u_ref = np.stack([np.stack([p["table"][orc.ROW_V], p["table"][orc.ROW_KAPPA]], axis=1) for p in problems])
     U = (u_ref[:, None] + rng.standard_normal((P, N, n, 2)) * np.array([2.0, 0.01])).astype(np.float32)
     eng = _engine(problems, mode, N, n)
+    if mode == 0:
+        eng.set_option("ACMPC_SHAPE", "256,4")
+    form = eng.describe_rollout(P, N, n, LAYOUT_SM)
+    assert (form["kernel"], form["block"], form["cpt"], form["solo"]) == ("step", 256, 4 if mode == 0 else 2, False), form
     x0 = np.stack([p["x0"] if mode == 0 else p["pose0"] for p in problems])
     out = eng.solve(x0, _as_layout(U, LAYOUT_SM), layout=LAYOUT_SM)
     out_cm = eng.solve(x0, U, layout=LAYOUT_CM)

@@ -14,6 +14,22 @@ from test_support import engine_kwargs, make_problem
 pytestmark = pytest.mark.gpu
 
 
+# The cases that are about lanes of several candidates force that width on the handle (mode S's default rule takes four per
+# lane from 1 M candidates and never two: tests/test_rollout_shapes.py); every other case runs the default rule's 256 x 1.
+FORCED_SHAPE = {(64, 4096, 50): "256,4", (301, 2048, 20): "256,2"}
+
+
+def _force_shape(eng, P, N, n):
+    """Sets the case's launch shape, if it has one, and returns the launch's description."""
+    shape = FORCED_SHAPE.get((P, N, n + 1))
+    if shape is not None:
+        eng.set_option("ACMPC_SHAPE", shape)
+    d = eng.describe_rollout(P, N, n, 1)
+    assert (d["kernel"], d["block"], d["cpt"]) == ("step", 256, int(shape[-1]) if shape else 1), d
+    assert d["workgroups"] == -(-N // (256 * d["cpt"])) and d["tailed_fits"] and not d["solo"], d
+    return d
+
+
 def _solve(monkeypatch, switch, problems, P, N, n, sampled):
     import torch
     from acmpc_amd import Engine, _capi
@@ -24,6 +40,7 @@ def _solve(monkeypatch, switch, problems, P, N, n, sampled):
     dev = torch.device("cuda", 0)
     eng = Engine(**engine_kwargs(problems[0], 0, P, N, n))      # (the switch is read when the handle is created)
     eng.set_paths(np.stack([p["table"] for p in problems]))
+    _force_shape(eng, P, N, n)
     s = torch.cuda.current_stream().cuda_stream
     x0 = torch.tensor(np.stack([p["x0"] for p in problems]), device=dev)
     u_ref = torch.tensor(np.stack([np.stack([p["table"][orc.ROW_V], p["table"][orc.ROW_KAPPA]], axis=1) for p in problems]),
@@ -51,9 +68,10 @@ def _solve(monkeypatch, switch, problems, P, N, n, sampled):
     return outs[0] + (U.cpu().numpy().transpose(0, 3, 1, 2).copy(),)
 
 
-@pytest.mark.parametrize("P,N,H", [(64, 4096, 50),      # 4 workgroups of 1 024 candidates per problem (the headline's shape)
-                                   (301, 2048, 20),     # two candidates per lane: 4 workgroups of 512; a last wavefront of
-                                                        # the finalize with one problem for its four quarters
+@pytest.mark.parametrize("P,N,H", [(64, 4096, 50),      # four candidates per lane (FORCED_SHAPE): 4 workgroups of 1 024 candidates
+                                                        # per problem, the headline's shape per problem
+                                   (301, 2048, 20),     # two candidates per lane (FORCED_SHAPE): 4 workgroups of 512; a last
+                                                        # wavefront of the finalize with one problem for its four quarters
                                    (3, 65536 + 1024, 50),   # beyond the one-launch solve's 1 024 workgroups of 64
                                    (520, 1000, 33),     # a ragged last workgroup, one candidate per lane
                                    (260, 1024, 80),     # 79 steps: more than one pass of a problem's lanes in the finalize
@@ -144,7 +162,8 @@ def test_two_shards_of_many_problems_in_every_finalize_form(monkeypatch, layout)
             np.testing.assert_array_equal(a, b, err_msg=switch)
 
 
-@pytest.mark.parametrize("P,N,H,sampled", [(64, 4096, 50, True),      # the headline's shape: chained (4 finalize rows of 4 workgroups)
+@pytest.mark.parametrize("P,N,H,sampled", [(64, 4096, 50, True),      # the headline's shape per problem, four candidates per lane
+                                                                      # (FORCED_SHAPE): chained, 4 finalize rows of 4 workgroups
                                            (301, 2048, 20, True),     # a ragged last finalize workgroup and a ragged last row
                                            (520, 1000, 33, False),    # winners read from the previous batch's matrix
                                            (3, 4096, 50, True),       # fewer problems than a finalize workgroup takes
@@ -167,6 +186,8 @@ def test_a_stream_of_batches_equals_one_call_per_batch(monkeypatch, P, N, H, sam
     dev = torch.device("cuda", 0)
     eng = Engine(**engine_kwargs(problems[0], 0, P, N, n))
     eng.set_paths(np.stack([p["table"] for p in problems]))
+    if P * N > 131072:   # (the smaller cases are about the stream's edges, on 64-thread workgroups)
+        assert _force_shape(eng, P, N, n)["chained_fits"] == (n <= 59)
     s = torch.cuda.current_stream().cuda_stream
     x0 = torch.tensor(np.stack([p["x0"] for p in problems]), device=dev)
     u_ref = torch.tensor(np.stack([np.stack([p["table"][orc.ROW_V], p["table"][orc.ROW_KAPPA]], axis=1) for p in problems]),
