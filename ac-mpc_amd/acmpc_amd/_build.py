@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libacmpc_hip.so")
 SOURCES = ("acmpc_kernels.hip", "acmpc_rollout.hip", "acmpc_solo.hip", "acmpc_softmin.hip",
            "acmpc_kernels_temporal.hip", "acmpc_capi.hip", "acmpc_prologue.hip", "acmpc_pf.hip",
            "acmpc_speed_profile.cpp", "acmpc_host_path.cpp", "acmpc_dynamic.hip", "acmpc_dynamic_terms.hip", "acmpc_dynamic_coupled.hip",
-           "acmpc_dynamic_loaded.hip", "acmpc_identify.hip",
+           "acmpc_dynamic_loaded.hip", "acmpc_dynamic_obstacles.hip", "acmpc_identify.hip",
            "acmpc_capi_solve.hip", "acmpc_capi_optimize.hip", "acmpc_capi_tick.hip", "acmpc_capi_dynamic.hip", "acmpc_capi_rccl.hip")
 HEADERS = ("acmpc_ctx.h", "acmpc_kernels.h", "acmpc_kernels_impl.h", "acmpc_rollout.h", "acmpc_device.h", "acmpc_dynamic.h", "acmpc_identify.h", "acmpc_frames.h", "acmpc_admm.h", "acmpc_prologue.h", "acmpc_lq.h", "acmpc_lq_box.h",
            os.path.join("..", "..", "include", "acmpc.h"))
@@ -22,7 +22,11 @@ HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-cont
 # per-source extras: the mode-T rollout is faster without the SLP vectoriser's v_pk_* re-packing (measured, see the source)
 # -mfma on the host-only solver: its three sequential sweeps spell out one fma per step (csrc/acmpc_admm.h), which
 # should be the instruction, not a libm call
-EXTRA_FLAGS = {"acmpc_kernels_temporal.hip": ("-fno-slp-vectorize",), "acmpc_speed_profile.cpp": ("-mfma",)}
+# the basic scalar-register allocator for the obstacle kernels: under the default (greedy) one the ensemble finalize over a
+# TermsLoaded keeps a 36-byte stack frame that no instruction touches (an 8-SGPR tuple's spill slot that ends up in VGPR lanes
+# anyway) and so asks for scratch at every launch; the vector registers and the arithmetic are the same either way
+EXTRA_FLAGS = {"acmpc_kernels_temporal.hip": ("-fno-slp-vectorize",), "acmpc_speed_profile.cpp": ("-mfma",),
+               "acmpc_dynamic_obstacles.hip": ("-mllvm", "-sgpr-regalloc=basic")}
 
 
 def find_hipcc() -> str:
@@ -49,7 +53,7 @@ def is_stale() -> bool:
     if not os.path.exists(LIB_PATH) or not os.path.exists(FLAGS_PATH):
         return True
     built = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC_DIR, f) for f in SOURCES + HEADERS]   # (acmpc_dynamic_terms.hip, acmpc_dynamic_coupled.hip and acmpc_dynamic_loaded.hip include acmpc_dynamic.hip; no other unit includes a unit)
+    deps = [os.path.join(CSRC_DIR, f) for f in SOURCES + HEADERS]   # (acmpc_dynamic_terms.hip, acmpc_dynamic_coupled.hip, acmpc_dynamic_loaded.hip and acmpc_dynamic_obstacles.hip include acmpc_dynamic.hip; no other unit includes a unit)
     deps.append(os.path.abspath(__file__))
     if any(os.path.getmtime(d) > built for d in deps):
         return True

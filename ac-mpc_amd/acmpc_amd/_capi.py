@@ -161,6 +161,8 @@ SIGNATURES = {
     "acmpc_set_dynamics_integration": (C.c_int, [_CTX, C.c_int32, C.c_double, C.c_double]),
     "acmpc_set_dynamics_terms": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "acmpc_set_previous_control": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
+    "acmpc_set_obstacles": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "acmpc_set_dynamics_clearance": (C.c_int, [_CTX, C.c_double, C.c_double]),
     "acmpc_set_dynamics_objective": (C.c_int, [_CTX, C.c_double, C.c_void_p]),
     "acmpc_set_dynamics_coupling": (C.c_int, [_CTX, C.c_void_p]),
     "acmpc_set_dynamics_load_transfer": (C.c_int, [_CTX, C.c_void_p]),
@@ -726,6 +728,32 @@ class Engine:
         if u.ndim != 2 or u.shape[1] != 2:
             raise ValueError("u_prev must be [P, 2]")
         self._check(self._lib.acmpc_set_previous_control(self._ctx, u.ctypes.data, u.shape[0]))
+
+    def set_dynamics_clearance(self, weight=0.0, margin=0.0):
+        """Mode D's soft clearance (acmpc_set_dynamics_clearance): inside `margin` of an obstacle disc's rim a candidate pays
+        0.5 `weight` times the squared depth, per disc and control step.  (0, 0) switches it off; the penetration of the
+        discs themselves counts as violation whatever this is.  The setting outlives a change of vehicle, of any other
+        setting and of the obstacles."""
+        self._check(self._lib.acmpc_set_dynamics_clearance(self._ctx, float(weight), float(margin)))
+
+    def set_obstacles(self, positions=None, radii=None):
+        """Mode D's moving obstacles (acmpc_set_obstacles): `positions` [P, n, K, 2] (or [n, K, 2]) in the caller's frame -
+        row i is where disc k is at the state after control step i, time (i + 1) dt - and `radii` [P, K] (or [K]): each
+        obstacle's radius plus the ego's.  Up to 8 discs per problem; a NaN position is a disc that does not exist at that
+        step.  None clears them.  They stay until replaced or cleared."""
+        if positions is None:
+            self._check(self._lib.acmpc_set_obstacles(self._ctx, None, None, 0, 0, 0))
+            return
+        o = np.ascontiguousarray(positions, dtype=np.float32)
+        r = np.ascontiguousarray(radii, dtype=np.float32)
+        if o.ndim == 3:
+            o, r = o[None], r[None] if r.ndim == 1 else r
+        if o.ndim != 4 or o.shape[3] != 2 or r.shape != (o.shape[0], o.shape[2]):
+            raise ValueError("positions must be [P, n, K, 2] and radii [P, K]")
+        if o.shape[2] == 0:
+            self._check(self._lib.acmpc_set_obstacles(self._ctx, None, None, 0, 0, 0))
+            return
+        self._check(self._lib.acmpc_set_obstacles(self._ctx, o.ctypes.data, r.ctypes.data, o.shape[0], o.shape[1], o.shape[2]))
 
     def score_grips(self, states, controls, dt: float, scales, segment: int = 1, weights=(1.0, 1.0, 1.0)):
         """Mode D's grip identification (acmpc_score_grips): `states` [W + 1, 3] = (vx, vy, r) - or [W + 1, 6], whose last

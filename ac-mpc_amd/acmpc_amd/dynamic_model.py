@@ -273,3 +273,28 @@ def objective_terms(states, U, table, progress_weight: float = 0.0, speed_ceilin
         scale, offset = (float(speed_ceiling), 0.0) if np.ndim(speed_ceiling) == 0 else (float(c) for c in speed_ceiling)
         extra_V = float(np.sum(np.maximum(states[1:, 3] - (scale * v[j] + offset), 0.0) ** 2))
     return float(s), extra_V
+
+
+def clearance_terms(xy, obstacles, radii, weight: float = 0.0, margin: float = 0.0) -> Tuple[float, float]:
+    """The obstacles' lines of acmpc_set_obstacles / acmpc_set_dynamics_clearance in float64 over `xy` [n, 2] - the
+    positions after each control step, states[1:, :2] of params.rollout(state, U, ...) - `obstacles` [n, K, 2], where row i
+    holds the discs at that same state, and `radii` [K] (each obstacle's plus the ego's): (cost, violation) with
+    cost = 1/2 weight sum_ik max(R_k + margin - d_ik, 0)^2 and violation = sum_ik max(R_k - d_ik, 0)^2, d_ik the distance
+    from the position to disc k's centre.  A NaN or infinite coordinate is a disc that does not exist at that step."""
+    xy = np.asarray(xy, dtype=np.float64)
+    obstacles = np.asarray(obstacles, dtype=np.float64)
+    radii = np.asarray(radii, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        d = np.sqrt(np.sum((xy[:, None, :] - obstacles) ** 2, axis=2))
+        h = np.fmax(radii[None, :] - d, 0.0)
+        g = np.fmax((radii[None, :] + float(margin)) - d, 0.0)
+    return 0.5 * float(weight) * float(np.sum(g * g)), float(np.sum(h * h))
+
+
+def predict_obstacles(position, velocity, n: int, dt: float) -> np.ndarray:
+    """The constant-velocity table acmpc_set_obstacles takes: [n, K, 2], row i = position + velocity (i + 1) dt - where
+    the K discs at `position` [K, 2] moving with `velocity` [K, 2] are when control step i has been taken."""
+    position = np.asarray(position, dtype=np.float64).reshape(-1, 2)
+    velocity = np.asarray(velocity, dtype=np.float64).reshape(-1, 2)
+    t = (np.arange(int(n), dtype=np.float64) + 1.0) * float(dt)
+    return position[None, :, :] + velocity[None, :, :] * t[:, None, None]

@@ -43,6 +43,12 @@ default None - lets each axle's load, and with it its Pacejka peak and its coupl
 under braking the front axle gains grip and the rear loses it.  Beside `tyre_coupling` it moves the braking limit (about 10 %
 more deceleration on the reference vehicle at h_cg = 0.35) and takes rear side force from a plan that turns in on the brakes.
 
+Obstacles (acmpc_set_obstacles, acmpc_set_dynamics_clearance): `solve(..., obstacles=(positions [n, K, 2], radii [K]))` - up
+to 8 discs with a position per control step (row i at time (i + 1) dt; dynamic_model.predict_obstacles makes the
+constant-velocity table), each radius with the ego's folded in - makes a candidate that enters a disc infeasible, as one
+that leaves the corridor is; `clearance_cost` / `clearance_margin` (default 0) add 0.5 cost depth^2 inside the margin round
+each disc.  An opponent car is two or three discs along its length.
+
 Grip adaptation (acmpc_score_grips, GripEstimator): `grip_adapt` - a dict, off by default - lets the solver find the road's
 grip from its own driving instead of being told an ensemble.  Every solve logs (state, the control applied since the
 previous solve - `previous_control`, else the last accepted plan's first control), scores a grid of grip hypotheses
@@ -140,6 +146,9 @@ class DynamicSamplingSolver:
         objective = _capi.dynamics_objective(config.get("progress_cost", 0.0), config.get("speed_ceiling"))
         coupling = _capi.dynamics_coupling(config.get("tyre_coupling"))
         load_transfer = _capi.dynamics_load_transfer(config.get("load_transfer"))
+        clearance = (float(config.get("clearance_cost", 0.0)), float(config.get("clearance_margin", 0.0)))
+        if not all(0.0 <= v <= float(np.finfo(np.float32).max) for v in clearance):   # (a NaN compares false)
+            raise ValueError("clearance_cost and clearance_margin must be finite and >= 0, not %r" % (clearance,))
         self._centre_update = config.get("sampling_update", "argmin")   # or "softmin" (MPPI-style weighted mean)
         if self._centre_update not in SAMPLING_UPDATES:
             raise ValueError("sampling_update is 'argmin' or 'softmin', not %r" % (self._centre_update,))
@@ -171,6 +180,9 @@ class DynamicSamplingSolver:
             self._engine.set_dynamics_coupling(coupling)
         if load_transfer is not None:
             self._engine.set_dynamics_load_transfer(load_transfer)
+        if clearance != (0.0, 0.0):
+            self._engine.set_dynamics_clearance(*clearance)
+        self._has_obstacles = False
         self._plan: Optional[np.ndarray] = None
         self._calls = 0
         self._adapt = adapt
@@ -219,10 +231,11 @@ class DynamicSamplingSolver:
             self._applied_grip = now
             self._base_grip = (now[0] * self._adapt["bracket"][0], now[1] * self._adapt["bracket"][0])
 
-    def solve(self, state, reference_path, previous_control=None):
+    def solve(self, state, reference_path, previous_control=None, obstacles=None):
         """state (X, Y, yaw, vx, vy, r); reference_path a [7, n] table (rows x, y, psi, kappa, ds, width, v) or an object
         with `as_table()` / `_reference_path` giving one.  `previous_control` = (delta, pedal) applied just before this
-        solve, for the rate terms' step 0; None: the first control of the last accepted plan (none before there is one)."""
+        solve, for the rate terms' step 0; None: the first control of the last accepted plan (none before there is one).
+        `obstacles` = (positions [n, K, 2], radii [K]) for this solve (Engine.set_obstacles); None: no obstacles."""
         table = reference_path
         if hasattr(reference_path, "as_table"):
             table = reference_path.as_table()
@@ -236,6 +249,13 @@ class DynamicSamplingSolver:
             if previous_control is None and self._plan is not None:
                 previous_control = self._plan[0]
             self._engine.set_previous_control(previous_control)
+        if obstacles is not None:
+            positions = np.asarray(obstacles[0], dtype=np.float32)[: self._n]
+            self._engine.set_obstacles(positions, np.asarray(obstacles[1], dtype=np.float32))
+            self._has_obstacles = True
+        elif self._has_obstacles:
+            self._engine.set_obstacles(None)
+            self._has_obstacles = False
         out = self._engine.optimize(np.asarray(state, dtype=np.float32).reshape(1, 6), self.warm_start()[None], None,
                                     self._N, self._rounds, self._sigma, seed=self._seed + self._calls)
         self._calls += 1

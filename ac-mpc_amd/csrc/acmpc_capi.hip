@@ -126,7 +126,19 @@ int ensure_device(acmpc_ctx* c) {
 }
 
 // mode D: the previous control staged by acmpc_set_previous_control goes up on the stream of the call that reads it
+// and with it the obstacles staged by acmpc_set_obstacles (one block: positions, then radii)
 int upload_previous_control(acmpc_ctx* c, hipStream_t s) {
+  if (c->obs_dirty && c->obs_K != 0 && c->device_ready) {
+    if (c->obs_capacity < c->h_obs.size()) {   // (hipFree waits for whatever still reads the old block)
+      (void)hipFree(c->d_obs);
+      c->d_obs = nullptr;
+      c->obs_capacity = 0;
+      ACMPC_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_obs), c->h_obs.size() * sizeof(float)));
+      c->obs_capacity = c->h_obs.size();
+    }
+    ACMPC_HIP(c, hipMemcpyAsync(c->d_obs, c->h_obs.data(), c->h_obs.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    c->obs_dirty = false;
+  }
   if (!c->uprev_dirty || c->uprev_P == 0 || c->d_uprev == nullptr) return ACMPC_OK;
   ACMPC_HIP(c, hipMemcpyAsync(c->d_uprev, c->h_uprev.data(), c->h_uprev.size() * sizeof(float), hipMemcpyHostToDevice, s));
   c->uprev_dirty = false;
@@ -211,6 +223,12 @@ int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call)
     char buf[160];
     std::snprintf(buf, sizeof buf, "P=%d does not match the previous controls set (P=%d): acmpc_set_previous_control", P,
                   c->uprev_P);
+    return fail(c, ACMPC_ESTATE, buf);
+  }
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC && c->obs_K != 0 && (P != c->obs_P || n != c->obs_n)) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "shape (P=%d, n=%d) does not match the obstacles set (P=%d, n=%d): acmpc_set_obstacles", P, n,
+                  c->obs_P, c->obs_n);
     return fail(c, ACMPC_ESTATE, buf);
   }
   return ACMPC_OK;
@@ -485,6 +503,7 @@ void acmpc_destroy(acmpc_ctx* c) {
     (void)hipFree(c->d_soft_partial);
     (void)hipFree(c->d_segments);
     (void)hipFree(c->d_uprev);
+    (void)hipFree(c->d_obs);
     (void)hipFree(c->d_progress);
     (void)hipFree(c->d_identify);
     (void)hipFree(c->d_identify_e);

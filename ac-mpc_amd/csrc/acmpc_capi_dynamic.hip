@@ -1,5 +1,5 @@
 // C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
-// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the previous control, and the grip
+// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the previous control, the obstacles and the clearance setting, and the grip
 // identification (acmpc_score_grips), with the checks that the kernels' limits are the public header's.
 #include <algorithm>
 
@@ -12,6 +12,7 @@ namespace {
 
 static_assert(acmpc::kIdentifyMaxSteps == ACMPC_MAX_LOG_STEPS && acmpc::kIdentifyMaxHypotheses == ACMPC_MAX_GRIP_HYPOTHESES,
               "the grip identification's limits of acmpc_identify.h are the header's");
+static_assert(acmpc::kMaxObstacles == ACMPC_MAX_OBSTACLES, "the obstacle limit of acmpc_dynamic.h is the header's");
 static_assert(acmpc::kMaxSubsteps == ACMPC_MAX_SUBSTEPS, "the sub-step limit of acmpc_dynamic.h is the header's");
 static_assert(acmpc::kMaxVehicles == ACMPC_MAX_VEHICLES && acmpc::kEnsembleMean == ACMPC_ENSEMBLE_MEAN &&
                   acmpc::kEnsembleMax == ACMPC_ENSEMBLE_MAX,
@@ -316,6 +317,43 @@ int acmpc_set_previous_control(acmpc_ctx* c, const float* u_prev, int32_t P) {
   c->h_uprev.assign(u_prev, u_prev + static_cast<size_t>(P) * 2);
   c->uprev_P = P;
   c->uprev_dirty = true;
+  return ACMPC_OK;
+}
+
+int acmpc_set_obstacles(acmpc_ctx* c, const float* positions, const float* radii, int32_t P, int32_t n, int32_t K) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_obstacles needs a mode D handle");
+  if (positions == nullptr || K == 0) {
+    c->h_obs.clear();
+    c->obs_P = c->obs_n = c->obs_K = 0;
+    c->obs_dirty = false;
+    return ACMPC_OK;
+  }
+  if (K < 0 || K > ACMPC_MAX_OBSTACLES) return fail(c, ACMPC_EINVAL, "a problem has 0 .. ACMPC_MAX_OBSTACLES = 8 obstacle discs");
+  if (P < 1 || P > c->prm.max_problems) return fail(c, ACMPC_EINVAL, "P must be 1 .. max_problems");
+  if (n < 1 || n > c->prm.max_steps) return fail(c, ACMPC_EINVAL, "n must be 1 .. max_steps");
+  if (radii == nullptr) return fail(c, ACMPC_EINVAL, "null radii");
+  const size_t discs = static_cast<size_t>(P) * K, floats = discs * n * 2;
+  for (size_t q = 0; q < discs; ++q)
+    if (!std::isfinite(radii[q]) || !(radii[q] >= 0.0f)) return fail(c, ACMPC_EINVAL, "an obstacle's radius must be finite and >= 0");
+  // everything is checked before anything is kept: refused data leaves the handle's as it was
+  c->h_obs.assign(positions, positions + floats);
+  c->h_obs.insert(c->h_obs.end(), radii, radii + discs);
+  c->obs_P = P;
+  c->obs_n = n;
+  c->obs_K = K;
+  c->obs_dirty = true;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_clearance(acmpc_ctx* c, double weight, double margin) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_dynamics_clearance needs a mode D handle");
+  // float32 is what the kernels get: a value that overflows it is not finite there
+  if (!std::isfinite(static_cast<float>(weight)) || !(weight >= 0.0)) return fail(c, ACMPC_EINVAL, "the clearance weight must be finite and >= 0");
+  if (!std::isfinite(static_cast<float>(margin)) || !(margin >= 0.0)) return fail(c, ACMPC_EINVAL, "the clearance margin must be finite and >= 0");
+  c->clearance_weight = weight + 0.0;   // (-0.0 is 0)
+  c->clearance_margin = margin + 0.0;
   return ACMPC_OK;
 }
 

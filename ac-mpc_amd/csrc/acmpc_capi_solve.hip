@@ -16,8 +16,10 @@ namespace capi __attribute__((visibility("hidden"))) {
 // objective ("Progress and ceiling"): the progress part is on with a weight that is not 0, the ceiling part when one is set.
 // And of its tyre coupling ("Tyre coupling"): the two ratios.
 // And of its load transfer ("Load transfer"): the six scalars of each vehicle, and the ratios +inf while the coupling is off.
-static acmpc::TermsLoaded dynamics_terms(const acmpc_ctx* c) {
-  acmpc::TermsLoaded t{};
+// And of its obstacles ("Obstacles"): the device block (positions, then radii), what it was set for, and the clearance
+// setting; K = 0 while none are set, the soft part on with a weight that is not 0.
+static acmpc::WithObstacles<acmpc::TermsLoaded> dynamics_terms(const acmpc_ctx* c) {
+  acmpc::WithObstacles<acmpc::TermsLoaded> t{};
   t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
             std::isfinite(c->rate_max[1])) ? 1 : 0;
   t.slip = (c->slip_weight != 0.0 || std::isfinite(c->slip_max)) ? 1 : 0;
@@ -47,6 +49,16 @@ static acmpc::TermsLoaded dynamics_terms(const acmpc_ctx* c) {
     t.a2_f[k] = lc[3];
     t.a1_r[k] = lc[4];
     t.a2_r[k] = lc[5];
+  }
+  t.K = c->obs_K;
+  if (t.K != 0 && !c->obs_dirty && c->d_obs != nullptr) {   // (every mode D call uploads first; a launch without the data is refused)
+    t.obs = c->d_obs;
+    t.radii = c->d_obs + static_cast<size_t>(c->obs_P) * c->obs_n * c->obs_K * 2;
+    t.P = c->obs_P;
+    t.n = c->obs_n;
+    t.soft = (static_cast<float>(c->clearance_weight) != 0.0f) ? 1 : 0;
+    t.hwo = 0.5f * static_cast<float>(c->clearance_weight);
+    t.mg = static_cast<float>(c->clearance_margin);
   }
   return t;
 }

@@ -294,6 +294,15 @@ struct acmpc_ctx {
   double load_setting[2] = {0.0, 0.0};
   double vehicle_axle[acmpc::kMaxVehicles][4] = {};
   float load_const[acmpc::kMaxVehicles][6] = {};
+  // mode D: the moving obstacles (acmpc_set_obstacles), staged here like the previous control until the next upload: positions
+  // [obs_P][obs_n][obs_K][2] then radii [obs_P][obs_K] in one block, on the host and on the device (allocated by the upload
+  // that first needs it, grown when a larger one arrives); and the clearance setting (acmpc_set_dynamics_clearance)
+  std::vector<float> h_obs;
+  int obs_P = 0, obs_n = 0, obs_K = 0;   // obs_K = 0: none set
+  bool obs_dirty = false;
+  float* d_obs = nullptr;
+  size_t obs_capacity = 0;               // floats
+  double clearance_weight = 0.0, clearance_margin = 0.0;
 
   mutable std::string err;
 };

@@ -412,6 +412,55 @@ struct TermsLoaded : TermsCoupled {
 };
 __host__ __device__ inline bool has_load_transfer(const TermsLoaded& t) { return t.loaded != 0; }
 
+// Moving obstacles of a handle (acmpc_set_obstacles, acmpc_set_dynamics_clearance; DESIGN.md section 2 "Mode D, obstacles"): up
+// to kMaxObstacles discs per problem, each with a position per control step - row i is where the discs are at the state AFTER
+// control step i, the state that step's dynamic_cost sees - and a radius with the ego's folded in.  Per step, after the ceiling
+// line, disc k's penetration depth joins V (the hard part, on while K > 0) and its depth into the margin joins E (the soft part,
+// on while K > 0 and the weight is not 0).  A pack type again, over the pack of the step the handle would take without obstacles
+// (TermsObjective: the general step, TermsCoupled, TermsLoaded): the kernels instantiated for the three (acmpc_dynamic_obstacles
+// .hip) run only while obstacles are set, every other kernel stays the code it was.  obs [P][n][K][2] in the caller's frame and
+// radii [P][K] are read from global memory (problem and step are uniform in every kernel: one broadcast per step, no LDS).
+// coef: the packed rows of the launch (the first two floats of a problem's are the origin of the path's own frame,
+// start_temporal); the launchers set it from their arguments, the handle leaves it null.
+constexpr int kMaxObstacles = 8;   // ACMPC_MAX_OBSTACLES
+template <typename Base>
+struct WithObstacles : Base {
+  const float* obs;
+  const float* radii;
+  const float* coef;
+  int K;                        // 0: none set (nothing else of this is read)
+  int soft;                     // 0: the soft part is off (hwo, mg not read)
+  int P, n;                     // what obs and radii were set for: the launchers refuse another shape
+  float hwo, mg;                // 0.5f * float32(weight): exact; float32(margin)
+};
+template <typename Base>
+__host__ __device__ inline bool has_obstacles(const WithObstacles<Base>& t) { return t.K != 0; }
+template <typename TT>
+struct PackBase { using type = TT; };
+template <typename Base>
+struct PackBase<WithObstacles<Base>> { using type = Base; };
+// the obstacles' pack over another base (the handle's settings are a WithObstacles<TermsLoaded>)
+template <typename Base, typename From>
+inline WithObstacles<Base> obstacles_over(const WithObstacles<From>& t) {
+  WithObstacles<Base> r{};
+  static_cast<Base&>(r) = static_cast<const Base&>(t);
+  r.obs = t.obs;
+  r.radii = t.radii;
+  r.coef = t.coef;
+  r.K = t.K;
+  r.soft = t.soft;
+  r.P = t.P;
+  r.n = t.n;
+  r.hwo = t.hwo;
+  r.mg = t.mg;
+  return r;
+}
+// whether the soft part adds to E: false for every pack without obstacles (a constant: their finish stays the code it was)
+template <typename TT>
+__device__ __forceinline__ bool soft_part(const TT&) { return false; }
+template <typename Base>
+__device__ __forceinline__ bool soft_part(const WithObstacles<Base>& t) { return t.soft != 0; }
+
 // what the terms carry from step to step: the previous step's control and the cost sum
 template <typename F>
 struct TermsState {
@@ -434,10 +483,11 @@ __device__ __forceinline__ TermsState<F>& state_of(TermsState<F>& ts, const Term
   return ts;
 }
 
-// Whether a kernel's pack (`TM...`, or roll_sampled's `TT...` with the terms' state first) holds a TermsCoupled, and the peak
+// Whether a kernel's pack (`TM...`, or roll_sampled's `TT...` with the terms' state first) holds a TermsCoupled (or the obstacles'
+// pack over one: PackBase sees through it), and the peak
 // source its control step then takes: dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(..., coupled_peaks(tm...))
 template <typename... TM>
-constexpr bool kCoupledPack = (std::is_same<typename std::remove_cv<TM>::type, TermsCoupled>::value || ...);
+constexpr bool kCoupledPack = (std::is_same<typename PackBase<typename std::remove_cv<TM>::type>::type, TermsCoupled>::value || ...);
 __device__ __forceinline__ CoupledPeaks<VehiclePeaks> coupled_peaks(const TermsCoupled& t) {
   return CoupledPeaks<VehiclePeaks>{{}, t.rho_f, t.rho_r};
 }
@@ -449,7 +499,7 @@ __device__ __forceinline__ CoupledPeaks<VehiclePeaks> coupled_peaks(const TermsS
 // The same for a TermsLoaded: dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(..., loaded_peaks(vk, tm...)), vk the
 // wave-uniform index of the vehicle rolled
 template <typename... TM>
-constexpr bool kLoadedPack = (std::is_same<typename std::remove_cv<TM>::type, TermsLoaded>::value || ...);
+constexpr bool kLoadedPack = (std::is_same<typename PackBase<typename std::remove_cv<TM>::type>::type, TermsLoaded>::value || ...);
 __device__ __forceinline__ LoadedPeaks<VehiclePeaks> loaded_peaks(int vk, const TermsLoaded& t) {
   return LoadedPeaks<VehiclePeaks>{{{}, t.rho_f, t.rho_r}, t.c_h[vk], t.w_max[vk], t.a1_f[vk], t.a2_f[vk], t.a1_r[vk], t.a2_r[vk]};
 }
@@ -469,12 +519,13 @@ __device__ __forceinline__ void keep_nearest(typename IndexOf<F>::type j, TermsS
   ts.j = j;
 }
 
-// the terms of one control step, on the state the step's dynamic_cost saw; `first`: step 0; wp, j: the staged rows and the
+// the terms of control step i of problem p, on the state the step's dynamic_cost saw; wp, j: the staged rows and the
 // nearest waypoint(s) that dynamic_cost used (the ceiling reads v_ref_j, float 5 of the row, again)
 template <typename F, typename TT>
-__device__ __forceinline__ void dynamic_terms(StateD_<F>& s, F delta, F pedal, bool first, const Vehicle& k,
+__device__ __forceinline__ void dynamic_terms(StateD_<F>& s, F delta, F pedal, int i, [[maybe_unused]] int p, const Vehicle& k,
                                               [[maybe_unused]] const float* wp, [[maybe_unused]] typename IndexOf<F>::type j,
                                               TermsState<F>& ts, const TT& t) {
+  const bool first = i == 0;
   if (t.rate != 0) {
     const bool own = first && t.u_prev == nullptr;
     const F pd = own ? delta : ts.pd;
@@ -504,8 +555,39 @@ __device__ __forceinline__ void dynamic_terms(StateD_<F>& s, F delta, F pedal, b
   }
 }
 
+// The same under the obstacles' pack: the base pack's terms, then the discs in k order on a kernel argument - a scalar loop, no
+// divergence.  Spec order: ox = o_x - x_0 (one subtraction), dx = X - ox, d = sqrt(fma(dy, dy, dx dx)), h = max(R - d, 0),
+// V = fma(h, h, V); and while the soft part is on g = max((R + mg) - d, 0), E = fma(hwo g, g, E).  max is maxNum: a NaN or
+// infinite coordinate gives h = g = 0 - that disc does not exist at that step.  Problem and step are wave-uniform: lane k of the
+// wave loads disc k of the step's row (one 8-byte load and the radius; the lanes past K - 1 repeat the last disc) and the loop
+// broadcasts lane k's three floats with v_readlane - one load's latency per step, not K scalar ones, and nothing of the row in
+// the SGPRs, which the step loop has none to spare of.
+template <typename F, typename Base>
+__device__ __forceinline__ void dynamic_terms(StateD_<F>& s, F delta, F pedal, int i, int p, const Vehicle& k, const float* wp,
+                                              typename IndexOf<F>::type j, TermsState<F>& ts, const WithObstacles<Base>& t) {
+  const float* __restrict__ coef = t.coef + static_cast<size_t>(p) * t.n * kCoefT;
+  const int mine = min(static_cast<int>(__lane_id()), t.K - 1);   // (issued ahead of the base pack's terms: the load's latency)
+  const f32x2 at = *reinterpret_cast<const f32x2*>(t.obs + ((static_cast<size_t>(p) * t.n + i) * t.K + mine) * 2);
+  const int ox_l = __float_as_int(at[0] - coef[0]), oy_l = __float_as_int(at[1] - coef[1]);
+  const int R_l = __float_as_int(t.radii[static_cast<size_t>(p) * t.K + mine]);
+  dynamic_terms<F, Base>(s, delta, pedal, i, p, k, wp, j, ts, static_cast<const Base&>(t));
+#pragma nounroll
+  for (int q = 0; q < t.K; ++q) {
+    const float ox = __int_as_float(__builtin_amdgcn_readlane(ox_l, q)), oy = __int_as_float(__builtin_amdgcn_readlane(oy_l, q));
+    const float R = __int_as_float(__builtin_amdgcn_readlane(R_l, q));
+    const F dx = s.t.X - splat<F>(ox), dy = s.t.Y - splat<F>(oy);
+    const F d = sqrt_(fma_(dy, dy, dx * dx));
+    const F h = vmax(splat<F>(R) - d, splat<F>(0.0f));
+    s.t.V = fma_(h, h, s.t.V);
+    if (t.soft != 0) {
+      const F g = vmax(splat<F>(R + t.mg) - d, splat<F>(0.0f));
+      ts.E = fma_(t.hwo * g, g, ts.E);
+    }
+  }
+}
+
 // finish_temporal (acmpc_device.h) with the terms: stage = stage + E after the last weighted sum when the rate or the slip
-// part is on (under a plain Terms one of them is), and J = fma(nwp, s, J) between J = stage + a and the violations' fma when the progress part is on.  wp, j: the
+// part is on (under a plain Terms one of them is) or the obstacles' soft part is, and J = fma(nwp, s, J) between J = stage + a and the violations' fma when the progress part is on.  wp, j: the
 // staged rows and the nearest waypoint(s) of the last control step; p: the problem, whose row of the progress table is read
 // from global memory (one gather per candidate).
 template <typename F, typename TT>
@@ -519,7 +601,7 @@ __device__ __forceinline__ F finish_dynamic_terms(const StateD_<F>& s, const Ter
   stage = fma_(splat<F>(w.hq1), st.S1, stage);
   stage = fma_(splat<F>(w.hr0), st.S2, stage);
   stage = fma_(splat<F>(w.hr1), st.S3, stage);
-  if (!kObjective || t.rate != 0 || t.slip != 0) stage = stage + ts.E;
+  if (!kObjective || t.rate != 0 || t.slip != 0 || soft_part(t)) stage = stage + ts.E;
   F a = (w.hqn0 * st.ey) * st.ey;
   a = fma_(w.hqn1 * st.ep, st.ep, a);
   a = fma_(splat<F>(w.hqn2 * tN), splat<F>(tN), a);
@@ -576,22 +658,23 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // `terms`: the handle's rate and slip terms and its objective; when any part is on, the kernels that hold them run, with the general step whatever the
 // integration setting (the default one as M = 1, no blend, h = float32(dt)).  And its tyre coupling: while that is on, the
 // coupled kernels run, whatever the parts.  And its load transfer: while that is on, the loaded kernels run, whatever the
-// coupling and the parts.
+// coupling and the parts.  And its obstacles: while any are set, the obstacle kernels of the step the handle would take
+// without them run (the general, the coupled or the loaded one), looked at first.
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& integration, const TermsLoaded& terms, hipStream_t s);
+                                  const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const TermsLoaded& terms, hipStream_t s);
+                                          const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& integration, const TermsLoaded& terms, hipStream_t s);
+                                   const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
 // what the three above call when has_terms(terms) or has_objective(terms) (acmpc_dynamic_terms.hip: the kernels of a plain
 // Terms in the first case alone, those of a TermsObjective otherwise)
 hipError_t launch_rollout_dynamic_terms(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
@@ -617,5 +700,15 @@ hipError_t launch_rollout_dynamic_sampled_loaded(const RolloutArgs& args, const 
                                                  const TermsLoaded& terms, hipStream_t s);
 hipError_t launch_finalize_dynamic_loaded(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
                                           const Integration& integration, const TermsLoaded& terms, hipStream_t s);
+// and while has_obstacles(terms), before anything else is looked at (acmpc_dynamic_obstacles.hip: the kernels of a
+// WithObstacles over TermsLoaded, TermsCoupled or TermsObjective - the step the handle would take without obstacles).
+// hipErrorInvalidValue unless 1 <= K <= kMaxObstacles and terms.P / terms.n are the launch's.
+hipError_t launch_rollout_dynamic_obstacles(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                            const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_sampled_obstacles(const RolloutArgs& args, const SampleArgs& sample,
+                                                    const VehicleEnsemble& vehicles, const Integration& integration,
+                                                    const WithObstacles<TermsLoaded>& terms, hipStream_t s);
+hipError_t launch_finalize_dynamic_obstacles(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                             const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
 
 }  // namespace acmpc

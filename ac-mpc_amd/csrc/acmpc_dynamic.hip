@@ -58,6 +58,12 @@
 // the general step with the peaks and the ratios (+inf while the coupling is off).  Sixteen instantiations of a fourth
 // translation unit, acmpc_dynamic_loaded.hip, launched only while the load transfer is on.
 //
+// And a seventh, for a handle with moving obstacles (acmpc_set_obstacles; acmpc_dynamic.h: WithObstacles, the second
+// dynamic_terms): the pack is a WithObstacles over the pack of the step the handle would take without them - TermsObjective
+// (the general step), TermsCoupled or TermsLoaded - and the discs' lines follow the ceiling's in every control step, their rows
+// read from global memory at wave-uniform addresses.  Three times sixteen instantiations of a fifth translation unit,
+// acmpc_dynamic_obstacles.hip, launched only while obstacles are set.
+//
 // Built with -ffp-contract=off: see acmpc_device.h.
 #include "acmpc_dynamic.h"
 
@@ -188,7 +194,7 @@ __global__ void __launch_bounds__(kDynBlock)
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
-      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, s_wp, nearest, ts, tm...);
+      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i, p, veh, s_wp, nearest, ts, tm...);
     }
   });
   F cost_v;
@@ -356,7 +362,7 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
-      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, s_wp, nearest, tt...);   // (the state keeps this step's blended control)
+      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i, p, veh, s_wp, nearest, tt...);   // (the state keeps this step's blended control)
     }
   });
   if constexpr (kTerms) keep_nearest<F>(nearest, tt...);   // (the progress part reads the last step's at the finish)
@@ -563,7 +569,7 @@ __global__ void __launch_bounds__(kWave)
     j = (j == 0x7fffffff) ? lo : j;
     j_prev = j;
     dynamic_settle(st, s_wp, j, d, q, w);
-    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i == 0, veh, s_wp, j, ts, tm...);
+    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i, p, veh, s_wp, j, ts, tm...);
     if (lane == 0) {
       sx[3 * (i + 1)] = st.t.X + coef[0];
       sx[3 * (i + 1) + 1] = st.t.Y + coef[1];
@@ -634,7 +640,7 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
-      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i == 0, veh, s_wp, nearest, ts, tm...);
+      if constexpr (kTerms) dynamic_terms<F>(st, d, q, i, p, veh, s_wp, nearest, ts, tm...);
     }
   });
   F cost_v;
@@ -846,7 +852,7 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
     j = (j == 0x7fffffff) ? lo : j;
     j_prev = j;
     dynamic_settle(st, s_wp, j, d, q, w);
-    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i == 0, veh, s_wp, j, ts, tm...);
+    if constexpr (kTerms) dynamic_terms<float>(st, d, q, i, p, veh, s_wp, j, ts, tm...);
     if (writer) {
       sx[3 * (i + 1)] = st.t.X + coef[0];
       sx[3 * (i + 1) + 1] = st.t.Y + coef[1];
@@ -1018,7 +1024,42 @@ hipError_t finalize_dynamic_launch(int layout, const FinalizeArgs& args, const V
 
 }  // namespace
 
-#if defined(ACMPC_DYNAMIC_LOADED_TU)
+#if defined(ACMPC_DYNAMIC_OBSTACLES_TU)
+
+// The handle's settings over the pack of the step it would take without obstacles, with the launch's packed rows beside them;
+// nothing is launched unless the obstacle data is what this launch's P and n index.
+bool obstacles_valid(const WithObstacles<TermsLoaded>& tm, int P, int n) {
+  return tm.K >= 1 && tm.K <= kMaxObstacles && tm.obs != nullptr && tm.radii != nullptr && tm.P == P && tm.n == n;
+}
+
+template <typename Launch>
+hipError_t with_obstacle_pack(WithObstacles<TermsLoaded> tm, const float* coef, Launch&& launch) {
+  tm.coef = coef;
+  if (has_load_transfer(tm)) return launch(tm);
+  if (has_coupling(tm)) return launch(obstacles_over<TermsCoupled>(tm));
+  return launch(obstacles_over<TermsObjective>(tm));
+}
+
+hipError_t launch_rollout_dynamic_obstacles(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                            const Integration& g, const WithObstacles<TermsLoaded>& tm, hipStream_t s) {
+  if (!obstacles_valid(tm, args.P, args.n)) return hipErrorInvalidValue;
+  return with_obstacle_pack(tm, args.coef, [&](const auto& pack) { return rollout_dynamic_launch(layout, args, vehicles, g, s, pack); });
+}
+
+hipError_t launch_rollout_dynamic_sampled_obstacles(const RolloutArgs& args, const SampleArgs& sample,
+                                                    const VehicleEnsemble& vehicles, const Integration& g,
+                                                    const WithObstacles<TermsLoaded>& tm, hipStream_t s) {
+  if (!obstacles_valid(tm, args.P, args.n)) return hipErrorInvalidValue;
+  return with_obstacle_pack(tm, args.coef, [&](const auto& pack) { return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s, pack); });
+}
+
+hipError_t launch_finalize_dynamic_obstacles(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                             const Integration& g, const WithObstacles<TermsLoaded>& tm, hipStream_t s) {
+  if (!obstacles_valid(tm, args.P, args.n)) return hipErrorInvalidValue;
+  return with_obstacle_pack(tm, args.coef, [&](const auto& pack) { return finalize_dynamic_launch(layout, args, vehicles, g, s, pack); });
+}
+
+#elif defined(ACMPC_DYNAMIC_LOADED_TU)
 
 hipError_t launch_rollout_dynamic_loaded(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
                                          const Integration& g, const TermsLoaded& tm, hipStream_t s) {
@@ -1090,7 +1131,8 @@ int dynamic_blocks_per_problem(int P, int N, int K) {
 }
 
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+                                  const Integration& g, const WithObstacles<TermsLoaded>& tm, hipStream_t s) {
+  if (has_obstacles(tm)) return launch_rollout_dynamic_obstacles(layout, args, vehicles, g, tm, s);
   if (has_load_transfer(tm)) return launch_rollout_dynamic_loaded(layout, args, vehicles, g, tm, s);
   if (has_coupling(tm)) return launch_rollout_dynamic_coupled(layout, args, vehicles, g, tm, s);
   if (has_terms(tm) || has_objective(tm)) return launch_rollout_dynamic_terms(layout, args, vehicles, g, tm, s);
@@ -1098,7 +1140,8 @@ hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const Veh
 }
 
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+                                          const Integration& g, const WithObstacles<TermsLoaded>& tm, hipStream_t s) {
+  if (has_obstacles(tm)) return launch_rollout_dynamic_sampled_obstacles(args, sample, vehicles, g, tm, s);
   if (has_load_transfer(tm)) return launch_rollout_dynamic_sampled_loaded(args, sample, vehicles, g, tm, s);
   if (has_coupling(tm)) return launch_rollout_dynamic_sampled_coupled(args, sample, vehicles, g, tm, s);
   if (has_terms(tm) || has_objective(tm)) return launch_rollout_dynamic_sampled_terms(args, sample, vehicles, g, tm, s);
@@ -1106,13 +1149,14 @@ hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleA
 }
 
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+                                   const Integration& g, const WithObstacles<TermsLoaded>& tm, hipStream_t s) {
+  if (has_obstacles(tm)) return launch_finalize_dynamic_obstacles(layout, args, vehicles, g, tm, s);
   if (has_load_transfer(tm)) return launch_finalize_dynamic_loaded(layout, args, vehicles, g, tm, s);
   if (has_coupling(tm)) return launch_finalize_dynamic_coupled(layout, args, vehicles, g, tm, s);
   if (has_terms(tm) || has_objective(tm)) return launch_finalize_dynamic_terms(layout, args, vehicles, g, tm, s);
   return finalize_dynamic_launch(layout, args, vehicles, g, s);
 }
 
-#endif  // ACMPC_DYNAMIC_LOADED_TU, ACMPC_DYNAMIC_COUPLED_TU, ACMPC_DYNAMIC_TERMS_TU
+#endif  // ACMPC_DYNAMIC_OBSTACLES_TU, ACMPC_DYNAMIC_LOADED_TU, ACMPC_DYNAMIC_COUPLED_TU, ACMPC_DYNAMIC_TERMS_TU
 
 }  // namespace acmpc

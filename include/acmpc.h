@@ -354,6 +354,35 @@ int acmpc_set_dynamics_load_transfer(acmpc_ctx* ctx, const double setting[2] /* 
  * stored one returns ACMPC_ESTATE. */
 int acmpc_set_previous_control(acmpc_ctx* ctx, const float* u_prev, int32_t P);
 
+/* Mode D, moving obstacles: up to ACMPC_MAX_OBSTACLES discs per problem that the candidates are to keep clear of, each with a
+ * position per control step.  positions host [P][n][K][2] in the caller's frame: row i is where disc k is at the state AFTER
+ * control step i (time (i + 1) dt), the state that step's cost sees.  radii host [P][K]: the obstacle's radius plus the ego's -
+ * the ego is one disc at the state's (X, Y).  positions == NULL or K == 0 clears the data (the other arguments are then
+ * ignored).  Per control step, after that step's cost and after the rate, slip and ceiling lines where those are on, for
+ * k = 0 .. K - 1 in that order, all float32, nothing fused but the named FMAs, max the IEEE maxNum, sqrt correctly rounded:
+ *   ox = o_x[i][k] - x_0;  oy = o_y[i][k] - y_0           (x_0, y_0): the first waypoint of the problem's packed rows
+ *   dx = X - ox;  dy = Y - oy;  d = sqrt(fma(dy, dy, dx dx))
+ *   h = max(R_k - d, 0);           V = fma(h, h, V)              hard: the penetration depth, like the corridor hinge
+ *   g = max((R_k + mg) - d, 0);    E = fma(hwo g, g, E)          soft: only with a weight (acmpc_set_dynamics_clearance)
+ * The hard part is on while obstacles are set, the soft part while they are set and the clearance weight is not 0; the cost's
+ * stage = stage + E is executed when the rate, the slip or the soft part is on.  A NaN or infinite coordinate gives h = g = 0:
+ * disc k does not exist at step i.  R_k = 0 never violates.  Under an ensemble every vehicle's cost and violation carry the
+ * lines with that vehicle's own trajectory.  acmpc_score_grips does not read obstacles.  Staged on the host; the data travels
+ * to the device with the tables, on the next call's stream (acmpc_sync_tables covers it), and stays until replaced or
+ * cleared.  The positions are not checked.  No device work.  ACMPC_ESTATE for a handle whose mode is not ACMPC_MODE_DYNAMIC;
+ * ACMPC_EINVAL for K outside 0 .. ACMPC_MAX_OBSTACLES, P outside 1 .. max_problems, n outside 1 .. max_steps, a NULL radii or
+ * a radius that is negative or not finite - the handle then keeps what it had; a later mode D call whose P or n is not the
+ * stored one returns ACMPC_ESTATE.  DESIGN.md section 2 "Mode D, obstacles". */
+#define ACMPC_MAX_OBSTACLES 8
+int acmpc_set_obstacles(acmpc_ctx* ctx, const float* positions, const float* radii, int32_t P, int32_t n, int32_t K);
+
+/* Mode D, the soft part of the obstacles' lines: hwo = 0.5f float32(weight) (an exact product), mg = float32(margin), each
+ * double rounded to float32 once.  (0, 0) by default: the soft part is off.  The setting belongs to the handle: it survives
+ * every other acmpc_set_dynamics* call and acmpc_set_obstacles.  No device work.  ACMPC_ESTATE for a handle whose mode is not
+ * ACMPC_MODE_DYNAMIC; ACMPC_EINVAL for a weight or margin that is negative or not finite (as a float32) - the handle then
+ * keeps its previous setting. */
+int acmpc_set_dynamics_clearance(acmpc_ctx* ctx, double weight, double margin);
+
 /* Mode D, grip identification: which vehicle did a logged stretch of driving come from?  K hypotheses - the handle's
  * vehicle 0 (the block of acmpc_set_dynamics, or member 0 of acmpc_set_dynamics_ensemble) with Df scales[k][0] and
  * Dr scales[k][1], derived as every block is (the two peaks in float64, rounded once; everything else vehicle 0's own
