@@ -14,7 +14,7 @@ SOURCES = ("acmpc_kernels.hip", "acmpc_rollout.hip", "acmpc_solo.hip", "acmpc_so
            "acmpc_speed_profile.cpp", "acmpc_host_path.cpp", "acmpc_dynamic.hip", "acmpc_dynamic_terms.hip", "acmpc_dynamic_coupled.hip",
            "acmpc_dynamic_loaded.hip", "acmpc_dynamic_obstacles.hip", "acmpc_identify.hip",
            "acmpc_capi_solve.hip", "acmpc_capi_optimize.hip", "acmpc_capi_tick.hip", "acmpc_capi_dynamic.hip", "acmpc_capi_rccl.hip")
-HEADERS = ("acmpc_ctx.h", "acmpc_kernels.h", "acmpc_kernels_impl.h", "acmpc_rollout.h", "acmpc_device.h", "acmpc_dynamic.h", "acmpc_identify.h", "acmpc_frames.h", "acmpc_admm.h", "acmpc_prologue.h", "acmpc_lq.h", "acmpc_lq_box.h",
+HEADERS = ("acmpc_ctx.h", "acmpc_kernels.h", "acmpc_kernels_impl.h", "acmpc_rollout.h", "acmpc_device.h", "acmpc_dynamic.h", "acmpc_dynamic_kernels.h", "acmpc_identify.h", "acmpc_frames.h", "acmpc_admm.h", "acmpc_prologue.h", "acmpc_lq.h", "acmpc_lq_box.h",
            os.path.join("..", "..", "include", "acmpc.h"))
 
 # -ffp-contract=off: no IMPLICIT fused multiply-add anywhere; the FMAs of mode T's specification are spelt out
@@ -53,7 +53,7 @@ def is_stale() -> bool:
     if not os.path.exists(LIB_PATH) or not os.path.exists(FLAGS_PATH):
         return True
     built = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC_DIR, f) for f in SOURCES + HEADERS]   # (acmpc_dynamic_terms.hip, acmpc_dynamic_coupled.hip, acmpc_dynamic_loaded.hip and acmpc_dynamic_obstacles.hip include acmpc_dynamic.hip; no other unit includes a unit)
+    deps = [os.path.join(CSRC_DIR, f) for f in SOURCES + HEADERS]
     deps.append(os.path.abspath(__file__))
     if any(os.path.getmtime(d) > built for d in deps):
         return True

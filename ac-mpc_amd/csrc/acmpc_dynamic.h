@@ -1,5 +1,6 @@
 // Mode D: candidates scored through the dynamic (Pacejka) bicycle of the reference (src/acmpc/control/
-// dynamic_bicycle_model.py) - device arithmetic and the launchers of its kernels (acmpc_dynamic.hip).
+// dynamic_bicycle_model.py) - device arithmetic and the launchers (acmpc_dynamic.hip) of its kernels
+// (acmpc_dynamic_kernels.h).
 //
 // The float32 "spec order" of DESIGN.md section 2 ("Mode D"), restated bit for bit by tests/dynamic_spec.py: the
 // reference's expression tree evaluated left to right, no fused multiply-add except inside the named polynomial kernels
@@ -675,40 +676,5 @@ hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleA
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
                                    const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
-// what the three above call when has_terms(terms) or has_objective(terms) (acmpc_dynamic_terms.hip: the kernels of a plain
-// Terms in the first case alone, those of a TermsObjective otherwise)
-hipError_t launch_rollout_dynamic_terms(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                        const Integration& integration, const TermsObjective& terms, hipStream_t s);
-hipError_t launch_rollout_dynamic_sampled_terms(const RolloutArgs& args, const SampleArgs& sample,
-                                                const VehicleEnsemble& vehicles, const Integration& integration,
-                                                const TermsObjective& terms, hipStream_t s);
-hipError_t launch_finalize_dynamic_terms(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                         const Integration& integration, const TermsObjective& terms, hipStream_t s);
-// and while has_coupling(terms) (acmpc_dynamic_coupled.hip: the kernels of a TermsCoupled, whichever term parts are on)
-hipError_t launch_rollout_dynamic_coupled(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const TermsCoupled& terms, hipStream_t s);
-hipError_t launch_rollout_dynamic_sampled_coupled(const RolloutArgs& args, const SampleArgs& sample,
-                                                  const VehicleEnsemble& vehicles, const Integration& integration,
-                                                  const TermsCoupled& terms, hipStream_t s);
-hipError_t launch_finalize_dynamic_coupled(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                           const Integration& integration, const TermsCoupled& terms, hipStream_t s);
-// and while has_load_transfer(terms), before the coupling is looked at (acmpc_dynamic_loaded.hip: the kernels of a TermsLoaded)
-hipError_t launch_rollout_dynamic_loaded(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                         const Integration& integration, const TermsLoaded& terms, hipStream_t s);
-hipError_t launch_rollout_dynamic_sampled_loaded(const RolloutArgs& args, const SampleArgs& sample,
-                                                 const VehicleEnsemble& vehicles, const Integration& integration,
-                                                 const TermsLoaded& terms, hipStream_t s);
-hipError_t launch_finalize_dynamic_loaded(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const TermsLoaded& terms, hipStream_t s);
-// and while has_obstacles(terms), before anything else is looked at (acmpc_dynamic_obstacles.hip: the kernels of a
-// WithObstacles over TermsLoaded, TermsCoupled or TermsObjective - the step the handle would take without obstacles).
-// hipErrorInvalidValue unless 1 <= K <= kMaxObstacles and terms.P / terms.n are the launch's.
-hipError_t launch_rollout_dynamic_obstacles(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                            const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
-hipError_t launch_rollout_dynamic_sampled_obstacles(const RolloutArgs& args, const SampleArgs& sample,
-                                                    const VehicleEnsemble& vehicles, const Integration& integration,
-                                                    const WithObstacles<TermsLoaded>& terms, hipStream_t s);
-hipError_t launch_finalize_dynamic_obstacles(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                             const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
 
 }  // namespace acmpc

@@ -1,6 +1,23 @@
-// Translation unit of mode D's kernels with the tyre coupling (acmpc_set_dynamics_coupling): the kernel templates of
-// acmpc_dynamic.hip instantiated with the TermsCoupled argument - the general step with the friction-ellipse block in every
-// sub-step, and the four term parts behind their switches - and their launchers.  Apart from acmpc_dynamic.hip and
-// acmpc_dynamic_terms.hip so that the code objects of the kernels without the coupling are not touched by them.
-#define ACMPC_DYNAMIC_COUPLED_TU 1
-#include "acmpc_dynamic.hip"
+// Mode D's kernels with the tyre coupling (acmpc_set_dynamics_coupling): the templates of acmpc_dynamic_kernels.h with a
+// TermsCoupled - the general step with the friction-ellipse block in every sub-step, the four term parts behind their switches.
+#include "acmpc_dynamic_kernels.h"
+
+namespace acmpc {
+
+hipError_t launch_rollout_dynamic_coupled(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                          const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+  return rollout_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+hipError_t launch_rollout_dynamic_sampled_coupled(const RolloutArgs& args, const SampleArgs& sample,
+                                                  const VehicleEnsemble& vehicles, const Integration& g,
+                                                  const TermsCoupled& tm, hipStream_t s) {
+  return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s, tm);
+}
+
+hipError_t launch_finalize_dynamic_coupled(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                           const Integration& g, const TermsCoupled& tm, hipStream_t s) {
+  return finalize_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+}  // namespace acmpc

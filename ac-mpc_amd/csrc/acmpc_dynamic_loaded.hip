@@ -1,7 +1,23 @@
-// Translation unit of mode D's kernels with the load transfer (acmpc_set_dynamics_load_transfer): the kernel templates of
-// acmpc_dynamic.hip instantiated with the TermsLoaded argument - the general step with the loaded peaks and the
-// friction-ellipse block in every sub-step (the ratios +inf while the coupling is off), and the four term parts behind their
-// switches - and their launchers.  Apart from acmpc_dynamic.hip, acmpc_dynamic_terms.hip and acmpc_dynamic_coupled.hip so that
-// the code objects of the kernels without the load transfer are not touched by them.
-#define ACMPC_DYNAMIC_LOADED_TU 1
-#include "acmpc_dynamic.hip"
+// Mode D's kernels with the load transfer (acmpc_set_dynamics_load_transfer): the templates of acmpc_dynamic_kernels.h with a
+// TermsLoaded - the coupled step on the loaded peaks (the ratios +inf while the coupling is off) and the four term parts.
+#include "acmpc_dynamic_kernels.h"
+
+namespace acmpc {
+
+hipError_t launch_rollout_dynamic_loaded(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                         const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+  return rollout_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+hipError_t launch_rollout_dynamic_sampled_loaded(const RolloutArgs& args, const SampleArgs& sample,
+                                                 const VehicleEnsemble& vehicles, const Integration& g,
+                                                 const TermsLoaded& tm, hipStream_t s) {
+  return rollout_dynamic_sampled_launch(args, sample, vehicles, g, s, tm);
+}
+
+hipError_t launch_finalize_dynamic_loaded(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                          const Integration& g, const TermsLoaded& tm, hipStream_t s) {
+  return finalize_dynamic_launch(layout, args, vehicles, g, s, tm);
+}
+
+}  // namespace acmpc

@@ -1,7 +1,7 @@
 // What the translation units of the gfx950 rollout-and-cost kernels share: the architecture guard, small device helpers,
 // the phase-stamp macros of the A/B tools, and the host side's launch plumbing.  Internal: included only by those units
 // (acmpc_rollout / _kernels_temporal / _kernels / _solo / _softmin .hip; which holds what: DESIGN.md section 4), directly or
-// through acmpc_rollout.h.  Built with -ffp-contract=off: see acmpc_device.h.
+// through acmpc_rollout.h, and by mode D's (acmpc_dynamic*.hip) through acmpc_dynamic_kernels.h for the launch plumbing.  Built with -ffp-contract=off: see acmpc_device.h.
 #pragma once
 #include "acmpc_kernels.h"
 

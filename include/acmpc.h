@@ -528,7 +528,7 @@ int acmpc_solve_sampled_device(acmpc_ctx* ctx, const float* d_x0, const float* d
 
 /* Mode D only: acmpc_sample_device into a matrix + acmpc_rollout_device of it WITHOUT the matrix - every lane draws its
  * candidate (global index index_offset + c: the same candidate as acmpc_sample_device's, bit for bit) inside the rollout
- * kernel and blends each step's control as it goes (csrc/acmpc_dynamic.hip rollout_dynamic_sampled_kernel).  d_x0 [P][6];
+ * kernel and blends each step's control as it goes (csrc/acmpc_dynamic_kernels.h rollout_dynamic_sampled_kernel).  d_x0 [P][6];
  * d_centre / centre_stride / d_u_ref / sigma_v, sigma_kappa (= sigma_delta, sigma_pedal) / seed / round as
  * acmpc_sample_device takes them; d_costs [P][N] or NULL and d_keys [P] or NULL as acmpc_rollout_device leaves them - the
  * same bits.  Follow it with acmpc_finalize_sampled_device (after acmpc_reduce_across_ranks when the candidates are spread

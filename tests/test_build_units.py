@@ -47,8 +47,16 @@ def test_every_quoted_include_is_a_member():
 
 
 def test_no_unit_is_compiled_twice_under_a_macro():
+    """No unit is another file's #include, and nothing defines or tests a which-unit-am-I macro (ACMPC_<NAME>_TU:
+    ACMPC_TEMPORAL_TU once, then ACMPC_DYNAMIC_TERMS_TU and three more)."""
+    units = {os.path.normpath(os.path.join(_build.CSRC_DIR, name)) for name in _build.SOURCES}
     for path in csrc_files():
-        assert "ACMPC_TEMPORAL_TU" not in open(path).read(), os.path.basename(path)
+        text = open(path).read()
+        for target in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M):
+            resolved = os.path.normpath(os.path.join(os.path.dirname(path), target))
+            assert resolved not in units, "%s includes the unit %s" % (os.path.basename(path), target)
+        found = re.search(r"\bACMPC_\w+_TU\b", text)
+        assert found is None, "%s: %s" % (os.path.basename(path), found and found.group(0))
 
 
 def test_the_lds_limit_is_keyed_by_the_kernel():

@@ -6,7 +6,8 @@ taken out where it is empty or one Terms, so that a file from before the pack ex
 of any other pack (TermsObjective) keeps its name and is counted among the new file's only.  Prints what differs and how many
 kernels are identical; exit status 1 unless every kernel of OLD is in NEW and identical.
 
-usage: hipcc <the library's flags> -c csrc/acmpc_dynamic.hip -o unit.o --save-temps     (at both commits, in two directories)
+usage: hipcc <the library's flags + the unit's own> -c csrc/acmpc_dynamic.hip -o unit.o --save-temps     (at both commits, in two
+       directories; mode D: each of the five csrc/acmpc_dynamic*.hip against its own counterpart)
        python3 tools/asm_same.py OLD/acmpc_dynamic-hip-amdgcn-amd-amdhsa-gfx950.s NEW/acmpc_dynamic-hip-amdgcn-amd-amdhsa-gfx950.s
        python3 tools/asm_same.py OLD/unit.s NEW/part_a.s NEW/part_b.s ...     (a unit split into several, ONE flag set: the same
                                                                                mangled name under other flags is another kernel)"""
