@@ -166,6 +166,7 @@ SIGNATURES = {
     "acmpc_set_dynamics_objective": (C.c_int, [_CTX, C.c_double, C.c_void_p]),
     "acmpc_set_dynamics_coupling": (C.c_int, [_CTX, C.c_void_p]),
     "acmpc_set_dynamics_load_transfer": (C.c_int, [_CTX, C.c_void_p]),
+    "acmpc_set_dynamics_downforce": (C.c_int, [_CTX, C.c_void_p]),
     "acmpc_get_progress_table": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_score_grips": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
@@ -570,6 +571,29 @@ def dynamics_load_transfer(value=None, w_frac=0.9):
     return np.array(pair, dtype=np.float64)
 
 
+def dynamics_downforce(value=None, v_sat=100.0):
+    """Mode D's downforce checked as acmpc_set_dynamics_downforce checks it: None (off), or the float64 triple (k_f, k_r,
+    v_sat) of a triple or of a (k_f, k_r) pair (with `v_sat`, 100 m/s by default).  ValueError for a k that is negative or
+    not finite as float32, or a v_sat that is not finite and > 0."""
+    if value is None:
+        return None
+    try:
+        triple = tuple(float(v) for v in value)
+    except (TypeError, ValueError):
+        raise ValueError("the downforce is None, a (k_f, k_r) pair or a (k_f, k_r, v_sat) triple, not %r" % (value,)) from None
+    if len(triple) == 2:
+        triple = triple + (float(v_sat),)
+    if len(triple) != 3:
+        raise ValueError("the downforce is a (k_f, k_r) pair or a (k_f, k_r, v_sat) triple, not %r" % (value,))
+    with np.errstate(over="ignore"):
+        as32 = np.array(triple, dtype=np.float64).astype(np.float32)
+    if not (np.isfinite(as32[0]) and as32[0] >= 0.0 and np.isfinite(as32[1]) and as32[1] >= 0.0):
+        raise ValueError("k_f, k_r are finite and >= 0, not %r" % (triple[:2],))
+    if not (np.isfinite(as32[2]) and as32[2] > 0.0):
+        raise ValueError("v_sat is finite and > 0, not %r" % (triple[2],))
+    return np.array(triple, dtype=np.float64)
+
+
 class Engine:
     """Owns one acmpc_ctx.  Construction does no device work (fork-safe, controller.py:293-297)."""
 
@@ -709,6 +733,16 @@ class Engine:
         load that may move.  The setting outlives a change of vehicle or of any other setting."""
         pair = dynamics_load_transfer(h_cg, w_frac)
         self._check(self._lib.acmpc_set_dynamics_load_transfer(self._ctx, None if pair is None else pair.ctypes.data))
+
+    def set_dynamics_downforce(self, downforce=None, v_sat=100.0):
+        """Mode D's aerodynamic downforce (acmpc_set_dynamics_downforce): `downforce` = (k_f, k_r), the downforce on the front
+        and the rear axle per vx^2 in the vehicle block's force unit per (m/s)^2 (dynamic_model.downforce_coefficients), or
+        (k_f, k_r, v_sat); it stops growing at `v_sat`.  Each axle's load, and with it its Pacejka peak and its coupling cap,
+        grows with the speed in every Euler sub-step.  None switches it off.  While it is on every vehicle needs positive peaks
+        and peak factors that stay positive up to the load at v_sat.  The setting outlives a change of vehicle or of any other
+        setting."""
+        triple = dynamics_downforce(downforce, v_sat)
+        self._check(self._lib.acmpc_set_dynamics_downforce(self._ctx, None if triple is None else triple.ctypes.data))
 
     def progress_table(self, problem: int = 0) -> np.ndarray:
         """Mode D's progress table q [n] of a problem (acmpc_get_progress_table), host only."""

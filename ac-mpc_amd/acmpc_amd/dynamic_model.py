@@ -119,21 +119,36 @@ class DynamicBicycleParams:
         D, eps = (self.Df, self.epsf) if axle == "f" else (self.Dr, self.epsr)
         return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0
 
-    def loaded_axles(self, F_fx: float, F_rx: float, coupling, load_transfer) -> Tuple[float, float, float]:
+    def downforce_at(self, vx: float, downforce) -> Tuple[float, float]:
+        """(d_f, d_r), the downforce on the two axles at the speed `vx` under `downforce` = (k_f, k_r) or (k_f, k_r, v_sat =
+        100) (acmpc_set_dynamics_downforce): k_a min(vx, v_sat)^2; None: (0, 0)."""
+        if downforce is None:
+            return 0.0, 0.0
+        k_f, k_r, v_sat = _downforce(downforce)
+        va = min(float(vx), v_sat)
+        return k_f * va * va, k_r * va * va
+
+    def loaded_axles(self, F_fx: float, F_rx: float, coupling, load_transfer, downforce=None, vx: float = 0.0) -> Tuple[float, float, float]:
         """(w, F_zf', F_zr') of the load transfer `load_transfer` = h_cg or (h_cg, w_frac = 0.9) for the longitudinal demands
         F_fx, F_rx (acmpc_set_dynamics_load_transfer, one explicit pass): the demands clipped at the STATIC caps of
         `coupling`, w = h_cg / (lf + lr) times their sum clipped at +-w_frac min(F_zf, F_zr) - the load moved to the rear,
-        negative under braking - and the loads F_zf - w, F_zr + w."""
+        negative under braking - and the loads F_zf - w, F_zr + w.  With `downforce` (downforce_at's, at the speed `vx`) each
+        axle's load has d_a on top of the static weight before anything moves: the caps are those AT THIS SPEED and the loads
+        F_zf + d_f - w, F_zr + d_r + w.  load_transfer = None: nothing moves (w = 0)."""
+        d_f, d_r = self.downforce_at(vx, downforce)
+        if load_transfer is None:
+            return 0.0, self.F_zf + d_f, self.F_zr + d_r
         h_cg, w_frac = (float(load_transfer), 0.9) if np.ndim(load_transfer) == 0 else (float(v) for v in load_transfer)
         rho_f, rho_r = _ratios(coupling)
-        cap_f, cap_r = rho_f * self.peak_front, rho_r * self.peak_rear
+        cap_f, cap_r = rho_f * self.peak("f", self.F_zf + d_f), rho_r * self.peak("r", self.F_zr + d_r)
         e_f = max(min(F_fx, cap_f), -cap_f)
         e_r = max(min(F_rx, cap_r), -cap_r)
         w_max = w_frac * min(self.F_zf, self.F_zr)
         w = max(min(h_cg / (self.lf + self.lr) * (e_f + e_r), w_max), -w_max)
-        return w, self.F_zf - w, self.F_zr + w
+        return w, self.F_zf + d_f - w, self.F_zr + d_r + w
 
-    def predict_next_state(self, state, u, dt: float = 0.05, coupling=None, load_transfer=None) -> Tuple[np.ndarray, np.ndarray, list]:
+    def predict_next_state(self, state, u, dt: float = 0.05, coupling=None, load_transfer=None,
+                           downforce=None) -> Tuple[np.ndarray, np.ndarray, list]:
         """One explicit Euler step in float64: state (X, Y, yaw, vx, vy, r), u = (delta, pedal) with the pedal in
         [-1, 1].  Returns (next_state, x_dot, [F_fy, F_ry, F_fx, F_rx]) like the reference; the caller clips vx >= 0
         (the reference's loop does, dynamic_bicycle_model.py:180; so do the kernels, inside the step).  `coupling` = rho
@@ -142,7 +157,9 @@ class DynamicBicycleParams:
         the coupled ones.  `load_transfer` = h_cg or (h_cg, w_frac) is the load transfer of
         acmpc_set_dynamics_load_transfer in float64 (None: off), the same one-pass formulation with the exact
         load-dependent peak: loaded_axles() gives each axle's load, which both the side force and the coupling's cap then
-        take; the returned forces are the final ones."""
+        take; the returned forces are the final ones.  `downforce` = (k_f, k_r) or (k_f, k_r, v_sat) is the downforce of
+        acmpc_set_dynamics_downforce in float64 (None: off): the same one pass with k_a min(vx, v_sat)^2 on each axle's load
+        under the load moved, and the exact load-dependent peak P(F_z + x); the force list holds the final forces."""
         delta, pedal = float(u[0]), float(u[1])
         X, Y, yaw, vx, vy, r = (float(s) for s in state)
         den = vx + 1e-3
@@ -155,8 +172,8 @@ class DynamicBicycleParams:
         F_rx = brake * (1 - self.brake_bias) * braking + motor * max(0.0, pedal)
         F_fx = brake * self.brake_bias * braking
         F_zf, F_zr = self.F_zf, self.F_zr
-        if load_transfer is not None:
-            _, F_zf, F_zr = self.loaded_axles(F_fx, F_rx, coupling, load_transfer)
+        if load_transfer is not None or downforce is not None:
+            _, F_zf, F_zr = self.loaded_axles(F_fx, F_rx, coupling, load_transfer, downforce, vx)
         F_fy = self._lateral(alpha_f, self.Bf, self.Cf, self.Df, self.Ef, self.epsf, F_zf)
         F_ry = self._lateral(alpha_r, self.Br, self.Cr, self.Dr, self.Er, self.epsr, F_zr)
         if coupling is not None:
@@ -180,12 +197,12 @@ class DynamicBicycleParams:
         return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0 * np.sin(C * np.arctan(ba - E * (ba - np.arctan(ba))))
 
     def rollout(self, state, U, dt: float = 0.05, substeps: int = 1, low_speed_blend=None, coupling=None,
-                load_transfer=None) -> np.ndarray:
+                load_transfer=None, downforce=None) -> np.ndarray:
         """The mirror over a control sequence U [n, 2] with vx clipped after every step: states [n + 1, 6].  `substeps`
         and `low_speed_blend` = (v_lo, v_hi) are the integration setting of acmpc_set_dynamics_integration in float64: a
         control step is `substeps` Euler steps of dt / substeps, and after each (vy, r) are blended towards the kinematic
         bicycle's r_k = vx tan(delta) / (lf + lr), vy_k = lr r_k by lam = clamp((vx - v_lo) / (v_hi - v_lo), 0, 1).
-        `coupling`, `load_transfer`: predict_next_state's, in every sub-step."""
+        `coupling`, `load_transfer`, `downforce`: predict_next_state's, in every sub-step."""
         substeps = int(substeps)
         if substeps < 1:
             raise ValueError("substeps must be positive")
@@ -194,7 +211,7 @@ class DynamicBicycleParams:
         for u in np.asarray(U, dtype=np.float64):
             nxt = out[-1]
             for _ in range(substeps):
-                nxt = self.predict_next_state(nxt, u, h, coupling=coupling, load_transfer=load_transfer)[0]
+                nxt = self.predict_next_state(nxt, u, h, coupling=coupling, load_transfer=load_transfer, downforce=downforce)[0]
                 nxt[3] = max(nxt[3], 0.0)
                 if low_speed_blend is not None:
                     v_lo, v_hi = (float(v) for v in low_speed_blend)
@@ -212,6 +229,29 @@ def _ratios(coupling) -> Tuple[float, float]:
         return float("inf"), float("inf")
     rho_f, rho_r = (float(coupling),) * 2 if np.ndim(coupling) == 0 else (float(v) for v in coupling)
     return rho_f, rho_r
+
+
+def _downforce(downforce) -> Tuple[float, float, float]:
+    """(k_f, k_r, v_sat) of a downforce setting: a pair takes v_sat = 100 m/s."""
+    values = tuple(float(v) for v in downforce)
+    if len(values) not in (2, 3):
+        raise ValueError("the downforce is (k_f, k_r) or (k_f, k_r, v_sat), not %r" % (downforce,))
+    return values + (100.0,) if len(values) == 2 else values
+
+
+def downforce_coefficients(cl_a: float, balance_front: float, air_density: float = 1.225, force_unit: float = 1000.0) -> Tuple[float, float]:
+    """(k_f, k_r) of acmpc_set_dynamics_downforce for a car with the downforce area `cl_a` = C_L A (m^2), the fraction
+    `balance_front` of it on the front axle, in air of `air_density` (kg/m^3): 1/2 rho C_L A split by the balance, in the
+    vehicle block's force unit (`force_unit` newtons: 1000 for the kN of the reference block) per (m/s)^2."""
+    cl_a, balance_front, air_density, force_unit = float(cl_a), float(balance_front), float(air_density), float(force_unit)
+    if not (np.isfinite(cl_a) and cl_a >= 0.0):
+        raise ValueError("cl_a is finite and >= 0 (lift is not modelled), not %r" % (cl_a,))
+    if not 0.0 <= balance_front <= 1.0:
+        raise ValueError("balance_front lies in [0, 1], not %r" % (balance_front,))
+    if not (np.isfinite(air_density) and air_density > 0.0 and np.isfinite(force_unit) and force_unit > 0.0):
+        raise ValueError("air_density and force_unit are finite and > 0")
+    k = 0.5 * air_density * cl_a / force_unit
+    return k * balance_front, k * (1.0 - balance_front)
 
 
 def _couple(F_x: float, F_y: float, cap: float) -> Tuple[float, float]:

@@ -49,6 +49,10 @@ constant-velocity table), each radius with the ego's folded in - makes a candida
 that leaves the corridor is; `clearance_cost` / `clearance_margin` (default 0) add 0.5 cost depth^2 inside the margin round
 each disc.  An opponent car is two or three discs along its length.
 
+Downforce (acmpc_set_dynamics_downforce): `downforce` - (k_f, k_r) or (k_f, k_r, v_sat), default None, v_sat 100 m/s - lets each
+axle's load grow with vx^2 (dynamic_model.downforce_coefficients gives the pair from C_L A and the aero balance): the peaks and
+the coupling caps are those the tyres have at the speed driven, 29 % more at 200 km/h on the reference vehicle with C_L A = 3.
+
 Grip adaptation (acmpc_score_grips, GripEstimator): `grip_adapt` - a dict, off by default - lets the solver find the road's
 grip from its own driving instead of being told an ensemble.  Every solve logs (state, the control applied since the
 previous solve - `previous_control`, else the last accepted plan's first control), scores a grid of grip hypotheses
@@ -146,6 +150,7 @@ class DynamicSamplingSolver:
         objective = _capi.dynamics_objective(config.get("progress_cost", 0.0), config.get("speed_ceiling"))
         coupling = _capi.dynamics_coupling(config.get("tyre_coupling"))
         load_transfer = _capi.dynamics_load_transfer(config.get("load_transfer"))
+        downforce = _capi.dynamics_downforce(config.get("downforce"))
         clearance = (float(config.get("clearance_cost", 0.0)), float(config.get("clearance_margin", 0.0)))
         if not all(0.0 <= v <= float(np.finfo(np.float32).max) for v in clearance):   # (a NaN compares false)
             raise ValueError("clearance_cost and clearance_margin must be finite and >= 0, not %r" % (clearance,))
@@ -180,6 +185,8 @@ class DynamicSamplingSolver:
             self._engine.set_dynamics_coupling(coupling)
         if load_transfer is not None:
             self._engine.set_dynamics_load_transfer(load_transfer)
+        if downforce is not None:
+            self._engine.set_dynamics_downforce(downforce)
         if clearance != (0.0, 0.0):
             self._engine.set_dynamics_clearance(*clearance)
         self._has_obstacles = False

@@ -1,5 +1,5 @@
 // C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
-// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the previous control, the obstacles and the clearance setting, and the grip
+// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the downforce, the previous control, the obstacles and the clearance setting, and the grip
 // identification (acmpc_score_grips), with the checks that the kernels' limits are the public header's.
 #include <algorithm>
 
@@ -87,8 +87,9 @@ void derive_axles(const double* coef, double* axle) {
 
 // The six float32 scalars of one vehicle under the setting (h_cg, w_frac), derived in float64 and rounded once each (include/
 // acmpc.h, acmpc_set_dynamics_load_transfer): nullptr, or why the vehicle is refused - N_a = 0, or a factor phi_a that is not
-// > 0 (in float64) at x = +-w_max or at its vertex inside
-const char* derive_load(const double* setting, double L, const double* axle, float* out) {
+// > 0 (in float64) at x = +-w_max or at its vertex inside.  `aero`: the downforce's (k_f, k_r, v_sat) as the kernels get them, or
+// nullptr while it is off (acmpc_set_dynamics_downforce): axle a's interval then ends at w_max + k_a v_sat^2.
+const char* derive_load(const double* setting, const float* aero, double L, const double* axle, float* out) {
   const double c_h = setting[0] / L;
   const double w_max = setting[1] * std::min(axle[0], axle[1]);
   if (!std::isfinite(c_h) || !std::isfinite(w_max)) return "the load transfer's c_h or w_max is not finite";
@@ -99,30 +100,41 @@ const char* derive_load(const double* setting, double L, const double* axle, flo
     const double N = F + e * F * F;
     if (N == 0.0 || !std::isfinite(N)) return "the load transfer divides by N = F_z + e F_z^2, which is 0 or not finite";
     const double a1 = (1 + 2 * e * F) / N, a2 = e / N;
-    double probe[3] = {-w_max, w_max, 0.0};
+    const double top = aero == nullptr ? w_max : w_max + static_cast<double>(aero[a]) * aero[2] * aero[2];
+    if (!std::isfinite(top)) return "the downforce at v_sat is not finite";
+    double probe[3] = {-w_max, top, 0.0};
     int probes = 2;
-    if (a2 > 0.0) {
+    if (a2 != 0.0) {   // (with a2 < 0 the vertex is the factor's maximum: looked at all the same, it refuses nothing more)
       const double vertex = -a1 / (2 * a2);
-      if (vertex > -w_max && vertex < w_max) probe[probes++] = vertex;
+      if (vertex > -w_max && vertex < top) probe[probes++] = vertex;
     }
     for (int q = 0; q < probes; ++q)
-      if (!(1 + probe[q] * (a1 + a2 * probe[q]) > 0.0)) return "the load transfer's peak factor phi is not > 0 over +-w_max";
+      if (!(1 + probe[q] * (a1 + a2 * probe[q]) > 0.0))
+        return aero == nullptr ? "the load transfer's peak factor phi is not > 0 over +-w_max"
+                               : "the peak factor is not > 0 over the load range -w_max .. w_max + k v_sat^2 of the downforce";
     out[2 + 2 * a] = static_cast<float>(a1);
     out[3 + 2 * a] = static_cast<float>(a2);
   }
   return nullptr;
 }
 
-// every vehicle of an ensemble under a setting: the scalars into out[k], or why one is refused
-const char* derive_loads(const double* setting, const acmpc::VehicleEnsemble& e, const double* L, const double (*axle)[4],
-                         float (*out)[6]) {
-  if (!peaks_couple(e)) return "the load transfer is on: every vehicle's axle peaks Pf, Pr must be finite and > 0 (as float32)";
+// every vehicle of an ensemble under a load transfer (nullptr: off, c_h = w_max = 0) and a downforce (nullptr: off): the scalars
+// into out[k], or why one is refused; with both off nothing is derived or refused
+const char* derive_loads(const double* setting, const float* aero, const acmpc::VehicleEnsemble& e, const double* L,
+                         const double (*axle)[4], float (*out)[6]) {
+  if (setting == nullptr && aero == nullptr) return nullptr;
+  if (!peaks_couple(e))
+    return setting != nullptr ? "the load transfer is on: every vehicle's axle peaks Pf, Pr must be finite and > 0 (as float32)"
+                              : "the downforce is on: every vehicle's axle peaks Pf, Pr must be finite and > 0 (as float32)";
+  const double none[2] = {0.0, 0.0};
   for (int k = 0; k < e.K; ++k) {
-    const char* why = derive_load(setting, L[k], axle[k], out[k]);
+    const char* why = derive_load(setting != nullptr ? setting : none, aero, L[k], axle[k], out[k]);
     if (why != nullptr) return why;
   }
   return nullptr;
 }
+const double* load_of(const acmpc_ctx* c) { return c->has_load ? c->load_setting : nullptr; }
+const float* aero_of(const acmpc_ctx* c) { return c->has_aero ? c->aero : nullptr; }
 
 }  // namespace
 
@@ -145,10 +157,8 @@ int acmpc_set_dynamics(acmpc_ctx* c, const double* coef, int32_t count) {
   double axle[1][4];
   float load[1][6] = {};
   derive_axles(coef, axle[0]);
-  if (c->has_load) {
-    const char* refused = derive_loads(c->load_setting, e, L, axle, load);
-    if (refused != nullptr) return fail(c, ACMPC_EINVAL, refused);
-  }
+  if (const char* refused = derive_loads(load_of(c), aero_of(c), e, L, axle, load); refused != nullptr)
+    return fail(c, ACMPC_EINVAL, refused);
   c->vehicles = e;
   std::memcpy(c->vehicle_axle[0], axle[0], sizeof axle[0]);
   std::memcpy(c->load_const[0], load[0], sizeof load[0]);
@@ -190,10 +200,8 @@ int acmpc_set_dynamics_ensemble(acmpc_ctx* c, const double* coef, int32_t K, con
     L[k] = ck[14] + ck[15];
     derive_axles(ck, axle[k]);
   }
-  if (c->has_load) {
-    const char* refused = derive_loads(c->load_setting, e, L, axle, load);
-    if (refused != nullptr) return fail(c, ACMPC_EINVAL, refused);
-  }
+  if (const char* refused = derive_loads(load_of(c), aero_of(c), e, L, axle, load); refused != nullptr)
+    return fail(c, ACMPC_EINVAL, refused);
   c->vehicles = e;
   std::memcpy(c->vehicle_axle, axle, sizeof(double) * 4 * K);
   std::memcpy(c->load_const, load, sizeof(float) * 6 * K);
@@ -284,8 +292,12 @@ int acmpc_set_dynamics_load_transfer(acmpc_ctx* c, const double setting[2]) {
   if (c == nullptr) return ACMPC_EINVAL;
   if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_dynamics_load_transfer needs a mode D handle");
   if (setting == nullptr) {
+    // (a smaller load range than the one that holds: nothing to refuse; the downforce's scalars with c_h = w_max = 0)
+    float load[acmpc::kMaxVehicles][6] = {};
+    if (c->has_dynamics) (void)derive_loads(nullptr, aero_of(c), c->vehicles, c->vehicle_L, c->vehicle_axle, load);
     c->has_load = false;
     c->load_setting[0] = c->load_setting[1] = 0.0;
+    std::memcpy(c->load_const, load, sizeof load);
     return ACMPC_OK;
   }
   if (!std::isfinite(setting[0]) || !(setting[0] >= 0.0)) return fail(c, ACMPC_EINVAL, "h_cg must be finite and >= 0");
@@ -293,13 +305,41 @@ int acmpc_set_dynamics_load_transfer(acmpc_ctx* c, const double setting[2]) {
   const double kept[2] = {setting[0] + 0.0, setting[1]};   // (-0.0 is 0)
   float load[acmpc::kMaxVehicles][6] = {};
   if (c->has_dynamics) {
-    const char* refused = derive_loads(kept, c->vehicles, c->vehicle_L, c->vehicle_axle, load);
+    const char* refused = derive_loads(kept, aero_of(c), c->vehicles, c->vehicle_L, c->vehicle_axle, load);
     if (refused != nullptr) return fail(c, ACMPC_EINVAL, refused);
   }
   // everything is checked before anything is kept: a refused setting leaves the handle's as it was
   c->has_load = true;
   c->load_setting[0] = kept[0];
   c->load_setting[1] = kept[1];
+  std::memcpy(c->load_const, load, sizeof load);
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_downforce(acmpc_ctx* c, const double setting[3]) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_dynamics_downforce needs a mode D handle");
+  float load[acmpc::kMaxVehicles][6] = {};
+  if (setting == nullptr) {
+    if (c->has_dynamics) (void)derive_loads(load_of(c), nullptr, c->vehicles, c->vehicle_L, c->vehicle_axle, load);
+    c->has_aero = false;
+    c->aero[0] = c->aero[1] = c->aero[2] = 0.0f;
+    std::memcpy(c->load_const, load, sizeof load);
+    return ACMPC_OK;
+  }
+  // float32 is what the kernels get: each of the three is rounded once
+  const float kept[3] = {static_cast<float>(setting[0]) + 0.0f, static_cast<float>(setting[1]) + 0.0f,   // (-0.0 is 0)
+                         static_cast<float>(setting[2])};
+  for (int a = 0; a < 2; ++a)   // (a NaN compares false)
+    if (!std::isfinite(kept[a]) || !(kept[a] >= 0.0f)) return fail(c, ACMPC_EINVAL, "k_f, k_r must be finite and >= 0 (as float32)");
+  if (!std::isfinite(kept[2]) || !(kept[2] > 0.0f)) return fail(c, ACMPC_EINVAL, "v_sat must be finite and > 0 (as float32)");
+  if (c->has_dynamics) {
+    const char* refused = derive_loads(load_of(c), kept, c->vehicles, c->vehicle_L, c->vehicle_axle, load);
+    if (refused != nullptr) return fail(c, ACMPC_EINVAL, refused);
+  }
+  // everything is checked before anything is kept: a refused setting leaves the handle's as it was
+  c->has_aero = true;
+  std::memcpy(c->aero, kept, sizeof kept);
   std::memcpy(c->load_const, load, sizeof load);
   return ACMPC_OK;
 }
@@ -435,8 +475,10 @@ int acmpc_score_grips(acmpc_ctx* c, const float* states, const float* controls, 
   // and its load transfer: the base vehicle's factors on each hypothesis' own peaks
   const float* lc = c->load_const[0];
   const acmpc::IdentifyLoad load{lc[0], lc[1], lc[2], lc[3], lc[4], lc[5]};
+  // and its downforce: the same factors at each sub-step's speed
+  const acmpc::IdentifyAero aero{c->aero[0], c->aero[1], c->aero[2]};
   ACMPC_HIP(c, acmpc::launch_identify_grip(a, c->vehicles.v[0], g, c->has_coupling ? c->coupling : nullptr,
-                                           c->has_load ? &load : nullptr, s));
+                                           c->has_load || c->has_aero ? &load : nullptr, c->has_aero ? &aero : nullptr, s));
   // one copy down: best key | errors
   ACMPC_HIP(c, hipMemcpyAsync(c->h_identify.data(), c->d_identify + kBestAt, down_bytes, hipMemcpyDeviceToHost, s));
   ACMPC_HIP(c, hipStreamSynchronize(s));

@@ -18,8 +18,8 @@ namespace capi __attribute__((visibility("hidden"))) {
 // And of its load transfer ("Load transfer"): the six scalars of each vehicle, and the ratios +inf while the coupling is off.
 // And of its obstacles ("Obstacles"): the device block (positions, then radii), what it was set for, and the clearance
 // setting; K = 0 while none are set, the soft part on with a weight that is not 0.
-static acmpc::WithObstacles<acmpc::TermsLoaded> dynamics_terms(const acmpc_ctx* c) {
-  acmpc::WithObstacles<acmpc::TermsLoaded> t{};
+static acmpc::WithObstacles<acmpc::TermsAero> dynamics_terms(const acmpc_ctx* c) {
+  acmpc::WithObstacles<acmpc::TermsAero> t{};
   t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
             std::isfinite(c->rate_max[1])) ? 1 : 0;
   t.slip = (c->slip_weight != 0.0 || std::isfinite(c->slip_max)) ? 1 : 0;
@@ -41,7 +41,11 @@ static acmpc::WithObstacles<acmpc::TermsLoaded> dynamics_terms(const acmpc_ctx* 
   t.rho_f = c->coupling[0];
   t.rho_r = c->coupling[1];
   t.loaded = c->has_load ? 1 : 0;
-  for (int k = 0; k < c->vehicles.K && t.loaded != 0; ++k) {
+  t.aero = c->has_aero ? 1 : 0;   // ("Downforce": c_h = w_max = 0 while the load transfer is off)
+  t.k_f = c->aero[0];
+  t.k_r = c->aero[1];
+  t.v_sat = c->aero[2];
+  for (int k = 0; k < c->vehicles.K && (t.loaded != 0 || t.aero != 0); ++k) {
     const float* lc = c->load_const[k];
     t.c_h[k] = lc[0];
     t.w_max[k] = lc[1];

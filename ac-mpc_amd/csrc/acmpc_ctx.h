@@ -294,6 +294,11 @@ struct acmpc_ctx {
   double load_setting[2] = {0.0, 0.0};
   double vehicle_axle[acmpc::kMaxVehicles][4] = {};
   float load_const[acmpc::kMaxVehicles][6] = {};
+  // mode D: the downforce (acmpc_set_dynamics_downforce), kept apart like the others: (k_f, k_r, v_sat) as the kernels get
+  // them.  While it is on load_const is derived too (c_h = w_max = 0 while the load transfer is off), and every vehicle of the
+  // handle has finite, positive peaks and factors > 0 over -w_max .. w_max + k_a v_sat^2.
+  bool has_aero = false;
+  float aero[3] = {0.0f, 0.0f, 0.0f};
   // mode D: the moving obstacles (acmpc_set_obstacles), staged here like the previous control until the next upload: positions
   // [obs_P][obs_n][obs_K][2] then radii [obs_P][obs_K] in one block, on the host and on the device (allocated by the upload
   // that first needs it, grown when a larger one arrives); and the clearance setting (acmpc_set_dynamics_clearance)

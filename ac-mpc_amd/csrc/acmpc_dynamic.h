@@ -223,6 +223,43 @@ __device__ __forceinline__ void loaded_peaks_of(F F_fx, F F_rx, const Vehicle& k
   Pr = pk.rear(k) * phi_r;
 }
 
+// Aerodynamic downforce of a handle (acmpc_set_dynamics_downforce, DESIGN.md section 2 "Mode D, downforce"): each axle's load
+// grows with the square of the sub-step's incoming speed, up to v_sat, and the load transfer then moves load on top of that.  A
+// LoadedPeaks with k_f, k_r (force per speed squared) and v_sat beside its six scalars, each rounded to float32 once; c_h = 0 and
+// w_max = 0 while the load transfer is off, rho = +inf while the coupling is off.  Not an IsLoaded: a block of its own again.
+template <typename PK>
+struct AeroPeaks : LoadedPeaks<PK> {
+  float k_f, k_r, v_sat;
+};
+template <typename PK>
+struct IsAero : std::false_type {};
+template <typename PK>
+struct IsAero<AeroPeaks<PK>> : std::true_type {};
+
+// The two peaks of a sub-step under the downforce, in spec order: va = min(vx, v_sat) (minNum: a NaN vx gives v_sat), q = va va,
+// d_a = k_a q, psi_a = 1 + d_a (a1_a + a2_a d_a), P_a0 = P_a psi_a - the peaks at this speed before any tyre force; the demands
+// clipped at the caps rho_a P_a0 AT THIS SPEED, w = c_h (e_f + e_r) clipped at +-w_max, x_f = d_f - w, x_r = d_r + w,
+// phi_a = 1 + x_a (a1_a + a2_a x_a), P_a' = P_a phi_a.  k = 0 gives d = +0, psi = 1, x = -+w: the loaded step's bits.
+template <typename F, typename PK>
+__device__ __forceinline__ void aero_peaks_of(F vx, F F_fx, F F_rx, const Vehicle& k, const AeroPeaks<PK>& pk, F& Pf, F& Pr) {
+  const F va = __builtin_elementwise_min(vx, splat<F>(pk.v_sat));
+  const F q = va * va;
+  const F d_f = pk.k_f * q, d_r = pk.k_r * q;
+  const F psi_f = splat<F>(1.0f) + d_f * (pk.a1_f + pk.a2_f * d_f);
+  const F psi_r = splat<F>(1.0f) + d_r * (pk.a1_r + pk.a2_r * d_r);
+  const F cap_f = pk.rho_f * (pk.front(k) * psi_f);
+  const F cap_r = pk.rho_r * (pk.rear(k) * psi_r);
+  const F e_f = vmax(__builtin_elementwise_min(F_fx, cap_f), -cap_f);
+  const F e_r = vmax(__builtin_elementwise_min(F_rx, cap_r), -cap_r);
+  F w = pk.c_h * (e_f + e_r);
+  w = vmax(__builtin_elementwise_min(w, splat<F>(pk.w_max)), splat<F>(-pk.w_max));
+  const F x_f = d_f - w, x_r = d_r + w;
+  const F phi_f = splat<F>(1.0f) + x_f * (pk.a1_f + pk.a2_f * x_f);
+  const F phi_r = splat<F>(1.0f) + x_r * (pk.a1_r + pk.a2_r * x_r);
+  Pf = pk.front(k) * phi_f;
+  Pr = pk.rear(k) * phi_r;
+}
+
 // What a step takes from its control alone: sincos_spec(delta) and the pedal's split.  The same for every sub-step of a
 // control step (dynamic_advance_fine computes it once).
 template <typename F>
@@ -243,7 +280,8 @@ __device__ __forceinline__ ControlTerms<F> control_terms(F delta, F pedal) {
 // through `pre` (the sub-steps of dynamic_advance_fine); otherwise they are computed here, where the single step has
 // always computed them - the default setting's kernels are to stay the code they were, instruction for instruction.
 // PK: the source of the peak factors (VehiclePeaks or LanePeaks), or a CoupledPeaks of one: the tyre coupling; or a LoadedPeaks
-// of one: the coupling with the load transfer in front of it (the side forces then wait for the loaded peaks).
+// of one: the coupling with the load transfer in front of it (the side forces then wait for the loaded peaks); or an AeroPeaks
+// of one: the same with the downforce of the sub-step's incoming speed under the load moved.
 template <bool HOISTED, typename F, typename PK = VehiclePeaks>
 __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, const ControlTerms<F>* pre, const Vehicle& k,
                                               float dt, const PK pk = PK{}) {
@@ -254,7 +292,7 @@ __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, c
   const F a_f = delta - atan_spec<F>(qf);   // the reference's -atan(q) + delta: the same float
   const F a_r = atan_spec<F>(qr);
   F F_fy, F_ry;
-  if constexpr (!IsLoaded<PK>::value) {
+  if constexpr (!IsLoaded<PK>::value && !IsAero<PK>::value) {
     F_fy = pacejka<F>(a_f, k.Bf, k.Cf, k.Ef, pk.front(k));
     F_ry = pacejka<F>(a_r, k.Br, k.Cr, k.Er, pk.rear(k));
   }
@@ -279,6 +317,14 @@ __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, c
   if constexpr (IsLoaded<PK>::value) {
     F Pf, Pr;
     loaded_peaks_of<F>(F_fx, F_rx, k, pk, Pf, Pr);
+    F_fy = pacejka_loaded<F>(a_f, k.Bf, k.Cf, k.Ef, Pf);
+    F_ry = pacejka_loaded<F>(a_r, k.Br, k.Cr, k.Er, Pr);
+    couple_axle_loaded<F>(F_fx, F_fy, pk.rho_f, Pf);
+    couple_axle_loaded<F>(F_rx, F_ry, pk.rho_r, Pr);
+  }
+  if constexpr (IsAero<PK>::value) {
+    F Pf, Pr;
+    aero_peaks_of<F>(vx, F_fx, F_rx, k, pk, Pf, Pr);
     F_fy = pacejka_loaded<F>(a_f, k.Bf, k.Cf, k.Ef, Pf);
     F_ry = pacejka_loaded<F>(a_r, k.Br, k.Cr, k.Er, Pr);
     couple_axle_loaded<F>(F_fx, F_fy, pk.rho_f, Pf);
@@ -413,12 +459,23 @@ struct TermsLoaded : TermsCoupled {
 };
 __host__ __device__ inline bool has_load_transfer(const TermsLoaded& t) { return t.loaded != 0; }
 
+// The TermsLoaded plus the downforce of a handle (acmpc_set_dynamics_downforce, DESIGN.md section 2 "Mode D, downforce"): a fifth
+// pack type.  The three floats of AeroPeaks are the handle's, not a vehicle's.  The kernels instantiated for it
+// (acmpc_dynamic_aero.hip) run only while `aero` is set, with c_h = w_max = 0 while the load transfer is off (the per-vehicle a1,
+// a2 are derived all the same) and rho = +inf while the coupling is off; every other kernel stays the code it was.  The
+// launchers take the handle's settings as one of these.
+struct TermsAero : TermsLoaded {
+  float k_f, k_r, v_sat;
+  int aero;                     // 0: off (the three floats not read); the kernels do not read it
+};
+__host__ __device__ inline bool has_downforce(const TermsAero& t) { return t.aero != 0; }
+
 // Moving obstacles of a handle (acmpc_set_obstacles, acmpc_set_dynamics_clearance; DESIGN.md section 2 "Mode D, obstacles"): up
 // to kMaxObstacles discs per problem, each with a position per control step - row i is where the discs are at the state AFTER
 // control step i, the state that step's dynamic_cost sees - and a radius with the ego's folded in.  Per step, after the ceiling
 // line, disc k's penetration depth joins V (the hard part, on while K > 0) and its depth into the margin joins E (the soft part,
 // on while K > 0 and the weight is not 0).  A pack type again, over the pack of the step the handle would take without obstacles
-// (TermsObjective: the general step, TermsCoupled, TermsLoaded): the kernels instantiated for the three (acmpc_dynamic_obstacles
+// (TermsObjective: the general step, TermsCoupled, TermsLoaded, TermsAero): the kernels instantiated for the four (acmpc_dynamic_obstacles
 // .hip) run only while obstacles are set, every other kernel stays the code it was.  obs [P][n][K][2] in the caller's frame and
 // radii [P][K] are read from global memory (problem and step are uniform in every kernel: one broadcast per step, no LDS).
 // coef: the packed rows of the launch (the first two floats of a problem's are the origin of the path's own frame,
@@ -440,7 +497,7 @@ template <typename TT>
 struct PackBase { using type = TT; };
 template <typename Base>
 struct PackBase<WithObstacles<Base>> { using type = Base; };
-// the obstacles' pack over another base (the handle's settings are a WithObstacles<TermsLoaded>)
+// the obstacles' pack over another base (the handle's settings are a WithObstacles<TermsAero>)
 template <typename Base, typename From>
 inline WithObstacles<Base> obstacles_over(const WithObstacles<From>& t) {
   WithObstacles<Base> r{};
@@ -507,6 +564,18 @@ __device__ __forceinline__ LoadedPeaks<VehiclePeaks> loaded_peaks(int vk, const 
 template <typename F>
 __device__ __forceinline__ LoadedPeaks<VehiclePeaks> loaded_peaks(int vk, const TermsState<F>&, const TermsLoaded& t) {
   return loaded_peaks(vk, t);
+}
+
+// And for a TermsAero: dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(..., aero_peaks(vk, tm...))
+template <typename... TM>
+constexpr bool kAeroPack = (std::is_same<typename PackBase<typename std::remove_cv<TM>::type>::type, TermsAero>::value || ...);
+__device__ __forceinline__ AeroPeaks<VehiclePeaks> aero_peaks(int vk, const TermsAero& t) {
+  return AeroPeaks<VehiclePeaks>{{{{}, t.rho_f, t.rho_r}, t.c_h[vk], t.w_max[vk], t.a1_f[vk], t.a2_f[vk], t.a1_r[vk], t.a2_r[vk]},
+                                 t.k_f, t.k_r, t.v_sat};
+}
+template <typename F>
+__device__ __forceinline__ AeroPeaks<VehiclePeaks> aero_peaks(int vk, const TermsState<F>&, const TermsAero& t) {
+  return aero_peaks(vk, t);
 }
 
 // one float of the staged waypoint row(s) j, or of a table of one float per waypoint (stride 1)
@@ -659,22 +728,23 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // `terms`: the handle's rate and slip terms and its objective; when any part is on, the kernels that hold them run, with the general step whatever the
 // integration setting (the default one as M = 1, no blend, h = float32(dt)).  And its tyre coupling: while that is on, the
 // coupled kernels run, whatever the parts.  And its load transfer: while that is on, the loaded kernels run, whatever the
-// coupling and the parts.  And its obstacles: while any are set, the obstacle kernels of the step the handle would take
-// without them run (the general, the coupled or the loaded one), looked at first.
+// coupling and the parts.  And its downforce: while that is on, the aero kernels run, whatever the load transfer, the coupling and
+// the parts.  And its obstacles: while any are set, the obstacle kernels of the step the handle would take
+// without them run (the general, the coupled, the loaded or the aero one), looked at first.
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
+                                  const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
+                                          const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
+                                   const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
 
 }  // namespace acmpc

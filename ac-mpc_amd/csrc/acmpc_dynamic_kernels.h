@@ -36,8 +36,10 @@
 // takes the first row whose setting is on:
 //
 //   unit                          pack                                setter (acmpc_set_...)        kernels  launched while
-//   acmpc_dynamic_obstacles.hip   WithObstacles<TermsObjective |      obstacles                     3 x 16   obstacles are set: the pack of the
-//                                 TermsCoupled | TermsLoaded>                                               step the handle would take without
+//   acmpc_dynamic_obstacles.hip   WithObstacles<TermsObjective |      obstacles                     4 x 16   obstacles are set: the pack of the
+//                                 TermsCoupled | TermsLoaded |                                              step the handle would take without
+//                                 TermsAero>
+//   acmpc_dynamic_aero.hip        TermsAero                           dynamics_downforce            16       the downforce is on
 //   acmpc_dynamic_loaded.hip      TermsLoaded                         dynamics_load_transfer        16       the load transfer is on
 //   acmpc_dynamic_coupled.hip     TermsCoupled                        dynamics_coupling             16       the tyre coupling is on
 //   acmpc_dynamic_terms.hip       TermsObjective                      dynamics_objective            16       progress or ceiling is on
@@ -168,7 +170,8 @@ __global__ void __launch_bounds__(kDynBlock)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
+      if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], aero_peaks(0, tm...));
+      else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
       else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
@@ -293,6 +296,8 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
   }
   [[maybe_unused]] LoadedPeaks<VehiclePeaks> loaded{};   // (the scalars of vehicle vk: read once, ahead of the step loop)
   if constexpr (kLoadedPack<TT...>) loaded = loaded_peaks(vk, tt...);
+  [[maybe_unused]] AeroPeaks<VehiclePeaks> aero{};
+  if constexpr (kAeroPack<TT...>) aero = aero_peaks(vk, tt...);
   int resident[2] = {-1, -1};   // the Philox block in slots 0, 1 and in slots 2, 3
   int knot = -1;
   I nearest = I(0);
@@ -336,7 +341,8 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
         d = dj[0];
         q = qj[0];
       }
-      if constexpr (kLoadedPack<TT...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, loaded);
+      if constexpr (kAeroPack<TT...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, aero);
+      else if constexpr (kLoadedPack<TT...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, loaded);
       else if constexpr (kCoupledPack<TT...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, coupled_peaks(tt...));
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
@@ -519,7 +525,8 @@ __global__ void __launch_bounds__(kWave)
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
     const float d = su[2 * i], q = su[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
-    if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
+    if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], aero_peaks(0, tm...));
+    else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
     else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
     else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[0]);
     // the first minimum of the key over the search's waypoints, the lanes side by side; ties -> the lower index, and the
@@ -614,7 +621,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
+      if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
+      else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
       else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
@@ -803,7 +811,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
     const float d = su[2 * i], q = su[2 * i + 1];
-    if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
+    if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
+    else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
     else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
     else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[k]);
     // finalize_dynamic_kernel's search, within this wave
@@ -1004,14 +1013,22 @@ hipError_t launch_rollout_dynamic_sampled_loaded(const RolloutArgs& args, const 
                                                  const TermsLoaded& terms, hipStream_t s);
 hipError_t launch_finalize_dynamic_loaded(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
                                           const Integration& integration, const TermsLoaded& terms, hipStream_t s);
-// acmpc_dynamic_obstacles.hip: the kernels of a WithObstacles over TermsLoaded, TermsCoupled or TermsObjective.
+// acmpc_dynamic_aero.hip: the kernels of a TermsAero
+hipError_t launch_rollout_dynamic_aero(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                       const Integration& integration, const TermsAero& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_sampled_aero(const RolloutArgs& args, const SampleArgs& sample,
+                                               const VehicleEnsemble& vehicles, const Integration& integration,
+                                               const TermsAero& terms, hipStream_t s);
+hipError_t launch_finalize_dynamic_aero(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                        const Integration& integration, const TermsAero& terms, hipStream_t s);
+// acmpc_dynamic_obstacles.hip: the kernels of a WithObstacles over TermsAero, TermsLoaded, TermsCoupled or TermsObjective.
 // hipErrorInvalidValue unless 1 <= K <= kMaxObstacles and terms.P / terms.n are the launch's.
 hipError_t launch_rollout_dynamic_obstacles(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                            const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
+                                            const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
 hipError_t launch_rollout_dynamic_sampled_obstacles(const RolloutArgs& args, const SampleArgs& sample,
                                                     const VehicleEnsemble& vehicles, const Integration& integration,
-                                                    const WithObstacles<TermsLoaded>& terms, hipStream_t s);
+                                                    const WithObstacles<TermsAero>& terms, hipStream_t s);
 hipError_t launch_finalize_dynamic_obstacles(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                             const Integration& integration, const WithObstacles<TermsLoaded>& terms, hipStream_t s);
+                                             const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
 
 }  // namespace acmpc

@@ -38,7 +38,12 @@ int identify_blocks(int K);            // workgroups (= partial keys) of K hypot
 struct IdentifyLoad {
   float c_h, w_max, a1_f, a2_f, a1_r, a2_r;
 };
+// `aero`: the handle's downforce (acmpc_dynamic.h: AeroPeaks), or nullptr while it is off; with it `load` holds the base
+// vehicle's a1, a2 (and c_h = w_max = 0 while the load transfer is off).
+struct IdentifyAero {
+  float k_f, k_r, v_sat;
+};
 hipError_t launch_identify_grip(const IdentifyArgs& args, const Vehicle& vehicle, const Integration& g, const float* coupling,
-                                const IdentifyLoad* load, hipStream_t s);
+                                const IdentifyLoad* load, const IdentifyAero* aero, hipStream_t s);
 
 }  // namespace acmpc

@@ -15,6 +15,8 @@
 //                           CoupledPeaks), each lane's caps from its own two peaks; launched only while the coupling is on.
 //                           identify_grip_loaded_kernel: the same under the handle's load transfer (LoadedPeaks), the base
 //                           vehicle's factors on each lane's own peaks; launched only while the load transfer is on.
+//                           identify_grip_aero_kernel: the same under the handle's downforce (AeroPeaks); launched only
+//                           while the downforce is on.
 //   identify_sum_kernel     one lane per hypothesis adds its S segment values IN ORDER (plain float32 adds: the
 //                           association is the specification's), writes errors [K], and the workgroup leaves one partial
 //                           (E, k) key - the rollouts' reduction: DPP inside the wave, LDS across the waves.
@@ -144,6 +146,44 @@ __global__ void __launch_bounds__(kIdBlock)
   }
 }
 
+// identify_grip_loaded_kernel under the handle's downforce as well (acmpc_dynamic.h: AeroPeaks): the handle's (k_f, k_r, v_sat)
+// and the base vehicle's six scalars (c_h = w_max = 0 while the load transfer is off) applied to each lane's own pair of peaks -
+// D cancels in psi and phi, so neither depends on a grip scale.  Launched only while the downforce is on.  The same lines again.
+__global__ void __launch_bounds__(kIdBlock)
+    identify_grip_aero_kernel(const float* __restrict__ states, const float* __restrict__ controls,
+                              const f32x2* __restrict__ peaks, float* __restrict__ e_out, const int W, const int L,
+                              const int S, const int K, const int run, const float w0, const float w1, const float w2,
+                              const Vehicle veh, const Integration g, const float rho_f, const float rho_r,
+                              const IdentifyLoad ld, const IdentifyAero ae) {
+  const int k_own = static_cast<int>(blockIdx.x) * kIdBlock + static_cast<int>(threadIdx.x);
+  const int k = min(k_own, K - 1);
+  const f32x2 pk = peaks[k];
+  const AeroPeaks<LanePeaks> lane_peaks{{{{pk[0], pk[1]}, rho_f, rho_r}, ld.c_h, ld.w_max, ld.a1_f, ld.a2_f, ld.a1_r, ld.a2_r},
+                                        ae.k_f, ae.k_r, ae.v_sat};
+  const int s_first = static_cast<int>(blockIdx.y) * run;
+  const int s_last = min(s_first + run, S);
+  for (int seg = s_first; seg < s_last; ++seg) {
+    const int j_first = seg * L;
+    const int j_last = min(j_first + L, W);
+    StateD st{};
+    st.vx = states[3 * j_first];
+    st.vy = states[3 * j_first + 1];
+    st.r = states[3 * j_first + 2];
+    float e = 0.0f;
+    for (int j = j_first; j < j_last; ++j) {
+      const float d = controls[2 * j], q = controls[2 * j + 1];
+      dynamic_advance_fine<float, AeroPeaks<LanePeaks>>(st, d, q, veh, g, g.inv_L[0], lane_peaks);
+      const float dvx = st.vx - states[3 * (j + 1)];
+      const float dvy = st.vy - states[3 * (j + 1) + 1];
+      const float dr = st.r - states[3 * (j + 1) + 2];
+      e = fma_(w0 * dvx, dvx, e);
+      e = fma_(w1 * dvy, dvy, e);
+      e = fma_(w2 * dr, dr, e);
+    }
+    if (k_own < K) e_out[static_cast<size_t>(seg) * K + k_own] = e;
+  }
+}
+
 __global__ void __launch_bounds__(kIdBlock)
     identify_sum_kernel(const float* __restrict__ e_in, float* __restrict__ errors, int64_t* __restrict__ partial_keys,
                         const int S, const int K) {
@@ -190,7 +230,7 @@ int identify_segments(int W, int L) { return (W + L - 1) / L; }
 int identify_blocks(int K) { return (K + kIdBlock - 1) / kIdBlock; }
 
 hipError_t launch_identify_grip(const IdentifyArgs& a, const Vehicle& vehicle, const Integration& g, const float* coupling,
-                                const IdentifyLoad* load, hipStream_t s) {
+                                const IdentifyLoad* load, const IdentifyAero* aero, hipStream_t s) {
   (void)hipGetLastError();
   if (g.substeps < 1 || g.substeps > kMaxSubsteps) return hipErrorInvalidValue;
   if (a.W < 1 || a.W > kIdentifyMaxSteps || a.L < 1 || a.L > a.W || a.K < 1 || a.K > kIdentifyMaxHypotheses)
@@ -205,7 +245,13 @@ hipError_t launch_identify_grip(const IdentifyArgs& a, const Vehicle& vehicle, c
   const int rows = std::min(S, std::max(1, 2048 / blocks));
   const int run = (S + rows - 1) / rows;
   const dim3 grid(blocks, (S + run - 1) / run);
-  if (load != nullptr) {
+  if (aero != nullptr) {
+    if (load == nullptr) return hipErrorInvalidValue;   // (the factors a1, a2 travel with the load transfer's scalars)
+    hipLaunchKernelGGL(identify_grip_aero_kernel, grid, dim3(kIdBlock), 0, s, a.states, a.controls,
+                       reinterpret_cast<const f32x2*>(a.peaks), a.e, a.W, a.L, S, a.K, run, a.w[0], a.w[1], a.w[2], vehicle, g,
+                       coupling != nullptr ? coupling[0] : __builtin_huge_valf(), coupling != nullptr ? coupling[1] : __builtin_huge_valf(),
+                       *load, *aero);
+  } else if (load != nullptr) {
     hipLaunchKernelGGL(identify_grip_loaded_kernel, grid, dim3(kIdBlock), 0, s, a.states, a.controls,
                        reinterpret_cast<const f32x2*>(a.peaks), a.e, a.W, a.L, S, a.K, run, a.w[0], a.w[1], a.w[2], vehicle, g,
                        coupling != nullptr ? coupling[0] : __builtin_huge_valf(), coupling != nullptr ? coupling[1] : __builtin_huge_valf(),

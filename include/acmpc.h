@@ -345,6 +345,33 @@ int acmpc_set_dynamics_coupling(acmpc_ctx* ctx, const double ratio[2] /* NULL: o
  * finite, or a w_frac outside (0, 1).  DESIGN.md section 2 "Mode D, load transfer". */
 int acmpc_set_dynamics_load_transfer(acmpc_ctx* ctx, const double setting[2] /* NULL: off */);
 
+/* Mode D's aerodynamic downforce: each axle's load, and with it its Pacejka peak factor and its coupling cap, grows with the
+ * square of the speed.  Off by default, when the axle loads are the static weights at every speed.  setting = (k_f, k_r,
+ * v_sat): k_f, k_r >= 0 and finite as float32, the downforce on the front and the rear axle per vx^2 in the vehicle block's
+ * force unit per (m/s)^2; v_sat > 0 and finite, the speed at which the downforce stops growing (vx is unbounded in a rollout
+ * and the peak factor must stay positive: the load range it is checked over has to be closed); each of the three is rounded to
+ * float32 once; NULL turns the setting off.  Per vehicle the host derives a1_a, a2_a as acmpc_set_dynamics_load_transfer does
+ * (they do not depend on h_cg); c_h = w_max = 0 while the load transfer is off.  In every Euler step (every sub-step), after
+ * the two longitudinal forces and before anything uses a peak, all float32, nothing fused, min / max the IEEE minNum / maxNum,
+ * vx the step's incoming speed, Pf, Pr the peaks the step would otherwise use, rho the coupling's ratios (+inf while it is off):
+ *   va = min(vx, v_sat);  q = va va;  d_f = k_f q;  d_r = k_r q            the downforce: it depends on the state alone
+ *   psi_a = 1 + d_a (a1_a + a2_a d_a);  Pf0 = Pf psi_f;  Pr0 = Pr psi_r     the peaks at this speed before any tyre force
+ *   e_f = max(min(F_fx, rho_f Pf0), -(rho_f Pf0));  e_r likewise            the demands clipped at the caps AT THIS SPEED
+ *   w = c_h (e_f + e_r);  w = max(min(w, w_max), -w_max)
+ *   x_f = d_f - w;  x_r = d_r + w;  phi_a = 1 + x_a (a1_a + a2_a x_a);  Pf' = Pf phi_f;  Pr' = Pr phi_r
+ * then exactly the step of the load transfer: the side forces with Pf', Pr', the coupling block on the original F_fx, F_rx
+ * with Pf', Pr'.  The drag stays in the friction map; the step carries no new state.  k_f = k_r = 0, and vx = 0 within one
+ * sub-step, give the step without the setting bit for bit (for finite forces); above v_sat the peaks are those at v_sat; a NaN
+ * vx takes va = v_sat.  acmpc_score_grips applies the setting and vehicle 0's factors to each hypothesis' own peaks.  The
+ * setting belongs to the handle: it survives every other acmpc_set_dynamics* call and acmpc_set_obstacles, and every call
+ * form of mode D takes it from the handle.  While it is on, every vehicle of the handle must have N_a != 0 and finite, Pf, Pr
+ * finite and > 0 as float32, and 1 + x (a1_a + a2_a x) > 0 (in float64) at x = -w_max, at x = w_max + k_a v_sat^2 and at the
+ * vertex -a1_a / (2 a2_a) when that lies strictly between the two, whatever the sign of a2_a: whichever call would break that
+ * - this one, acmpc_set_dynamics_load_transfer, acmpc_set_dynamics or acmpc_set_dynamics_ensemble - returns ACMPC_EINVAL and
+ * leaves the handle as it was.  No device work.  ACMPC_ESTATE for a handle whose mode is not ACMPC_MODE_DYNAMIC; ACMPC_EINVAL
+ * for a k that is negative or not finite, or a v_sat that is not finite and > 0.  DESIGN.md section 2 "Mode D, downforce". */
+int acmpc_set_dynamics_downforce(acmpc_ctx* ctx, const double setting[3] /* NULL: off */);
+
 /* The control applied just before each problem's plan starts: u_prev host [P][2] = (delta, pedal), what step 0's rates
  * are taken against; NULL clears it (P is then ignored), and step 0's own control stands for it: an increment of +0.
  * Staged on the host; it travels to the device with the tables, on the next call's stream (acmpc_sync_tables covers it),

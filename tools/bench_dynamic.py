@@ -52,6 +52,12 @@ w_frac, 0.9 when left out): the TermsLoaded kernels of csrc/acmpc_dynamic_loaded
 `--identify`, identify_grip_loaded_kernel (`identify_grip_loaded`).  To price it, alternate `--coupling 1,1` with
 `--coupling 1,1 --load-transfer 0.35` in one job on one card.
 
+With `--downforce KF,KR[,VSAT]` every handle is given the downforce (acmpc_set_dynamics_downforce: the two coefficients and
+v_sat, 100 m/s when left out): the TermsAero kernels of csrc/acmpc_dynamic_aero.hip, with whatever `--load-transfer` /
+`--coupling` / `--terms` / `--objective` / `--substeps` / `--blend` set beside it, priced with `dynamic_aero_step` + M
+`dynamic_aero_substep`; and with `--identify`, identify_grip_aero_kernel (`identify_grip_aero`).  To price it, alternate
+`--coupling 1,1 --load-transfer 0.35` with the same plus `--downforce 7.35e-4,1.1025e-3` in one job on one card.
+
 With `--identify` the grip identification (acmpc_score_grips: host pointers, one blocking round trip) is timed at K = 4 096
 (the 64 x 64 split grid) and K = 65 536 (256 x 256) hypotheses over a window of W = 40 steps, in one-step (L = 1) and
 eight-step (L = 8) segments, under the run's integration setting: p50 / p99 of the call, the static VALU count per
@@ -60,7 +66,7 @@ and the vector-issue time that count needs (bench.valu_roofline) as a fraction o
 kernel's own fraction, which a `rocprofv3 --kernel-trace --stats` run of this command gives (kernel identify_grip_kernel).
 
 usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms] [--objective] [--coupling RF,RR]
-                                      [--load-transfer H[,FRAC]]
+                                      [--load-transfer H[,FRAC]] [--downforce KF,KR[,VSAT]]
                                       [--sampled | --optimize [--update softmin] | --identify]"""
 import argparse
 import json
@@ -88,6 +94,7 @@ OBJECTIVE_ON = dict(progress_weight=1.0, speed_ceiling=(1.1, 0.0))
 
 COUPLING = None           # --coupling: the tyre coupling (rho_f, rho_r) every handle of this run is given
 LOAD_TRANSFER = None      # --load-transfer: the load transfer (h_cg, w_frac) every handle of this run is given
+DOWNFORCE = None          # --downforce: the downforce (k_f, k_r, v_sat) every handle of this run is given
 
 
 def integrate(eng):
@@ -103,6 +110,8 @@ def integrate(eng):
         eng.set_dynamics_coupling(COUPLING)
     if LOAD_TRANSFER is not None:
         eng.set_dynamics_load_transfer(LOAD_TRANSFER)
+    if DOWNFORCE is not None:
+        eng.set_dynamics_downforce(DOWNFORCE)
     return eng
 
 
@@ -110,7 +119,7 @@ def fine_issue_roof(bench, candidates, steps, kernel_s, name):
     """issue_roof for a FINE kernel: VALU per control step = the step loop's trip + M sub-step trips, priced with the
     sub-step loop's mix (which is nearly all of it)."""
     mix, mix_path = bench.newest_profile("isa_mix.json")
-    kind = "_loaded_" if LOAD_TRANSFER is not None else "_coupled_" if COUPLING is not None else "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
+    kind = "_aero_" if DOWNFORCE is not None else "_loaded_" if LOAD_TRANSFER is not None else "_coupled_" if COUPLING is not None else "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
     step, sub = mix["entries"][name + kind + "step"], mix["entries"][name + kind + "substep"]
     per_step = (sum(step["valu"].values()) + INTEGRATION[0] * sum(sub["valu"].values())) / float(sub["candidates_per_lane"])
     counted = (per_step, mix_path + " (static count: step trip + M sub-step trips)", {"source_sha256": mix.get("source_sha256")})
@@ -124,7 +133,7 @@ def issue_roof(bench, candidates, steps, kernel_s, name="dynamic"):
     """bench.valu_roofline for the `dynamic` entry (`dynamic_ensemble`: candidates = vehicle-candidates): the step loop's
     static VALU count per candidate-step (the isa mix, whose sources must be the loaded build's -
     `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
-    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None or COUPLING is not None or LOAD_TRANSFER is not None) and name in ("dynamic", "dynamic_ensemble"):
+    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None or COUPLING is not None or LOAD_TRANSFER is not None or DOWNFORCE is not None) and name in ("dynamic", "dynamic_ensemble"):
         return fine_issue_roof(bench, candidates, steps, kernel_s, name)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     entry = mix["entries"][name]
@@ -153,8 +162,14 @@ def main():
     ap.add_argument("--objective", action="store_true", help="the progress reward and a speed ceiling on every handle (OBJECTIVE_ON)")
     ap.add_argument("--coupling", default=None, help="RF,RR (or one ratio for both axles): the tyre coupling on every handle")
     ap.add_argument("--load-transfer", default=None, help="H[,FRAC]: the load transfer (CG height, w_frac = 0.9) on every handle")
+    ap.add_argument("--downforce", default=None, help="KF,KR[,VSAT]: the downforce (per-axle coefficients, v_sat = 100) on every handle")
     args = ap.parse_args()
-    global INTEGRATION, TERMS, OBJECTIVE, COUPLING, LOAD_TRANSFER
+    global INTEGRATION, TERMS, OBJECTIVE, COUPLING, LOAD_TRANSFER, DOWNFORCE
+    if args.downforce is not None:
+        aero = tuple(float(v) for v in args.downforce.split(","))
+        if len(aero) not in (2, 3):
+            ap.error("--downforce takes KF,KR or KF,KR,VSAT")
+        DOWNFORCE = aero + (100.0,) if len(aero) == 2 else aero
     if args.load_transfer is not None:
         load = tuple(float(v) for v in args.load_transfer.split(","))
         if len(load) not in (1, 2):
@@ -359,7 +374,7 @@ def measure_identify(args):
     integrate(eng)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     M = INTEGRATION[0]
-    entry = "identify_grip_loaded" if LOAD_TRANSFER is not None else "identify_grip_coupled" if COUPLING is not None else "identify_grip"
+    entry = "identify_grip_aero" if DOWNFORCE is not None else "identify_grip_loaded" if LOAD_TRANSFER is not None else "identify_grip_coupled" if COUPLING is not None else "identify_grip"
     per_step = M * sum(mix["entries"][entry]["valu"].values()) + sum(mix["entries"][entry + "_step"]["valu"].values())
     out = {"tool": "tools/bench_dynamic.py --identify", "W": W, "substeps": M, "low_speed_blend": INTEGRATION[1],
            "valu_per_hypothesis_step": per_step}
@@ -367,6 +382,8 @@ def measure_identify(args):
         out["coupling"] = list(COUPLING)
     if LOAD_TRANSFER is not None:
         out["load_transfer"] = list(LOAD_TRANSFER)
+    if DOWNFORCE is not None:
+        out["downforce"] = list(DOWNFORCE)
     calls = 20 if args.quick else 200
     for side in (64, 256):
         scales = grip_scales(np.linspace(0.3, 1.5, side), "split")
@@ -475,6 +492,8 @@ def measure(args, K):
         out.update(coupling=list(COUPLING))
     if LOAD_TRANSFER is not None:
         out.update(load_transfer=list(LOAD_TRANSFER))
+    if DOWNFORCE is not None:
+        out.update(downforce=list(DOWNFORCE))
     if K > 1:
         out.update(vehicles=K, reduce=args.reduce, grips=list(GRIPS[:K]))
 

@@ -77,6 +77,14 @@ ENTRIES = {
     "dynamic_loaded_substep": ("acmpc_dynamic_loaded.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_11TermsLoadedEEE", None),
     "dynamic_ensemble_loaded_step": ("acmpc_dynamic_loaded.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_11TermsLoadedEEE", None),
     "dynamic_ensemble_loaded_substep": ("acmpc_dynamic_loaded.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_11TermsLoadedEEE", None),
+    # mode D with the downforce (acmpc_set_dynamics_downforce: the TermsAero kernels of acmpc_dynamic_aero.hip, the loaded step
+    # with the downforce of the sub-step's speed under the load moved): the block's instructions = `dynamic_aero_substep` -
+    # `dynamic_loaded_substep` - the clip at v_sat, the square, two products, two more quadratics and products for the caps at
+    # this speed, and the caps' negations per lane
+    "dynamic_aero_step": ("acmpc_dynamic_aero.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_9TermsAeroEEE", None),
+    "dynamic_aero_substep": ("acmpc_dynamic_aero.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_9TermsAeroEEE", None),
+    "dynamic_ensemble_aero_step": ("acmpc_dynamic_aero.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_9TermsAeroEEE", None),
+    "dynamic_ensemble_aero_substep": ("acmpc_dynamic_aero.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_9TermsAeroEEE", None),
     # mode D's grip identification (acmpc_score_grips, one hypothesis per lane): the sub-step loop of its step kernel - the
     # dynamics and the blend's block, WITHOUT the pose (nothing reads it there: no sincos_spec(yaw), no X, Y, yaw updates).
     # VALU per hypothesis and control step = M trips of it + `identify_grip_step`: the control's terms and the residual, the
@@ -89,18 +97,23 @@ ENTRIES = {
     # and under the load transfer (the base vehicle's factors on each lane's own two peaks)
     "identify_grip_loaded": ("acmpc_identify.hip", "identify_grip_loaded_kernel", None),
     "identify_grip_loaded_step": ("acmpc_identify.hip", "identify_grip_loaded_kernel", None),
+    # and under the downforce (the handle's coefficients and the base vehicle's factors on each lane's own two peaks)
+    "identify_grip_aero": ("acmpc_identify.hip", "identify_grip_aero_kernel", None),
+    "identify_grip_aero_step": ("acmpc_identify.hip", "identify_grip_aero_kernel", None),
 }
 CANDIDATES_PER_LANE = {"fused_round": 1, "identify_grip": 1, "identify_grip_step": 1, "identify_grip_coupled": 1,
-                       "identify_grip_coupled_step": 1, "identify_grip_loaded": 1, "identify_grip_loaded_step": 1}
+                       "identify_grip_coupled_step": 1, "identify_grip_loaded": 1, "identify_grip_loaded_step": 1,
+                       "identify_grip_aero": 1, "identify_grip_aero_step": 1}
 OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dynamic_ensemble_fine_step",
          "dynamic_terms_step", "dynamic_ensemble_terms_step", "dynamic_objective_step", "dynamic_ensemble_objective_step",
          "dynamic_coupled_step", "dynamic_ensemble_coupled_step", "dynamic_loaded_step", "dynamic_ensemble_loaded_step",
-         "identify_grip_step", "identify_grip_coupled_step", "identify_grip_loaded_step")
+         "dynamic_aero_step", "dynamic_ensemble_aero_step",
+         "identify_grip_step", "identify_grip_coupled_step", "identify_grip_loaded_step", "identify_grip_aero_step")
 # (exit test at the head: closes with s_branch)
 ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep",
            "dynamic_objective_substep", "dynamic_ensemble_objective_substep", "dynamic_coupled_substep",
-           "dynamic_ensemble_coupled_substep", "dynamic_loaded_substep", "dynamic_ensemble_loaded_substep", "identify_grip",
-           "identify_grip_coupled", "identify_grip_loaded")
+           "dynamic_ensemble_coupled_substep", "dynamic_loaded_substep", "dynamic_ensemble_loaded_substep", "dynamic_aero_substep",
+           "dynamic_ensemble_aero_substep", "identify_grip", "identify_grip_coupled", "identify_grip_loaded", "identify_grip_aero")
 
 
 def source_hash():
