@@ -34,6 +34,9 @@ ROUND_FIELDS = ("kernel", "fused_finalize", "traced", "chained", "frames_in_lds"
 
 # acmpc_describe_rollout's out[4] (ACMPC_ROLLOUT_*): the kernel family and the rows kernel's table choice
 ROLLOUT_KERNELS = (("step", None), ("tile", None), ("rows", "lds"), ("rows", "scalar"))
+# acmpc_describe_softmin's `form` (ACMPC_SOFTMIN_*): a matrix in either layout, or the candidates re-drawn
+SOFTMIN_CANDIDATE_MAJOR, SOFTMIN_STEP_MAJOR, SOFTMIN_SAMPLED = 0, 1, 2
+GRIP_GRID_FIELDS = ("segments", "blocks", "rows", "run", "grid_y", "last_run", "last_segment")   # acmpc_describe_score_grips
 
 
 class EngineError(RuntimeError):
@@ -215,6 +218,8 @@ SIGNATURES = {
     "acmpc_tick_read_device_frames": (C.c_int, [_CTX, C.c_void_p, C.c_int64]),
     "acmpc_describe_rounds": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, _I32P]),
     "acmpc_describe_rollout": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I32P]),
+    "acmpc_describe_softmin": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I32P]),
+    "acmpc_describe_score_grips": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, _I32P]),
     "acmpc_speed_profile_qp_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double,
                                                 C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p,
                                                 C.c_void_p, C.c_int32, _I32P]),
@@ -989,6 +994,28 @@ class Engine:
         return dict(block=int(out[0]), cpt=int(out[1]), pack=int(out[2]), workgroups=int(out[3]),
                     kernel=ROLLOUT_KERNELS[int(out[4])][0], table=ROLLOUT_KERNELS[int(out[4])][1],
                     tailed_fits=bool(out[5]), chained_fits=bool(out[6]), solo=bool(out[7]))
+
+    def describe_softmin(self, P: int, N: int, n: int, form: int) -> dict:
+        """The launches the softmin mean of this shape makes on this handle (acmpc_describe_softmin; test hook, no device
+        work).  `form` = a layout - `softmin_device` over a matrix - or SOFTMIN_SAMPLED - `softmin_sampled_device`.
+        dict(chunks), and with it: candidate-major dict(groups, passes) - the thread groups and the 256-entry passes over a
+        row; sampled dict(items, grid_z, items_per_wave) - the workgroups per chunk and the most items one wave walks."""
+        out = np.zeros(8, dtype=np.int32)
+        self._check(self._lib.acmpc_describe_softmin(self._ctx, int(P), int(N), int(n), int(form), out.ctypes.data_as(_I32P)))
+        d = dict(chunks=int(out[0]))
+        if form == SOFTMIN_CANDIDATE_MAJOR:
+            d.update(groups=int(out[1]), passes=int(out[2]))
+        elif form == SOFTMIN_SAMPLED:
+            d.update(items=int(out[3]), grid_z=int(out[4]), items_per_wave=int(out[5]))
+        return d
+
+    def describe_score_grips(self, W: int, segment: int, K: int) -> dict:
+        """The grid `score_grips` launches for a log of W steps in segments of `segment` and K hypotheses
+        (acmpc_describe_score_grips; test hook, no device work): dict(segments, blocks, rows, run, grid_y, last_run =
+        segments in the last run, last_segment = steps in the last segment)."""
+        out = np.zeros(8, dtype=np.int32)
+        self._check(self._lib.acmpc_describe_score_grips(self._ctx, int(W), int(segment), int(K), out.ctypes.data_as(_I32P)))
+        return {name: int(v) for name, v in zip(GRIP_GRID_FIELDS, out)}
 
     def speed_profile_qp_device(self, v_hi, ds, a_min, a_max, v_min, max_iter=4000, eps_abs=1e-3, eps_rel=1e-3,
                                 warm=None, check_every=10):

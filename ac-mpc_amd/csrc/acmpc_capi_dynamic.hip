@@ -397,19 +397,57 @@ int acmpc_set_dynamics_clearance(acmpc_ctx* c, double weight, double margin) {
   return ACMPC_OK;
 }
 
+// the refusals of acmpc_score_grips that its shape alone decides, in the order it makes them (the log's period, the weights
+// and the scales come between the second and the third): acmpc_describe_score_grips makes the same three calls
+static int grip_handle_ready(const acmpc_ctx* c) {
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_score_grips needs a mode D handle");
+  if (!c->has_dynamics) return fail(c, ACMPC_ESTATE, "mode D: acmpc_set_dynamics has not been called");
+  return ACMPC_OK;
+}
+
+static int grip_shape_valid(const acmpc_ctx* c, int W, int segment, int K) {
+  if (W < 1 || W > ACMPC_MAX_LOG_STEPS) return fail(c, ACMPC_EINVAL, "the log has 1 .. ACMPC_MAX_LOG_STEPS = 512 steps");
+  if (segment < 1 || segment > W) return fail(c, ACMPC_EINVAL, "segment is 1 .. W");
+  if (K < 1) return fail(c, ACMPC_EINVAL, "K must be positive");
+  return ACMPC_OK;
+}
+
+static int grip_shape_fits(const acmpc_ctx* c, int W, int segment, int K) {
+  if (K > ACMPC_MAX_GRIP_HYPOTHESES) return fail(c, ACMPC_ECAPACITY, "at most ACMPC_MAX_GRIP_HYPOTHESES = 65536 hypotheses");
+  if (static_cast<int64_t>(acmpc::identify_segments(W, segment)) * K > acmpc::kIdentifyMaxValues)
+    return fail(c, ACMPC_ECAPACITY, "segments x hypotheses exceeds 2^22");
+  return ACMPC_OK;
+}
+
+int acmpc_describe_score_grips(const acmpc_ctx* c, int32_t W, int32_t segment, int32_t K, int32_t out[8]) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (out == nullptr) return fail(c, ACMPC_EINVAL, "null output");
+  ACMPC_TRY(grip_handle_ready(c));
+  ACMPC_TRY(grip_shape_valid(c, W, segment, K));
+  ACMPC_TRY(grip_shape_fits(c, W, segment, K));
+  const int S = acmpc::identify_segments(W, segment);
+  const acmpc::IdentifyGrid g = acmpc::identify_grid(S, K);
+  out[0] = S;
+  out[1] = g.blocks;
+  out[2] = g.rows;
+  out[3] = g.run;
+  out[4] = g.grid_y;
+  out[5] = S - (g.grid_y - 1) * g.run;   // segments of the last run
+  out[6] = W - (S - 1) * segment;        // steps of the last segment
+  out[7] = 0;
+  return ACMPC_OK;
+}
+
 int acmpc_score_grips(acmpc_ctx* c, const float* states, const float* controls, int32_t W, double dt, int32_t segment,
                       const double weights[3], const double* scales, int32_t K, float* errors, int64_t* best) {
   if (c == nullptr) return ACMPC_EINVAL;
   // every refusal comes before any device work
   if (states == nullptr || controls == nullptr || weights == nullptr || scales == nullptr || best == nullptr)
     return fail(c, ACMPC_EINVAL, "acmpc_score_grips: null pointer");
-  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_score_grips needs a mode D handle");
-  if (!c->has_dynamics) return fail(c, ACMPC_ESTATE, "mode D: acmpc_set_dynamics has not been called");
+  ACMPC_TRY(grip_handle_ready(c));
   if (c->stream_pending)
     return fail(c, ACMPC_ESTATE, "a batch of acmpc_solve_stream_device is pending: acmpc_solve_stream_flush first");
-  if (W < 1 || W > ACMPC_MAX_LOG_STEPS) return fail(c, ACMPC_EINVAL, "the log has 1 .. ACMPC_MAX_LOG_STEPS = 512 steps");
-  if (segment < 1 || segment > W) return fail(c, ACMPC_EINVAL, "segment is 1 .. W");
-  if (K < 1) return fail(c, ACMPC_EINVAL, "K must be positive");
+  ACMPC_TRY(grip_shape_valid(c, W, segment, K));
   if (!std::isfinite(dt) || !(dt > 0.0)) return fail(c, ACMPC_EINVAL, "dt must be finite and positive");
   bool any_weight = false;
   for (int q = 0; q < 3; ++q) {
@@ -419,10 +457,8 @@ int acmpc_score_grips(acmpc_ctx* c, const float* states, const float* controls, 
     any_weight = any_weight || static_cast<float>(weights[q]) != 0.0f;
   }
   if (!any_weight) return fail(c, ACMPC_EINVAL, "the residual's weights are all zero");
-  if (K > ACMPC_MAX_GRIP_HYPOTHESES) return fail(c, ACMPC_ECAPACITY, "at most ACMPC_MAX_GRIP_HYPOTHESES = 65536 hypotheses");
+  ACMPC_TRY(grip_shape_fits(c, W, segment, K));
   const int S = acmpc::identify_segments(W, segment);
-  if (static_cast<int64_t>(S) * K > acmpc::kIdentifyMaxValues)
-    return fail(c, ACMPC_ECAPACITY, "segments x hypotheses exceeds 2^22");
   for (int64_t q = 0; q < 2 * static_cast<int64_t>(K); ++q)
     if (!std::isfinite(scales[q]) || !(scales[q] > 0.0))
       return fail(c, ACMPC_EINVAL, "hypothesis " + std::to_string(q / 2) + ": a grip scale must be finite and positive");

@@ -203,14 +203,10 @@ int finalize(acmpc_ctx* c, const int64_t* d_keys_in, int64_t* d_keys_out, const 
   return ACMPC_OK;
 }
 
-// raised-cosine blend between kSampleKnots knots spread evenly over the n steps
-int upload_segments(acmpc_ctx* c, int n, hipStream_t s) {
-  if (c->segments_n == n) return ACMPC_OK;
-  // a pending batch of acmpc_solve_stream_device re-draws its winners with the knot table of ITS horizon, in place in
-  // d_segments: it must have run before the table is rewritten for another (acmpc_solve_stream_device flushes it itself)
-  if (c->stream_pending)
-    return fail(c, ACMPC_ESTATE, "a batch of acmpc_solve_stream_device with another horizon is pending: acmpc_solve_stream_flush first");
-  std::vector<float> seg(static_cast<size_t>(n) * 2);
+// raised-cosine blend between kSampleKnots knots spread evenly over the n steps: seg [n][2] = (left knot, its weight) and
+// the first step of every knot's segment.  upload_segments and acmpc_describe_softmin both take the table from here.
+static void knot_table(int n, std::vector<float>& seg, int (&knot_begin)[acmpc::kKnots + 1]) {
+  seg.assign(static_cast<size_t>(n) * 2, 0.0f);
   const double width = static_cast<double>(n - 1) / (acmpc::kSampleKnots - 1);
   for (int i = 0; i < n; ++i) {
     const double pos = (n > 1) ? i / width : 0.0;
@@ -221,11 +217,21 @@ int upload_segments(acmpc_ctx* c, int n, hipStream_t s) {
     seg[2 * i + 1] = static_cast<float>(0.5 * (1.0 + std::cos(3.14159265358979323846 * frac)));
   }
   // first step of every knot's segment (left knots are non-decreasing in the step index)
-  for (int k = 0; k <= acmpc::kSampleKnots; ++k) c->knot_begin[k] = n;
-  for (int i = n - 1; i >= 0; --i) c->knot_begin[static_cast<int>(seg[2 * i])] = i;
+  for (int k = 0; k <= acmpc::kSampleKnots; ++k) knot_begin[k] = n;
+  for (int i = n - 1; i >= 0; --i) knot_begin[static_cast<int>(seg[2 * i])] = i;
   for (int k = acmpc::kSampleKnots - 1; k >= 0; --k)
-    if (c->knot_begin[k] > c->knot_begin[k + 1]) c->knot_begin[k] = c->knot_begin[k + 1];
-  c->knot_begin[0] = 0;
+    if (knot_begin[k] > knot_begin[k + 1]) knot_begin[k] = knot_begin[k + 1];
+  knot_begin[0] = 0;
+}
+
+int upload_segments(acmpc_ctx* c, int n, hipStream_t s) {
+  if (c->segments_n == n) return ACMPC_OK;
+  // a pending batch of acmpc_solve_stream_device re-draws its winners with the knot table of ITS horizon, in place in
+  // d_segments: it must have run before the table is rewritten for another (acmpc_solve_stream_device flushes it itself)
+  if (c->stream_pending)
+    return fail(c, ACMPC_ESTATE, "a batch of acmpc_solve_stream_device with another horizon is pending: acmpc_solve_stream_flush first");
+  std::vector<float> seg;
+  knot_table(n, seg, c->knot_begin);
   ACMPC_HIP(c, hipMemcpyAsync(c->d_segments, seg.data(), seg.size() * sizeof(float), hipMemcpyHostToDevice, s));
   ACMPC_HIP(c, hipStreamSynchronize(s));  // `seg` is a local
   c->segments_n = n;
@@ -778,6 +784,40 @@ int acmpc_softmin_sampled_device(acmpc_ctx* c, const float* d_costs, const int64
   ACMPC_TRY(ensure_device(c));
   return softmin_sampled(c, d_costs, d_keys, d_centre, centre_stride, d_u_ref, P, N, n, index_offset, sigma_v, sigma_kappa,
                          seed, round, d_mean, d_weight_sum, static_cast<hipStream_t>(stream));
+}
+
+static_assert(ACMPC_SOFTMIN_CANDIDATE_MAJOR == ACMPC_LAYOUT_CANDIDATE_MAJOR && ACMPC_SOFTMIN_STEP_MAJOR == ACMPC_LAYOUT_STEP_MAJOR,
+              "include/acmpc.h");
+
+int acmpc_describe_softmin(const acmpc_ctx* c, int32_t P, int32_t N, int32_t n, int32_t form, int32_t out[8]) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (out == nullptr) return fail(c, ACMPC_EINVAL, "null output");
+  // what check_shape refuses of a shape alone, and the softmin calls after it
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC && !c->has_dynamics)
+    return fail(c, ACMPC_ESTATE, "mode D: acmpc_set_dynamics has not been called");
+  if (P < 1 || N < 1 || n < 1) return fail(c, ACMPC_EINVAL, "P, N and n must be positive");
+  if (form != ACMPC_SOFTMIN_CANDIDATE_MAJOR && form != ACMPC_SOFTMIN_STEP_MAJOR && form != ACMPC_SOFTMIN_SAMPLED)
+    return fail(c, ACMPC_EINVAL, "unknown form");
+  if (P > c->prm.max_problems || N > c->prm.max_candidates || n > c->prm.max_steps)
+    return fail(c, ACMPC_ECAPACITY, "shape exceeds the handle's capacity");
+  if (!(c->prm.softmin_lambda > 0.0)) return fail(c, ACMPC_EINVAL, "softmin_lambda must be positive");
+  for (int q = 0; q < 8; ++q) out[q] = 0;
+  out[0] = acmpc::softmin_chunks(N);
+  if (form == ACMPC_SOFTMIN_CANDIDATE_MAJOR) {
+    const acmpc::SoftminRows rows = acmpc::softmin_rows(n);
+    out[1] = rows.groups;
+    out[2] = rows.passes;
+  } else if (form == ACMPC_SOFTMIN_SAMPLED) {
+    std::vector<float> seg;
+    int knot_begin[acmpc::kKnots + 1];
+    knot_table(n, seg, knot_begin);
+    const int items = acmpc::softmin_item_count(knot_begin);
+    const acmpc::SoftminItems walk = acmpc::softmin_items(out[0], P, items);
+    out[3] = items;
+    out[4] = walk.grid_z;
+    out[5] = walk.per_wave;
+  }
+  return ACMPC_OK;
 }
 
 }  // extern "C"

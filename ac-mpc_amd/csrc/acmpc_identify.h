@@ -30,6 +30,13 @@ struct IdentifyArgs {
 
 int identify_segments(int W, int L);   // ceil(W / L)
 int identify_blocks(int K);            // workgroups (= partial keys) of K hypotheses: <= 256
+// the grid of identify_grip_kernel over S segments of K hypotheses: `blocks` x `grid_y` workgroups, workgroup (x, y) rolling
+// segments [y run, min((y + 1) run, S)) - `rows` is the number of runs aimed at.  launch_identify_grip launches what this
+// returns and acmpc_describe_score_grips reports it.
+struct IdentifyGrid {
+  int blocks, rows, run, grid_y;
+};
+IdentifyGrid identify_grid(int S, int K);
 // `vehicle`: the base vehicle (its Pf, Pr are not read); `g`: the integration setting with h of the LOG's period and
 // inv_L[0] the base vehicle's; `coupling`: the two ratios of the handle's tyre coupling, or nullptr while it is off.  hipErrorInvalidValue
 // beyond the limits above.

@@ -229,6 +229,16 @@ int identify_segments(int W, int L) { return (W + L - 1) / L; }
 
 int identify_blocks(int K) { return (K + kIdBlock - 1) / kIdBlock; }
 
+// a run of segments per workgroup once the grid would be thousands of one-segment workgroups: about 2 048 in all
+IdentifyGrid identify_grid(int S, int K) {
+  IdentifyGrid g{};
+  g.blocks = identify_blocks(K);   // <= 256
+  g.rows = std::min(S, std::max(1, 2048 / g.blocks));
+  g.run = (S + g.rows - 1) / g.rows;
+  g.grid_y = (S + g.run - 1) / g.run;
+  return g;
+}
+
 hipError_t launch_identify_grip(const IdentifyArgs& a, const Vehicle& vehicle, const Integration& g, const float* coupling,
                                 const IdentifyLoad* load, const IdentifyAero* aero, hipStream_t s) {
   (void)hipGetLastError();
@@ -240,11 +250,9 @@ hipError_t launch_identify_grip(const IdentifyArgs& a, const Vehicle& vehicle, c
   if (a.states == nullptr || a.controls == nullptr || a.peaks == nullptr || a.e == nullptr || a.errors == nullptr ||
       a.partial_keys == nullptr || a.best == nullptr)
     return hipErrorInvalidValue;
-  const int blocks = identify_blocks(a.K);   // <= 256
-  // a run of segments per workgroup once the grid would be thousands of one-segment workgroups: about 2 048 in all
-  const int rows = std::min(S, std::max(1, 2048 / blocks));
-  const int run = (S + rows - 1) / rows;
-  const dim3 grid(blocks, (S + run - 1) / run);
+  const IdentifyGrid shape = identify_grid(S, a.K);
+  const int blocks = shape.blocks, run = shape.run;
+  const dim3 grid(blocks, shape.grid_y);
   if (aero != nullptr) {
     if (load == nullptr) return hipErrorInvalidValue;   // (the factors a1, a2 travel with the load transfer's scalars)
     hipLaunchKernelGGL(identify_grip_aero_kernel, grid, dim3(kIdBlock), 0, s, a.states, a.controls,

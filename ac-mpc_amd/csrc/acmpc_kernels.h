@@ -201,6 +201,20 @@ bool traced_finalize_fits(int mode, int n);
 // whether rollout + fused finalize fit one workgroup's 64 KB of LDS (mode T at the longest horizons does not)
 bool fused_finalize_fits(int mode, int n);
 int softmin_chunks(int N);
+// the geometry of the softmin launches, for the launchers and for acmpc_describe_softmin alike.
+// softmin_rows: the candidate-major partial kernel's thread groups (rows summed side by side) and 256-entry passes over a row
+// of 2n floats - the kernel computes both itself, from the same two lines.
+struct SoftminRows {
+  int groups, passes;
+};
+SoftminRows softmin_rows(int n);
+// the sampled form: items = runs of at most 8 steps that share a left knot (from the sampler's knot table of this horizon);
+// softmin_items = the workgroups per chunk (gridDim.z) launch_softmin_sampled launches and the most items one wave walks
+int softmin_item_count(const int (&knot_begin)[kKnotsMax + 1]);
+struct SoftminItems {
+  int grid_z, per_wave;
+};
+SoftminItems softmin_items(int chunks_per_problem, int P, int items);
 hipError_t launch_softmin(int layout, const SoftminArgs& args, hipStream_t s);
 // launch_softmin(step-major) over the matrix launch_sample(step-major, `sample`) would write, without the matrix: the
 // candidates are re-drawn inside the partial kernel (args.U is not read; sample.U neither).  The same partial sums, mean and

@@ -126,12 +126,6 @@ __global__ void __launch_bounds__(kSoftBlock) softmin_partial_kernel(const Softm
 constexpr int kSoftTile = 8;
 constexpr int kSoftItemsMax = 160;   // >= max_steps / kSoftTile + kKnots - 1 (max_steps <= 1024)
 
-inline int softmin_item_count(const int (&knot_begin)[kKnotsMax + 1]) {
-  int m = 0;
-  for (int k = 0; k < kKnots - 1; ++k) m += (knot_begin[k + 1] - knot_begin[k] + kSoftTile - 1) / kSoftTile;
-  return m;
-}
-
 template <int TILE>
 __global__ void __launch_bounds__(kSoftBlock) softmin_sampled_partial_kernel(const SoftminArgs a, const SampleArgs smp) {
   extern __shared__ __attribute__((aligned(16))) float s_draw[];   // [n] weight of the left knot | [n][2] centre | [n][2] reference
@@ -277,6 +271,30 @@ __global__ void __launch_bounds__(kSoftBlock) softmin_final_kernel(const Softmin
 
 int softmin_chunks(int N) { return (N + kSoftChunk - 1) / kSoftChunk; }
 
+// softmin_partial_kernel<0>'s own two numbers: G = 256 / 2n thread groups (1 once a row is wider than the workgroup) and the
+// trips of its e0 loop, one per 256 entries of a row
+SoftminRows softmin_rows(int n) {
+  const int n2 = 2 * n;
+  return SoftminRows{kSoftBlock / n2 > 0 ? kSoftBlock / n2 : 1, (n2 + kSoftBlock - 1) / kSoftBlock};
+}
+
+int softmin_item_count(const int (&knot_begin)[kKnotsMax + 1]) {
+  int m = 0;
+  for (int k = 0; k < kKnots - 1; ++k) m += (knot_begin[k + 1] - knot_begin[k] + kSoftTile - 1) / kSoftTile;
+  return m;
+}
+
+// workgroups per chunk: enough of them that a lone problem of a few chunks still covers the chip, never more than
+// there are items for their four waves
+SoftminItems softmin_items(int chunks_per_problem, int P, int items) {
+  constexpr int kWaves = kSoftBlock / kWave;
+  const long long chunks = static_cast<long long>(chunks_per_problem) * P;
+  const int by_items = (items + kWaves - 1) / kWaves;
+  const int by_chip = static_cast<int>(std::min<long long>((512 + chunks - 1) / chunks, by_items));
+  const int z = std::max(by_chip, 1);
+  return SoftminItems{z, (items + z * kWaves - 1) / (z * kWaves)};
+}
+
 hipError_t launch_softmin(int layout, const SoftminArgs& args, hipStream_t s) {
   clear_stale_error();
   const dim3 grid(args.chunks, args.P);
@@ -300,13 +318,7 @@ hipError_t launch_softmin_sampled(const SoftminArgs& args, const SampleArgs& sam
     if (kb[k + 1] < kb[k]) return hipErrorInvalidValue;
   const int items = softmin_item_count(kb);
   if (items < 1 || items > kSoftItemsMax) return hipErrorInvalidValue;
-  // workgroups per chunk: enough of them that a lone problem of a few chunks still covers the chip, never more than
-  // there are items for their four waves
-  constexpr int kWaves = kSoftBlock / kWave;
-  const long long chunks = static_cast<long long>(args.chunks) * args.P;
-  const int by_items = (items + kWaves - 1) / kWaves;
-  const int by_chip = static_cast<int>(std::min<long long>((512 + chunks - 1) / chunks, by_items));
-  const dim3 grid(args.chunks, args.P, std::max(by_chip, 1));
+  const dim3 grid(args.chunks, args.P, softmin_items(args.chunks, args.P, items).grid_z);
   const size_t lds = static_cast<size_t>(5) * args.n * sizeof(float);
   const hipError_t e = launch_kernel(softmin_sampled_partial_kernel<kSoftTile>, grid, dim3(kSoftBlock), lds, s, nullptr, nullptr, args, sample);
   if (e != hipSuccess) return e;

@@ -748,6 +748,41 @@ int acmpc_describe_rounds(const acmpc_ctx* ctx, int32_t P, int32_t N, int32_t n,
 #define ACMPC_ROLLOUT_ROWS_SCALAR 3  /* ... the table's rows by scalar loads */
 int acmpc_describe_rollout(const acmpc_ctx* ctx, int32_t P, int32_t N, int32_t n, int32_t layout, int32_t out[8]);
 
+/* Test hook of the softmin mean (any mode): the launches acmpc_softmin_device (`form` = the matrix's layout) and
+ * acmpc_softmin_sampled_device (`form` = ACMPC_SOFTMIN_SAMPLED) make for (P, N, n) on this handle.  The answer comes from
+ * the functions the launchers themselves ask (csrc: softmin_chunks, softmin_rows, softmin_item_count, softmin_items) and,
+ * for the sampled form, from the sampler's knot table of this horizon; no device work, the GPU is not initialised.  out[8] =
+ *   [0] chunks of 1 024 candidates per problem: the partial kernel's workgroups per problem (and per gridDim.z)
+ *   [1] candidate-major: thread groups that sum rows side by side, 256 / 2n (1 from n = 65 on)
+ *   [2] candidate-major: passes of 256 entries over a row of 2n floats (1 up to n = 128)
+ *   [3] sampled: items - runs of at most 8 steps that share a left knot
+ *   [4] sampled: workgroups per chunk (gridDim.z), four waves each
+ *   [5] sampled: the most items one wave walks, ceil(items / (4 gridDim.z))
+ *   [6], [7] 0; so are the entries of the other forms
+ * Refuses what the calls refuse of a shape: ACMPC_EINVAL for a size below 1, an unknown form or a softmin_lambda that is
+ * not positive, ACMPC_ECAPACITY beyond the handle's capacities, ACMPC_ESTATE on a mode D handle without a vehicle.  (That
+ * n is the horizon of the tables set - at least 2 - is the calls' own check.) */
+#define ACMPC_SOFTMIN_CANDIDATE_MAJOR 0 /* = ACMPC_LAYOUT_CANDIDATE_MAJOR */
+#define ACMPC_SOFTMIN_STEP_MAJOR 1      /* = ACMPC_LAYOUT_STEP_MAJOR */
+#define ACMPC_SOFTMIN_SAMPLED 2
+int acmpc_describe_softmin(const acmpc_ctx* ctx, int32_t P, int32_t N, int32_t n, int32_t form, int32_t out[8]);
+
+/* Test hook of the grip identification (mode D): the grid acmpc_score_grips launches for a log of W steps cut into
+ * segments of `segment` steps and K hypotheses, from the function the launcher itself asks (csrc: identify_grid); no
+ * device work, the GPU is not initialised.  out[8] =
+ *   [0] S = ceil(W / segment) segments
+ *   [1] blocks = ceil(K / 256): workgroups along the hypotheses = partial keys
+ *   [2] rows = min(S, 2048 / blocks): the runs of segments aimed at
+ *   [3] run = ceil(S / rows): segments one workgroup rolls
+ *   [4] grid.y = ceil(S / run)
+ *   [5] segments in the last run, 1 .. run
+ *   [6] steps in the last segment, 1 .. segment
+ *   [7] 0
+ * Refuses what acmpc_score_grips refuses of a shape, with its codes: ACMPC_ESTATE off mode D or without a vehicle,
+ * ACMPC_EINVAL for W outside 1 .. ACMPC_MAX_LOG_STEPS, segment outside 1 .. W or K < 1, ACMPC_ECAPACITY for
+ * K > ACMPC_MAX_GRIP_HYPOTHESES or S K > 2^22. */
+int acmpc_describe_score_grips(const acmpc_ctx* ctx, int32_t W, int32_t segment, int32_t K, int32_t out[8]);
+
 /* Host-side float64 helpers round one solve (csrc/acmpc_host_path.cpp; no GPU work, no handle).
  * Replaces: SpatialMPC.construct_waypoints (spatial_mpc.py:125-154).  coords [H][3] = (x, y, width) ->
  * table [7][n], n = H - 1, rows [x, y, psi, kappa, ds, width, v = 0]. */

@@ -87,6 +87,168 @@ def test_errors_and_best_are_the_specification(shape, integration):
     eng.close()
 
 
+# ---- the launch at its thresholds ---------------------------------------------------------------------------------------
+# identify_grip_kernel's workgroup (x, y) rolls the run of segments [y run, min((y + 1) run, S)); run = 1 up to 2 048
+# workgroups, that is whenever K <= 1 024 and S <= 2048 / blocks.  Every shape below is asserted through
+# `describe_score_grips` - the launcher's own numbers (tests/test_grip_identification.py has them as literals) - and then
+# compared bit for bit with the restatement, the best index included.
+# (W, L, K): dict(blocks, rows, run, grid_y, last_run = segments in the last run, last_segment = steps in the last segment)
+RUN_SHAPES = {
+    (512, 1, 1024): dict(segments=512, blocks=4, rows=512, run=1, grid_y=512, last_run=1, last_segment=1),    # the last with run = 1
+    (205, 1, 2305): dict(segments=205, blocks=10, rows=204, run=2, grid_y=103, last_run=1, last_segment=1),   # a last run of one
+    (409, 2, 2305): dict(segments=205, blocks=10, rows=204, run=2, grid_y=103, last_run=1, last_segment=1),   # ... of one step
+    (409, 1, 2305): dict(segments=409, blocks=10, rows=204, run=3, grid_y=137, last_run=1, last_segment=1),   # run = 3, ragged
+    (511, 1, 1025): dict(segments=511, blocks=5, rows=409, run=2, grid_y=256, last_run=1, last_segment=1),
+}
+RUN_CASES = [(shape, (1, None)) for shape in RUN_SHAPES] + [((205, 1, 2305), (4, (3.0, 5.0)))]
+
+
+@pytest.mark.parametrize("shape,integration", RUN_CASES,
+                         ids=["W%d_L%d_K%d-%s" % (*s, "default" if i == (1, None) else "fine") for s, i in RUN_CASES])
+def test_runs_of_segments_are_the_specification(shape, integration):
+    """The restatement of these shapes takes 1.4 .. 2.9 s on one slow core under the default integration and 6.4 s under the
+    fine one (4 sub-steps: four times the arithmetic), which is why only the smallest shape with run > 1 runs there; on the
+    MI355X host the whole cases took 0.4 .. 1.0 s and 2.1 s."""
+    W, L, K = shape
+    states, controls = _log(W, slow=integration != (1, None))
+    scales = _scales(K)
+    eng = _engine(integration)
+    try:
+        assert eng.describe_score_grips(W, L, K) == RUN_SHAPES[shape]
+        errors, best = eng.score_grips(states, controls, HANDLE_DT, scales, segment=L)
+    finally:
+        eng.close()
+    want, want_best = gs.score(_vehicle0().coefficients(), states, controls, HANDLE_DT, scales, segment=L,
+                               substeps=integration[0], low_speed_blend=integration[1])
+    assert np.isfinite(want).all()
+    _same_bits(errors, want)
+    assert best == want_best
+
+
+@pytest.mark.parametrize("variant", ["coupled", "loaded", "aero"])
+def test_runs_of_segments_in_the_other_three_kernels(variant):
+    """identify_grip_coupled_kernel, _loaded_kernel and _aero_kernel each hold the run's lines again: (205, 1, 2305) - run = 2,
+    a last run of one segment - under the coupling alone, the load transfer and the downforce, each against its own
+    restatement on its own module's log (1.4 .. 1.5 s each on one core)."""
+    import dynamic_aero_spec as das
+    import dynamic_coupling_spec as dcs
+    import dynamic_load_spec as dls
+    import test_gpu_dynamic_coupling as tgc
+    import test_gpu_dynamic_downforce as tgf
+    import test_gpu_dynamic_load_transfer as tgl
+    W, L, K = shape = (205, 1, 2305)
+    ratio = (0.9, 1.1)
+    scales = _scales(K)
+    if variant == "coupled":
+        states, controls = tgc._braking_log(W)
+        want, want_best = dcs.score(ratio, tgc._vehicle().coefficients(), states, controls, 0.05, scales, segment=L)
+    elif variant == "loaded":
+        states, controls = tgl._braking_log(W)
+        want, want_best = dls.score(ratio, tgl.LOAD, tgl._vehicle().coefficients(), states, controls, 0.05, scales, segment=L)
+    else:
+        states, controls = tgf._fast_log(W)
+        want, want_best = das.score(ratio, tgf.LOAD, tgf.AERO, tgf._vehicle().coefficients(), states, controls, 0.05, scales,
+                                    segment=L)
+    eng = _engine()
+    try:
+        assert eng.describe_score_grips(W, L, K) == RUN_SHAPES[shape]
+        before = [eng.score_grips(states, controls, 0.05, scales, segment=L)[0]]     # the kernels this variant is built on
+        eng.set_dynamics_coupling(ratio)
+        if variant != "coupled":
+            before.append(eng.score_grips(states, controls, 0.05, scales, segment=L)[0])
+            eng.set_dynamics_load_transfer(tgl.LOAD if variant == "loaded" else tgf.LOAD)
+        if variant == "aero":
+            before.append(eng.score_grips(states, controls, 0.05, scales, segment=L)[0])
+            eng.set_dynamics_downforce(tgf.AERO)
+        errors, best = eng.score_grips(states, controls, 0.05, scales, segment=L)
+    finally:
+        eng.close()
+    assert np.isfinite(want).all()
+    _same_bits(errors, want)
+    assert best == want_best
+    for earlier in before:          # the setting is in these errors
+        assert not np.array_equal(errors.view(np.uint32), earlier.view(np.uint32))
+
+
+def test_the_best_of_65_partial_keys():
+    """K = 16 385 is 65 workgroups, so identify_best_kernel's lanes go round their loop twice: the true vehicle alone in the
+    65th workgroup, then three times - the lowest index wins across the passes."""
+    W, L, K = 5, 2, 16385
+    states, controls = gs.steering_log(_vehicle0().with_axle_grip(0.5, 0.7), 0.02, steps=W)
+    scales = _scales(K, seed=5)
+    scales[16384] = (0.5, 0.7)
+    eng = _engine()
+    try:
+        assert eng.describe_score_grips(W, L, K) == dict(segments=3, blocks=65, rows=3, run=1, grid_y=3, last_run=1, last_segment=1)
+        errors, best = eng.score_grips(states, controls, HANDLE_DT, scales, segment=L)
+        want, want_best = gs.score(_vehicle0().coefficients(), states, controls, HANDLE_DT, scales, segment=L)
+        _same_bits(errors, want)
+        assert best == want_best == 16384 and errors[16384] < np.delete(errors, 16384).min()
+        scales[[300, 9000]] = (0.5, 0.7)
+        errors, best = eng.score_grips(states, controls, HANDLE_DT, scales, segment=L)
+        assert best == 300 and errors[300] == errors[16384] == errors[9000] == errors.min()
+        assert np.count_nonzero(errors == errors.min()) == 3
+    finally:
+        eng.close()
+
+
+def test_the_limits_65536_hypotheses_and_two_to_the_22_values():
+    """K = 65 536 and S K = 2^22: 256 workgroups along the hypotheses (256 partial keys), runs of 8 segments.  The whole
+    restatement would take 17 s, so: the errors are those of the same hypotheses scored 1 024 at a time (run = 1, tied to
+    the restatement above); they are the restatement's on every workgroup's first and last lane and every 97th
+    hypothesis; and the best index is the key rule over the device's own errors, the minimum planted in the last workgroup."""
+    import acmpc_oracle as orc
+    W, L, K = 64, 1, 65536
+    states, controls = gs.steering_log(_vehicle0().with_axle_grip(0.5, 0.7), 0.02, steps=W)
+    scales = _scales(K, seed=6)
+    scales[K - 100] = (0.5, 0.7)
+    eng = _engine()
+    try:
+        assert eng.describe_score_grips(W, L, K) == dict(segments=64, blocks=256, rows=8, run=8, grid_y=8, last_run=8, last_segment=1)
+        assert eng.describe_score_grips(W, L, 1024) == dict(segments=64, blocks=4, rows=64, run=1, grid_y=64, last_run=1, last_segment=1)
+        errors, best = eng.score_grips(states, controls, HANDLE_DT, scales, segment=L)
+        pieces = [eng.score_grips(states, controls, HANDLE_DT, scales[k:k + 1024], segment=L)[0] for k in range(0, K, 1024)]
+    finally:
+        eng.close()
+    _same_bits(errors, np.concatenate(pieces))
+    subset = np.unique(np.concatenate([np.arange(0, K, 256), np.arange(255, K, 256), np.arange(0, K, 97), [K - 100]]))
+    want, _ = gs.score(_vehicle0().coefficients(), states, controls, HANDLE_DT, scales[subset], segment=L)
+    assert np.isfinite(want).all()
+    _same_bits(errors[subset], want)
+    assert best == int(orc.pick_best(errors)[0]) == K - 100
+
+
+def test_a_larger_call_after_a_smaller_one_and_back():
+    """The per-segment scratch e [S][K] grows with the call: S K = 3, then 2^20 (64 workgroups, runs of 2), then 3 again on
+    one handle, each the bits of a fresh handle."""
+    calls = [(3, 1, 1), (64, 1, 16384), (3, 1, 1)]
+    inputs = [(_log(W, slow=False, seed=i), _scales(K, seed=i)) for i, (W, L, K) in enumerate(calls)]
+
+    def run(eng, i):
+        (states, controls), scales = inputs[i]
+        return eng.score_grips(states, controls, HANDLE_DT, scales, segment=calls[i][1])
+
+    eng = _engine()
+    try:
+        assert eng.describe_score_grips(*calls[1]) == dict(segments=64, blocks=64, rows=32, run=2, grid_y=32, last_run=2, last_segment=1)
+        got = [run(eng, i) for i in range(3)]
+    finally:
+        eng.close()
+    for i in range(3):
+        fresh = _engine()
+        try:
+            errors, best = run(fresh, i)
+        finally:
+            fresh.close()
+        _same_bits(got[i][0], errors)
+        assert got[i][1] == best
+    for i in (0, 2):
+        (states, controls), scales = inputs[i]
+        want, want_best = gs.score(_vehicle0().coefficients(), states, controls, HANDLE_DT, scales)
+        _same_bits(got[i][0], want)
+        assert got[i][1] == want_best
+
+
 def test_a_nan_in_the_log_makes_every_error_nan():
     states, controls = _log(5, slow=False)
     states[2, 0] = np.nan

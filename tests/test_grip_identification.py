@@ -209,6 +209,11 @@ def test_every_refusal_comes_before_any_device_work():
     assert code(eng, scales=np.ones((65537, 2))) == _capi.ECAPACITY
     wide = np.zeros((513, 3), dtype=np.float32)                     # S K = 512 x 8193 > 2^22
     assert code(eng, states=wide, controls=np.zeros((512, 2), dtype=np.float32), scales=np.ones((8193, 2))) == _capi.ECAPACITY
+    # one segment more than fits under the largest K: S K = 2^22 + K; S K = 2^22 itself is a good call
+    full = np.ones((65536, 2))
+    assert code(eng, states=wide[:66], controls=np.zeros((65, 2), dtype=np.float32), scales=full) == _capi.ECAPACITY
+    if not torch.cuda.is_available():
+        assert code(eng, states=wide[:65], controls=np.zeros((64, 2), dtype=np.float32), scales=full) == _capi.ENODEVICE
     # null pointers, W = 0 and a null handle: the raw call
     lib = _capi.load_library()
     w3, best = np.ones(3), C.c_int64(0)
@@ -225,6 +230,69 @@ def test_every_refusal_comes_before_any_device_work():
         eng.score_grips(x, u[:3], 0.05, one)                        # states and controls of different logs
     if not torch.cuda.is_available():
         assert code(eng) == _capi.ENODEVICE
+    eng.close()
+
+
+def test_the_grid_of_a_scoring_launch_as_literal_numbers():
+    """`acmpc_describe_score_grips` answers from the function the launcher asks (csrc: identify_grid), so these are the sizes at
+    which acmpc_score_grips starts to give a workgroup a run of segments, and how ragged the last run is.  Fixed here on
+    purpose: whoever changes the rule moves the cases of tests/test_gpu_grip_identification.py, which run them on the
+    device, with it."""
+    from acmpc_amd import Engine, EngineError, _capi
+
+    def engine(mode=_capi.MODE_DYNAMIC):
+        return Engine(mode=mode, max_problems=1, max_candidates=8, max_steps=4, step_cost=(1, 1, 0), r_term=(1, 1),
+                      final_cost=(1, 1, 0), u_min=(-0.3, -1), u_max=(0.3, 1), margin=0.0, wheelbase=2.9)
+
+    eng = engine()
+    eng.set_dynamics(_base())
+
+    def grid(W, L, K):
+        d = eng.describe_score_grips(W, L, K)
+        # what the numbers mean: every segment in exactly one run, every run but the last full
+        assert d["segments"] == -(-W // L) and d["blocks"] == -(-K // 256) and d["rows"] == min(d["segments"], max(1, 2048 // d["blocks"]))
+        assert (d["grid_y"] - 1) * d["run"] + d["last_run"] == d["segments"] and 1 <= d["last_run"] <= d["run"]
+        assert (d["segments"] - 1) * L + d["last_segment"] == W and 1 <= d["last_segment"] <= L
+        return d["segments"], d["blocks"], d["rows"], d["run"], d["grid_y"], d["last_run"], d["last_segment"]
+
+    # every shape under test before these had run = 1
+    for W, L, K in ((1, 1, 1), (5, 1, 3), (7, 3, 65), (33, 8, 257), (12, 12, 64), (40, 1, 625), (512, 512, 2), (512, 1, 2), (40, 8, 625)):
+        assert grid(W, L, K)[3:6] == (1, -(-W // L), 1), (W, L, K)
+    assert grid(7, 3, 65) == (3, 1, 3, 1, 3, 1, 1) and grid(33, 8, 257) == (5, 2, 5, 1, 5, 1, 1)
+    # run = 1 up to 1 024 hypotheses whatever the log; one hypothesis more and 512 segments go in runs of 2
+    assert grid(512, 1, 1024) == (512, 4, 512, 1, 512, 1, 1)
+    assert grid(512, 1, 1025) == (512, 5, 409, 2, 256, 2, 1)
+    assert grid(511, 1, 1025) == (511, 5, 409, 2, 256, 1, 1)          # a last run of one segment
+    assert grid(409, 1, 1025) == (409, 5, 409, 1, 409, 1, 1) and grid(410, 1, 1025) == (410, 5, 409, 2, 205, 2, 1)
+    # 10 workgroups along the hypotheses: 204 runs aimed at
+    assert grid(204, 1, 2305) == (204, 10, 204, 1, 204, 1, 1)
+    assert grid(205, 1, 2305) == (205, 10, 204, 2, 103, 1, 1)
+    assert grid(409, 2, 2305) == (205, 10, 204, 2, 103, 1, 1)          # ... whose one segment has one step
+    assert grid(408, 1, 2305) == (408, 10, 204, 2, 204, 2, 1)
+    assert grid(409, 1, 2305) == (409, 10, 204, 3, 137, 1, 1)          # runs of 3, the last ragged
+    # 65 and 256 partial keys for identify_best_kernel's 64 lanes; the limits K = 65 536, S K = 2^22
+    assert grid(5, 2, 16384) == (3, 64, 3, 1, 3, 1, 1) and grid(5, 2, 16385) == (3, 65, 3, 1, 3, 1, 1)
+    assert grid(64, 1, 16384) == (64, 64, 32, 2, 32, 2, 1)
+    assert grid(64, 1, 65536) == (64, 256, 8, 8, 8, 8, 1)
+    assert grid(64, 1, 1024) == (64, 4, 64, 1, 64, 1, 1)
+    assert grid(63, 1, 65536) == (63, 256, 8, 8, 8, 7, 1) and grid(57, 1, 65536) == (57, 256, 8, 8, 8, 1, 1)
+    assert grid(512, 1, 8192) == (512, 32, 64, 8, 64, 8, 1)
+
+    # it refuses what acmpc_score_grips refuses of a shape, with its codes
+    def code(e, *shape):
+        with pytest.raises(EngineError) as refused:
+            e.describe_score_grips(*shape)
+        return refused.value.code
+
+    assert code(engine(_capi.MODE_TEMPORAL), 4, 1, 1) == _capi.ESTATE
+    assert code(engine(), 4, 1, 1) == _capi.ESTATE                        # mode D without a vehicle
+    for shape in ((0, 1, 1), (513, 1, 1), (4, 0, 1), (4, -1, 1), (4, 5, 1), (4, 1, 0)):
+        assert code(eng, *shape) == _capi.EINVAL, shape
+    for shape in ((4, 1, 65537), (512, 1, 8193), (65, 1, 65536)):
+        assert code(eng, *shape) == _capi.ECAPACITY, shape
+    lib = _capi.load_library()
+    assert lib.acmpc_describe_score_grips(eng._ctx, 4, 1, 1, None) == _capi.EINVAL
+    assert lib.acmpc_describe_score_grips(None, 4, 1, 1, None) == _capi.EINVAL
     eng.close()
 
 
