@@ -82,6 +82,163 @@ __global__ void __launch_bounds__(256) sample_kernel(const SampleArgs a) {
 // (The trace is addressed off `s_fused` itself, not through a pointer that may be null: a select of pointers would lose
 // the LDS address space.)
 constexpr int kStagedSteps = 128;   // steps whose uniform operands travel through registers (longer horizons: the rest by a loop)
+constexpr int kStagedPairs = (kStagedSteps + kWave - 1) / kWave;   // (v, kappa) pairs per lane
+
+// ---- what the four forms of a sampled round share -----------------------------------------------------------
+// The forms (one wave below; two, four and three waves further down) differ in how a step is shared out over waves.  The
+// control side of it is one thing in all of them: StagedControls brings the wave-uniform control operands into LDS,
+// CandidateControls reads them back per lane and blends, publish_traced_round ends a traced round.  The two-, four- and
+// three-wave forms use all three.  The single-wave body keeps its own lines for the same rules: with the helpers its traced
+// round at n = 118 measured 29.36 us against the parent's 28.72, outside the parent's 0.32 us spread (LABNOTES).
+
+// Centre, reference, candidate 2's controls and knot weights of every step on their way into LDS, by the lanes of ONE wave,
+// in phases that the wave interleaves with its Philox draws: a request's round trip to memory is what the draws that follow
+// it cover, so the requests precede the draws.
+struct StagedControls {
+  const float* centre;
+  const float* ref;           // null: no reference controls (the centre stands in for them)
+  const float* extra;         // null: this launch holds no candidate 2
+  const float* knot_weight;   // (knot, weight) pairs: the weight is [1]
+  bool chained;               // wave-uniform: the centre is the previous launch's winner
+  f32x2 g_centre[kStagedPairs], g_ref[kStagedPairs], g_extra[kStagedPairs], g_weight[kStagedPairs];
+  int64_t prev_key[kChainBlocks / kWave];
+
+  // the loads that depend on nothing: the first kStagedSteps steps' operands, clamped at the last step, and - chained - the
+  // previous launch's partial keys, four per lane
+  __device__ __forceinline__ void request(const RolloutArgs& a, const SampleArgs& smp, const int p, const int lane, const int n) {
+    centre = smp.centre + static_cast<size_t>(p) * smp.centre_stride;
+    ref = (smp.u_ref != nullptr) ? smp.u_ref + static_cast<size_t>(p) * n * 2 : nullptr;
+    extra = holds_candidate_2(a, smp) ? smp.u_extra + static_cast<size_t>(p) * n * 2 : nullptr;
+    knot_weight = smp.spec.segments;
+    chained = smp.prev_keys != nullptr;
+#pragma unroll
+    for (int q = 0; q < kStagedPairs; ++q) {
+      const int j = min(lane + q * kWave, n - 1);
+      if (!chained) g_centre[q] = reinterpret_cast<const f32x2*>(centre)[j];
+      if (ref != nullptr) g_ref[q] = reinterpret_cast<const f32x2*>(ref)[j];
+      if (extra != nullptr) g_extra[q] = reinterpret_cast<const f32x2*>(extra)[j];
+      g_weight[q] = reinterpret_cast<const f32x2*>(knot_weight)[j];
+    }
+    if (chained) {
+#pragma unroll
+      for (int q = 0; q < kChainBlocks / kWave; ++q)
+        prev_key[q] = smp.prev_keys[static_cast<size_t>(p) * smp.prev_blocks + min(lane + q * kWave, smp.prev_blocks - 1)];
+    }
+  }
+
+  // chained rounds: the previous round's winner is the argmin over its workgroups' keys, and its controls head that
+  // workgroup's trace (workgroup b rolled the candidates b * 64 ..: the winner's workgroup follows from its index); the
+  // request for THEM is the second round trip
+  __device__ __forceinline__ void follow_chain(const RolloutArgs& a, const SampleArgs& smp, const int p, const int lane, const int n) {
+    if (!chained) return;
+    int64_t best = kKeyMax;
+#pragma unroll
+    for (int q = 0; q < kChainBlocks / kWave; ++q) {
+      const int64_t kb = (lane + q * kWave < smp.prev_blocks) ? prev_key[q] : kKeyMax;
+      best = (kb < best) ? kb : best;
+    }
+    const int64_t winner = wave_min_key(best);
+    const int block = static_cast<int>(static_cast<int64_t>(static_cast<uint32_t>(winner & 0xffffffffLL)) - a.index_offset) / kWave;
+    centre = smp.prev_trace + (static_cast<size_t>(p) * smp.prev_blocks + block) * smp.prev_pitch;
+#pragma unroll
+    for (int q = 0; q < kStagedPairs; ++q) g_centre[q] = reinterpret_cast<const f32x2*>(centre)[min(lane + q * kWave, n - 1)];
+  }
+
+  // registers -> LDS: [n][2] centre | [n][2] reference (or the centre again) | [n][2] candidate 2's, when given | [n] weights
+  __device__ __forceinline__ void store(const int lane, const int n, float* s_centre, float* s_ref, float* s_extra,
+                                        float* s_weight) const {
+#pragma unroll
+    for (int q = 0; q < kStagedPairs; ++q) {
+      const int j = lane + q * kWave;
+      if (j < n) {
+        reinterpret_cast<f32x2*>(s_centre)[j] = g_centre[q];
+        reinterpret_cast<f32x2*>(s_ref)[j] = (ref != nullptr) ? g_ref[q] : g_centre[q];
+        if (extra != nullptr) reinterpret_cast<f32x2*>(s_extra)[j] = g_extra[q];
+        s_weight[j] = g_weight[q][1];
+      }
+    }
+  }
+
+  // horizons beyond the registers' share: plain copies (one more round trip)
+  __device__ __forceinline__ void store_beyond(const int lane, const int n, float* s_centre, float* s_ref, float* s_extra,
+                                               float* s_weight) const {
+    for (int j = lane + kStagedPairs * kWave; j < n; j += kWave) {
+      const f32x2 cj = reinterpret_cast<const f32x2*>(centre)[j];
+      reinterpret_cast<f32x2*>(s_centre)[j] = cj;
+      reinterpret_cast<f32x2*>(s_ref)[j] = (ref != nullptr) ? reinterpret_cast<const f32x2*>(ref)[j] : cj;
+      if (extra != nullptr) reinterpret_cast<f32x2*>(s_extra)[j] = reinterpret_cast<const f32x2*>(extra)[j];
+      s_weight[j] = knot_weight[2 * j + 1];
+    }
+  }
+};
+
+// Which controls a lane blends its noise round, out of what StagedControls left in LDS.  Candidate 1 = the reference
+// controls, candidate 2 = `u_extra` (the LQ plan), each when given: amplitude 0, own centre; every other candidate the centre.
+struct CandidateControls {
+  struct Step {
+    f32x2 centre, ref;
+    float weight;
+  };
+  const f32x2* s_centre;
+  const f32x2* s_alt;   // (per lane)
+  const float* s_weight;
+  bool use_ref;
+  float amp;
+
+  __device__ __forceinline__ CandidateControls(const uint32_t gidx, const SampleArgs& smp, const float* centre, const float* ref,
+                                               const float* extra, const float* weight)
+      : s_centre(reinterpret_cast<const f32x2*>(centre)), s_weight(weight) {
+    const bool use_extra = (gidx == 2u) && (smp.u_extra != nullptr);
+    use_ref = ((gidx == 1u) && (smp.u_ref != nullptr)) || use_extra;
+    s_alt = reinterpret_cast<const f32x2*>(use_extra ? extra : ref);
+    amp = use_ref ? 0.0f : candidate_amplitude(gidx);
+  }
+  // Step i's operands, asked for ahead of the arithmetic.  (The requests behind the last step - one step past the end,
+  // two in the form that strides by two - read inside the block, the next array or the padding, and are never used.)
+  __device__ __forceinline__ Step at(const int i) const { return Step{s_centre[i], s_alt[i], s_weight[i]}; }
+  __device__ __forceinline__ void blend(const SampleSpec& sp, const Step& now, const float (&z)[kKnots][2], const int knot,
+                                        float& v, float& k) const {
+    const float cv = use_ref ? now.ref[0] : now.centre[0];
+    const float ck = use_ref ? now.ref[1] : now.centre[1];
+    blend_control(sp, amp, now.weight, cv, ck, z[knot][0], z[knot][1], z[knot + 1][0], z[knot + 1][1], v, k);
+  }
+};
+
+// The end of a traced round, by the wave that holds the candidates' costs (the only one left of its workgroup): V and cost
+// into rows 5n, 5n + 1 of the lane's trace column, the workgroup's best key and feasible count, and the best lane's column
+// copied to this workgroup's slot of `fused.trace`.  SHIFT: the X and Y rows (2n + 3i, 2n + 3i + 1) were exchanged in the
+// path's own frame - start_temporal() - and leave in the caller's, by the same add as in every other form.
+template <bool SHIFT>
+__device__ __forceinline__ void publish_traced_round(const RolloutArgs& a, const FusedFinalize& fused, float* s_trace,
+                                                     const int p, const int lane, const int c, const float V, const float cost,
+                                                     const float ox = 0.0f, const float oy = 0.0f) {
+  const int n = a.n;
+  const bool active = c < a.N;
+  s_trace[(5 * n) * kWave + lane] = V;
+  s_trace[(5 * n + 1) * kWave + lane] = cost;
+  if (active && a.costs != nullptr) a.costs[static_cast<size_t>(p) * a.N + c] = cost;
+  const int64_t own_key = active ? pack_key(cost, static_cast<uint32_t>(a.index_offset + c)) : kKeyMax;
+  int best_lane;
+  const int64_t key = wave_min_key_by_lane(own_key, best_lane);   // (the index rises with the lane)
+  const int nfeas = wave_sum_int((active && V == 0.0f) ? 1 : 0);
+  __syncthreads();   // this wave alone by now: orders its column writes before the row reads
+  const size_t slot = static_cast<size_t>(p) * gridDim.x + blockIdx.x;
+  float* trace_out = fused.trace + slot * fused.trace_pitch;
+  for (int e = lane; e < 5 * n + 2; e += kWave) {
+    const float value = s_trace[e * kWave + best_lane];
+    if constexpr (SHIFT) {
+      const int k = e - 2 * n;
+      const bool is_x = k >= 0 && k < 3 * n && k % 3 == 0, is_y = k >= 0 && k < 3 * n && k % 3 == 1;
+      publish(&trace_out[e], is_x ? value + ox : is_y ? value + oy : value);
+    } else {
+      publish(&trace_out[e], value);
+    }
+  }
+  if (lane == 0) {
+    publish(&a.partial_keys[slot], key);
+    publish(&a.partial_feas[slot], nfeas);
+  }
+}
 
 template <int MODE>
 __device__ __forceinline__ void rollout_sampled_body(const RolloutArgs& a, const SampleArgs& smp, float* s_fused,
@@ -1067,96 +1224,32 @@ __global__ void __launch_bounds__(2 * kWave) rollout_sampled_pair_kernel(const R
   float* s_exchange = s_fused + exchange_lds_floats + lane;   // [buffer][step of the chunk][v | kappa][lane]
   constexpr int kStepFloats = kPairValues * kWave, kBufferFloats = kPairChunk * kStepFloats;
   const int c = blockIdx.x * kWave + lane;
-  const bool active = c < a.N;
   const Weights w = a.w;
 
   if (!consumer) {
     // ---- producer: requests, draws, the uniform operands of ITS half into LDS, then the controls chunk by chunk ----
     const SampleSpec sp = smp.spec;
-    const float* __restrict__ centre = smp.centre + static_cast<size_t>(p) * smp.centre_stride;
-    const float* __restrict__ ref = (smp.u_ref != nullptr) ? smp.u_ref + static_cast<size_t>(p) * n * 2 : nullptr;
-    const float* __restrict__ extra = holds_candidate_2(a, smp) ? smp.u_extra + static_cast<size_t>(p) * n * 2 : nullptr;
-    const float* __restrict__ knot_weight = sp.segments;
-    const bool chained = smp.prev_keys != nullptr;
-    constexpr int kPairs = (kStagedSteps + kWave - 1) / kWave;
-    f32x2 g_centre[kPairs], g_ref[kPairs], g_extra[kPairs], g_weight[kPairs];
-#pragma unroll
-    for (int q = 0; q < kPairs; ++q) {
-      const int j = min(lane + q * kWave, n - 1);
-      if (!chained) g_centre[q] = reinterpret_cast<const f32x2*>(centre)[j];
-      if (ref != nullptr) g_ref[q] = reinterpret_cast<const f32x2*>(ref)[j];
-      if (extra != nullptr) g_extra[q] = reinterpret_cast<const f32x2*>(extra)[j];
-      g_weight[q] = reinterpret_cast<const f32x2*>(knot_weight)[j];
-    }
-    int64_t prev_key[kChainBlocks / kWave];
-    if (chained) {
-#pragma unroll
-      for (int q = 0; q < kChainBlocks / kWave; ++q)
-        prev_key[q] = smp.prev_keys[static_cast<size_t>(p) * smp.prev_blocks + min(lane + q * kWave, smp.prev_blocks - 1)];
-    }
+    StagedControls staged;
+    staged.request(a, smp, p, lane, n);
     float z[kKnots][2] = {};
     const uint32_t gidx = static_cast<uint32_t>(a.index_offset + c);
     draw_normals<0, kKnots / 4>(sp, gidx, static_cast<uint32_t>(p), z);
-    if (chained) {
-      int64_t best = kKeyMax;
-#pragma unroll
-      for (int q = 0; q < kChainBlocks / kWave; ++q) {
-        const int64_t kb = (lane + q * kWave < smp.prev_blocks) ? prev_key[q] : kKeyMax;
-        best = (kb < best) ? kb : best;
-      }
-      const int64_t winner = wave_min_key(best);
-      const int block = static_cast<int>(static_cast<int64_t>(static_cast<uint32_t>(winner & 0xffffffffLL)) - a.index_offset) / kWave;
-      centre = smp.prev_trace + (static_cast<size_t>(p) * smp.prev_blocks + block) * smp.prev_pitch;
-#pragma unroll
-      for (int q = 0; q < kPairs; ++q) g_centre[q] = reinterpret_cast<const f32x2*>(centre)[min(lane + q * kWave, n - 1)];
-    }
+    staged.follow_chain(a, smp, p, lane, n);
     draw_normals<kKnots / 4, kKnots / 2>(sp, gidx, static_cast<uint32_t>(p), z);
-#pragma unroll
-    for (int q = 0; q < kPairs; ++q) {
-      const int j = lane + q * kWave;
-      if (j < n) {
-        reinterpret_cast<f32x2*>(s_centre)[j] = g_centre[q];
-        reinterpret_cast<f32x2*>(s_ref)[j] = (ref != nullptr) ? g_ref[q] : g_centre[q];
-        if (extra != nullptr) reinterpret_cast<f32x2*>(s_extra)[j] = g_extra[q];
-        s_weight[j] = g_weight[q][1];
-      }
-    }
-    for (int j = lane + kPairs * kWave; j < n; j += kWave) {   // horizons beyond the registers' share
-      const f32x2 cj = reinterpret_cast<const f32x2*>(centre)[j];
-      reinterpret_cast<f32x2*>(s_centre)[j] = cj;
-      reinterpret_cast<f32x2*>(s_ref)[j] = (ref != nullptr) ? reinterpret_cast<const f32x2*>(ref)[j] : cj;
-      if (extra != nullptr) reinterpret_cast<f32x2*>(s_extra)[j] = reinterpret_cast<const f32x2*>(extra)[j];
-      s_weight[j] = knot_weight[2 * j + 1];
-    }
+    staged.store(lane, n, s_centre, s_ref, s_extra, s_weight);
+    staged.store_beyond(lane, n, s_centre, s_ref, s_extra, s_weight);
     __syncthreads();   // (0) the consumer has put the table rows in, this wave the rest
-    // candidate 1 = the reference controls, candidate 2 = `u_extra` (the LQ plan), each when given: amplitude 0, own centre
-    const bool use_extra = (gidx == 2u) && (smp.u_extra != nullptr);
-    const bool use_ref = ((gidx == 1u) && (smp.u_ref != nullptr)) || use_extra;
-    const f32x2* s_alt = reinterpret_cast<const f32x2*>(use_extra ? s_extra : s_ref);   // (per lane)
-    const float amp = use_ref ? 0.0f : candidate_amplitude(gidx);
-    struct Operands {
-      f32x2 centre, ref;
-      float weight;
-    };
-    auto request = [&](int i) {   // (one step past the end is read - inside the block - and never used)
-      Operands o;
-      o.centre = reinterpret_cast<const f32x2*>(s_centre)[i];
-      o.ref = s_alt[i];
-      o.weight = s_weight[i];
-      return o;
-    };
-    Operands now = request(sp.knot_begin[0]);
+    const CandidateControls controls(gidx, smp, s_centre, s_ref, s_extra, s_weight);
+    CandidateControls::Step now = controls.at(sp.knot_begin[0]);
     float* out = s_exchange;          // slot of the step being produced
     float* u_out = s_trace + lane;    // its place in the trace (rows 2i, 2i + 1)
     int in_chunk = 0, buffer = 0;
 #pragma unroll
     for (int knot = 0; knot < kKnots - 1; ++knot) {
       for (int i = sp.knot_begin[knot]; i < sp.knot_begin[knot + 1]; ++i) {
-        const Operands next = request(i + 1);
+        const CandidateControls::Step next = controls.at(i + 1);
         float v, k;
-        const float cv = use_ref ? now.ref[0] : now.centre[0];
-        const float ck = use_ref ? now.ref[1] : now.centre[1];
-        blend_control(sp, amp, now.weight, cv, ck, z[knot][0], z[knot][1], z[knot + 1][0], z[knot + 1][1], v, k);
+        controls.blend(sp, now, z, knot, v, k);
         out[0] = v;
         out[kWave] = k;
         u_out[0] = v;
@@ -1219,25 +1312,7 @@ __global__ void __launch_bounds__(2 * kWave) rollout_sampled_pair_kernel(const R
       for (int j = 0; first + j < n; ++j) advance(first + j, inputs_of(in + j * kStepFloats, first + j));
     }
   }
-  const float cost = finish_spatial<float>(st, w);
-  s_trace[(5 * n) * kWave + lane] = st.V;
-  s_trace[(5 * n + 1) * kWave + lane] = cost;
-  if (active && a.costs != nullptr) a.costs[static_cast<size_t>(p) * a.N + c] = cost;
-  const int64_t own_key = active ? pack_key(cost, static_cast<uint32_t>(a.index_offset + c)) : kKeyMax;
-  int nfeas = (active && st.V == 0.0f) ? 1 : 0;
-  int best_lane;
-  const int64_t key = wave_min_key_by_lane(own_key, best_lane);   // (the index rises with the lane)
-  nfeas = wave_sum_int(nfeas);
-  {
-    __syncthreads();   // this wave alone by now: orders its column writes before the row reads
-    float* trace_out = fused.trace + (static_cast<size_t>(p) * gridDim.x + blockIdx.x) * fused.trace_pitch;
-    for (int e = lane; e < 5 * n + 2; e += kWave) publish(&trace_out[e], s_trace[e * kWave + best_lane]);
-  }
-  if (lane == 0) {
-    const size_t slot = static_cast<size_t>(p) * gridDim.x + blockIdx.x;
-    publish(&a.partial_keys[slot], key);
-    publish(&a.partial_feas[slot], nfeas);
-  }
+  publish_traced_round<false>(a, fused, s_trace, p, lane, c, st.V, finish_spatial<float>(st, w));
   fused_tail<0>(a, smp, fused, true, nullptr);
 }
 
@@ -1281,7 +1356,6 @@ __global__ void __launch_bounds__(kQuadWaves * kWave) rollout_sampled_quad_kerne
   float* s_z = s_fused + normals_lds_floats;          // [knot][component][lane]
   float* s_j = s_z + 2 * kKnots * kWave;
   const int c = blockIdx.x * kWave + lane;
-  const bool active = c < a.N;
   const Weights w = a.w;
   const SampleSpec sp = smp.spec;
   const uint32_t gidx = static_cast<uint32_t>(a.index_offset + c);
@@ -1305,34 +1379,18 @@ __global__ void __launch_bounds__(kQuadWaves * kWave) rollout_sampled_quad_kerne
   // the controls of the steps i = parity, parity + 2, ... (every step with one control wave's worth of work halved): blend,
   // leave (v, kappa) in the trace; one barrier per chunk, taken by both control waves
   auto produce_controls = [&](const float (&z)[kKnots][2], const int parity) {
-    // candidate 1 = the reference controls, candidate 2 = `u_extra` (the LQ plan), each when given: amplitude 0, own centre
-    const bool use_extra = (gidx == 2u) && (smp.u_extra != nullptr);
-    const bool use_ref = ((gidx == 1u) && (smp.u_ref != nullptr)) || use_extra;
-    const f32x2* s_alt = reinterpret_cast<const f32x2*>(use_extra ? s_extra : s_ref);   // (per lane)
-    const float amp = use_ref ? 0.0f : candidate_amplitude(gidx);
-    struct Operands {
-      f32x2 centre, ref;
-      float weight;
-    };
-    auto request = [&](int i) {   // (up to two steps past the end are read - inside the block's padding - and never used)
-      Operands o;
-      o.centre = reinterpret_cast<const f32x2*>(s_centre)[i];
-      o.ref = s_alt[i];
-      o.weight = s_weight[i];
-      return o;
-    };
+    const CandidateControls controls(gidx, smp, s_centre, s_ref, s_extra, s_weight);
     // (Broadcasting the operands out of the registers they were fetched into with v_readlane, instead of reading them
     // back from LDS one step ahead: 187 ns per step against 144 - measured, not kept.)
-    Operands now = request(parity);
+    CandidateControls::Step now = controls.at(parity);
     int in_chunk = 0;
 #pragma unroll
     for (int knot = 0; knot < kKnots - 1; ++knot) {
       for (int i = sp.knot_begin[knot]; i < sp.knot_begin[knot + 1]; ++i) {
         if ((i & 1) == parity) {   // (wave-uniform)
-          const Operands next = request(i + 2);   // one own step ahead of the arithmetic
+          const CandidateControls::Step next = controls.at(i + 2);   // one own step ahead of the arithmetic
           float v, k;
-          blend_control(sp, amp, now.weight, use_ref ? now.ref[0] : now.centre[0], use_ref ? now.ref[1] : now.centre[1],
-                        z[knot][0], z[knot][1], z[knot + 1][0], z[knot + 1][1], v, k);
+          controls.blend(sp, now, z, knot, v, k);
           col[(2 * i) * kWave] = v;
           col[(2 * i + 1) * kWave] = k;
           now = next;
@@ -1360,58 +1418,12 @@ __global__ void __launch_bounds__(kQuadWaves * kWave) rollout_sampled_quad_kerne
   }
   if (wave == 2) {
     // ---- controls: requests, its quarter of the draws, the uniform operands of the control waves into LDS, then chunk by chunk ----
-    const float* __restrict__ centre = smp.centre + static_cast<size_t>(p) * smp.centre_stride;
-    const float* __restrict__ ref = (smp.u_ref != nullptr) ? smp.u_ref + static_cast<size_t>(p) * n * 2 : nullptr;
-    const float* __restrict__ extra = holds_candidate_2(a, smp) ? smp.u_extra + static_cast<size_t>(p) * n * 2 : nullptr;
-    const float* __restrict__ knot_weight = sp.segments;
-    const bool chained = smp.prev_keys != nullptr;
-    constexpr int kPairs = (kStagedSteps + kWave - 1) / kWave;
-    f32x2 g_centre[kPairs], g_ref[kPairs], g_extra[kPairs], g_weight[kPairs];
-#pragma unroll
-    for (int q = 0; q < kPairs; ++q) {
-      const int j = min(lane + q * kWave, n - 1);
-      if (!chained) g_centre[q] = reinterpret_cast<const f32x2*>(centre)[j];
-      if (ref != nullptr) g_ref[q] = reinterpret_cast<const f32x2*>(ref)[j];
-      if (extra != nullptr) g_extra[q] = reinterpret_cast<const f32x2*>(extra)[j];
-      g_weight[q] = reinterpret_cast<const f32x2*>(knot_weight)[j];
-    }
-    int64_t prev_key[kChainBlocks / kWave];
-    if (chained) {
-#pragma unroll
-      for (int q = 0; q < kChainBlocks / kWave; ++q)
-        prev_key[q] = smp.prev_keys[static_cast<size_t>(p) * smp.prev_blocks + min(lane + q * kWave, smp.prev_blocks - 1)];
-    }
+    StagedControls staged;
+    staged.request(a, smp, p, lane, n);
     draw_quarter(std::integral_constant<int, 2>{});
-    if (chained) {
-      int64_t best = kKeyMax;
-#pragma unroll
-      for (int q = 0; q < kChainBlocks / kWave; ++q) {
-        const int64_t kb = (lane + q * kWave < smp.prev_blocks) ? prev_key[q] : kKeyMax;
-        best = (kb < best) ? kb : best;
-      }
-      const int64_t winner = wave_min_key(best);
-      const int block = static_cast<int>(static_cast<int64_t>(static_cast<uint32_t>(winner & 0xffffffffLL)) - a.index_offset) / kWave;
-      centre = smp.prev_trace + (static_cast<size_t>(p) * smp.prev_blocks + block) * smp.prev_pitch;
-#pragma unroll
-      for (int q = 0; q < kPairs; ++q) g_centre[q] = reinterpret_cast<const f32x2*>(centre)[min(lane + q * kWave, n - 1)];
-    }
-#pragma unroll
-    for (int q = 0; q < kPairs; ++q) {
-      const int j = lane + q * kWave;
-      if (j < n) {
-        reinterpret_cast<f32x2*>(s_centre)[j] = g_centre[q];
-        reinterpret_cast<f32x2*>(s_ref)[j] = (ref != nullptr) ? g_ref[q] : g_centre[q];
-        if (extra != nullptr) reinterpret_cast<f32x2*>(s_extra)[j] = g_extra[q];
-        s_weight[j] = g_weight[q][1];
-      }
-    }
-    for (int j = lane + kPairs * kWave; j < n; j += kWave) {   // horizons beyond the registers' share
-      const f32x2 cj = reinterpret_cast<const f32x2*>(centre)[j];
-      reinterpret_cast<f32x2*>(s_centre)[j] = cj;
-      reinterpret_cast<f32x2*>(s_ref)[j] = (ref != nullptr) ? reinterpret_cast<const f32x2*>(ref)[j] : cj;
-      if (extra != nullptr) reinterpret_cast<f32x2*>(s_extra)[j] = reinterpret_cast<const f32x2*>(extra)[j];
-      s_weight[j] = knot_weight[2 * j + 1];
-    }
+    staged.follow_chain(a, smp, p, lane, n);
+    staged.store(lane, n, s_centre, s_ref, s_extra, s_weight);
+    staged.store_beyond(lane, n, s_centre, s_ref, s_extra, s_weight);
     __syncthreads();   // (S) every wave's normals and the table rows are in
     float z[kKnots][2];
 #pragma unroll
@@ -1510,24 +1522,8 @@ __global__ void __launch_bounds__(kQuadWaves * kWave) rollout_sampled_quad_kerne
     st.t = col[(2 * n + 3 * (n - 1) + 2) * kWave];
   }
   st.J = s_j[lane];
-  const float cost = finish_spatial<float>(st, w);   // (st.ey / ep / t: the state after the last step)
-  s_trace[(5 * n) * kWave + lane] = st.V;
-  s_trace[(5 * n + 1) * kWave + lane] = cost;
-  if (active && a.costs != nullptr) a.costs[static_cast<size_t>(p) * a.N + c] = cost;
-  const int64_t own_key = active ? pack_key(cost, static_cast<uint32_t>(a.index_offset + c)) : kKeyMax;
-  int best_lane;
-  const int64_t key = wave_min_key_by_lane(own_key, best_lane);   // (the index rises with the lane)
-  const int nfeas = wave_sum_int((active && st.V == 0.0f) ? 1 : 0);
-  {
-    __syncthreads();   // this wave alone by now: orders its column writes before the row reads
-    float* trace_out = fused.trace + (static_cast<size_t>(p) * gridDim.x + blockIdx.x) * fused.trace_pitch;
-    for (int e = lane; e < 5 * n + 2; e += kWave) publish(&trace_out[e], s_trace[e * kWave + best_lane]);
-  }
-  if (lane == 0) {
-    const size_t slot = static_cast<size_t>(p) * gridDim.x + blockIdx.x;
-    publish(&a.partial_keys[slot], key);
-    publish(&a.partial_feas[slot], nfeas);
-  }
+  // (st.ey / ep / t: the state after the last step)
+  publish_traced_round<false>(a, fused, s_trace, p, lane, c, st.V, finish_spatial<float>(st, w));
   fused_tail<0>(a, smp, fused, true, nullptr);
 }
 
@@ -1575,7 +1571,6 @@ __global__ void __launch_bounds__(3 * kWave) rollout_sampled_trio_kernel(const R
   // trace at the mapping controller's horizon of 100 once the key table grew to 32 bytes per waypoint)
   unsigned short* s_index = reinterpret_cast<unsigned short*>(s_fused + index_lds_floats);
   const int c = blockIdx.x * kWave + lane;
-  const bool active = c < a.N;
   const float* __restrict__ coef = a.coef + static_cast<size_t>(p) * n * kCoefT;
   const float* __restrict__ x0 = a.x0 + p * 3;
   const int chunks = (n + kTrioChunk - 1) / kTrioChunk;
@@ -1584,90 +1579,28 @@ __global__ void __launch_bounds__(3 * kWave) rollout_sampled_trio_kernel(const R
   if (wave == 2) {
     // ---- poses: requests, draws, uniform operands into LDS, then controls and poses chunk by chunk ----
     const SampleSpec sp = smp.spec;
-    const float* __restrict__ centre = smp.centre + static_cast<size_t>(p) * smp.centre_stride;
-    const float* __restrict__ ref = (smp.u_ref != nullptr) ? smp.u_ref + static_cast<size_t>(p) * n * 2 : nullptr;
-    const float* __restrict__ extra = holds_candidate_2(a, smp) ? smp.u_extra + static_cast<size_t>(p) * n * 2 : nullptr;
-    const float* __restrict__ knot_weight = sp.segments;
-    const bool chained = smp.prev_keys != nullptr;
-    constexpr int kPairs = (kStagedSteps + kWave - 1) / kWave;
-    f32x2 g_centre[kPairs], g_ref[kPairs], g_extra[kPairs], g_weight[kPairs];
-#pragma unroll
-    for (int q = 0; q < kPairs; ++q) {
-      const int j = min(lane + q * kWave, n - 1);
-      if (!chained) g_centre[q] = reinterpret_cast<const f32x2*>(centre)[j];
-      if (ref != nullptr) g_ref[q] = reinterpret_cast<const f32x2*>(ref)[j];
-      if (extra != nullptr) g_extra[q] = reinterpret_cast<const f32x2*>(extra)[j];
-      g_weight[q] = reinterpret_cast<const f32x2*>(knot_weight)[j];
-    }
-    int64_t prev_key[kChainBlocks / kWave];
-    if (chained) {
-#pragma unroll
-      for (int q = 0; q < kChainBlocks / kWave; ++q)
-        prev_key[q] = smp.prev_keys[static_cast<size_t>(p) * smp.prev_blocks + min(lane + q * kWave, smp.prev_blocks - 1)];
-    }
+    StagedControls staged;
+    staged.request(a, smp, p, lane, n);
     float z[kKnots][2] = {};
     const uint32_t gidx = static_cast<uint32_t>(a.index_offset + c);
     draw_normals<0, kKnots / 4>(sp, gidx, static_cast<uint32_t>(p), z);
-    if (chained) {
-      int64_t best = kKeyMax;
-#pragma unroll
-      for (int q = 0; q < kChainBlocks / kWave; ++q) {
-        const int64_t kb = (lane + q * kWave < smp.prev_blocks) ? prev_key[q] : kKeyMax;
-        best = (kb < best) ? kb : best;
-      }
-      const int64_t winner = wave_min_key(best);
-      const int block = static_cast<int>(static_cast<int64_t>(static_cast<uint32_t>(winner & 0xffffffffLL)) - a.index_offset) / kWave;
-      centre = smp.prev_trace + (static_cast<size_t>(p) * smp.prev_blocks + block) * smp.prev_pitch;
-#pragma unroll
-      for (int q = 0; q < kPairs; ++q) g_centre[q] = reinterpret_cast<const f32x2*>(centre)[min(lane + q * kWave, n - 1)];
-    }
+    staged.follow_chain(a, smp, p, lane, n);
     draw_normals<kKnots / 4, kKnots / 2>(sp, gidx, static_cast<uint32_t>(p), z);
-#pragma unroll
-    for (int q = 0; q < kPairs; ++q) {
-      const int j = lane + q * kWave;
-      if (j < n) {
-        reinterpret_cast<f32x2*>(s_centre)[j] = g_centre[q];
-        reinterpret_cast<f32x2*>(s_ref)[j] = (ref != nullptr) ? g_ref[q] : g_centre[q];
-        if (extra != nullptr) reinterpret_cast<f32x2*>(s_extra)[j] = g_extra[q];
-        s_weight[j] = g_weight[q][1];
-      }
-    }
-    for (int j = lane + kPairs * kWave; j < n; j += kWave) {   // horizons beyond the registers' share
-      const f32x2 cj = reinterpret_cast<const f32x2*>(centre)[j];
-      reinterpret_cast<f32x2*>(s_centre)[j] = cj;
-      reinterpret_cast<f32x2*>(s_ref)[j] = (ref != nullptr) ? reinterpret_cast<const f32x2*>(ref)[j] : cj;
-      if (extra != nullptr) reinterpret_cast<f32x2*>(s_extra)[j] = reinterpret_cast<const f32x2*>(extra)[j];
-      s_weight[j] = knot_weight[2 * j + 1];
-    }
+    staged.store(lane, n, s_centre, s_ref, s_extra, s_weight);
+    staged.store_beyond(lane, n, s_centre, s_ref, s_extra, s_weight);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // this wave reads what its own lanes staged
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // candidate 1 = the reference controls, candidate 2 = `u_extra` (the LQ plan), each when given: amplitude 0, own centre
-    const bool use_extra = (gidx == 2u) && (smp.u_extra != nullptr);
-    const bool use_ref = ((gidx == 1u) && (smp.u_ref != nullptr)) || use_extra;
-    const f32x2* s_alt = reinterpret_cast<const f32x2*>(use_extra ? s_extra : s_ref);   // (per lane)
-    const float amp = use_ref ? 0.0f : candidate_amplitude(gidx);
+    const CandidateControls controls(gidx, smp, s_centre, s_ref, s_extra, s_weight);
     StateT pose = start_temporal<float>(x0, coef);
-    struct Operands {
-      f32x2 centre, ref;
-      float weight;
-    };
-    auto request = [&](int i) {   // (one step past the end is read - inside the block - and never used)
-      Operands o;
-      o.centre = reinterpret_cast<const f32x2*>(s_centre)[i];
-      o.ref = s_alt[i];
-      o.weight = s_weight[i];
-      return o;
-    };
-    Operands now = request(sp.knot_begin[0]);
+    CandidateControls::Step now = controls.at(sp.knot_begin[0]);
     int in_chunk = 0;
 #pragma unroll
     for (int knot = 0; knot < kKnots - 1; ++knot) {
       for (int i = sp.knot_begin[knot]; i < sp.knot_begin[knot + 1]; ++i) {
-        const Operands next = request(i + 1);
+        const CandidateControls::Step next = controls.at(i + 1);
         float v, k;
-        blend_control(sp, amp, now.weight, use_ref ? now.ref[0] : now.centre[0], use_ref ? now.ref[1] : now.centre[1],
-                      z[knot][0], z[knot][1], z[knot + 1][0], z[knot + 1][1], v, k);
+        controls.blend(sp, now, z, knot, v, k);
         now = next;
         temporal_advance<float>(pose, v, k, w);
         col[(2 * i) * kWave] = v;
@@ -1747,32 +1680,7 @@ __global__ void __launch_bounds__(3 * kWave) rollout_sampled_trio_kernel(const R
     }
     if (t <= chunks) __syncthreads();   // (the last chunk times have no partner left to wait for)
   }
-  const float cost = finish_temporal<float>(st, n, w);
-  s_trace[(5 * n) * kWave + lane] = st.V;
-  s_trace[(5 * n + 1) * kWave + lane] = cost;
-  if (active && a.costs != nullptr) a.costs[static_cast<size_t>(p) * a.N + c] = cost;
-  const int64_t own_key = active ? pack_key(cost, static_cast<uint32_t>(a.index_offset + c)) : kKeyMax;
-  int best_lane;
-  const int64_t key = wave_min_key_by_lane(own_key, best_lane);   // (the index rises with the lane)
-  const int nfeas = wave_sum_int((active && st.V == 0.0f) ? 1 : 0);
-  {
-    __syncthreads();   // this wave alone by now: orders its column writes before the row reads
-    float* trace_out = fused.trace + (static_cast<size_t>(p) * gridDim.x + blockIdx.x) * fused.trace_pitch;
-    // (the waves exchanged the poses in the path's own frame - start_temporal() - and they leave in the caller's: rows
-    // 2n + 3i and 2n + 3i + 1 of the trace are X and Y after step i)
-    const float ox = coef[0], oy = coef[1];
-    for (int e = lane; e < 5 * n + 2; e += kWave) {
-      const int k = e - 2 * n;
-      const bool is_x = k >= 0 && k < 3 * n && k % 3 == 0, is_y = k >= 0 && k < 3 * n && k % 3 == 1;
-      const float value = s_trace[e * kWave + best_lane];
-      publish(&trace_out[e], is_x ? value + ox : is_y ? value + oy : value);   // (the same add as every other form's)
-    }
-  }
-  if (lane == 0) {
-    const size_t slot = static_cast<size_t>(p) * gridDim.x + blockIdx.x;
-    publish(&a.partial_keys[slot], key);
-    publish(&a.partial_feas[slot], nfeas);
-  }
+  publish_traced_round<true>(a, fused, s_trace, p, lane, c, st.V, finish_temporal<float>(st, n, w), coef[0], coef[1]);
   fused_tail<1>(a, smp, fused, true, nullptr);
 }
 
