@@ -21,6 +21,11 @@ MAX_VEHICLES = 8      # ACMPC_MAX_VEHICLES: vehicles in a mode D ensemble
 MAX_SUBSTEPS = 16     # ACMPC_MAX_SUBSTEPS: Euler sub-steps per control step of mode D
 MAX_LOG_STEPS = 512   # ACMPC_MAX_LOG_STEPS: control steps in the log of acmpc_score_grips
 MAX_GRIP_HYPOTHESES = 65536   # ACMPC_MAX_GRIP_HYPOTHESES
+TRACE_TERM_FLOATS = 22        # ACMPC_TRACE_TERM_FLOATS: floats per control step of acmpc_trace_plans' terms
+# name -> columns of a terms row (include/acmpc.h, acmpc_trace_plans): Engine.trace_plans exposes each as a view
+TRACE_TERMS = {"j": 0, "e_y": 1, "e_psi": 2, "dv": 3, "dk": 4, "box": slice(5, 7), "corridor": 7, "rate": slice(8, 10),
+               "slip": 10, "ceiling": 11, "obstacles": slice(12, 20), "V": 20, "E": 21}
+TRACE_HINGES = slice(5, 20)   # what a step squares into V, in this order
 ENSEMBLE_MEAN, ENSEMBLE_MAX = 0, 1
 ENSEMBLE_REDUCE = {"mean": ENSEMBLE_MEAN, "max": ENSEMBLE_MAX}
 LAYOUT_CANDIDATE_MAJOR, LAYOUT_STEP_MAJOR = 0, 1
@@ -173,6 +178,8 @@ SIGNATURES = {
     "acmpc_get_progress_table": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_score_grips": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
+    "acmpc_trace_plans": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "acmpc_get_coefficients": (C.c_int, [_CTX, C.c_int32, _F32P, C.c_int32]),
     "acmpc_set_coefficients": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_record_floats": (C.c_int32, [C.c_int32]),
@@ -637,6 +644,7 @@ class Engine:
             raise EngineError(rc, (self._lib.acmpc_last_error(None) or b"").decode())
         self.P = 0
         self.n = 0
+        self.K = 0   # mode D: vehicles of the handle (0: none set)
 
     # -- plumbing -----------------------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -681,6 +689,7 @@ class Engine:
         block = params.coefficients() if hasattr(params, "coefficients") else params
         block = np.ascontiguousarray(block, dtype=np.float64).ravel()
         self._check(self._lib.acmpc_set_dynamics(self._ctx, block.ctypes.data, block.size))
+        self.K = 1
 
     def set_dynamics_ensemble(self, vehicles, weights=None, reduce: str = "mean"):
         """Mode D's ensemble (acmpc_set_dynamics_ensemble): `vehicles` a list of DynamicBicycleParams / 26-double blocks,
@@ -697,6 +706,7 @@ class Engine:
         self._check(self._lib.acmpc_set_dynamics_ensemble(self._ctx, blocks.ctypes.data, blocks.shape[0],
                                                           None if w is None else w.ctypes.data,
                                                           ENSEMBLE_REDUCE[reduce]))
+        self.K = blocks.shape[0]
 
     def set_dynamics_integration(self, substeps: int = 1, low_speed_blend=None):
         """Mode D's integration setting (acmpc_set_dynamics_integration): `substeps` Euler steps per control step (1 ..
@@ -820,6 +830,34 @@ class Engine:
                                                 w.ctypes.data, sc.ctypes.data, sc.shape[0], errors.ctypes.data,
                                                 C.byref(best)))
         return errors, key_index(best.value)
+
+    def trace_plans(self, x0: np.ndarray, U: np.ndarray, want=("states", "totals", "terms")):
+        """Mode D's plan trace (acmpc_trace_plans): the plans `U` [P, M, n, 2] - or [P, n, 2]: one plan per problem -
+        re-rolled from `x0` [P, 6] under each of the handle's K vehicles with all of its settings, by the arithmetic that
+        scores candidates.  Returns dict(states [P, M, K, n + 1, 6], cost [P, M, K], violation [P, M, K], terms
+        [P, M, K, n, 22]) and, as views of `terms`, one entry per name of TRACE_TERMS: j, e_y, e_psi, dv, dk, box [.., 2],
+        corridor, rate [.., 2], slip, ceiling, obstacles [.., 8], V, E.  A step is infeasible exactly where one of
+        terms[..., TRACE_HINGES] is not 0.  `want` drops outputs that are not needed."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float32)
+        U = np.ascontiguousarray(U, dtype=np.float32)
+        if x0.ndim == 1:
+            x0 = x0[None]
+        if U.ndim == 3:
+            U = U[:, None]
+        if U.ndim != 4 or U.shape[3] != 2 or x0.shape != (U.shape[0], STATE_FLOATS[MODE_DYNAMIC]):
+            raise ValueError("U must be [P, M, n, 2] (or [P, n, 2]) and x0 [P, 6]")
+        P, M, n = U.shape[:3]
+        K = max(self.K, 1)
+        states = np.empty((P, M, K, n + 1, 6), dtype=np.float32) if "states" in want else None
+        totals = np.empty((P, M, K, 2), dtype=np.float32) if "totals" in want else None
+        terms = np.empty((P, M, K, n, TRACE_TERM_FLOATS), dtype=np.float32) if "terms" in want else None
+        self._check(self._lib.acmpc_trace_plans(self._ctx, x0.ctypes.data, U.ctypes.data, P, M, n,
+                                                *(None if a is None else a.ctypes.data for a in (states, totals, terms))))
+        out = dict(states=states, terms=terms, cost=None if totals is None else totals[..., 0],
+                   violation=None if totals is None else totals[..., 1])
+        if terms is not None:
+            out.update((name, terms[..., cols]) for name, cols in TRACE_TERMS.items())
+        return out
 
     def set_coefficients(self, coef: np.ndarray):
         """The packed float32 tables themselves, [P, n, 12] (mode S) / [P, n, 8] (mode T) or one [n, stride] table
@@ -1170,6 +1208,27 @@ def unpack_decision_temporal(z: np.ndarray, n: int, dt: float, wheelbase: float)
     if rc != OK:
         raise EngineError(rc, "acmpc_unpack_decision_temporal: bad arguments")
     return arrays
+
+
+def unpack_decision_dynamic(states: np.ndarray, u: np.ndarray, dt: float):
+    """A mode D plan - `states` [n + 1, 6] = (X, Y, yaw, vx, vy, r) of Engine.trace_plans, `u` [n, 2] = (delta, pedal) ->
+    the six arrays of `unpack_decision_temporal` with mode T's meaning, and the pedals: projected_control[0][i] = vx_{i+1},
+    the speed the plan reaches under control i (the speed PID's target while that control holds), projected_control[1][i]
+    = delta_i, prediction[i] = (X_i, Y_i), cum_time[i] = i dt, accelerations and steer_rates the differences of the two rows
+    over dt.  Returns (projected_control [2, n], prediction [n, 2], cum_time [n], times, accelerations, steer_rates [n - 1],
+    projected_pedal [n]), float64."""
+    states = np.asarray(states, dtype=np.float64)
+    u = np.asarray(u, dtype=np.float64)
+    n = u.shape[0]
+    if u.shape != (n, 2) or states.shape != (n + 1, 6) or n < 2 or not dt > 0.0:
+        raise ValueError("states are [n + 1, 6] and u [n, 2] with n >= 2, dt > 0")
+    projected_control = np.stack([states[1:, 3], u[:, 0]])
+    prediction = states[:n, :2].copy()
+    cum_time = np.arange(n, dtype=np.float64) * float(dt)
+    times = np.full(n - 1, float(dt))
+    accelerations = np.diff(projected_control[0]) / float(dt)
+    steer_rates = np.diff(projected_control[1]) / float(dt)
+    return projected_control, prediction, cum_time, times, accelerations, steer_rates, u[:, 1].copy()
 
 
 def search_window():

@@ -338,3 +338,70 @@ def predict_obstacles(position, velocity, n: int, dt: float) -> np.ndarray:
     velocity = np.asarray(velocity, dtype=np.float64).reshape(-1, 2)
     t = (np.arange(int(n), dtype=np.float64) + 1.0) * float(dt)
     return position[None, :, :] + velocity[None, :, :] * t[:, None, None]
+
+
+TRACE_HINGES = ("box", "corridor", "rate", "slip", "ceiling", "obstacles")   # what a step squares into V, in this order
+
+
+def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min=(-0.3, -1.0), u_max=(0.3, 1.0),
+          margin: float = 0.0, wheelbase=None, nn_window=None, substeps: int = 1, low_speed_blend=None, coupling=None,
+          load_transfer=None, downforce=None, u_prev=None, rate_max=None, slip_max=None, speed_ceiling=None, obstacles=None,
+          radii=None) -> dict:
+    """The float64 mirror of Engine.trace_plans for one plan under one vehicle: `params.rollout(state, U, ...)` with the
+    handle's step settings, and per control step - on the state after it, against its nearest waypoint j of `table` [7, n]
+    (objective_terms' search: `nn_window` from waypoint 0, None: all) - what the cost lines see and the hinges they square
+    into V, as stage_terms, objective_terms and clearance_terms define them: dict(states [n + 1, 6], j [n], e_y, e_psi, dv,
+    dk [n], box [n, 2] = u - clip(u, u_min, u_max), corridor [n] = max(|e_y| - (width_j / 2 - margin), 0), rate [n, 2] and
+    slip [n] = max(|.| - limit, 0) of stage_terms' rd, rp, b (step 0 against `u_prev`, or a zero increment; None: no limit, 0),
+    ceiling [n] = max(vx - (scale v_j + offset), 0), obstacles [n, 8] = max(R_k - d_ik, 0) of clearance_terms (a NaN coordinate
+    is a disc that is not there), V [n] the running sum of their squares, kink [n, 15] each hinge's distance from its kink).  `wheelbase` (default lf + lr) makes delta_ref =
+    atan(wheelbase kappa_j)."""
+    U = np.asarray(U, dtype=np.float64)
+    table = np.asarray(table, dtype=np.float64)
+    n = U.shape[0]
+    x, y, psi, kappa, width, v = (table[row][:n] for row in (0, 1, 2, 3, 5, 6))
+    L = params.lf + params.lr if wheelbase is None else float(wheelbase)
+    states = params.rollout(state, U, dt, substeps=substeps, low_speed_blend=low_speed_blend, coupling=coupling,
+                            load_transfer=load_transfer, downforce=downforce)
+    after = states[1:]
+    d2 = (after[:, 0, None] - x[None, :]) ** 2 + (after[:, 1, None] - y[None, :]) ** 2
+    if nn_window is None:
+        j = np.argmin(d2, axis=1)
+    else:
+        back, ahead = nn_window
+        span = back + ahead + 1
+        j = np.empty(n, dtype=np.int64)
+        prev = 0
+        for i, row in enumerate(d2):
+            first = min(max(prev - back, 0), max(n - span, 0))
+            prev = j[i] = first + int(np.argmin(row[first:first + span]))
+    e_y = -np.sin(psi[j]) * (after[:, 0] - x[j]) + np.cos(psi[j]) * (after[:, 1] - y[j])
+    e_psi = np.mod(after[:, 2] - psi[j] + np.pi, 2.0 * np.pi) - np.pi
+    out = dict(states=states, j=j, e_y=e_y, e_psi=e_psi, dv=after[:, 3] - v[j], dk=U[:, 0] - np.arctan(L * kappa[j]))
+    lo, hi = np.asarray(u_min, dtype=np.float64), np.asarray(u_max, dtype=np.float64)
+    out["box"] = U - np.clip(U, lo, hi)
+    # every other hinge is max(argument, 0): the arguments, in TRACE_HINGES' order behind the box's two
+    first = U[0] if u_prev is None else np.asarray(u_prev, dtype=np.float64)
+    rates = np.diff(np.concatenate([first[None], U]), axis=0) / dt
+    limits = [np.inf, np.inf] if rate_max is None else [np.inf if m is None else float(m) for m in rate_max]
+    b = (after[:, 5] * params.lr - after[:, 4]) / (after[:, 3] + 1e-3)
+    over = np.full((n, 13), -np.inf)
+    over[:, 0] = np.abs(e_y) - (width[j] / 2.0 - float(margin))
+    over[:, 1:3] = np.abs(rates) - np.asarray(limits)[None, :]
+    over[:, 3] = np.abs(b) - (np.inf if slip_max is None else float(slip_max))
+    if speed_ceiling is not None:
+        scale, offset = (float(speed_ceiling), 0.0) if np.ndim(speed_ceiling) == 0 else (float(c) for c in speed_ceiling)
+        over[:, 4] = after[:, 3] - (scale * v[j] + offset)
+    if obstacles is not None:
+        discs = np.asarray(obstacles, dtype=np.float64)[:n]
+        with np.errstate(invalid="ignore"):
+            d = np.sqrt(np.sum((after[:, None, :2] - discs) ** 2, axis=2))
+        gap = np.asarray(radii, dtype=np.float64)[None, :] - d
+        over[:, 5:5 + discs.shape[1]] = np.where(np.isfinite(gap), gap, -np.inf)   # (a disc that is not there)
+    hinge = np.maximum(over, 0.0)
+    out.update(corridor=hinge[:, 0], rate=hinge[:, 1:3], slip=hinge[:, 3], ceiling=hinge[:, 4], obstacles=hinge[:, 5:])
+    # how far every hinge's argument is from its kink (the box: from the nearer bound): where a float32 trace may differ in kind
+    out["kink"] = np.concatenate([np.minimum(np.abs(U - lo), np.abs(U - hi)), np.abs(over)], axis=1)
+    hinges = np.concatenate([out["box"], hinge], axis=1)
+    out["V"] = np.cumsum(np.sum(hinges * hinges, axis=1))
+    return out

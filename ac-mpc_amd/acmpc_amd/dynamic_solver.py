@@ -8,7 +8,13 @@ pedal), `sampling_seed`, `sampling_update` ("argmin", the default: a round recen
 softmin-weighted mean of its candidates, MPPI's update, with the winner kept as candidate 1), `softmin_lambda` (default
 1.0), `w_bound`, `nn_window`, `rollout_dt`; the weights `step_cost` (e_y, e_psi, -), `r_term` (speed
 error, steering against delta_ref), `final_cost`; the input box `u_min` / `u_max` (default delta +-0.3 rad, pedal +-1).
-The warm start is the previous plan shifted by one step.
+The warm start is the previous plan shifted by one step (`warm_start(steps)`: by that many).
+
+Plan states (acmpc_trace_plans): `plan_states: True` (default off) adds `obj.states` [n + 1, 6] = (X, Y, yaw, vx, vy, r) - the
+accepted plan re-rolled on the device under vehicle 0 by the arithmetic that scored it, so the speed the plan reaches at every
+step is the float32 one the GPU saw - from one more call per solve; `solver.trace()` is the full trace of the last accepted plan
+(or of a given one) under every vehicle: the states, each vehicle's cost and violation, and per step what every limit saw
+(Engine.trace_plans) - which limit made a plan infeasible, at which step, and where the low-grip member of an ensemble goes.
 
 Robust scoring (acmpc_set_dynamics_ensemble): `vehicle_ensemble` - a list of DynamicBicycleParams or 26-double blocks -
 or `grip_ensemble` - grip scales, each giving `params.with_grip(scale)` - scores every candidate under each vehicle;
@@ -190,6 +196,8 @@ class DynamicSamplingSolver:
         if clearance != (0.0, 0.0):
             self._engine.set_dynamics_clearance(*clearance)
         self._has_obstacles = False
+        self._plan_states = bool(config.get("plan_states", False))
+        self._last_state: Optional[np.ndarray] = None   # the start state of the last solve: what trace() re-rolls from
         self._plan: Optional[np.ndarray] = None
         self._calls = 0
         self._adapt = adapt
@@ -208,11 +216,25 @@ class DynamicSamplingSolver:
     def engine(self):
         return self._engine
 
-    def warm_start(self) -> np.ndarray:
-        """The centre of the next solve: the last plan shifted by one step (its last control repeated), zeros at first."""
+    def warm_start(self, steps: int = 1) -> np.ndarray:
+        """The centre of the next solve: the last plan shifted by `steps` control steps (its last control repeated), zeros
+        at first."""
         if self._plan is None:
             return np.zeros((self._n, 2), dtype=np.float32)
-        return np.concatenate([self._plan[1:], self._plan[-1:]]).astype(np.float32)
+        steps = min(max(int(steps), 0), self._n)
+        return np.concatenate([self._plan[steps:], np.repeat(self._plan[-1:], steps, axis=0)]).astype(np.float32)
+
+    def trace(self, plan=None):
+        """Engine.trace_plans of `plan` [n, 2] (default: the last accepted plan) from the last solve's start state, on its
+        path, previous control and obstacles, under every vehicle of the handle: dict(states [K, n + 1, 6], cost [K],
+        violation [K], terms [K, n, 22] and its named views)."""
+        if self._last_state is None:
+            raise ValueError("trace() follows a solve")
+        plan = self._plan if plan is None else np.asarray(plan, dtype=np.float32)
+        if plan is None or plan.shape != (self._n, 2):
+            raise ValueError("no accepted plan to trace" if plan is None else "a plan is [n, 2]")
+        out = self._engine.trace_plans(self._last_state[None], plan[None, None])
+        return {name: (None if a is None else a[0, 0]) for name, a in out.items()}
 
     def _score_grips(self, states, controls, dt, scales, segment=1, weights=(1.0, 1.0, 1.0)):
         return self._engine.score_grips(states, controls, dt, np.asarray(scales) / np.asarray(self._base_grip), segment=segment,
@@ -238,11 +260,12 @@ class DynamicSamplingSolver:
             self._applied_grip = now
             self._base_grip = (now[0] * self._adapt["bracket"][0], now[1] * self._adapt["bracket"][0])
 
-    def solve(self, state, reference_path, previous_control=None, obstacles=None):
+    def solve(self, state, reference_path, previous_control=None, obstacles=None, warm_steps: int = 1):
         """state (X, Y, yaw, vx, vy, r); reference_path a [7, n] table (rows x, y, psi, kappa, ds, width, v) or an object
         with `as_table()` / `_reference_path` giving one.  `previous_control` = (delta, pedal) applied just before this
         solve, for the rate terms' step 0; None: the first control of the last accepted plan (none before there is one).
-        `obstacles` = (positions [n, K, 2], radii [K]) for this solve (Engine.set_obstacles); None: no obstacles."""
+        `obstacles` = (positions [n, K, 2], radii [K]) for this solve (Engine.set_obstacles); None: no obstacles.
+        `warm_steps`: control steps since the previous solve (warm_start's shift)."""
         table = reference_path
         if hasattr(reference_path, "as_table"):
             table = reference_path.as_table()
@@ -263,7 +286,8 @@ class DynamicSamplingSolver:
         elif self._has_obstacles:
             self._engine.set_obstacles(None)
             self._has_obstacles = False
-        out = self._engine.optimize(np.asarray(state, dtype=np.float32).reshape(1, 6), self.warm_start()[None], None,
+        self._last_state = np.asarray(state, dtype=np.float32).reshape(6).copy()
+        out = self._engine.optimize(self._last_state[None], self.warm_start(warm_steps)[None], None,
                                     self._N, self._rounds, self._sigma, seed=self._seed + self._calls)
         self._calls += 1
         u = np.asarray(out["u"][0], dtype=np.float64).reshape(self._n, 2)
@@ -272,9 +296,13 @@ class DynamicSamplingSolver:
         if ok:
             self._plan = u.astype(np.float32)
         status = SOLVED if ok else "failed"
-        return SimpleNamespace(x=np.concatenate([x.ravel(), u.ravel()]), info=SimpleNamespace(status=status),
-                               cost=float(out["cost"][0]), violation=float(out["violation"][0]),
-                               n_feasible=int(out["n_feasible"][0]))
+        obj = SimpleNamespace(x=np.concatenate([x.ravel(), u.ravel()]), info=SimpleNamespace(status=status),
+                              cost=float(out["cost"][0]), violation=float(out["violation"][0]),
+                              n_feasible=int(out["n_feasible"][0]))
+        if self._plan_states:   # the winner under vehicle 0, re-rolled by the arithmetic that scored it
+            traced = self._engine.trace_plans(self._last_state[None], u.astype(np.float32)[None, None], want=("states",))
+            obj.states = traced["states"][0, 0, 0].astype(np.float64)
+        return obj
 
     def close(self):
         self._engine.close()

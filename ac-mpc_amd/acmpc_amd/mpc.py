@@ -124,13 +124,24 @@ class SpatialMPC:
 
     # -- the entry point ----------------------------------------------------------------------------------
     def get_control(self, reference_path: np.ndarray, is_localised: bool = False, offset: float = 0.0,
-                    elapsed: float = None):
+                    elapsed: float = None, motion=None):
         """One MPC solve for an H x 3 reference path given in the vehicle frame (car at the origin, heading +y,
         laterally displaced by `offset`).  Returns None; results are left in attributes.  `elapsed` (optional,
         not in the reference's signature): seconds since the previous solve - the sampler then starts from the
-        previous plan advanced by that time instead of the plan as it was."""
+        previous plan advanced by that time instead of the plan as it was.  `motion` = (vx, vy, r), the measured body
+        velocities: required with `rollout_mode: "D"`, whose start state is (offset, 0, pi / 2, vx, vy, r) in that frame
+        (`elapsed` then shifts the warm start by round(elapsed / rollout_dt) control steps, None: one); not read otherwise.
+        In mode D `projected_control` = (the speed the plan reaches under each control, the steering angle) - what the
+        command selectors and the speed PID take, as in mode T - and `projected_pedal` [n], `plan_states` [n + 1, 6] and
+        `plan_violation` are left beside the reference's attributes."""
         n = self.MPC_horizon - 1
-        if elapsed is not None and self.cum_time.shape[0] == n:
+        solver = self._control_solver
+        if solver.dynamic:
+            if motion is None:
+                raise ValueError("rollout_mode 'D' needs motion = (vx, vy, r), the measured body velocities")
+            solver.motion = tuple(float(v) for v in motion)
+            solver.warm_steps = 1 if elapsed is None else int(min(max(round(float(elapsed) / solver._dt), 0), n))
+        elif elapsed is not None and self.cum_time.shape[0] == n:
             self._control_solver.shift_warm_start(elapsed, self.cum_time)
         if self._device_prologue and self._control_solver.supports_tick():
             return self._get_control_tick(reference_path, is_localised, offset)
@@ -147,7 +158,12 @@ class SpatialMPC:
             self.infeasibility_counter += 1
             return
 
-        if self._control_solver.temporal:
+        if self._control_solver.dynamic:
+            u = dec.x[3 * (n + 1):].reshape(n, 2)
+            (self.projected_control, self.current_prediction, self.cum_time, self.times, self.accelerations,
+             self.steer_rates, self.projected_pedal) = _capi.unpack_decision_dynamic(dec.states, u, self._control_solver._dt)
+            self.plan_states, self.plan_violation = dec.states, dec.violation
+        elif self._control_solver.temporal:
             (self.projected_control, self.current_prediction, self.cum_time, self.times, self.accelerations,
              self.steer_rates) = _capi.unpack_decision_temporal(dec.x, n, self._control_solver._dt, self.model.length)
         else:

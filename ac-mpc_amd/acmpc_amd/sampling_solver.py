@@ -28,6 +28,12 @@ default up to horizon 107; `nn_window: [back, ahead]` searches only that many wa
 per solve instead of 0.066, and is the default beyond), Frenet errors against it (dynamics.py:23-40), the same weights and
 bounds.
 The plan is then a TIME-indexed one (control i holds from i * dt), which is what `TemporalCommandSelector` consumes.
+
+`rollout_mode: "D"` scores with the dynamic (Pacejka) bicycle instead: a `DynamicSamplingSolver` built from the same control
+config, so every mode D key of dynamic_solver.py passes through (`dynamic_vehicle`: a DynamicBicycleParams or a 26-double
+block, default the reference vehicle; `margin` is the model's; `plan_states` is forced on).  The controls are then (steering
+angle, pedal), the start state is the pose with the measured body velocities `motion` = (vx, vy, r), and the plan is
+time-indexed like mode T's.  There is no one-round-trip tick in mode D: `supports_tick()` is false.
 """
 from __future__ import annotations
 
@@ -98,10 +104,23 @@ class ControlSolver:
         self._incumbent = None
         self._engine = None  # built on first solve: the input box follows the live velocity limits
         mode = str(config.get("rollout_mode", "S")).upper()
-        if mode not in ("S", "T"):
-            raise ValueError("rollout_mode must be 'S' or 'T'")
+        if mode not in ("S", "T", "D"):
+            raise ValueError("rollout_mode must be 'S', 'T' or 'D'")
         self.temporal = mode == "T"
+        self.dynamic = mode == "D"
         self._dt = float(config.get("rollout_dt", 0.05))
+        self.motion = None       # mode D: (vx, vy, r) of the start state, set by SpatialMPC before `solve`
+        self.warm_steps = 1      # mode D: control steps since the previous solve (the warm start's shift)
+        self._dynamic_solver = None
+        if self.dynamic:
+            from .dynamic_model import DynamicBicycleParams
+            from .dynamic_solver import DynamicSamplingSolver
+            vehicle = config.get("dynamic_vehicle")
+            if vehicle is not None and not isinstance(vehicle, DynamicBicycleParams):
+                vehicle = DynamicBicycleParams.from_coefficients(vehicle)
+            dynamic_config = {k: v for k, v in config.items() if k not in ("dynamic_vehicle", "speed_profile_constraints")}
+            dynamic_config.update(margin=float(model.margin), plan_states=True)
+            self._dynamic_solver = DynamicSamplingSolver(dynamic_config, vehicle)
         # None: the nearest of all waypoints (the verified window search).  Absent: that, up to the 100 steps whose search
         # frames fit the round's LDS; a longer horizon gets the (2,5) window, which costs it a third of a scan of every waypoint
         window = config["nn_window"] if "nn_window" in config else (None if self._n_horizon <= 106 else (2, 5))
@@ -155,8 +174,8 @@ class ControlSolver:
 
     def supports_tick(self) -> bool:
         """Whether `solve_tick` (the one-round-trip path, prologue on the device) applies: argmin centre update and a
-        horizon the single-workgroup prologue holds."""
-        return self._centre_update == "argmin" and self._n_horizon <= 128
+        horizon the single-workgroup prologue holds; never in mode D (acmpc_control_tick refuses a mode D handle)."""
+        return not self.dynamic and self._centre_update == "argmin" and self._n_horizon <= 128
 
     def bind_map(self, centre: np.ndarray, spacing: float):
         """Map centre line the tick may cut its reference path from (`solve_tick(None, ..., map_index=...)`)."""
@@ -228,7 +247,18 @@ class ControlSolver:
         self._explore = status != SOLVED
         return out, status, total_rounds
 
+    @property
+    def dynamic_solver(self):
+        """Mode D: the DynamicSamplingSolver that scores (its `trace()` explains the last plan); None in modes S and T."""
+        return self._dynamic_solver
+
     def solve(self, spatial_state: np.ndarray, reference_path: ReferencePath) -> SimpleNamespace:
+        if self.dynamic:
+            # mode D rolls the pose and the measured body velocities; the result carries `states` [n + 1, 6] beside `x`
+            if self.motion is None:
+                raise ValueError("rollout_mode 'D' needs motion = (vx, vy, r), the measured body velocities")
+            state = np.concatenate([np.asarray(self.pose, dtype=np.float64), np.asarray(self.motion, dtype=np.float64)])
+            return self._dynamic_solver.solve(state, reference_path.table, warm_steps=self.warm_steps)
         engine = self._ensure_engine()
         n = self._n_horizon
         engine.set_paths(reference_path.table)

@@ -507,6 +507,7 @@ void acmpc_destroy(acmpc_ctx* c) {
     (void)hipFree(c->d_progress);
     (void)hipFree(c->d_identify);
     (void)hipFree(c->d_identify_e);
+    (void)hipFree(c->d_plan_trace);
     (void)hipFree(c->d_centre);
     (void)hipFree(c->d_uref);
     (void)hipFree(c->d_U);

@@ -1,9 +1,10 @@
 // C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
 // (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the downforce, the previous control, the obstacles and the clearance setting, and the grip
-// identification (acmpc_score_grips), with the checks that the kernels' limits are the public header's.
+// identification (acmpc_score_grips) and the plan trace (acmpc_trace_plans), with the checks that the kernels' limits are the public header's.
 #include <algorithm>
 
 #include "acmpc_ctx.h"
+#include "acmpc_dynamic_trace.h"
 #include "acmpc_identify.h"
 
 using namespace acmpc::capi;
@@ -520,6 +521,69 @@ int acmpc_score_grips(acmpc_ctx* c, const float* states, const float* controls, 
   ACMPC_HIP(c, hipStreamSynchronize(s));
   std::memcpy(best, c->h_identify.data(), sizeof(int64_t));
   if (errors != nullptr) std::memcpy(errors, c->h_identify.data() + sizeof(int64_t), static_cast<size_t>(K) * sizeof(float));
+  return ACMPC_OK;
+}
+
+int acmpc_trace_plans(acmpc_ctx* c, const float* x0, const float* U, int32_t P, int32_t M, int32_t n, float* states,
+                      float* totals, float* terms) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  // every refusal comes before any device work
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_trace_plans needs a mode D handle");
+  if (!c->has_dynamics) return fail(c, ACMPC_ESTATE, "mode D: acmpc_set_dynamics has not been called");
+  if (x0 == nullptr || U == nullptr) return fail(c, ACMPC_EINVAL, "acmpc_trace_plans: null x0 or U");
+  if (states == nullptr && totals == nullptr && terms == nullptr)
+    return fail(c, ACMPC_EINVAL, "acmpc_trace_plans: at least one of states, totals and terms");
+  if (M < 1) return fail(c, ACMPC_EINVAL, "P, M and n must be positive");
+  // (pending stream, P and n positive, within the handle's capacity and the paths', the previous controls' and the obstacles')
+  ACMPC_TRY(check_shape(c, P, 1, n, ACMPC_LAYOUT_CANDIDATE_MAJOR));
+  static_assert(acmpc::kTraceTermFloats == ACMPC_TRACE_TERM_FLOATS, "the trace row of acmpc_dynamic_trace.h is the header's");
+  const int K = c->vehicles.K;
+  // the device block: x0 | U | states | totals | terms, each part a multiple of 16 bytes
+  auto padded = [](size_t floats) { return (floats + 3) & ~static_cast<size_t>(3); };
+  const size_t plans = static_cast<size_t>(P) * M, rolls = plans * K;
+  const size_t x0_floats = static_cast<size_t>(P) * acmpc::kDynamicStateFloats, u_floats = plans * n * 2;
+  const size_t state_floats = rolls * (static_cast<size_t>(n) + 1) * acmpc::kDynamicStateFloats, total_floats = rolls * 2,
+               term_floats = rolls * n * acmpc::kTraceTermFloats;
+  constexpr size_t kMaxOutputBytes = size_t{1} << 30;
+  if (plans > 0x7fffffff || (state_floats + total_floats + term_floats) * sizeof(float) > kMaxOutputBytes)
+    return fail(c, ACMPC_ECAPACITY, "acmpc_trace_plans: the outputs of one call exceed 1 GiB");
+  const size_t at_u = padded(x0_floats), at_states = at_u + padded(u_floats), at_totals = at_states + padded(state_floats),
+               at_terms = at_totals + padded(total_floats);
+  const size_t bytes = (at_terms + padded(term_floats)) * sizeof(float);
+
+  ACMPC_TRY(ensure_device(c));
+  if (c->stream == nullptr) ACMPC_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  hipStream_t s = c->stream;
+  if (c->plan_trace_bytes < bytes) {   // (drained first: nothing of an earlier call reads the block that goes)
+    ACMPC_HIP(c, hipStreamSynchronize(s));
+    (void)hipFree(c->d_plan_trace);
+    c->d_plan_trace = nullptr;
+    c->plan_trace_bytes = 0;
+    ACMPC_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_plan_trace), bytes));
+    c->plan_trace_bytes = bytes;
+  }
+  float* block = reinterpret_cast<float*>(c->d_plan_trace);
+  ACMPC_TRY(upload_tables(c, s));
+  ACMPC_HIP(c, hipMemcpyAsync(block, x0, x0_floats * sizeof(float), hipMemcpyHostToDevice, s));
+  ACMPC_HIP(c, hipMemcpyAsync(block + at_u, U, u_floats * sizeof(float), hipMemcpyHostToDevice, s));
+  acmpc::TraceArgs a{};
+  a.U = block + at_u;
+  a.x0 = block;
+  a.coef = c->d_coef;
+  a.states = states != nullptr ? block + at_states : nullptr;
+  a.totals = totals != nullptr ? block + at_totals : nullptr;
+  a.terms = terms != nullptr ? block + at_terms : nullptr;
+  a.P = P;
+  a.M = M;
+  a.n = n;
+  a.w = c->w;
+  ACMPC_HIP(c, acmpc::launch_trace_dynamic(a, c->vehicles, dynamics_integration(c), dynamics_terms(c), s));
+  if (states != nullptr)
+    ACMPC_HIP(c, hipMemcpyAsync(states, a.states, state_floats * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (totals != nullptr)
+    ACMPC_HIP(c, hipMemcpyAsync(totals, a.totals, total_floats * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (terms != nullptr) ACMPC_HIP(c, hipMemcpyAsync(terms, a.terms, term_floats * sizeof(float), hipMemcpyDeviceToHost, s));
+  ACMPC_HIP(c, hipStreamSynchronize(s));
   return ACMPC_OK;
 }
 

@@ -18,7 +18,7 @@ namespace capi __attribute__((visibility("hidden"))) {
 // And of its load transfer ("Load transfer"): the six scalars of each vehicle, and the ratios +inf while the coupling is off.
 // And of its obstacles ("Obstacles"): the device block (positions, then radii), what it was set for, and the clearance
 // setting; K = 0 while none are set, the soft part on with a weight that is not 0.
-static acmpc::WithObstacles<acmpc::TermsAero> dynamics_terms(const acmpc_ctx* c) {
+acmpc::WithObstacles<acmpc::TermsAero> dynamics_terms(const acmpc_ctx* c) {
   acmpc::WithObstacles<acmpc::TermsAero> t{};
   t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
             std::isfinite(c->rate_max[1])) ? 1 : 0;

@@ -308,6 +308,10 @@ struct acmpc_ctx {
   float* d_obs = nullptr;
   size_t obs_capacity = 0;               // floats
   double clearance_weight = 0.0, clearance_margin = 0.0;
+  // mode D: the plan trace's device block (acmpc_trace_plans): x0 | U | states | totals | terms of ONE call, made on the call's
+  // first use, kept between calls and regrown when a later call needs more
+  unsigned char* d_plan_trace = nullptr;
+  size_t plan_trace_bytes = 0;
 
   mutable std::string err;
 };
@@ -336,6 +340,7 @@ struct Regenerate {
   const float* d_extra = nullptr;   // candidate 2's controls (the LQ plan), or nullptr
 };
 acmpc::Integration dynamics_integration(const acmpc_ctx* c);
+acmpc::WithObstacles<acmpc::TermsAero> dynamics_terms(const acmpc_ctx* c);   // (after the call's uploads: upload_tables)
 acmpc::SampleSpec make_spec(const acmpc_ctx* c, double sigma_v, double sigma_k, uint64_t seed, uint32_t round);
 // (`set`: which half of the partial keys / feasible counts - chained rounds and the stream of batches alternate)
 acmpc::RolloutArgs rollout_args(const acmpc_ctx* c, const float* d_x0, const float* d_U, float* d_costs, int P, int N, int n,

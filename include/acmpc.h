@@ -438,6 +438,37 @@ int acmpc_score_grips(acmpc_ctx* ctx, const float* states, const float* controls
                       const double weights[3], const double* scales /* [K][2] front, rear */, int32_t K,
                       float* errors /* [K] or NULL */, int64_t* best);
 
+/* Mode D, plan trace: what does a plan do, step by step, under every vehicle of the handle?  M plans per problem are
+ * re-rolled from x0 with ALL of the handle's settings - paths (acmpc_set_paths: n must be theirs), vehicle or ensemble,
+ * integration, terms, previous control, objective, coupling, load transfer, downforce, obstacles and clearance - by the
+ * arithmetic of the kernels that score candidates, one wavefront per (problem, plan, vehicle), and every control step
+ * leaves what it saw.  K = the handle's vehicles (1 after acmpc_set_dynamics).
+ *   x0      host [P][6] float32 (X, Y, yaw, vx, vy, r);  U host [P][M][n][2] float32 (delta, pedal)
+ *   states  [P][M][K][n + 1][6] float32 (X, Y, yaw, vx, vy, r): row 0 the start, row i + 1 the state after control step i,
+ *           positions in the caller's frame (a record's x is columns 0 .. 2 of vehicle 0)
+ *   totals  [P][M][K][2] float32 (c_k, V_k): vehicle k's cost and violation of that plan, before the ensemble's reduction
+ *   terms   [P][M][K][n][ACMPC_TRACE_TERM_FLOATS] float32, one row per control step on the state that step's cost saw:
+ *             0        the nearest waypoint j (as a float: exact)
+ *             1, 2     e_y, e_psi                    3, 4   dv = vx - v_ref_j, dk = delta - delta_ref_j
+ *             5, 6     the input box: u - med3(u, lo, hi) of steering and of pedal (signed)
+ *             7        the corridor: max(|e_y| - half-width_j, 0)
+ *             8, 9     the rate limits of steering and pedal     10   the slip limit     11   the speed ceiling
+ *             12 .. 19 disc q's penetration depth, q < the obstacles' K; +0 beyond
+ *             20       V after this step                         21   E after this step (+0 without terms)
+ *           Slots 5 .. 19 are the float32 hinges the cost squares into V, a part that is off leaves +0: from the previous
+ *           step's slot 20 (+0 at step 0), V = fma(h, h, V) over slots 5, 6, .., 19 in that order gives this step's slot 20
+ *           bit for bit, and the last step's is V_k.  A plan is infeasible exactly where a slot of 5 .. 19 is not 0.
+ * Any of the three outputs may be NULL (not all).  Host pointers; the call blocks and makes one round trip on the handle's
+ * stream, the inputs travelling with the tables as in acmpc_optimize.  Its device scratch is the call's own, kept between
+ * calls and regrown when a later call needs more.  It changes nothing a later call reads.  Refused before any device work,
+ * the handle as it was: ACMPC_ESTATE for a handle that is not mode D, has no vehicle or no paths, whose stored previous
+ * controls or obstacles are of another shape, or while a batch of acmpc_solve_stream_device is pending; ACMPC_EINVAL for a
+ * null x0 or U, three null outputs, P, M or n below 1, or P, n other than the paths'; ACMPC_ECAPACITY for P or n beyond the
+ * handle's, or outputs beyond 1 GiB in all.  DESIGN.md section 2 "Mode D, plan trace". */
+#define ACMPC_TRACE_TERM_FLOATS 22
+int acmpc_trace_plans(acmpc_ctx* ctx, const float* x0, const float* U, int32_t P, int32_t M, int32_t n, float* states,
+                      float* totals, float* terms);
+
 /* Copies the packed float32 table of problem `problem` (n rows of ACMPC_COEF_STRIDE_* floats) to `out`.
  * Host only; lets CPU tests pin the host-side arithmetic against the oracle. */
 int acmpc_get_coefficients(const acmpc_ctx* ctx, int32_t problem, float* out, int32_t capacity_floats);

@@ -65,9 +65,13 @@ hypothesis and control step (profiles/*_isa_mix.json, entry `identify_grip`: M s
 and the vector-issue time that count needs (bench.valu_roofline) as a fraction of the CALL - a lower bound on the step
 kernel's own fraction, which a `rocprofv3 --kernel-trace --stats` run of this command gives (kernel identify_grip_kernel).
 
+With `--trace` the plan trace (acmpc_trace_plans: host pointers, one blocking round trip, a latency call) is timed at
+(P, M, K, n) = (1, 1, 1, 49) - one plan under one vehicle, what `plan_states` adds to a solve - and (1, 64, 8, 49), under the
+run's settings: p50 / p99 of the call with all three outputs, and of the states alone.
+
 usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms] [--objective] [--coupling RF,RR]
                                       [--load-transfer H[,FRAC]] [--downforce KF,KR[,VSAT]]
-                                      [--sampled | --optimize [--update softmin] | --identify]"""
+                                      [--sampled | --optimize [--update softmin] | --identify | --trace]"""
 import argparse
 import json
 import os
@@ -155,6 +159,7 @@ def main():
     ap.add_argument("--update", default="argmin", choices=("argmin", "softmin"),
                     help="with --optimize: softmin = one softmin round, matrix-free against through the matrix")
     ap.add_argument("--identify", action="store_true", help="acmpc_score_grips at K = 4 096 and 65 536, W = 40, L = 1 and 8")
+    ap.add_argument("--trace", action="store_true", help="acmpc_trace_plans at (P, M, K, n) = (1, 1, 1, 49) and (1, 64, 8, 49)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--substeps", type=int, default=1, help="Euler sub-steps per control step (1 .. 16)")
     ap.add_argument("--blend", default=None, help="LO,HI m/s: the low-speed blend")
@@ -187,6 +192,9 @@ def main():
         ap.error("--update softmin goes with --optimize")
     if args.identify:
         emit(args, measure_identify(args))
+        return
+    if args.trace:
+        emit(args, measure_trace(args))
         return
     if args.sampled or args.optimize:
         ks = [int(k) for k in (args.vehicles or "1").split(",")]
@@ -405,6 +413,33 @@ def measure_identify(args):
                                            vector_issue_time_over_call_p50=roof["frac"],
                                            opcode_mix_matches_loaded_sources=roof["opcode_mix_matches_loaded_sources"])
     eng.close()
+    return out
+
+
+def measure_trace(args):
+    """acmpc_trace_plans' latency at the two shapes DESIGN.md section 4.10 records."""
+    import acmpc_oracle as orc
+    import dynamic_spec as ds
+
+    n = 49
+    dp = ds.make_dynamic_problem(orc, "monza", n + 1, 64, 0)
+    out = {"tool": "tools/bench_dynamic.py --trace", "substeps": INTEGRATION[0], "low_speed_blend": INTEGRATION[1]}
+    calls = 20 if args.quick else 200
+    for M, K in ((1, 1), (64, 8)):
+        eng = _engine(dp, 1, 64, n, K, args.reduce, 0)
+        U = np.ascontiguousarray(dp["U"][None, :M])
+        x0 = dp["x0"][None]
+        shape = {"P": 1, "M": M, "K": K, "n": n}
+        for name, want in (("all_outputs", ("states", "totals", "terms")), ("states_only", ("states",))):
+            lat = []
+            for i in range(10 + calls):
+                t0 = time.perf_counter()
+                eng.trace_plans(x0, U, want=want)
+                if i >= 10:
+                    lat.append(time.perf_counter() - t0)
+            shape[name] = dict(p50_ms=float(np.percentile(lat, 50)) * 1e3, p99_ms=float(np.percentile(lat, 99)) * 1e3, calls=len(lat))
+        out["M%d_K%d" % (M, K)] = shape
+        eng.close()
     return out
 
 
