@@ -10,11 +10,12 @@ CSRC_DIR = os.path.normpath(os.path.join(PKG_DIR, "..", "csrc"))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libacmpc_hip.so")
 SOURCES = ("acmpc_kernels.hip", "acmpc_rollout.hip", "acmpc_solo.hip", "acmpc_softmin.hip",
-           "acmpc_kernels_temporal.hip", "acmpc_capi.hip", "acmpc_prologue.hip", "acmpc_pf.hip",
+           "acmpc_kernels_temporal.hip", "acmpc_capi.hip", "acmpc_prologue.hip",
+           "acmpc_pf.hip", "acmpc_pf_score.hip", "acmpc_pf_filter.hip", "acmpc_pf_grid.cpp",
            "acmpc_speed_profile.cpp", "acmpc_host_path.cpp", "acmpc_dynamic.hip", "acmpc_dynamic_terms.hip", "acmpc_dynamic_coupled.hip",
            "acmpc_dynamic_loaded.hip", "acmpc_dynamic_aero.hip", "acmpc_dynamic_obstacles.hip", "acmpc_dynamic_trace.hip", "acmpc_identify.hip",
            "acmpc_capi_solve.hip", "acmpc_capi_optimize.hip", "acmpc_capi_tick.hip", "acmpc_capi_dynamic.hip", "acmpc_capi_rccl.hip")
-HEADERS = ("acmpc_ctx.h", "acmpc_kernels.h", "acmpc_kernels_impl.h", "acmpc_rollout.h", "acmpc_device.h", "acmpc_dynamic.h", "acmpc_dynamic_kernels.h", "acmpc_dynamic_trace.h", "acmpc_identify.h", "acmpc_frames.h", "acmpc_admm.h", "acmpc_prologue.h", "acmpc_lq.h", "acmpc_lq_box.h",
+HEADERS = ("acmpc_ctx.h", "acmpc_alloc.h", "acmpc_pf.h", "acmpc_pf_grid.h", "acmpc_kernels.h", "acmpc_kernels_impl.h", "acmpc_rollout.h", "acmpc_device.h", "acmpc_dynamic.h", "acmpc_dynamic_kernels.h", "acmpc_dynamic_trace.h", "acmpc_identify.h", "acmpc_frames.h", "acmpc_admm.h", "acmpc_prologue.h", "acmpc_lq.h", "acmpc_lq_box.h",
            os.path.join("..", "..", "include", "acmpc.h"))
 
 # -ffp-contract=off: no IMPLICIT fused multiply-add anywhere; the FMAs of mode T's specification are spelt out

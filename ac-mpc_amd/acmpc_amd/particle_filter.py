@@ -4,7 +4,7 @@ states + downsampled track-limit observations in, the reference's `particles` di
 (`track_indices`, `centreline_idx`, `minimum_offset`, `heading_offset`, `observation_error`, `score`).
 
 The data-parallel work - three nearest-point queries per particle against the map (scipy KD-trees in the
-reference), observation placement, error, score, validity - runs in `csrc/acmpc_pf.hip`.  `ParticleFilter` adds
+reference), observation placement, error, score, validity - runs in `csrc/acmpc_pf_score.hip` (C API: `csrc/acmpc_pf.hip`).  `ParticleFilter` adds
 the sequential, random part round it (resampling, reset, convergence flag: localiser.py:420-570) in NumPy with
 the reference's draw order, so that a run seeded like the reference reproduces it.
 """

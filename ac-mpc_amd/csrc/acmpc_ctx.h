@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/acmpc.h"
+#include "acmpc_alloc.h"  // alloc_once, host_alloc_once
 #include "acmpc_dynamic.h"
 #include "acmpc_kernels.h"
 #include "acmpc_lq_box.h"
@@ -44,19 +45,8 @@ int fail_hip(const acmpc_ctx* ctx, hipError_t e, const char* what);
     if (rc_ != ACMPC_OK) return rc_;      \
   } while (0)
 
-// Allocate only what is not there yet: after a mid-way failure (out of memory) the buffers already obtained stay
-// owned by the handle, a retry on the same handle picks up where the failed call stopped, and acmpc_destroy frees
-// whatever exists.
-template <typename T>
-hipError_t alloc_once(T** slot, size_t bytes) {
-  if (*slot != nullptr) return hipSuccess;
-  return hipMalloc(reinterpret_cast<void**>(slot), bytes);
-}
-template <typename T>
-hipError_t host_alloc_once(T** slot, size_t bytes) {
-  if (*slot != nullptr) return hipSuccess;
-  return hipHostMalloc(reinterpret_cast<void**>(slot), bytes, hipHostMallocDefault);
-}
+using ::acmpc::alloc_once;
+using ::acmpc::host_alloc_once;
 
 int upload_segments(acmpc_ctx* c, int n, hipStream_t s);
 

@@ -1335,7 +1335,7 @@ def pf_weights_fixed_point(score: np.ndarray) -> np.ndarray:
 
 
 def pf_resample_counter_based(states, scores, score, valid, n_desired, minimum_particles, noise_sigma, seed, counter):
-    """Restates csrc/acmpc_pf.hip pf_resample_kernel (the device-resident filter's resampling; BUILD-DEFINED draws - the
+    """Restates csrc/acmpc_pf_filter.hip pf_resample_kernel (the device-resident filter's resampling; BUILD-DEFINED draws - the
     reference's own come from NumPy's global stream, see `pf_resample`): keep the valid particles in order; with fewer
     than `minimum_particles` return None (the caller resets); otherwise particle j of the top-up is a copy of kept
     particle  upper_bound(cdf, (r_j * total) >> 64)  with r_j the first 64 bits of Philox4x32-10 at counter
@@ -1378,7 +1378,7 @@ def pf_resample_counter_based(states, scores, score, valid, n_desired, minimum_p
 def pf_control_normals(n, seed, counter):
     """The two standard normals (float32, bit-specified) of the control noise of particles 0 ... n - 1 at filter step
     `counter`: Philox4x32-10 at counter (p, counter, "CTRL", 0), key (seed & 0xffffffff, seed >> 32), words 0 and 1
-    through `uniform_open` into one `box_muller_spec` pair (csrc/acmpc_pf.hip pf_step_kernel)."""
+    through `uniform_open` into one `box_muller_spec` pair (csrc/acmpc_pf_filter.hip pf_step_kernel)."""
     p = np.arange(n, dtype=np.uint32)
     ctr = np.stack([p, np.full_like(p, counter), np.full_like(p, PF_TAG_CONTROL), np.zeros_like(p)], axis=1)
     key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32)
@@ -1388,7 +1388,7 @@ def pf_control_normals(n, seed, counter):
 
 
 def pf_step_counter_based(states, tyre_angle, velocity, dt, sigma_yaw, sigma_v, wheel_base, seed, counter):
-    """Restates csrc/acmpc_pf.hip pf_step_kernel (Localiser.step, localiser.py:41-77, with BUILD-DEFINED counter-based
+    """Restates csrc/acmpc_pf_filter.hip pf_step_kernel (Localiser.step, localiser.py:41-77, with BUILD-DEFINED counter-based
     draws in place of NumPy's global stream): particle p steers delta = tyre_angle + sigma_yaw z0 at speed
     |velocity + sigma_v z1| with (z0, z1) = pf_control_normals, then one kinematic step of `kinematic_x_dot`.
     The draws are exact; the step is float64 here on the float32 states and fast float32 transcendentals on the device

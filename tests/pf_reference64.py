@@ -6,7 +6,7 @@ tests/test_pf_reference64.py holds it to the reference's own vectors and to the 
 
 Two things are float32 because they are the specification and not an accuracy choice: the particle states and the
 observation are float32 data, and the observation is PLACED in a particle's frame in float32 (the reference does so,
-localiser.py:330-353; csrc/acmpc_pf.hip says the same where it places).  Everything behind the placement is float64.
+localiser.py:330-353; csrc/acmpc_pf_score.hip says the same where it places).  Everything behind the placement is float64.
 The normals of the control noise are specified bit for bit (oracle `box_muller_spec`), so they are taken from there.
 
 Nothing here calls `oracle.pf_score_particles`."""

@@ -52,7 +52,7 @@ def _scorer(scene, switch):
 
 
 def given_form(track, counts):
-    """Which pf_score_given_kernel launch_score picks (csrc/acmpc_pf.hip): 0 no wrap possible, 1 wrap and K <= 256, 2 K > 256."""
+    """Which pf_score_given_kernel launch_score picks (csrc/acmpc_pf_score.hip): 0 no wrap possible, 1 wrap and K <= 256, 2 K > 256."""
     K = sum(counts)
     lengths = (len(track["left"]), len(track["right"]))
     no_wrap = max(lengths) + K <= 65536 and K <= min(lengths)

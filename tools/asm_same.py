@@ -4,7 +4,9 @@ instruction lines are compared in order - comments, directives and block labels'
 by their mangled names with the template parameter pack of mode D's kernels (`J...E`, and the pack in the argument list)
 taken out where it is empty or one Terms, so that a file from before the pack existed compares with one from after; a kernel
 of any other pack (TermsObjective) keeps its name and is counted among the new file's only.  Prints what differs and how many
-kernels are identical; exit status 1 unless every kernel of OLD is in NEW and identical.
+kernels are identical; exit status 1 unless every kernel of OLD is in NEW and identical.  The particle filter's kernels
+(csrc/acmpc_pf*.hip) take argument structs that were in the one unit's anonymous namespace and are in acmpc::pf since its
+split: that namespace is taken out of their names likewise.
 
 usage: hipcc <the library's flags + the unit's own> -c csrc/acmpc_dynamic.hip -o unit.o --save-temps     (at both commits, in two
        directories; mode D: each of the five csrc/acmpc_dynamic*.hip against its own counterpart)
@@ -28,6 +30,8 @@ def kernels(path):
             elif line and not line.startswith("."):
                 body.append(re.sub(r"\.LBB\d+_", ".LBBN_", line))
         name = re.sub(r"DpK?T\d*_", "", re.sub(r"J(?:NS_5TermsE)?E(E+v)", r"\1", m.group(1)))
+        if "N5acmpc2pf" in name:   # the particle filter's argument structs: acmpc::pf::GridArgs was (anonymous namespace)::GridArgs
+            name = name.replace("N5acmpc2pf", "NS_").replace("NS1_", "NS_")
         out[name] = body
     return out
 

@@ -2,8 +2,10 @@
 # Development aid (GPU box): the particle-scoring kernels under rocprofv3 --kernel-trace --stats for several settings of the
 # library's A/B switches, alternating, on one box.   usage: tools/pf_ab.sh [label="VAR=1 ..."] ...
 # default: the tree's default against ACMPC_PF_WORKGROUP_SCORE=1 (pf_score_kernel<8> behind the grid search).
-# A label `head` runs tools/_ab_old/head/acmpc_pf.hip (an earlier source, see tools/ab_old.sh) instead; BUILD=<flag> in a
-# label's settings builds the library with that compiler flag first (tools/ab_build.sh).
+# An earlier commit's kernels: a single-file acmpc_pf.hip from before the unit was split cannot be dropped into the split
+# tree (tools/ab_old.sh), so build that commit's library from a checkout of it and give it in the label's settings,
+# old="ACMPC_HIP_LIBRARY=/path/to/libacmpc_hip.so".  BUILD=<flag> in a label's settings builds the library with that compiler
+# flag first (tools/ab_build.sh).
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 [ $# -eq 0 ] && set -- tree= workgroup="ACMPC_PF_WORKGROUP_SCORE=1"
@@ -18,7 +20,6 @@ for rep in 1 2; do
           *) export "$kv" ;;
         esac
       done
-      if [ "$label" = head ]; then export ACMPC_HIP_LIBRARY=$(AB_OLD_DIR=head "$ROOT/tools/ab_old.sh" headpf acmpc_pf.hip | tail -1); fi
       for P in 500 100000; do
         rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/gpurun_out/pfab_${label}_${rep}_$P -- python3 $ROOT/tools/bench_pf.py $P \
           > $ROOT/gpurun_out/pfab_${label}_${rep}_$P.log 2>&1
