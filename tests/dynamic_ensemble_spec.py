@@ -46,18 +46,19 @@ def combine(costs, violations, reduce=MEAN, weights=None):
 
 
 def rollout_ensemble(x0, wp, U, vehicles, Q, R, QN, u_lo, u_hi, w_bound, dt, wheelbase, reduce=MEAN, weights=None,
-                     nn_window=None, return_states=False):
+                     nn_window=None, return_states=False, **kwargs):
     """The ensemble's cost and violation of every candidate (and vehicle 0's states): rollout_dynamic once per vehicle
-    block of `vehicles`, then combine()."""
+    block of `vehicles` - with `kwargs`: its settings, u_prev and obstacles - then combine()."""
     per = [ds.rollout_dynamic(x0, wp, U, v, Q, R, QN, u_lo, u_hi, w_bound, dt, wheelbase, nn_window=nn_window,
-                              return_states=return_states and k == 0) for k, v in enumerate(vehicles)]
+                              return_states=return_states and k == 0, **kwargs) for k, v in enumerate(vehicles)]
     J, V = combine([r[0] for r in per], [r[1] for r in per], reduce, weights)
     return (J, V, per[0][2]) if return_states else (J, V)
 
 
-def spec_ensemble(orc, dp, coef, vehicles, reduce=MEAN, weights=None, nn_window=None, U=None, return_states=False):
-    """The ensemble specification of problem `dp` (dynamic_spec.make_dynamic_problem) on the packed table `coef`."""
+def spec_ensemble(orc, dp, coef, vehicles, reduce=MEAN, weights=None, nn_window=None, U=None, return_states=False, **kwargs):
+    """The ensemble specification of problem `dp` (dynamic_spec.make_dynamic_problem) on the packed table `coef`; `kwargs`:
+    rollout_dynamic's settings, u_prev and obstacles."""
     kw = dp["kw"]
     return rollout_ensemble(dp["x0"], coef, dp["U"] if U is None else U, vehicles, kw["step_cost"], kw["r_term"],
                             kw["final_cost"], kw["u_min"], kw["u_max"], kw["w_bound"], kw["dt"], kw["wheelbase"],
-                            reduce=reduce, weights=weights, nn_window=nn_window, return_states=return_states)
+                            reduce=reduce, weights=weights, nn_window=nn_window, return_states=return_states, **kwargs)

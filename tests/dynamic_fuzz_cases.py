@@ -29,16 +29,11 @@ dynamic's estimate with the step taken M times.  A case above BUDGET_S gives up 
 sub-steps, then candidates - never its horizon, window, layout, family or which parts are on."""
 from __future__ import annotations
 
-import contextlib
-
 import numpy as np
 
-import dynamic_integration_spec as dis
-import dynamic_load_spec as dls
-import dynamic_objective_spec as dos
 import dynamic_sampled_spec as dss
 import dynamic_spec as ds
-import dynamic_terms_spec as dts
+from dynamic_spec import Settings
 
 T = np.float32
 INF = float("inf")
@@ -110,7 +105,7 @@ def accepts(block, ratio, load):
         return False
     if load is None:
         return True
-    c = dls.constants64(block, load)
+    c = ds.constants64(block, load)
     if not (np.isfinite(c["c_h"]) and np.isfinite(c["w_max"])):
         return False
     for a in "fr":
@@ -134,7 +129,7 @@ def spec_seconds(c):
 
 def parts(c):
     """Which parts of the cost are on, as the kernels' switches see them."""
-    t = dts.constants(0.05, **c["terms"])
+    t = ds.constants(None, Settings(**c["terms"]))
     return dict(rate=t.rate, slip=t.slip, progress=float(c["objective"]["progress_weight"]) != 0.0,
                 ceiling=c["objective"]["speed_ceiling"] is not None)
 
@@ -228,7 +223,7 @@ def _settings(rng, family, slot):
     c["objective"] = dict(progress_weight=progress, speed_ceiling=ceiling)
     # the previous control: none set, finite, or (where the existing tests show it legal: the terms' own kernels, the rate
     # part off beside a slip part, or both rate weights on) a NaN steering in one problem
-    t = dts.constants(0.05, **c["terms"])
+    t = ds.constants(None, Settings(**c["terms"]))
     choices = ["none", "finite"]
     if family == "terms" and ((not t.rate and t.slip) or (t.hwd != 0 and t.hwp != 0)):
         choices.append("nan")
@@ -410,26 +405,6 @@ def identification_cases():
 
 # ---- the composed restatement of a case ------------------------------------------------------------------------------------
 KIND = [dict(), dict(vx0=0.0), dict(yaw_turns=-1), dict(origin=(3000.0, 2700.0))]   # test_gpu_dynamic._problems' four
-OFF_TERMS = dict(rate=dict(rate_weight=(0.0, 0.0), rate_max=None), slip=dict(slip_weight=0.0, slip_max=None))
-OFF_OBJECTIVE = dict(progress=dict(progress_weight=0.0), ceiling=dict(speed_ceiling=None))
-
-
-@contextlib.contextmanager
-def restatement(c, u_prev=None, without=()):
-    """The float32 restatements composed for case `c` with ONE problem's previous control, in the nesting of
-    test_gpu_dynamic_load_transfer._spec: the load transfer's block (in the coupling's place) outermost of the step-level
-    settings, the objective's, the terms', the integration's innermost.  `without` names parts to switch off - "rate", "slip",
-    "progress", "ceiling", and "step" for the coupling and the load transfer together."""
-    terms, objective = dict(c["terms"]), dict(c["objective"])
-    for name in without:
-        terms.update(OFF_TERMS.get(name, {}))
-        objective.update(OFF_OBJECTIVE.get(name, {}))
-    ratio, load = (None, None) if "step" in without else (c["ratio"], c["load"])
-    with dls.setting(ratio, load):
-        with dos.setting(**objective):
-            with dts.setting(u_prev=u_prev, **terms):
-                with dis.setting(c["M"], c["blend"]):
-                    yield
 
 
 def problems(c, orc, limit=None):
@@ -464,23 +439,27 @@ def centres(c, orc, dps):
     return centre, (ref if c["with_ref"] else None)
 
 
-def specification(c, orc, dps, coefs, centre=None, ref=None, limit=None, without=(), only=None):
+def specification(c, orc, dps, coefs, centre=None, ref=None, limit=None, without=(), only=None, obstacles=None,
+                  clearance=(0.0, 0.0)):
     """What the kernels must give for case `c`, per problem.  Matrix form: (cost, V, states).  Sampled form: dynamic_sampled_
-    spec.rollout_sampled's dict.  `limit`: the first candidates only; `without`: restatement()'s; `only`: these problems only."""
+    spec.rollout_sampled's dict.  `limit`: the first candidates only; `without`: Settings.without's parts; `only`: these
+    problems only; `obstacles`: per problem (positions [n, K, 2], radii [K]) or None, under `clearance` = (weight, margin)."""
     vehicles = [blocks()[v] for v in c["vehicles"]]
     u_prev = previous(c)
+    settings = Settings.of_case(c, clearance_weight=clearance[0], clearance_margin=clearance[1]).without(*without)
     N = c["N"] if limit is None else min(c["N"], limit)
     out = []
     for p in (range(len(dps)) if only is None else only):
         dp, coef = dps[p], coefs[p]
-        with restatement(c, None if u_prev is None else u_prev[p], without):
-            if c["form"] == "sampled":
-                out.append(dss.rollout_sampled(orc, dp, coef, vehicles, centre[p], None if ref is None else ref[p], N,
-                                               c["index_offset"], p, c["round"], c["sample_seed"], c["sigma"], reduce=c["reduce"],
-                                               weights=c["weights"], nn_window=c["window"], return_states=True))
-            else:
-                out.append(dss.costs(orc, dp, coef, vehicles, dp["U"][:N], c["reduce"], c["weights"], c["window"],
-                                     return_states=True))
+        kwargs = dict(settings=settings, u_prev=None if u_prev is None else u_prev[p],
+                      obstacles=None if obstacles is None else obstacles[p])
+        if c["form"] == "sampled":
+            out.append(dss.rollout_sampled(orc, dp, coef, vehicles, centre[p], None if ref is None else ref[p], N,
+                                           c["index_offset"], p, c["round"], c["sample_seed"], c["sigma"], reduce=c["reduce"],
+                                           weights=c["weights"], nn_window=c["window"], return_states=True, **kwargs))
+        else:
+            out.append(dss.costs(orc, dp, coef, vehicles, dp["U"][:N], c["reduce"], c["weights"], c["window"],
+                                 return_states=True, **kwargs))
     return out
 
 

@@ -25,21 +25,21 @@ def candidates(orc, dp, centre, u_ref, n_candidates, index_offset, problem, roun
                                  kw["u_max"], u_extra=None)
 
 
-def costs(orc, dp, coef, vehicles, U, reduce=es.MEAN, weights=None, nn_window=None, return_states=False):
+def costs(orc, dp, coef, vehicles, U, reduce=es.MEAN, weights=None, nn_window=None, return_states=False, **kwargs):
     """(cost [N], violation [N][, states [N, n + 1, 3]]) of the candidates U under the vehicle blocks `vehicles` (one block:
-    dynamic_spec; several: the ensemble's combine)."""
+    dynamic_spec; several: the ensemble's combine); `kwargs`: rollout_dynamic's settings, u_prev and obstacles."""
     if len(vehicles) == 1:
-        return ds.spec_costs(orc, dp, coef, vehicles[0], nn_window=nn_window, U=U, return_states=return_states)
+        return ds.spec_costs(orc, dp, coef, vehicles[0], nn_window=nn_window, U=U, return_states=return_states, **kwargs)
     return es.spec_ensemble(orc, dp, coef, vehicles, reduce=reduce, weights=weights, nn_window=nn_window, U=U,
-                            return_states=return_states)
+                            return_states=return_states, **kwargs)
 
 
 def rollout_sampled(orc, dp, coef, vehicles, centre, u_ref, n_candidates, index_offset, problem, round_, seed, sigma,
-                    reduce=es.MEAN, weights=None, nn_window=None, return_states=False):
+                    reduce=es.MEAN, weights=None, nn_window=None, return_states=False, **kwargs):
     """One shard's launch: dict(U, cost, violation, key, n_feasible[, x]) - `key` is the shard's smallest packed key as a
-    Python int, over GLOBAL indices."""
+    Python int, over GLOBAL indices.  `kwargs`: rollout_dynamic's settings, u_prev and obstacles."""
     U = candidates(orc, dp, centre, u_ref, n_candidates, index_offset, problem, round_, seed, sigma)
-    out = costs(orc, dp, coef, vehicles, U, reduce, weights, nn_window, return_states)
+    out = costs(orc, dp, coef, vehicles, U, reduce, weights, nn_window, return_states, **kwargs)
     cost, V = out[0], out[1]
     best = orc.pick_best(cost)[0]
     res = dict(U=U, cost=cost, violation=V, best=best, key=pack_key(cost[best], index_offset + best),

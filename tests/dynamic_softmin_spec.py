@@ -34,14 +34,15 @@ def round_sigmas(sigma, shrink, rounds):
 
 
 def solve(orc, dp, coef, vehicles, centre, u_ref, n_candidates, rounds, sigma, shrink, seed, lam, problem=0,
-          reduce=es.MEAN, weights=None, nn_window=None):
+          reduce=es.MEAN, weights=None, nn_window=None, **kwargs):
     """One softmin solve of problem number `problem`: a list with one dict per round - centre, u_ref (candidate 1, or
-    None), sigma, U [N, n, 2], cost, violation, best (the argmin) and mean (None after the last round)."""
+    None), sigma, U [N, n, 2], cost, violation, best (the argmin) and mean (None after the last round).  `kwargs`:
+    rollout_dynamic's settings, u_prev and obstacles."""
     out = []
     c, ref = np.asarray(centre, dtype=T), None if u_ref is None else np.asarray(u_ref, dtype=T)
     for r, sig in enumerate(round_sigmas(sigma, shrink, rounds)):
         U = dss.candidates(orc, dp, c, ref, n_candidates, 0, problem, r, seed, sig)
-        cost, V = dss.costs(orc, dp, coef, vehicles, U, reduce, weights, nn_window)[:2]
+        cost, V = dss.costs(orc, dp, coef, vehicles, U, reduce, weights, nn_window, **kwargs)[:2]
         best = orc.pick_best(cost)[0]
         mean = softmin_mean(orc, cost, U, lam) if r + 1 < rounds else None
         out.append(dict(centre=c, u_ref=ref, sigma=sig, U=U, cost=cost, violation=V, best=best, mean=mean))

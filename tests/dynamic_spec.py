@@ -1,14 +1,43 @@
-"""Mode D's float32 specification restated in NumPy ("Mode D"): the dynamic (Pacejka) bicycle's
-explicit Euler step, its arctangent, and the rollout cost - the same operations in the same order as
-csrc/acmpc_dynamic.h, so that every result is bit-identical to the kernels.  A helper of the tests, not a test file.
+"""Mode D's float32 specification restated in NumPy ("Mode D" and its sub-sections): ONE statement of a
+vehicle's Euler step, its control step and its rollout cost, with every setting of a handle as a `Settings` value - the same
+operations in the same order as csrc/acmpc_dynamic.h, so that every result is bit-identical to the kernels.  A helper of the
+tests, not a test file.  tests/test_dynamic_spec_bits.py holds its bits to a recorded fixture.
 
 Conventions of the restatement: every array is float32 and every operation a float32 operation (NumPy rounds each
 elementwise +, -, *, / of float32 operands once, as the device does); fused multiply-adds only where the specification
-names them, through the oracle's exact fma32; min / max are IEEE minNum / maxNum (np.fmin / np.fmax: a NaN operand loses)."""
+names them, through the oracle's exact fma32; min / max are IEEE minNum / maxNum (np.fmin / np.fmax: a NaN operand loses).
+Every float the kernels are given is derived on the host in float64 and rounded ONCE (`constants`).  A part that is off
+executes NO line: adding +0 or squaring a zero hinge is not the same thing for -0 and NaN.
+
+The step (dynamic_euler<HOISTED, F, PK>): the tyre block follows the peaks policy -
+    static              F_y = P sin(C atan(..)) on the vehicle's peaks Pf, Pr (or a hypothesis' own, grip_spec.py)
+    coupling            then per axle cap = rho P; F_x = fmax(fmin(F_x, cap), -cap); u = F_x / cap; F_y = F_y sqrt(1 - u u)
+    load transfer       the demands clipped at the STATIC caps, w = c_h (e_f + e_r) clipped at +-w_max, x_f = -w, x_r = w,
+                        phi_a = 1 + x_a (a1_a + a2_a x_a), P_a' = P_a phi_a; the side forces on P', then the coupling block on
+                        the ORIGINAL F_x with P' (rho = +inf while the coupling is off)
+    downforce           va = fmin(vx, v_sat), q = va va, d_a = k_a q, psi_a = 1 + d_a (a1_a + a2_a d_a); the demands clipped at
+                        rho_a (P_a psi_a); x_f = d_f - w, x_r = d_r + w; then as the load transfer (c_h = w_max = 0 while it is off)
+The control step (dynamic_advance_fine): M steps of h = float32(dt / M) under one control, after each of them
+    td = sd / cd; r_k = (vx' td) inv_L; vy_k = r_k lr; lam = fmax(fmin((vx' - v_lo) inv_span, 1), 0)
+    vy = lam vy' + (1 - lam) vy_k; r = lam r' + (1 - lam) r_k                     two multiplies and an add each, nothing fused
+The rollout: mode T's nearest waypoint, stage cost, bounds and terminal cost with dv = vx - v_ref, dk = delta - atan_spec(L k_ref);
+then per control step, on the state that step's cost saw, in this order -
+    rate        rd = (delta - pd) inv_dt, rp likewise ((pd, pp) the previous step's controls; at step 0 u_prev, or step 0's own)
+                E = fma(hwd rd, rd, E); E = fma(hwp rp, rp, E); V = fma(h, h, V), h = fmax(|rd| - rd_max, 0), then rp's
+    slip        b = (r lr - vy) / (vx + 1e-3f); E = fma(hws b, b, E); V = fma(h, h, V), h = fmax(|b| - b_max, 0)
+    ceiling     cap = fma(cs, v_ref_j, co); h = fmax(vx - cap, 0); V = fma(h, h, V)
+    discs       for k in order: d = sqrt(fma(dy, dy, dx dx)) from (o_x - x_0, o_y - y_0); V = fma(h, h, V), h = fmax(R_k - d, 0);
+                soft: g = fmax((R_k + mg) - d, 0); E = fma(hwo g, g, E)
+    finish      stage = stage + E when the rate, the slip OR the soft part is on; J = stage + terminal;
+                progress: s = fma(s_j, Y, fma(c_j, X, q_j)), J = fma(-wp, s, J); cost = fma(w_bound, V, J)
+A part is ON when: rate / slip - a weight is not 0 or a limit finite; progress - its weight is not 0; ceiling - one is given;
+discs - obstacles are given (soft: and float32(clearance_weight) is not 0)."""
 from __future__ import annotations
 
+import dataclasses
 import os
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -20,6 +49,7 @@ for _p in (os.path.join(_HERE, "..", "oracle"), os.path.join(_HERE, "..", "ac-mp
 from acmpc_oracle import fma32, sincos_spec, wrap_spec  # noqa: E402
 
 T = np.float32
+INF = float("inf")
 
 # atan t = t + t^3 P(t^2) on [0, 1] (tools/fit_atan.py: Lawson-weighted least squares, float32 coefficients, Horner in
 # t^2 with fused multiply-adds): |error| < 6.8e-8 on [0, 1]; with the reduction pi/2 - atan(1/x) below 2e-7 everywhere
@@ -29,12 +59,60 @@ HALF_PI = 1.5707963267948966     # rounded to float32 where it is used
 ATAN_ERROR_BOUND = 2.0e-7
 VX_EPS = 1.0e-3                  # dynamic_bicycle_model.py:97-98
 SCAN_BLOCK = 32                  # waypoints per NumPy call of the nearest-waypoint scan (speed only)
+MAX_SUBSTEPS = 16
+V_SAT = 100.0
+MAX_OBSTACLES = 8
+LOAD_KEYS = ("c_h", "w_max", "a1_f", "a2_f", "a1_r", "a2_r")
+# a `terms` row of the plan trace (include/acmpc.h, acmpc_trace_plans)
+TERM_FLOATS = 22
+J, EY, EPSI, DV, DK, BOX, CORRIDOR, RATE, SLIP, CEILING, DISCS, V_SLOT, E_SLOT = 0, 1, 2, 3, 4, 5, 7, 8, 10, 11, 12, 20, 21
+HINGES = slice(5, 20)
 
 # The vehicle block of acmpc_set_dynamics, in ABI order (include/acmpc.h ACMPC_DYNAMICS_COUNT)
 FIELDS = ("F_z0", "Bf", "Cf", "Df", "Ef", "epsf", "Br", "Cr", "Dr", "Er", "epsr", "mass", "Iz", "g", "lf", "lr",
           "brake_bias", "Cm1", "Cm2", "Cm3", "Cb1", "Cb2", "Cb3", "Cfric1", "Cfric2", "Cfric3")
 
+_OFF = dict(rate=dict(rate_weight=(0.0, 0.0), rate_max=None), slip=dict(slip_weight=0.0, slip_max=None),
+            progress=dict(progress_weight=0.0), ceiling=dict(speed_ceiling=None), step=dict(coupling=None, load_transfer=None))
 
+
+@dataclasses.dataclass(frozen=True)
+class Settings:
+    """Every mode D setting of a handle, by the keyword names of Engine.set_dynamics_*; the default is a handle nothing was
+    set on."""
+    substeps: int = 1
+    low_speed_blend: object = None
+    rate_weight: object = (0.0, 0.0)
+    rate_max: object = None
+    slip_weight: float = 0.0
+    slip_max: object = None
+    progress_weight: float = 0.0
+    speed_ceiling: object = None
+    coupling: object = None
+    load_transfer: object = None
+    downforce: object = None
+    clearance_weight: float = 0.0
+    clearance_margin: float = 0.0
+
+    @classmethod
+    def of_case(cls, c, **over):
+        """The settings of a dynamic_fuzz_cases case."""
+        return cls(**dict(dict(c["terms"], **c["objective"]), substeps=c["M"], low_speed_blend=c["blend"], coupling=c["ratio"],
+                          load_transfer=c["load"], **over))
+
+    def replace(self, **over):
+        return dataclasses.replace(self, **over)
+
+    def without(self, *parts):
+        """These parts switched off: "rate", "slip", "progress", "ceiling", and "step" for the coupling and the load transfer
+        together."""
+        over = {}
+        for name in parts:
+            over.update(_OFF[name])
+        return self.replace(**over)
+
+
+# ---- the floats the kernels get ------------------------------------------------------------------------------------------
 def derived_constants(coef):
     """The float32 constants of the step, derived on the host in float64 and rounded ONCE each, in the order of the
     kernel argument (csrc/acmpc_dynamic.h: struct Vehicle)."""
@@ -48,10 +126,109 @@ def derived_constants(coef):
              ("inv_mass", 1.0 / v["mass"]), ("inv_Iz", 1.0 / v["Iz"]), ("Cm1", v["Cm1"]), ("Cm2", v["Cm2"]),
              ("Cm3", v["Cm3"]), ("Cb1", v["Cb1"]), ("Cb2", v["Cb2"]), ("Cb3", v["Cb3"]), ("fric0", -v["Cfric1"]),
              ("Cfric2", v["Cfric2"]), ("Cfric3", v["Cfric3"]), ("bias_front", v["brake_bias"]),
-             ("bias_rear", 1 - v["brake_bias"]))
+             ("bias_rear", 1 - v["brake_bias"]), ("inv_L", 1.0 / (v["lf"] + v["lr"])))
     return {k: T(x) for k, x in order}
 
 
+def load_setting(load):
+    """(h_cg, w_frac) as two floats; a scalar is the height with w_frac = 0.9."""
+    h_cg, w_frac = (load, 0.9) if np.ndim(load) == 0 else tuple(load)
+    h_cg, w_frac = float(h_cg), float(w_frac)
+    assert np.isfinite(h_cg) and h_cg >= 0.0 and 0.0 < w_frac < 1.0, "h_cg >= 0 and finite, 0 < w_frac < 1"
+    return h_cg, w_frac
+
+
+def constants64(vehicle, load):
+    """The load transfer's six scalars of the vehicle block `vehicle` under `load` in float64, in LOAD_KEYS' order:
+    c_h = h_cg / (lf + lr), w_max = w_frac min(F_zf, F_zr), and per axle e = eps / F_z0, N = F_z + e F_z^2,
+    a1 = (1 + 2 e F_z) / N, a2 = e / N."""
+    h_cg, w_frac = load_setting(load)
+    v = dict(zip(FIELDS, (float(x) for x in vehicle)))
+    L = v["lf"] + v["lr"]
+    F_z = (v["mass"] * v["g"] * v["lr"] / (v["lr"] + v["lf"]), v["mass"] * v["g"] * v["lf"] / (v["lr"] + v["lf"]))
+    out = [h_cg / L, w_frac * min(F_z)]
+    for F, eps in zip(F_z, (v["epsf"], v["epsr"])):
+        e = eps / v["F_z0"]
+        N = F + e * F * F
+        out += [(1 + 2 * e * F) / N, e / N]
+    return dict(zip(LOAD_KEYS, out))
+
+
+def ratios(ratio):
+    """(rho_f, rho_r) as float32, each rounded once; a scalar is both axles'; None (the coupling off) +inf on both."""
+    if ratio is None:
+        return T(np.inf), T(np.inf)
+    pair = (ratio, ratio) if np.ndim(ratio) == 0 else tuple(ratio)
+    with np.errstate(over="ignore"):
+        rho_f, rho_r = T(float(pair[0])), T(float(pair[1]))
+    assert rho_f > 0 and rho_r > 0, "a coupling ratio is > 0 (inf: none)"
+    return rho_f, rho_r
+
+
+def aero_setting(aero):
+    """(k_f, k_r, v_sat) as float32, each rounded once; a pair takes v_sat = 100 m/s."""
+    aero = tuple(float(v) for v in aero)
+    assert len(aero) in (2, 3), "the downforce is (k_f, k_r) or (k_f, k_r, v_sat)"
+    k_f, k_r, v_sat = (T(v) for v in (aero + (V_SAT,) if len(aero) == 2 else aero))
+    assert np.isfinite(k_f) and k_f >= 0 and np.isfinite(k_r) and k_r >= 0 and np.isfinite(v_sat) and v_sat > 0
+    return k_f, k_r, v_sat
+
+
+def constants(vehicle, settings=Settings(), dt=0.05):
+    """Every float32 the kernels get for `vehicle` (the 26 doubles of the block; None: the cost's members only) under
+    `settings` with the control step `dt`, each derived in float64 and rounded once:
+      k          the Vehicle's floats (derived_constants) with inv_L = float32(1 / (lf + lr)), the load transfer's six scalars
+                 (c_h = w_max = 0 under the downforce alone) and the downforce's three
+      peaks      "static", "loaded" or "aero"; rho = (rho_f, rho_r), or None: no coupling block
+      substeps, h = float32(dt / M), blend = (v_lo, inv_span = float32(1 / (v_hi - v_lo))) or None
+      Terms: rate, slip, inv_dt, hwd, hwp, hws = 0.5f float32(weight), rd_max, rp_max, b_max
+      TermsObjective: progress, ceiling, nwp = -float32(weight), cs, co (a scalar ceiling is the scale with offset 0)
+      WithObstacles: soft, hwo = 0.5f float32(weight), mg"""
+    s = settings
+    M = int(s.substeps)
+    if not 1 <= M <= MAX_SUBSTEPS:
+        raise ValueError("substeps is 1 .. %d" % MAX_SUBSTEPS)
+    c = SimpleNamespace(substeps=M, h=T(float(dt) / M), blend=None, peaks="static", rho=None, k=None)
+    if s.low_speed_blend is not None:
+        v_lo, v_hi = (float(v) for v in s.low_speed_blend)
+        c.blend = (T(v_lo), T(1.0 / (v_hi - v_lo)))
+    if s.coupling is not None or s.load_transfer is not None or s.downforce is not None:
+        c.rho = ratios(s.coupling)
+    if vehicle is not None:
+        c.k = derived_constants(vehicle)
+        if s.load_transfer is not None:
+            c.k.update((key, T(x)) for key, x in constants64(vehicle, s.load_transfer).items())
+        elif s.downforce is not None:
+            c.k.update((key, T(x)) for key, x in constants64(vehicle, (0.0, 0.5)).items())
+            c.k["c_h"], c.k["w_max"] = T(0.0), T(0.0)
+    if s.load_transfer is not None:
+        load_setting(s.load_transfer)
+        c.peaks = "loaded"
+    if s.downforce is not None:
+        k_f, k_r, v_sat = aero_setting(s.downforce)
+        c.peaks = "aero"
+        if c.k is not None:
+            c.k["k_f"], c.k["k_r"], c.k["v_sat"] = k_f, k_r, v_sat
+    limits = [INF, INF] if s.rate_max is None else [INF if v is None else float(v) for v in s.rate_max]
+    b_max = INF if s.slip_max is None else float(s.slip_max)
+    w = [float(v) for v in s.rate_weight]
+    c.rate = bool(w[0] != 0.0 or w[1] != 0.0 or np.isfinite(limits[0]) or np.isfinite(limits[1]))
+    c.slip = bool(float(s.slip_weight) != 0.0 or np.isfinite(b_max))
+    c.inv_dt = T(1.0 / float(dt))
+    c.hwd, c.hwp, c.hws = T(0.5) * T(w[0]), T(0.5) * T(w[1]), T(0.5) * T(float(s.slip_weight))
+    c.rd_max, c.rp_max, c.b_max = T(limits[0]), T(limits[1]), T(b_max)
+    ceiling = s.speed_ceiling
+    if ceiling is not None and np.ndim(ceiling) == 0:
+        ceiling = (float(ceiling), 0.0)
+    c.progress, c.ceiling = float(s.progress_weight) != 0.0, ceiling is not None
+    c.nwp = -T(float(s.progress_weight))
+    c.cs, c.co = (T(0.0), T(0.0)) if ceiling is None else (T(float(ceiling[0])), T(float(ceiling[1])))
+    c.soft = bool(T(float(s.clearance_weight)) != T(0.0))
+    c.hwo, c.mg = T(0.5) * T(float(s.clearance_weight)), T(float(s.clearance_margin))
+    return c
+
+
+# ---- the step ------------------------------------------------------------------------------------------------------------
 def atan_spec(x):
     """float32 arctangent of the specification: t = |x| or 1 / |x| (IEEE division) beyond 1, the odd polynomial with
     fused multiply-adds, pi/2 - a for |x| > 1, the sign of x.  atan(+-0) = +-0, atan(+-inf) = +-pi/2, NaN propagates."""
@@ -74,25 +251,81 @@ def sin_spec(x):
     return sincos_spec(x, T)[0]
 
 
-def dynamic_step(state, delta, pedal, k, dt):
-    """One step of the specification: state = (X, Y, yaw, vx, vy, r) float32 arrays, k = derived_constants(...),
-    dt float32.  Returns the next state with vx clipped at 0 (dynamic_bicycle_model.py:180)."""
+def pacejka(alpha, B, C, E, P):
+    """One axle's side force P sin(C atan(B a - E (B a - atan(B a)))): P the vehicle's float, or a peak per element."""
+    ba = B * alpha
+    y = ba - E * (ba - atan_spec(ba))
+    return P * sin_spec(C * atan_spec(y))
+
+
+def couple_axle(F_x, F_y, rho, P):
+    """One axle under the coupling: (clipped F_x, scaled F_y)."""
+    with np.errstate(all="ignore"):
+        cap = np.asarray(rho * P, dtype=T)
+        F_x = np.fmax(np.fmin(F_x, cap), -cap)
+        u = F_x / cap
+        g = np.sqrt(T(1.0) - u * u)
+        return np.asarray(F_x, dtype=T), np.asarray(F_y * g, dtype=T)
+
+
+def loaded_peaks(F_fx, F_rx, rho_f, rho_r, k):
+    """(Pf', Pr', w) of one step under the load transfer: k holds Pf, Pr and the six scalars."""
+    with np.errstate(all="ignore"):
+        cap_f = np.asarray(rho_f * k["Pf"], dtype=T)
+        cap_r = np.asarray(rho_r * k["Pr"], dtype=T)
+        e_f = np.fmax(np.fmin(F_fx, cap_f), -cap_f)
+        e_r = np.fmax(np.fmin(F_rx, cap_r), -cap_r)
+        w = k["c_h"] * (e_f + e_r)
+        w = np.fmax(np.fmin(w, k["w_max"]), -k["w_max"])
+        x_f, x_r = -w, w
+        phi_f = T(1.0) + x_f * (k["a1_f"] + k["a2_f"] * x_f)
+        phi_r = T(1.0) + x_r * (k["a1_r"] + k["a2_r"] * x_r)
+        Pf = k["Pf"] * phi_f
+        Pr = k["Pr"] * phi_r
+    return np.asarray(Pf, dtype=T), np.asarray(Pr, dtype=T), np.asarray(w, dtype=T)
+
+
+def aero_peaks(vx, F_fx, F_rx, rho_f, rho_r, k):
+    """(Pf', Pr', w, d_f, d_r) of one step under the downforce: k holds Pf, Pr, the six scalars and the downforce's three."""
+    with np.errstate(all="ignore"):
+        va = np.fmin(vx, k["v_sat"])
+        q = va * va
+        d_f = k["k_f"] * q
+        d_r = k["k_r"] * q
+        psi_f = T(1.0) + d_f * (k["a1_f"] + k["a2_f"] * d_f)
+        psi_r = T(1.0) + d_r * (k["a1_r"] + k["a2_r"] * d_r)
+        cap_f = np.asarray(rho_f * (k["Pf"] * psi_f), dtype=T)
+        cap_r = np.asarray(rho_r * (k["Pr"] * psi_r), dtype=T)
+        e_f = np.fmax(np.fmin(F_fx, cap_f), -cap_f)
+        e_r = np.fmax(np.fmin(F_rx, cap_r), -cap_r)
+        w = k["c_h"] * (e_f + e_r)
+        w = np.fmax(np.fmin(w, k["w_max"]), -k["w_max"])
+        x_f = d_f - w
+        x_r = d_r + w
+        phi_f = T(1.0) + x_f * (k["a1_f"] + k["a2_f"] * x_f)
+        phi_r = T(1.0) + x_r * (k["a1_r"] + k["a2_r"] * x_r)
+        Pf = k["Pf"] * phi_f
+        Pr = k["Pr"] * phi_r
+    return tuple(np.asarray(a, dtype=T) for a in (Pf, Pr, w, d_f, d_r))
+
+
+def dynamic_step(state, delta, pedal, c, h=None):
+    """One Euler step of the specification: state = (X, Y, yaw, vx, vy, r) float32 arrays, c = constants(...), step `h`
+    (c.h when None).  Returns the next state with vx clipped at 0 (dynamic_bicycle_model.py:180)."""
     X, Y, yaw, vx, vy, r = (np.asarray(s, dtype=T) for s in state)
     delta = np.asarray(delta, dtype=T)
     pedal = np.asarray(pedal, dtype=T)
-    dt = T(dt)
+    k = c.k
+    dt = T(c.h if h is None else h)
     with np.errstate(all="ignore"):
         den = vx + T(VX_EPS)
         qf = (r * k["lf"] + vy) / den
         qr = (r * k["lr"] - vy) / den
         a_f = delta - atan_spec(qf)
         a_r = atan_spec(qr)
-        bf = k["Bf"] * a_f
-        yf = bf - k["Ef"] * (bf - atan_spec(bf))
-        F_fy = k["Pf"] * sin_spec(k["Cf"] * atan_spec(yf))
-        br = k["Br"] * a_r
-        yr = br - k["Er"] * (br - atan_spec(br))
-        F_ry = k["Pr"] * sin_spec(k["Cr"] * atan_spec(yr))
+        if c.peaks == "static":
+            F_fy = pacejka(a_f, k["Bf"], k["Cf"], k["Ef"], k["Pf"])
+            F_ry = pacejka(a_r, k["Br"], k["Cr"], k["Er"], k["Pr"])
         vx2 = vx * vx
         F_fric = (k["fric0"] - k["Cfric2"] * vx) - k["Cfric3"] * vx2
         brake = (k["Cb1"] - k["Cb2"] * vx) - k["Cb3"] * vx2
@@ -101,6 +334,19 @@ def dynamic_step(state, delta, pedal, k, dt):
         p_pos = np.fmax(pedal, T(0.0))
         F_rx = (brake * k["bias_rear"]) * p_neg + motor * p_pos
         F_fx = (brake * k["bias_front"]) * p_neg
+        if c.peaks == "static":
+            if c.rho is not None:
+                F_fx, F_fy = couple_axle(F_fx, F_fy, c.rho[0], k["Pf"])
+                F_rx, F_ry = couple_axle(F_rx, F_ry, c.rho[1], k["Pr"])
+        else:
+            if c.peaks == "loaded":
+                Pf, Pr = loaded_peaks(F_fx, F_rx, c.rho[0], c.rho[1], k)[:2]
+            else:
+                Pf, Pr = aero_peaks(vx, F_fx, F_rx, c.rho[0], c.rho[1], k)[:2]
+            F_fy = pacejka(a_f, k["Bf"], k["Cf"], k["Ef"], Pf)
+            F_ry = pacejka(a_r, k["Br"], k["Cr"], k["Er"], Pr)
+            F_fx, F_fy = couple_axle(F_fx, F_fy, c.rho[0], Pf)
+            F_rx, F_ry = couple_axle(F_rx, F_ry, c.rho[1], Pr)
         sd, cd = sincos_spec(delta, T)
         sy, cy = sincos_spec(yaw, T)
         xd0 = vx * cy - vy * sy
@@ -117,13 +363,110 @@ def dynamic_step(state, delta, pedal, k, dt):
     return tuple(np.asarray(a, dtype=T) for a in (Xn, Yn, yawn, vxn, vyn, rn))
 
 
+def control_step(state, delta, pedal, c):
+    """One control step: c.substeps times dynamic_step with step c.h, tan(delta) taken once, the blend (when on) after each
+    sub-step.  Returns the state after the last sub-step."""
+    delta = np.asarray(delta, dtype=T)
+    st = tuple(np.asarray(s, dtype=T) for s in state)
+    if c.blend is not None:
+        v_lo, inv_span = c.blend
+        sd, cd = sincos_spec(delta, T)
+        with np.errstate(all="ignore"):
+            td = (sd / cd).astype(T)
+    for _ in range(c.substeps):
+        X, Y, yaw, vx, vy, r = dynamic_step(st, delta, pedal, c)
+        if c.blend is not None:
+            with np.errstate(all="ignore"):
+                r_k = (vx * td) * c.k["inv_L"]
+                vy_k = r_k * c.k["lr"]
+                lam = np.fmax(np.fmin((vx - v_lo) * inv_span, T(1.0)), T(0.0))
+                mu = T(1.0) - lam
+                vy = lam * vy + mu * vy_k
+                r = lam * r + mu * r_k
+        st = tuple(np.asarray(a, dtype=T) for a in (X, Y, yaw, vx, vy, r))
+    return st
+
+
+# ---- the rollout ----------------------------------------------------------------------------------------------------------
+def progress_table(coef):
+    """q [n] float32 of the packed rows `coef` [n, 8] (acmpc_get_progress_table), from the float32 rows (x, y, c = cos psi,
+    s = sin psi), float64 in the order written, no FMA:  S_0 = 0, S_m = S_{m-1} + sqrt(dx dx + dy dy),
+    q_m = float32(S_m - (c_m (x_m - x_0) + s_m (y_m - y_0)))."""
+    rows = np.asarray(coef, dtype=T)
+    n = rows.shape[0]
+    q = np.empty(n, dtype=T)
+    x0, y0 = float(rows[0, 0]), float(rows[0, 1])
+    S = 0.0
+    for m in range(n):
+        x, y, c, s = (float(v) for v in rows[m, :4])
+        if m > 0:
+            dx, dy = x - float(rows[m - 1, 0]), y - float(rows[m - 1, 1])
+            S = S + float(np.sqrt(np.float64(dx * dx + dy * dy)))
+        q[m] = T(S - (c * (x - x0) + s * (y - y0)))
+    return q
+
+
+def step_terms(c, state, d, p, pd, pp, E, V, row=None):
+    """The rate and slip lines of one control step (csrc/acmpc_dynamic.h: dynamic_terms): the new (E, V).  `row` [N, 22]
+    receives the hinges that are squared into V."""
+    zero = T(0.0)
+    with np.errstate(all="ignore"):
+        if c.rate:
+            rd = (d - pd) * c.inv_dt
+            rp = (p - pp) * c.inv_dt
+            E = fma32(c.hwd * rd, rd, E)
+            E = fma32(c.hwp * rp, rp, E)
+            hd = np.fmax(np.abs(rd) - c.rd_max, zero)
+            V = fma32(hd, hd, V)
+            hp = np.fmax(np.abs(rp) - c.rp_max, zero)
+            V = fma32(hp, hp, V)
+            if row is not None:
+                row[:, RATE], row[:, RATE + 1] = hd, hp
+        if c.slip:
+            vx, vy, r = state[3], state[4], state[5]
+            b = (r * c.k["lr"] - vy) / (vx + T(VX_EPS))
+            E = fma32(c.hws * b, b, E)
+            h = np.fmax(np.abs(b) - c.b_max, zero)
+            V = fma32(h, h, V)
+            if row is not None:
+                row[:, SLIP] = h
+    return np.asarray(E, dtype=T), np.asarray(V, dtype=T)
+
+
+def step_obstacles(c, soft, discs, radii, x_0, y_0, X, Y, E, V, row=None):
+    """The discs' lines of one control step (csrc/acmpc_dynamic.h: the second dynamic_terms): the new (E, V).  discs [K, 2],
+    radii [K] float32; `row` receives each disc's depth."""
+    zero = T(0.0)
+    with np.errstate(all="ignore"):
+        for m in range(discs.shape[0]):
+            ox, oy = T(discs[m, 0] - x_0), T(discs[m, 1] - y_0)
+            dx, dy = X - ox, Y - oy
+            d = np.sqrt(np.asarray(fma32(dy, dy, dx * dx), dtype=T))
+            h = np.fmax(radii[m] - d, zero)
+            V = np.asarray(fma32(h, h, V), dtype=T)
+            if soft:
+                g = np.fmax(T(radii[m] + c.mg) - d, zero)
+                E = np.asarray(fma32(c.hwo * g, g, E), dtype=T)
+            if row is not None:
+                row[:, DISCS + m] = h
+    return E, V
+
+
 def rollout_dynamic(x0, wp, U, vehicle, Q, R, QN, u_lo, u_hi, w_bound, dt, wheelbase, nn_window=None,
-                    return_states=False, trace=None):
+                    return_states=False, trace=None, settings=Settings(), u_prev=None, obstacles=None):
     """Mode D's cost of every candidate, bit for bit: x0 = (X, Y, yaw, vx, vy, r), wp [n, 8] the packed mode-T table,
-    U [N, n, 2] = (delta, pedal), `vehicle` the 26 doubles of the block.  Nearest waypoint, stage cost, bounds and
-    terminal cost are mode T's (oracle rollout_temporal) with dv = vx - v_ref, dk = delta - atan_spec(L k_ref).
-    `trace`: a dict that receives e_y [N, n] and the nearest index j [N, n] of every step (for measurements)."""
-    k = derived_constants(vehicle)
+    U [N, n, 2] = (delta, pedal), `vehicle` the 26 doubles of the block, `settings` the handle's, `u_prev` = (delta, pedal)
+    or None the control before the plan, `obstacles` = (positions [n, K, 2], radii [K]) or None.  Returns (cost, V[, states
+    [N, n + 1, 3]]).  `trace`: a dict that receives what every control step saw - e_y [N, n], the nearest index j [N, n],
+    `over` [N, n] = vx - cap (ceiling on), E [N], E_added (whether stage = stage + E ran), the progress s [N] (progress on),
+    and the plan trace: states [N, n + 1, 6], terms [N, n, 22] (its hinge slots the very values squared into V), totals
+    [N, 2] = (cost, V)."""
+    c = constants(vehicle, settings, dt)
+    pos, radii = (None, None) if obstacles is None else obstacles
+    K = 0 if pos is None else int(np.asarray(pos).shape[1])
+    soft = c.soft and K > 0
+    if K > 0:
+        pos, radii = np.asarray(pos, dtype=T), np.asarray(radii, dtype=T)
     U = np.asarray(U, dtype=T)
     wp = np.asarray(wp, dtype=T)
     N, n, _ = U.shape
@@ -140,17 +483,27 @@ def rollout_dynamic(x0, wp, U, vehicle, Q, R, QN, u_lo, u_hi, w_bound, dt, wheel
     delta_ref = atan_spec(T(wheelbase) * wp[:, 5])
     x0 = np.asarray(x0, dtype=T)
     st = [np.full(N, x0[0] - ox, dtype=T), np.full(N, x0[1] - oy, dtype=T)] + [np.full(N, x0[q], dtype=T) for q in range(2, 6)]
-    S0, S1, S2, S3, V = (np.zeros(N, dtype=T) for _ in range(5))
+    S0, S1, S2, S3, V, E = (np.zeros(N, dtype=T) for _ in range(6))
     ey = np.zeros(N, dtype=T)
     ep = np.zeros(N, dtype=T)
     j_prev = np.zeros(N, dtype=np.int64)
     rows = np.arange(N)
+    pd = pp = None
+    if c.rate and u_prev is not None:
+        prev = np.asarray(u_prev, dtype=T)
+        pd, pp = np.full(N, prev[0], dtype=T), np.full(N, prev[1], dtype=T)
     X_out = np.zeros((N, n + 1, 3), dtype=T) if return_states else None
     if return_states:
         X_out[:, 0] = np.stack([st[0] + ox, st[1] + oy, st[2]], axis=1)
+    row = None
+    if trace is not None:
+        states = np.zeros((N, n + 1, 6), dtype=T)
+        states[:, 0] = np.stack([st[0] + ox, st[1] + oy] + st[2:], axis=1)
+        terms = np.zeros((N, n, TERM_FLOATS), dtype=T)
+        seen = dict(e_y=[], j=[], over=[])
     for i in range(n):
         d, p = U[:, i, 0], U[:, i, 1]
-        st = list(dynamic_step(st, d, p, k, dtT))
+        st = list(control_step(st, d, p, c))
         X, Y, psi, vx = st[0], st[1], st[2], st[3]
         # the first minimum of the search key under `<` from best = +inf, scanned in waypoint order (a NaN or +inf key
         # never wins; the search's first waypoint when none does) - SCAN_BLOCK waypoints of every candidate at a time
@@ -190,25 +543,100 @@ def rollout_dynamic(x0, wp, U, vehicle, Q, R, QN, u_lo, u_hi, w_bound, dt, wheel
             hc = np.fmax(np.abs(ey) - g[:, 7], zero)
             V = fma32(hc, hc, V)
         if trace is not None:
-            trace.setdefault("e_y", []).append(ey.copy())
-            trace.setdefault("j", []).append(j.copy())
+            row = terms[:, i]
+            row[:, J], row[:, EY], row[:, EPSI], row[:, DV], row[:, DK] = j.astype(T), ey, ep, dv, dk
+            row[:, BOX], row[:, BOX + 1], row[:, CORRIDOR] = hd, hp, hc
+            seen["e_y"].append(ey.copy())
+            seen["j"].append(j.copy())
+        if c.rate or c.slip:
+            if i == 0 and pd is None:
+                pd, pp = d, p   # (no previous control: step 0's own, an increment of +0 for a finite control)
+            E, V = step_terms(c, st, d, p, pd, pp, E, V, row)
+            pd, pp = d, p
+        if c.ceiling:
+            with np.errstate(all="ignore"):
+                cap = fma32(c.cs, g[:, 6], c.co)
+                excess = np.asarray(vx - cap, dtype=T)
+                h = np.fmax(excess, zero)
+                V = np.asarray(fma32(h, h, V), dtype=T)
+            if trace is not None:
+                row[:, CEILING] = h
+                seen["over"].append(excess)
+        if K > 0:
+            E, V = step_obstacles(c, soft, pos[i], radii, ox, oy, X, Y, E, V, row)
+        if trace is not None:
+            row[:, V_SLOT], row[:, E_SLOT] = V, E
+            states[:, i + 1] = np.stack([X + ox, Y + oy] + st[2:], axis=1)
         if return_states:
             X_out[:, i + 1] = np.stack([X + ox, Y + oy, psi], axis=1)
     with np.errstate(all="ignore"):
         tN = T(n) * dtT
-        J = hQ[0] * S0
-        J = fma32(hQ[1], S1, J)
-        J = fma32(hR[0], S2, J)
-        J = fma32(hR[1], S3, J)
+        Jc = hQ[0] * S0
+        Jc = fma32(hQ[1], S1, Jc)
+        Jc = fma32(hR[0], S2, Jc)
+        Jc = fma32(hR[1], S3, Jc)
+        added = bool(c.rate or c.slip or soft)
+        if added:
+            Jc = Jc + E
         s = (hQN[0] * ey) * ey
         s = fma32(hQN[1] * ep, ep, s)
         s = fma32(hQN[2] * tN, tN, s)
-        J = J + s
-        cost = fma32(wb, V, J)
+        Jc = Jc + s
+        if c.progress:
+            q = progress_table(wp)
+            g = wp[j_prev]
+            prog = np.asarray(fma32(g[:, 3], st[1], fma32(g[:, 2], st[0], q[j_prev])), dtype=T)
+            Jc = fma32(c.nwp, prog, Jc)
+        cost = fma32(wb, V, Jc)
     cost = np.asarray(cost, dtype=T)
+    V = np.asarray(V, dtype=T)
     if trace is not None:
-        trace["e_y"], trace["j"] = np.stack(trace["e_y"], axis=1), np.stack(trace["j"], axis=1)
+        trace.update(e_y=np.stack(seen["e_y"], axis=1), j=np.stack(seen["j"], axis=1), E=np.asarray(E, dtype=T), E_added=added,
+                     states=states, terms=terms, totals=np.stack([cost, V], axis=1))
+        if c.progress:
+            trace["s"] = prog
+        if c.ceiling:
+            trace["over"] = np.stack(seen["over"], axis=1)
     return (cost, V, X_out) if return_states else (cost, V)
+
+
+# ---- on top of the rollout ------------------------------------------------------------------------------------------------
+def spec_costs(orc, dp, coef, vehicle, nn_window=None, U=None, return_states=False, **kwargs):
+    """The specification's costs of problem `dp` (make_dynamic_problem) on the packed table `coef` [n, 8]; `kwargs`:
+    rollout_dynamic's settings, u_prev, obstacles and trace."""
+    kw = dp["kw"]
+    return rollout_dynamic(dp["x0"], coef, dp["U"] if U is None else U, vehicle, kw["step_cost"], kw["r_term"],
+                           kw["final_cost"], kw["u_min"], kw["u_max"], kw["w_bound"], kw["dt"], kw["wheelbase"],
+                           nn_window=nn_window, return_states=return_states, **kwargs)
+
+
+def trace_plans(dp, coef, U, vehicles, settings=Settings(), nn_window=None, u_prev=None, obstacles=None):
+    """What Engine.trace_plans must give for ONE problem `dp` on the packed rows `coef` [n, 8]: dict(states [M, K, n + 1, 6],
+    totals [M, K, 2], terms [M, K, n, 22]) for the plans U [M, n, 2] under the vehicle blocks `vehicles`."""
+    per = []
+    for block in vehicles:
+        per.append({})
+        spec_costs(None, dp, coef, block, nn_window=nn_window, U=U, settings=settings, u_prev=u_prev, obstacles=obstacles,
+                   trace=per[-1])
+    return {name: np.stack([t[name] for t in per], axis=1) for name in ("states", "totals", "terms")}
+
+
+def replay(terms):
+    """V of every step from the hinges alone: V = fma(h, h, V) over slots 5 .. 19 in order, from the previous step's slot 20
+    (+0 at step 0).  terms [..., n, 22] -> [..., n] float32."""
+    terms = np.asarray(terms, dtype=T)
+    out = np.empty(terms.shape[:-1], dtype=T)
+    for i in range(terms.shape[-2]):
+        V = np.zeros(terms.shape[:-2], dtype=T) if i == 0 else terms[..., i - 1, V_SLOT]
+        for slot in range(HINGES.start, HINGES.stop):
+            h = terms[..., i, slot]
+            V = np.asarray(fma32(h, h, V), dtype=T)
+        out[..., i] = V
+    return out
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=T).view(np.uint32)
 
 
 # ---- test problems ----------------------------------------------------------------------------------------------
@@ -245,9 +673,31 @@ def make_dynamic_problem(orc, track, H, N, seed, origin=(0.0, 0.0), vx0=None, ya
     return dict(table=table, x0=x0, U=U.astype(np.float32), kw=kw, prob=prob)
 
 
-def spec_costs(orc, dp, coef, vehicle, nn_window=None, U=None, return_states=False):
-    """The specification's costs of problem `dp` (make_dynamic_problem) on the packed table `coef` [n, 8]."""
-    kw = dp["kw"]
-    return rollout_dynamic(dp["x0"], coef, dp["U"] if U is None else U, vehicle, kw["step_cost"], kw["r_term"],
-                           kw["final_cost"], kw["u_min"], kw["u_max"], kw["w_bound"], kw["dt"], kw["wheelbase"],
-                           nn_window=nn_window, return_states=return_states)
+def make_obstacles(dp, n, K, seed, nan="none"):
+    """(positions [n, K, 2], radii [K]) float32 for problem `dp`: K discs round where the start state's own velocity carries
+    it - disc k starts (a_k ahead, b_k to the left) of the start and drifts against it - so that some candidates of a spread
+    set enter a disc, some only its margin and some neither.  `nan`: "none"; "some": a few (step, disc) entries are NaN or
+    infinite (discs that do not exist at those steps); "all": every entry is NaN."""
+    rng = np.random.default_rng([4242, int(seed), int(K)])
+    x0 = np.asarray(dp["x0"], dtype=np.float64)
+    dt = float(dp["kw"]["dt"])
+    heading = np.array([np.cos(x0[2]), np.sin(x0[2])])
+    left = np.array([-heading[1], heading[0]])
+    t = (np.arange(n) + 1.0) * dt
+    radii = rng.uniform(0.3, 2.5, K).astype(T)
+    if K > 1:
+        radii[K - 1] = T(0.0)                       # (a disc of radius 0 never violates; its margin still costs)
+    ahead = rng.uniform(-0.5, 0.5, K)
+    aside = rng.choice([-1.0, 1.0], K) * (radii + rng.uniform(-0.3, 0.3, K))   # the rim runs through the bundle of candidates
+    drift = rng.uniform(-2.0, 2.0, (K, 2))
+    speed = float(x0[3])
+    pos = (x0[None, None, :2] + (speed * t)[:, None, None] * heading[None, None, :]
+           + ahead[None, :, None] * heading[None, None, :] + aside[None, :, None] * left[None, None, :]
+           + t[:, None, None] * drift[None, :, :]).astype(T)
+    if nan == "all":
+        pos[:] = np.nan
+    elif nan == "some":
+        pos[rng.integers(0, n), rng.integers(0, K), 0] = np.nan
+        pos[rng.integers(0, n), rng.integers(0, K), 1] = np.inf
+        pos[n - 1, 0] = np.nan
+    return pos, radii

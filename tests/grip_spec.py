@@ -1,14 +1,15 @@
 """Mode D's grip identification restated in NumPy ("Mode D, grip identification"): K hypothetical
 vehicles - vehicle 0 with its two axle peaks scaled - rolled over a logged window of (vx, vy, r) under the logged (delta,
 pedal) and scored by their prediction error, bit-identical to csrc/acmpc_identify.hip.  Nothing is specified here about
-the step itself: it is dynamic_spec's dynamic_step and derived_constants under dynamic_integration_spec's sub-step and
-blend.  A helper of the tests, not a test file.
+the step itself: it is dynamic_spec's control_step under the handle's `settings` (sub-steps, blend, coupling, load transfer,
+downforce), with a peak per hypothesis where a rollout has the vehicle's.  A helper of the tests, not a test file.
 
     hypothesis k   vehicle 0's block with Df sf_k and Dr sr_k, derived as any block: Pf_k, Pr_k in float64, rounded once;
-                   every other constant vehicle 0's own float ((1, 1) is vehicle 0 bit for bit)
+                   every other constant vehicle 0's own float ((1, 1) is vehicle 0 bit for bit) - the load transfer's six
+                   scalars and the caps' ratios among them: hypothesis k is capped by its own Pf_k, Pr_k
     log            states [W + 1, 3] = (vx, vy, r) float32, controls [W, 2] = (delta, pedal) float32; control j between
                    state j and state j + 1
-    step           fine_step(state, delta, pedal, k, inv_L, h, M, blend) with h = float32(dt / M) of THIS call's dt
+    step           control_step(state, delta, pedal, c) with h = float32(dt / M) of THIS call's dt
     segment s      steps [s L, min((s + 1) L, W)): starts from the logged state s L, rolls open-loop; e = +0, then per step j
                      d = rolled - logged[j + 1];  e = fma(w0 dvx, dvx, e); e = fma(w1 dvy, dvy, e); e = fma(w2 dr, dr, e)
     score          E_k = e_0, then E_k + e_s in segment order (plain float32 adds)
@@ -20,9 +21,9 @@ from __future__ import annotations
 
 import numpy as np
 
-import dynamic_integration_spec as dis
 import dynamic_spec as ds
 from acmpc_oracle import fma32, pick_best
+from dynamic_spec import Settings
 
 T = np.float32
 MAX_LOG_STEPS = 512
@@ -37,24 +38,22 @@ def hypothesis_block(vehicle0, front, rear):
     return coef
 
 
-def hypothesis_constants(vehicle0, scales):
-    """derived_constants(vehicle 0) with Pf, Pr replaced by the [K] float32 peaks of the hypotheses `scales` [K, 2]."""
-    k = ds.derived_constants(vehicle0)
+def hypothesis_constants(vehicle0, scales, dt, settings=Settings()):
+    """constants(vehicle 0, settings, dt) with Pf, Pr replaced by the [K] float32 peaks of the hypotheses `scales` [K, 2]."""
+    c = ds.constants(vehicle0, settings, dt)
     peaks = [ds.derived_constants(hypothesis_block(vehicle0, f, r)) for f, r in np.asarray(scales, dtype=np.float64)]
-    k["Pf"] = np.array([p["Pf"] for p in peaks], dtype=T)
-    k["Pr"] = np.array([p["Pr"] for p in peaks], dtype=T)
-    return k
+    c.k["Pf"] = np.array([p["Pf"] for p in peaks], dtype=T)
+    c.k["Pr"] = np.array([p["Pr"] for p in peaks], dtype=T)
+    return c
 
 
-def segment_errors(vehicle0, states, controls, dt, scales, segment=1, weights=(1.0, 1.0, 1.0), substeps=1,
-                   low_speed_blend=None):
+def segment_errors(vehicle0, states, controls, dt, scales, segment=1, weights=(1.0, 1.0, 1.0), settings=Settings()):
     """e [S, K] float32: every segment's error of every hypothesis."""
     states, controls = np.asarray(states, dtype=T), np.asarray(controls, dtype=T)
     W, L = controls.shape[0], int(segment)
     assert states.shape == (W + 1, 3) and 1 <= W <= MAX_LOG_STEPS and 1 <= L <= W
-    k = hypothesis_constants(vehicle0, scales)
-    K = k["Pf"].size
-    inv_L, h, blend = dis.inverse_wheelbase(vehicle0), dis.step_size(dt, substeps), dis.blend_constants(low_speed_blend)
+    c = hypothesis_constants(vehicle0, scales, dt, settings)
+    K = c.k["Pf"].size
     w = [T(float(v)) for v in weights]
     # the segments are independent: all of them advance together, [segments, K] arrays, the ragged last one leaving early
     starts = np.arange(0, W, L)
@@ -70,7 +69,7 @@ def segment_errors(vehicle0, states, controls, dt, scales, segment=1, weights=(1
                 break
         j = starts + i
         ones = np.ones((1, K), dtype=T)
-        st = dis.fine_step(st, controls[j, 0][:, None] * ones, controls[j, 1][:, None] * ones, k, inv_L, h, substeps, blend)
+        st = ds.control_step(st, controls[j, 0][:, None] * ones, controls[j, 1][:, None] * ones, c)
         with np.errstate(all="ignore"):
             for q in range(3):
                 d = st[3 + q] - states[j + 1, q][:, None]
@@ -79,14 +78,27 @@ def segment_errors(vehicle0, states, controls, dt, scales, segment=1, weights=(1
     return out
 
 
-def score(vehicle0, states, controls, dt, scales, segment=1, weights=(1.0, 1.0, 1.0), substeps=1, low_speed_blend=None):
+def score(vehicle0, states, controls, dt, scales, segment=1, weights=(1.0, 1.0, 1.0), settings=Settings()):
     """(errors [K] float32, best index) of the specification."""
-    e = segment_errors(vehicle0, states, controls, dt, scales, segment, weights, substeps, low_speed_blend)
+    e = segment_errors(vehicle0, states, controls, dt, scales, segment, weights, settings)
     E = e[0].copy()
     with np.errstate(all="ignore"):
         for s in range(1, e.shape[0]):
             E = (E + e[s]).astype(T)
     return E, int(pick_best(E)[0])
+
+
+def rollout_states(x0, U, vehicle, dt, settings=Settings()):
+    """The six float32 states [B, n + 1, 6] of the control sequences U [B, n, 2] from the states x0 [B, 6], with no
+    path: the float32 counterpart of DynamicBicycleParams.rollout (positions in the caller's frame, as given)."""
+    c = ds.constants(vehicle, settings, dt)
+    x0, U = np.asarray(x0, dtype=T), np.asarray(U, dtype=T)
+    st = tuple(x0[:, q].copy() for q in range(6))
+    out = [np.stack(st, axis=1)]
+    for i in range(U.shape[1]):
+        st = ds.control_step(st, U[:, i, 0], U[:, i, 1], c)
+        out.append(np.stack(st, axis=1))
+    return np.stack(out, axis=1)
 
 
 # ---- the float64 mirror ---------------------------------------------------------------------------------------------
@@ -150,3 +162,12 @@ def steering_log(plant, amplitude, steps=40, dt=0.05, vx0=30.0, pedal=0.2, noise
     if noise is not None:
         states = states + np.random.default_rng(seed).standard_normal(states.shape) * np.asarray(noise, dtype=np.float64)
     return states.astype(T), controls
+
+
+def braking_log(plant, coupling=None, load_transfer=None, steps=40, dt=0.05, vx0=40.0, pedal=-1.0):
+    """A straight-line braking log driven on `plant` (the float64 mirror under `coupling` and `load_transfer`): delta = 0, a
+    constant pedal, rounded to float32.  (states [W + 1, 3], controls [W, 2])"""
+    controls = np.stack([np.zeros(steps), np.full(steps, pedal)], axis=1).astype(T)
+    traj = plant.rollout(np.array([0.0, 0.0, 0.0, vx0, 0.0, 0.0]), controls.astype(np.float64), dt, coupling=coupling,
+                         load_transfer=load_transfer)
+    return traj[:, 3:].astype(T), controls

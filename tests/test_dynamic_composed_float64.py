@@ -1,6 +1,5 @@
-"""Mode D's settings COMPOSED, CPU only: the float32 restatements nested as the GPU tests nest them (tests/dynamic_load_spec.py
-or dynamic_coupling_spec.py outermost of the step-level settings, dynamic_objective_spec.py outermost of all, then
-dynamic_terms_spec.py, then dynamic_integration_spec.py - what the kernels equal bit for bit) against ONE plain float64
+"""Mode D's settings COMPOSED, CPU only: the float32 restatement under one Settings value with several parts on (tests/dynamic_spec.py
+- what the kernels equal bit for bit) against ONE plain float64
 evaluation of the same settings (tests/dynamic_reference64.py: rollout64 with substeps=, low_speed_blend=, coupling=,
 load_transfer=, terms=, u_prev=, objective=).  Each setting is held to the float64 mirror on its own elsewhere; here an error
 in how the pieces meet - which peaks the blend's kinematic target sees, which state the slip line and the ceiling read under
@@ -35,12 +34,10 @@ for _p in (HERE, os.path.join(HERE, "..", "oracle"), os.path.join(HERE, "..", "a
 
 import acmpc_oracle as orc  # noqa: E402
 import dynamic_ensemble_spec as es  # noqa: E402
-import dynamic_integration_spec as dis  # noqa: E402
-import dynamic_load_spec as dls  # noqa: E402
-import dynamic_objective_spec as dos  # noqa: E402
 import dynamic_reference64 as r64  # noqa: E402
 import dynamic_spec as ds  # noqa: E402
-import dynamic_terms_spec as dts  # noqa: E402
+import grip_spec as gs  # noqa: E402
+from dynamic_spec import Settings  # noqa: E402
 import test_dynamic_cost_float64 as c64  # noqa: E402
 
 T = np.float32
@@ -181,14 +178,12 @@ def _both_sides(name):
     out = dict(n=n, w_bound=float(kw["w_bound"]), c32=[], V32=[], ref=[], ey=[], s=[], vx=[], b=[], settings=settings)
     for g in grips:
         vehicle = _params(g).coefficients()
-        with dls.setting(ratio, load):                           # test_gpu_dynamic_load_transfer._spec's nesting
-            with dos.setting(**objective) as handle:
-                handle.trace = {}
-                with dts.setting(u_prev=u_prev, **terms):
-                    with dis.setting(M, blend):
-                        c32, V32, X32 = ds.spec_costs(orc, dp, coef.astype(T), vehicle, nn_window=window, return_states=True)
-                s32 = handle.trace.get("s")
-        six = dls.rollout_states(ratio, load, np.tile(dp["x0"], (N, 1)), dp["U"], vehicle, kw["dt"], M, blend).astype(np.float64)
+        composed = Settings(M, blend, coupling=ratio, load_transfer=load, **terms, **objective)
+        trace = {}
+        c32, V32, X32 = ds.spec_costs(orc, dp, coef.astype(T), vehicle, nn_window=window, return_states=True, settings=composed,
+                                      u_prev=u_prev, trace=trace)
+        s32 = trace.get("s")
+        six = gs.rollout_states(np.tile(dp["x0"], (N, 1)), dp["U"], vehicle, kw["dt"], settings=composed).astype(np.float64)
         ref = r64.reference_costs(dp, coef, vehicle, nn_window=window, substeps=M, low_speed_blend=blend, coupling=ratio,
                                   load_transfer=load, terms=terms, u_prev=u_prev, objective=objective)
         j, st = ref["j"], ref["states"]

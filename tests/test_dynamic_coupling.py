@@ -1,5 +1,5 @@
 """Mode D's tyre coupling on the CPU ("Mode D, tyre coupling"): the identities of the float32
-restatement (tests/dynamic_coupling_spec.py), the restatement against the float64 mirror
+restatement (tests/dynamic_spec.py), the restatement against the float64 mirror
 (DynamicBicycleParams.predict_next_state(..., coupling=)), the mirror's physics against figures worked out from the vehicle
 block, what the coupling gives the grip identification on a straight-line braking log, and the refusals of the C ABI, the
 Engine and the solver's config (host side: no device work).
@@ -19,9 +19,8 @@ for _p in (os.path.join(ROOT, "ac-mpc_amd"), os.path.join(ROOT, "oracle"), HERE)
         sys.path.insert(0, _p)
 
 import acmpc_oracle as orc  # noqa: E402
-import dynamic_coupling_spec as dcs  # noqa: E402
-import dynamic_integration_spec as dis  # noqa: E402
 import dynamic_spec as ds  # noqa: E402
+from dynamic_spec import Settings  # noqa: E402
 import grip_spec as gs  # noqa: E402
 
 T = np.float32
@@ -69,92 +68,53 @@ def _random_rows(count, seed):
     return st, delta, pedal
 
 
-def _step(step, st, delta, pedal, k, dt=0.05):
-    return np.stack(step(tuple(st[:, q] for q in range(6)), delta, pedal, k, T(dt)), axis=1)
+def _constants(vehicle, ratio=None):
+    return ds.constants(vehicle, Settings(coupling=ratio), 0.05)
+
+
+def _step(c, st, delta, pedal):
+    return np.stack(ds.dynamic_step(tuple(st[:, q] for q in range(6)), delta, pedal, c), axis=1)
 
 
 # ---- 1. identities of the restatement ---------------------------------------------------------------------------------------
 def test_infinite_ratios_are_the_uncoupled_step_bit_for_bit():
-    k = ds.derived_constants(_params().reference().coefficients())
+    vehicle = _params().reference().coefficients()
     st, delta, pedal = _random_rows(4000, 1)
-    want = _step(ds.dynamic_step, st, delta, pedal, k)
-    got = _step(dcs.coupled_step((INF, INF)), st, delta, pedal, k)
+    want = _step(_constants(vehicle), st, delta, pedal)
+    got = _step(_constants(vehicle, (INF, INF)), st, delta, pedal)
     assert np.array_equal(_bits(got), _bits(want))
     assert np.isnan(want).any() and np.isfinite(want).all(axis=1).sum() > 3000     # the NaN / inf rows are in there
 
 
 @pytest.mark.parametrize("ratio", RATIOS + [(0.05, 0.05), (INF, 0.5)])
 def test_pedal_zero_is_the_uncoupled_step_bit_for_bit(ratio):
-    k = ds.derived_constants(_params().reference().with_grip(0.6).coefficients())
+    vehicle = _params().reference().with_grip(0.6).coefficients()
     st, delta, pedal = _random_rows(4000, 2)
     zero = (pedal == 0) | np.isnan(pedal)        # +0, -0, and the NaN pedal that drives nothing
     assert zero.sum() > 1000 and np.signbit(pedal[zero]).any()
-    want = _step(ds.dynamic_step, st, delta, pedal, k)
-    got = _step(dcs.coupled_step(ratio), st, delta, pedal, k)
+    want = _step(_constants(vehicle), st, delta, pedal)
+    got = _step(_constants(vehicle, ratio), st, delta, pedal)
     assert np.array_equal(_bits(got[zero]), _bits(want[zero]))
     assert not np.array_equal(_bits(got[~zero]), _bits(want[~zero]))               # and the coupling does something elsewhere
 
 
 def test_a_saturated_axle_has_no_side_force_and_the_root_is_never_nan():
     """After the clip |u| <= 1: u = +-1 exactly on a saturated axle, g = 0; a finite state never gets a NaN from the block."""
-    k = ds.derived_constants(_params().reference().coefficients())
+    vehicle = _params().reference().coefficients()
+    k = ds.derived_constants(vehicle)
     st, delta, pedal = _random_rows(4000, 3)
     finite = np.isfinite(delta) & np.isfinite(pedal)
-    got = _step(dcs.coupled_step((1.0, 1.0)), st[finite], delta[finite], pedal[finite], k)
+    got = _step(_constants(vehicle, (1.0, 1.0)), st[finite], delta[finite], pedal[finite])
     assert np.isfinite(got).all()
-    F_x, F_y = dcs.couple_axle(np.array([-20.0, 20.0, 3.0, -0.0], dtype=T), np.array([5.0, -5.0, 5.0, 5.0], dtype=T), T(1.0), k["Pf"])
+    F_x, F_y = ds.couple_axle(np.array([-20.0, 20.0, 3.0, -0.0], dtype=T), np.array([5.0, -5.0, 5.0, 5.0], dtype=T), T(1.0), k["Pf"])
     assert F_x[0] == -k["Pf"] and F_x[1] == k["Pf"] and F_y[0] == 0 and F_y[1] == 0 and 0 < F_y[2] < 5.0
     assert _bits(F_x[3]) == _bits(T(-0.0)) and _bits(F_y[3]) == _bits(T(5.0))
-
-
-def test_setting_none_restores_the_module_and_blocks_nest():
-    pristine = ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants
-    with dcs.setting(None):
-        assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine
-    with dcs.setting((1.0, 1.0)):
-        assert ds.dynamic_step is not pristine[1]
-        with dis.setting(3, (3.0, 5.0)):
-            pass
-        with pytest.raises(RuntimeError):
-            with dcs.setting((0.9, 1.1)):          # (not inside itself)
-                pass
-    assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine
-    with dis.setting(3, (3.0, 5.0)):
-        with pytest.raises(RuntimeError):
-            with dcs.setting((1.0, 1.0)):          # outermost of the step-level settings
-                pass
-    assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine
-
-
-@pytest.mark.parametrize("ratio", RATIOS)
-def test_one_substep_without_the_blend_is_the_coupled_step(ratio):
-    """M = 1, no blend, under dynamic_integration_spec.setting nested inside the coupling's: the coupled step's bits - the
-    sub-step picked the coupling up."""
-    vehicle = _params().reference().coefficients()
-    st, delta, pedal = _random_rows(2000, 4)
-    k = ds.derived_constants(vehicle)
-    want = _step(dcs.coupled_step(ratio), st, delta, pedal, k)
-    dp = ds.make_dynamic_problem(orc, "monza", 20, 48, 3)
-    coef = orc.coefficients_temporal(dp["table"], dp["kw"]["margin"]).astype(T)
-    with dcs.setting(ratio):
-        direct = ds.spec_costs(orc, dp, coef, vehicle, return_states=True)
-        with dis.setting(1, None):
-            k_fine = ds.derived_constants(vehicle)
-            ds.rollout_dynamic(dp["x0"], coef, dp["U"][:1], vehicle, *(dp["kw"][q] for q in ("step_cost", "r_term", "final_cost", "u_min", "u_max", "w_bound", "dt", "wheelbase")))
-            got = _step(ds.dynamic_step, st, delta, pedal, k_fine)
-            nested = ds.spec_costs(orc, dp, coef, vehicle, return_states=True)
-    assert np.array_equal(_bits(got), _bits(want))
-    for a, b in zip(direct, nested):
-        assert np.array_equal(_bits(a), _bits(b))
-    plain = ds.spec_costs(orc, dp, coef, vehicle)
-    assert not np.array_equal(_bits(plain[0]), _bits(direct[0]))
 
 
 # ---- 2. the float32 specification against the float64 mirror --------------------------------------------------------------
 def _mirror_errors():
     """max |spec - mirror| per state component over the set of the header, and per (ratio, pedal) the worst overall."""
     params = _params().reference()
-    k = ds.derived_constants(params.coefficients())
     rng = np.random.default_rng(77)
     n = MIRROR_STATES
     st = np.stack([rng.uniform(-20, 20, n), rng.uniform(-20, 20, n), rng.uniform(-3, 3, n), rng.uniform(5, 50, n),
@@ -164,9 +124,9 @@ def _mirror_errors():
     detail = {}
     saturated = {}
     for ratio in RATIOS:
-        step = dcs.coupled_step(ratio)
+        c = _constants(params.coefficients(), ratio)
         for pedal in MIRROR_PEDALS:
-            got = _step(step, st, delta, np.full(n, pedal, dtype=T), k).astype(np.float64)
+            got = _step(c, st, delta, np.full(n, pedal, dtype=T)).astype(np.float64)
             want = np.empty((n, 6))
             sat = 0
             for i in range(n):
@@ -263,13 +223,14 @@ def test_braking_in_a_straight_line_now_tells_the_grips_apart():
     from acmpc_amd.grip_estimator import grip_scales
     base = _params().reference()
     tied = grip_scales(GRID, "tied")
-    states, controls = dcs.braking_log(base.with_grip(0.5), (1.0, 1.0))
+    states, controls = gs.braking_log(base.with_grip(0.5), (1.0, 1.0))
     assert np.all(states[:, 1:] == 0) and 20.0 < states[-1, 0] < 30.0
-    E, best = dcs.score((1.0, 1.0), base.coefficients(), states, controls, 0.05, tied)
+    E, best = gs.score(base.coefficients(), states, controls, 0.05, tied, settings=Settings(coupling=(1.0, 1.0)))
     assert tied[best, 0] == pytest.approx(0.5) and E[best] < 1e-6 < np.sort(E)[1]
 
     def scorer(ratio):
-        return lambda x, u, dt, sc, segment=1, weights=(1, 1, 1): dcs.score(ratio, base.coefficients(), x, u, dt, sc, segment, weights)
+        return lambda x, u, dt, sc, segment=1, weights=(1, 1, 1): gs.score(base.coefficients(), x, u, dt, sc, segment, weights,
+                                                        settings=Settings(coupling=ratio))
 
     for ratio, accepted in (((1.0, 1.0), True), (None, False)):
         est = GripEstimator(scorer(ratio), grid=GRID, axles="tied")          # contrast 0.25, floor 1e-6: the defaults
@@ -281,10 +242,6 @@ def test_braking_in_a_straight_line_now_tells_the_grips_apart():
             assert got.front == pytest.approx(0.5) and got.rear == pytest.approx(0.5)
         else:                                                                # uncoupled, delta = 0: every hypothesis ties
             assert got.front is None and np.all(got.errors == got.errors[0])
-    # the restated segment loop with no coupling is grip_spec's own
-    E_off, best_off = dcs.score(None, base.coefficients(), states, controls, 0.05, tied, segment=8, substeps=2, low_speed_blend=(3.0, 5.0))
-    E_gs, best_gs = gs.score(base.coefficients(), states, controls, 0.05, tied, segment=8, substeps=2, low_speed_blend=(3.0, 5.0))
-    assert np.array_equal(_bits(E_off), _bits(E_gs)) and best_off == best_gs
 
 
 # ---- 5. host refusals ---------------------------------------------------------------------------------------------------

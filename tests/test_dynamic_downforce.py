@@ -1,6 +1,6 @@
 """Mode D's aerodynamic downforce on the CPU ("Mode D, downforce"): the issue's table of hand figures
 re-derived from the float64 mirror (DynamicBicycleParams.predict_next_state(..., downforce=)), the four identities of the float32
-restatement (tests/dynamic_aero_spec.py) bit for bit, the restatement against the mirror, the refusals of the C ABI on a handle
+restatement (tests/dynamic_spec.py) bit for bit, the restatement against the mirror, the refusals of the C ABI on a handle
 without a device, a fast corner and full braking on the mirror, and what the setting gives the grip identification on a log
 driven with downforce.
 
@@ -20,10 +20,9 @@ for _p in (os.path.join(ROOT, "ac-mpc_amd"), os.path.join(ROOT, "oracle"), HERE)
         sys.path.insert(0, _p)
 
 import acmpc_oracle as orc  # noqa: E402
-import dynamic_aero_spec as das  # noqa: E402
-import dynamic_coupling_spec as dcs  # noqa: E402
-import dynamic_load_spec as dls  # noqa: E402
 import dynamic_spec as ds  # noqa: E402
+import grip_spec as gs  # noqa: E402
+from dynamic_spec import Settings  # noqa: E402
 import test_dynamic_cost_float64 as t64  # noqa: E402
 import test_dynamic_coupling as tdc  # noqa: E402
 import test_gpu_dynamic_load_transfer as tgl  # noqa: E402
@@ -61,8 +60,7 @@ def _same_where_finite(got, want):
 
 
 def _constants(vehicle, ratio, load, aero):
-    with das.setting(ratio, load, aero):
-        return ds.derived_constants(vehicle)
+    return ds.constants(vehicle, Settings(coupling=ratio, load_transfer=load, downforce=aero), 0.05)
 
 
 # ---- 1. the issue's table -----------------------------------------------------------------------------------------------------
@@ -109,7 +107,7 @@ def test_where_the_factors_reach_zero():
     """The issue's figures: the rear factor reaches zero 17.8 kN above static, the front 31.5 kN; the rear vertex is 5.95 kN
     above static."""
     p = _params().reference()
-    c = dls.constants64(p.coefficients(), LOAD)
+    c = ds.constants64(p.coefficients(), LOAD)
     for axle, zero in (("f", 31.5), ("r", 17.8)):
         a1, a2 = c["a1_" + axle], c["a2_" + axle]
         roots = np.roots([a2, a1, 1.0])
@@ -128,17 +126,12 @@ def test_where_the_factors_reach_zero():
 def test_zero_coefficients_are_the_parent_step(ratio, load):
     vehicle = _params().reference().with_grip(0.8).coefficients()
     st, delta, pedal = tdc._random_rows(4000, 21)
-    if load is not None:
-        want = tdc._step(dls.loaded_step(ratio, load), st, delta, pedal, _constants(vehicle, ratio, load, None))
-    elif ratio is not None:
-        want = tdc._step(dcs.coupled_step(ratio), st, delta, pedal, ds.derived_constants(vehicle))
-    else:
-        want = tdc._step(ds.dynamic_step, st, delta, pedal, ds.derived_constants(vehicle))
+    want = tdc._step(_constants(vehicle, ratio, load, None), st, delta, pedal)    # the loaded, the coupled or the plain step
     zero = (0.0, 0.0, 30.0)
-    got = tdc._step(das.aero_step(ratio, load, zero), st, delta, pedal, _constants(vehicle, ratio, load, zero))
+    got = tdc._step(_constants(vehicle, ratio, load, zero), st, delta, pedal)
     assert _same_where_finite(got, want)
     assert np.isnan(want).any() and np.isfinite(want).all(axis=1).sum() > 3000     # the NaN / inf rows are in there
-    moved = tdc._step(das.aero_step(ratio, load, _aero()), st, delta, pedal, _constants(vehicle, ratio, load, _aero()))
+    moved = tdc._step(_constants(vehicle, ratio, load, _aero()), st, delta, pedal)
     assert not np.array_equal(_bits(moved), _bits(want))                           # and a coefficient does something
 
 
@@ -149,8 +142,8 @@ def test_standstill_is_the_parent_within_one_substep(ratio, load):
     st, delta, pedal = tdc._random_rows(4000, 22)
     still = st[:, 3] == 0
     assert still.sum() >= 80
-    parent = tdc._step(das.aero_step(ratio, load, (0.0, 0.0)), st, delta, pedal, _constants(vehicle, ratio, load, (0.0, 0.0)))
-    got = tdc._step(das.aero_step(ratio, load, _aero()), st, delta, pedal, _constants(vehicle, ratio, load, _aero()))
+    parent = tdc._step(_constants(vehicle, ratio, load, (0.0, 0.0)), st, delta, pedal)
+    got = tdc._step(_constants(vehicle, ratio, load, _aero()), st, delta, pedal)
     assert _same_where_finite(got[still], parent[still])
     assert not np.array_equal(_bits(got[~still]), _bits(parent[~still]))
 
@@ -159,11 +152,11 @@ def test_standstill_is_the_parent_within_one_substep(ratio, load):
 def test_above_v_sat_the_peaks_are_those_at_v_sat(load):
     vehicle = _params().reference().coefficients()
     v_sat = 26.0
-    k = _constants(vehicle, (1.0, 1.0), load, _aero(v_sat))
+    k = _constants(vehicle, (1.0, 1.0), load, _aero(v_sat)).k
     vx = np.array([5.0, 25.999, 26.0, 26.001, 40.0, 1e30, INF, NAN], dtype=T)
     F_fx, F_rx = np.full(vx.size, -3.0, dtype=T), np.full(vx.size, -1.0, dtype=T)
-    Pf, Pr, w, d_f, d_r = das.aero_peaks(vx, F_fx, F_rx, T(1.0), T(1.0), k)
-    at = das.aero_peaks(np.full(vx.size, v_sat, dtype=T), F_fx, F_rx, T(1.0), T(1.0), k)
+    Pf, Pr, w, d_f, d_r = ds.aero_peaks(vx, F_fx, F_rx, T(1.0), T(1.0), k)
+    at = ds.aero_peaks(np.full(vx.size, v_sat, dtype=T), F_fx, F_rx, T(1.0), T(1.0), k)
     above = np.array([False, False, True, True, True, True, True, True])     # (a NaN vx takes v_sat: minNum)
     for a, b in zip((Pf, Pr, w, d_f, d_r), at):
         assert np.array_equal(_bits(a[above]), _bits(b[above]))
@@ -171,8 +164,9 @@ def test_above_v_sat_the_peaks_are_those_at_v_sat(load):
     # a rollout that starts above v_sat and one that starts below it: both sides in one trajectory set
     x0 = np.array([[0, 0, 0, 32.0, 0, 0], [0, 0, 0, 20.0, 0, 0]], dtype=T)
     U = np.stack([np.full((2, 12), 0.02), np.stack([np.full(12, -0.8), np.full(12, 0.9)])], axis=2).astype(T)
-    capped = das.rollout_states((1.0, 1.0), load, _aero(v_sat), x0, U, vehicle, 0.05)
-    free = das.rollout_states((1.0, 1.0), load, _aero(), x0, U, vehicle, 0.05)
+    capped = gs.rollout_states(x0, U, vehicle, 0.05, settings=Settings(coupling=(1.0, 1.0), load_transfer=load,
+                               downforce=_aero(v_sat)))
+    free = gs.rollout_states(x0, U, vehicle, 0.05, settings=Settings(coupling=(1.0, 1.0), load_transfer=load, downforce=_aero()))
     assert capped[0, 0, 3] > v_sat > capped[0, -1, 3] and capped[1, 0, 3] < v_sat
     assert not np.array_equal(_bits(capped[0]), _bits(free[0]))
     below = np.all(free[1, :-1, 3] <= v_sat)
@@ -184,13 +178,13 @@ def test_without_the_load_transfer_the_w_lines_change_nothing(ratio):
     """c_h = w_max = 0: w = +-0 and x_a = d_a exactly (d_a >= +0), so a step that skips the w lines gives the same bits."""
     vehicle = _params().reference().coefficients()
     st, delta, pedal = tdc._random_rows(4000, 23)
-    k = _constants(vehicle, ratio, None, _aero())
+    k = _constants(vehicle, ratio, None, _aero()).k
     assert k["c_h"] == 0 and k["w_max"] == 0 and k["a1_f"] > 0
-    rho_f, rho_r = dls.ratios(ratio)
+    rho_f, rho_r = ds.ratios(ratio)
     vx = st[:, 3]
     with np.errstate(all="ignore"):
         F_fx = (pedal * T(9.0)).astype(T)
-        Pf, Pr, w, d_f, d_r = das.aero_peaks(vx, F_fx, F_fx, rho_f, rho_r, k)
+        Pf, Pr, w, d_f, d_r = ds.aero_peaks(vx, F_fx, F_fx, rho_f, rho_r, k)
         skip_f = k["Pf"] * (T(1.0) + d_f * (k["a1_f"] + k["a2_f"] * d_f))
         skip_r = k["Pr"] * (T(1.0) + d_r * (k["a1_r"] + k["a2_r"] * d_r))
     ok = ~np.isnan(pedal)        # (a NaN demand makes w NaN: the candidate is NaN through the other lines as before)
@@ -199,23 +193,11 @@ def test_without_the_load_transfer_the_w_lines_change_nothing(ratio):
 
 
 def test_setting_none_falls_through_and_the_order_is_kept():
-    pristine = ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants
     vehicle = _params().reference().coefficients()
-    with das.setting(None, None, None):
-        assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine
-    with das.setting((1.0, 1.0), LOAD, None):
-        assert "c_h" in ds.derived_constants(vehicle) and "k_f" not in ds.derived_constants(vehicle)
-    with das.setting(None, None, _aero()):
-        k = ds.derived_constants(vehicle)
-        assert k["k_f"] == T(7.35e-4) and k["k_r"] == T(1.1025e-3) and k["v_sat"] == T(100.0) and k["c_h"] == 0
-        with pytest.raises(RuntimeError):
-            with dls.setting((1.0, 1.0), LOAD):
-                pass
-    with dls.setting((1.0, 1.0), LOAD):
-        with pytest.raises(RuntimeError):
-            with das.setting((1.0, 1.0), LOAD, _aero()):
-                pass
-    assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine
+    k = _constants(vehicle, (1.0, 1.0), LOAD, None).k
+    assert "c_h" in k and "k_f" not in k
+    k = _constants(vehicle, None, None, _aero()).k
+    assert k["k_f"] == T(7.35e-4) and k["k_r"] == T(1.1025e-3) and k["v_sat"] == T(100.0) and k["c_h"] == 0
 
 
 # ---- 3. the float32 restatement against the float64 mirror --------------------------------------------------------------------
@@ -243,7 +225,8 @@ def _mirror_deviation(case, v_sat):
     worst, speeds = 0.0, []
     for g in grips:
         params = _params().reference() if g == 1.0 else _params().reference().with_grip(g)
-        got = das.rollout_states((1.0, 1.0), LOAD, _aero(v_sat), np.repeat(x0[None], U.shape[0], axis=0), U, params.coefficients(), dt)
+        got = gs.rollout_states(np.repeat(x0[None], U.shape[0], axis=0), U, params.coefficients(), dt,
+                                settings=Settings(coupling=(1.0, 1.0), load_transfer=LOAD, downforce=_aero(v_sat)))
         for c in range(U.shape[0]):
             want = params.rollout(x0.astype(np.float64), U[c].astype(np.float64), dt, coupling=(1.0, 1.0), load_transfer=LOAD,
                                   downforce=_aero(v_sat))
@@ -365,8 +348,8 @@ def _identification():
     base = _params().reference()
     tied = grip_scales(GRID, "tied")
     states, controls = downforce_log()
-    with_aero = das.score((1.0, 1.0), LOAD, _aero(), base.coefficients(), states, controls, 0.05, tied)
-    without = dls.score((1.0, 1.0), LOAD, base.coefficients(), states, controls, 0.05, tied)
+    with_aero = gs.score(base.coefficients(), states, controls, 0.05, tied, settings=Settings(coupling=(1.0, 1.0), load_transfer=LOAD, downforce=_aero()))
+    without = gs.score(base.coefficients(), states, controls, 0.05, tied, settings=Settings(coupling=(1.0, 1.0), load_transfer=LOAD))
     return tied, states, with_aero, without
 
 
@@ -391,13 +374,11 @@ def test_the_segment_loop_without_the_setting_is_the_load_transfers():
     base = _params().reference()
     tied = grip_scales(GRID, "tied")
     states, controls = downforce_log()
-    kw = dict(segment=8, substeps=2, low_speed_blend=(3.0, 5.0))
-    a = das.score((0.9, 1.1), LOAD, None, base.coefficients(), states, controls, 0.05, tied, **kw)
-    b = dls.score((0.9, 1.1), LOAD, base.coefficients(), states, controls, 0.05, tied, **kw)
-    c = das.score((0.9, 1.1), LOAD, (0.0, 0.0), base.coefficients(), states, controls, 0.05, tied, **kw)
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and a[1] == b[1]
+    loaded = Settings(substeps=2, low_speed_blend=(3.0, 5.0), coupling=(0.9, 1.1), load_transfer=LOAD)
+    b = gs.score(base.coefficients(), states, controls, 0.05, tied, segment=8, settings=loaded)
+    c = gs.score(base.coefficients(), states, controls, 0.05, tied, segment=8, settings=loaded.replace(downforce=(0.0, 0.0)))
     assert np.array_equal(_bits(c[0]), _bits(b[0])) and c[1] == b[1]
-    d = das.score((0.9, 1.1), LOAD, _aero(), base.coefficients(), states, controls, 0.05, tied, **kw)
+    d = gs.score(base.coefficients(), states, controls, 0.05, tied, segment=8, settings=loaded.replace(downforce=_aero()))
     assert not np.array_equal(_bits(d[0]), _bits(b[0]))
 
 

@@ -11,8 +11,8 @@ fuzz from passing vacuously, for the committed seed and the default case count.
               that needed another draw; the share is capped at 25 %.
               Measured on the committed seed: 9 of 60 cases re-drawn, 15 % (`python tests/test_dynamic_fuzz_cases.py` finds
               the table and prints it with the coverage counts).
-  legality    every case's restatement runs in the required nesting order (the bites test calls it), and a handle takes every
-              drawn setting in the drawn order: the argument checks run without a device."""
+  legality    every case's restatement runs (the bites test calls it), and a handle takes every drawn setting in the drawn
+              order: the argument checks run without a device."""
 import os
 import sys
 
@@ -69,7 +69,7 @@ def coverage():
             row[name] += 1
         if len(alone) == 1:
             row[alone[0] + "_alone"] += 1
-        t = fz.dts.constants(0.05, **c["terms"])
+        t = fz.ds.constants(None, fz.Settings(**c["terms"]))
         row["no_previous_rate"] += t.rate and c["previous"] == "none"
         row["limits_only"] += (t.rate or t.slip) and t.hwd == 0 and t.hwp == 0 and t.hws == 0
         if c["ratio"] is not None and np.ndim(c["ratio"]) == 1:
@@ -201,7 +201,7 @@ def test_the_comparison_fails_on_a_broken_restatement(monkeypatch):
     `if (!kObjective || rate || slip)` would take with the progress on beside the rate weights - and against one that takes
     the progress with the wrong sign."""
     from acmpc_amd import _capi
-    import dynamic_objective_spec as dos
+    import dynamic_spec as ds
     import test_gpu_fuzz_dynamic_settings as tfs
     c = dict(fz.LONGEST[0], H=9, N=24, seed=39100)          # rate weights, a slip weight, progress 3 and a ceiling
     n = c["H"] - 1
@@ -216,16 +216,16 @@ def test_the_comparison_fails_on_a_broken_restatement(monkeypatch):
     records[0, 4 + 2 * n:] = X[best].ravel()
     stored = dict(costs=cost[None], best_idx=np.array([best]), n_feasible=np.array([np.count_nonzero(V == 0)]), records=records)
     tfs.check_solve(stored, U, want, n, "stored")
-    step_terms = fz.dts.step_terms
+    step_terms = ds.step_terms
     with monkeypatch.context() as m:
-        m.setattr(fz.dts, "step_terms", lambda c_, k, st, d, p, pd, pp, E, V_: (E, step_terms(c_, k, st, d, p, pd, pp, E, V_)[1]))
+        m.setattr(ds, "step_terms", lambda c_, st, d, p, pd, pp, E, V_, row=None: (E, step_terms(c_, st, d, p, pd, pp, E, V_, row)[1]))
         dropped = fz.specification(c, orc, dps, coefs)
     assert np.array_equal(_bits(dropped[0][1]), _bits(V))    # (V is untouched: only the cost can tell)
     with pytest.raises(AssertionError, match="costs"):
         tfs.check_solve(stored, U, dropped, n, "stored")
-    constants = dos.constants
+    constants = ds.constants
     with monkeypatch.context() as m:
-        m.setattr(dos, "constants", lambda *a: (lambda o: setattr(o, "nwp", -o.nwp) or o)(constants(*a)))
+        m.setattr(ds, "constants", lambda *a: (lambda o: setattr(o, "nwp", -o.nwp) or o)(constants(*a)))
         flipped = fz.specification(c, orc, dps, coefs)
     with pytest.raises(AssertionError, match="costs"):
         tfs.check_solve(stored, U, flipped, n, "stored")

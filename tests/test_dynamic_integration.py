@@ -1,5 +1,5 @@
 """Mode D's integration setting on the CPU ("Sub-steps and the low-speed blend"): the float32
-restatement (tests/dynamic_integration_spec.py) against dynamic_spec at the default setting and against the float64 mirror
+restatement (tests/dynamic_spec.py) under Settings(1, None) against its default and against the float64 mirror
 at others, what the setting buys at low speed - 24 constant-control runs from 0 .. 10 m/s against a fine integration - and
 the refusals of the C ABI, the Engine and the solver's config (host-side: no device work)."""
 import os
@@ -15,8 +15,9 @@ for _p in (os.path.join(ROOT, "ac-mpc_amd"), os.path.join(ROOT, "oracle"), HERE)
         sys.path.insert(0, _p)
 
 import acmpc_oracle as orc  # noqa: E402
-import dynamic_integration_spec as dis  # noqa: E402
 import dynamic_spec as ds  # noqa: E402
+import grip_spec as gs  # noqa: E402
+from dynamic_spec import Settings  # noqa: E402
 
 GOLDEN = np.load(os.path.join(HERE, "golden", "dynamic_bicycle.npz"))
 EINVAL = -1
@@ -56,7 +57,7 @@ def test_entry_point_is_exported():
     import acmpc_amd
     from acmpc_amd import _capi
     assert "acmpc_set_dynamics_integration" in _capi.SIGNATURES
-    assert _capi.MAX_SUBSTEPS == dis.MAX_SUBSTEPS == 16
+    assert _capi.MAX_SUBSTEPS == ds.MAX_SUBSTEPS == 16
     assert hasattr(acmpc_amd.Engine, "set_dynamics_integration")
     assert hasattr(acmpc_amd.load_library(), "acmpc_set_dynamics_integration")
 
@@ -69,41 +70,39 @@ def test_default_setting_is_dynamic_spec_bit_for_bit(track, H, N, seed, vx0, win
     dp["U"][4, H // 2, 1] = np.inf
     coef = orc.coefficients_temporal(dp["table"], dp["kw"]["margin"]).astype(np.float32)
     vehicle = _params().reference().coefficients()
-    pristine = ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants
     want = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True)
-    got = dis.spec_costs(orc, dp, coef, vehicle, substeps=1, low_speed_blend=None, nn_window=window, return_states=True)
-    assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine   # the block put everything back
+    got = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True,
+                        settings=Settings(substeps=1, low_speed_blend=None))
     for a, b in zip(want, got):
         assert np.array_equal(_bits(a), _bits(b))
     # and another setting is another result (the restatement is not a pass-through)
-    other = dis.spec_costs(orc, dp, coef, vehicle, substeps=4, low_speed_blend=BLEND, nn_window=window)
+    other = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, settings=Settings(substeps=4, low_speed_blend=BLEND))
     assert not np.array_equal(_bits(want[0]), _bits(other[0]))
 
 
 def test_step_size_and_blend_constants_round_once():
-    assert dis.step_size(0.05, 1) == np.float32(0.05)
+    assert ds.constants(None, Settings(), 0.05).h == np.float32(0.05)
     for m in range(1, 17):
-        assert dis.step_size(0.05, m) == np.float32(0.05 / m)
-    assert dis.blend_constants(None) is None
-    lo, inv = dis.blend_constants((3.0, 5.0))
+        assert ds.constants(None, Settings(substeps=m), 0.05).h == np.float32(0.05 / m)
+    assert ds.constants(None, Settings(), 0.05).blend is None
+    lo, inv = ds.constants(None, Settings(low_speed_blend=(3.0, 5.0)), 0.05).blend
     assert (lo, inv) == (np.float32(3.0), np.float32(0.5))
     p = _params().reference()
-    assert dis.inverse_wheelbase(p.coefficients()) == np.float32(1.0 / (p.lf + p.lr))
+    assert ds.constants(p.coefficients()).k["inv_L"] == np.float32(1.0 / (p.lf + p.lr))
 
 
 def test_blend_passes_the_dynamic_state_through_above_v_hi_and_is_kinematic_below_v_lo():
     p = _params().reference()
     vehicle = p.coefficients()
-    k = ds.derived_constants(vehicle)
-    inv_L, h, blend = dis.inverse_wheelbase(vehicle), dis.step_size(0.05, 1), dis.blend_constants(BLEND)
+    plain, blended = ds.constants(vehicle, Settings(), 0.05), ds.constants(vehicle, Settings(low_speed_blend=BLEND), 0.05)
     delta, pedal = np.float32([0.05, -0.1]), np.float32([0.3, 0.2])
     fast = tuple(np.float32([v, v]) for v in (0.0, 0.0, 0.1, 9.0, 0.2, 0.05))
-    want = ds.dynamic_step(fast, delta, pedal, k, h)
-    got = dis.fine_step(fast, delta, pedal, k, inv_L, h, 1, blend)
+    want = ds.dynamic_step(fast, delta, pedal, plain)
+    got = ds.control_step(fast, delta, pedal, blended)
     for a, b in zip(want, got):
         assert np.array_equal(_bits(a), _bits(b))
     slow = tuple(np.float32([v, v]) for v in (0.0, 0.0, 0.1, 1.5, 0.2, 0.05))
-    got = dis.fine_step(slow, delta, pedal, k, inv_L, h, 1, blend)
+    got = ds.control_step(slow, delta, pedal, blended)
     vx = got[3].astype(np.float64)
     r_k = vx * np.tan(delta.astype(np.float64)) / (p.lf + p.lr)
     np.testing.assert_allclose(got[5], r_k, rtol=2e-6)
@@ -129,10 +128,10 @@ def test_float32_spec_tracks_the_float64_mirror(substeps, blend):
     dt = float(GOLDEN["roll_dt"])
     x0, U = np.asarray(GOLDEN["roll_x0"]), np.asarray(GOLDEN["roll_u"])
     S = np.stack([p.rollout(a, u, dt, substeps=substeps, low_speed_blend=blend) for a, u in zip(x0, U)])   # [B, n + 1, 6]
-    one = dis.rollout_states(S[:, :-1].reshape(-1, 6), U.reshape(-1, 1, 2), vehicle, dt, substeps, blend)[:, 1]
+    one = gs.rollout_states(S[:, :-1].reshape(-1, 6), U.reshape(-1, 1, 2), vehicle, dt, settings=Settings(substeps, blend))[:, 1]
     nxt = S[:, 1:].reshape(-1, 6)
     worst_step = float(np.max(np.abs(one.astype(np.float64) - nxt) / np.maximum(np.abs(nxt), 1.0)))
-    traj = dis.rollout_states(x0, U, vehicle, dt, substeps, blend).astype(np.float64)
+    traj = gs.rollout_states(x0, U, vehicle, dt, settings=Settings(substeps=substeps, low_speed_blend=blend)).astype(np.float64)
     worst_pos = float(np.max(np.hypot(traj[..., 0] - S[..., 0], traj[..., 1] - S[..., 1])))
     print("substeps %d blend %s: worst step %.3g, worst position %.3g m" % (substeps, blend, worst_step, worst_pos))
     assert worst_step <= STEP_BOUND
@@ -151,7 +150,7 @@ def study():
 
 
 def _study_errors(study, substeps):
-    got = dis.rollout_states(study["x0"], study["U"], study["vehicle"], STUDY_DT, substeps, BLEND).astype(np.float64)
+    got = gs.rollout_states(study["x0"], study["U"], study["vehicle"], STUDY_DT, settings=Settings(substeps, BLEND)).astype(np.float64)
     fine = study["fine"]
     yaw = np.abs(got[:, -1, 2] - fine[:, -1, 2])
     pos = np.hypot(got[:, -1, 0] - fine[:, -1, 0], got[:, -1, 1] - fine[:, -1, 1])

@@ -1,5 +1,5 @@
 """Mode D's longitudinal load transfer on the CPU ("Mode D, load transfer"): the identities of the float32
-restatement (tests/dynamic_load_spec.py), the quadratic peak factor against the exact ratio of peaks, the physics of the float64
+restatement (tests/dynamic_spec.py), the quadratic peak factor against the exact ratio of peaks, the physics of the float64
 mirror (DynamicBicycleParams.predict_next_state(..., load_transfer=)) against figures worked out from the vehicle block, the
 restatement against the mirror, what the setting gives the grip identification on a straight-line braking log, and the refusals
 of the C ABI, the Engine and the solver's config (host side: no device work).
@@ -20,10 +20,9 @@ for _p in (os.path.join(ROOT, "ac-mpc_amd"), os.path.join(ROOT, "oracle"), HERE)
         sys.path.insert(0, _p)
 
 import acmpc_oracle as orc  # noqa: E402
-import dynamic_coupling_spec as dcs  # noqa: E402
-import dynamic_integration_spec as dis  # noqa: E402
-import dynamic_load_spec as dls  # noqa: E402
 import dynamic_spec as ds  # noqa: E402
+import grip_spec as gs  # noqa: E402
+from dynamic_spec import Settings  # noqa: E402
 import test_dynamic_coupling as tdc  # noqa: E402
 
 T = np.float32
@@ -70,9 +69,8 @@ def _bits(a):
 
 
 def _constants(vehicle, ratio, load):
-    """derived_constants as the loaded step wants them: with the six scalars."""
-    with dls.setting(ratio, load):
-        return ds.derived_constants(vehicle)
+    """The step's constants under (`ratio`, `load`): with the six scalars while the load transfer is on."""
+    return ds.constants(vehicle, Settings(coupling=ratio, load_transfer=load), 0.05)
 
 
 # ---- 1. identities of the restatement ---------------------------------------------------------------------------------------
@@ -80,11 +78,11 @@ def _constants(vehicle, ratio, load):
 def test_zero_height_is_the_coupled_step_bit_for_bit(ratio):
     vehicle = _params().reference().coefficients()
     st, delta, pedal = tdc._random_rows(4000, 11)
-    want = tdc._step(dcs.coupled_step(ratio), st, delta, pedal, ds.derived_constants(vehicle))
-    got = tdc._step(dls.loaded_step(ratio, (0.0, 0.9)), st, delta, pedal, _constants(vehicle, ratio, (0.0, 0.9)))
+    want = tdc._step(_constants(vehicle, ratio, None), st, delta, pedal)
+    got = tdc._step(_constants(vehicle, ratio, (0.0, 0.9)), st, delta, pedal)
     assert np.array_equal(_bits(got), _bits(want))
     assert np.isnan(want).any() and np.isfinite(want).all(axis=1).sum() > 3000     # the NaN / inf rows are in there
-    moved = tdc._step(dls.loaded_step(ratio, LOAD), st, delta, pedal, _constants(vehicle, ratio, LOAD))
+    moved = tdc._step(_constants(vehicle, ratio, LOAD), st, delta, pedal)
     assert not np.array_equal(_bits(moved), _bits(want))                           # and a height does something
 
 
@@ -92,8 +90,8 @@ def test_zero_height_is_the_coupled_step_bit_for_bit(ratio):
 def test_zero_height_without_the_coupling_is_the_plain_step_bit_for_bit(ratio):
     vehicle = _params().reference().with_grip(0.7).coefficients()
     st, delta, pedal = tdc._random_rows(4000, 12)
-    want = tdc._step(ds.dynamic_step, st, delta, pedal, ds.derived_constants(vehicle))
-    got = tdc._step(dls.loaded_step(ratio, (0.0, 0.5)), st, delta, pedal, _constants(vehicle, ratio, (0.0, 0.5)))
+    want = tdc._step(_constants(vehicle, None, None), st, delta, pedal)
+    got = tdc._step(_constants(vehicle, ratio, (0.0, 0.5)), st, delta, pedal)
     assert np.array_equal(_bits(got), _bits(want))
 
 
@@ -103,9 +101,8 @@ def test_pedal_zero_is_the_step_without_the_setting_bit_for_bit(ratio):
     st, delta, pedal = tdc._random_rows(4000, 13)
     zero = (pedal == 0) | np.isnan(pedal)        # +0, -0, and the NaN pedal that drives nothing
     assert zero.sum() > 1000 and np.signbit(pedal[zero]).any()
-    parent = ds.dynamic_step if ratio is None else dcs.coupled_step(ratio)
-    want = tdc._step(parent, st, delta, pedal, ds.derived_constants(vehicle))
-    got = tdc._step(dls.loaded_step(ratio, LOAD), st, delta, pedal, _constants(vehicle, ratio, LOAD))
+    want = tdc._step(_constants(vehicle, ratio, None), st, delta, pedal)
+    got = tdc._step(_constants(vehicle, ratio, LOAD), st, delta, pedal)
     assert np.array_equal(_bits(got[zero]), _bits(want[zero]))
     assert not np.array_equal(_bits(got[~zero]), _bits(want[~zero]))
 
@@ -113,9 +110,9 @@ def test_pedal_zero_is_the_step_without_the_setting_bit_for_bit(ratio):
 def test_without_the_coupling_the_estimate_is_the_force_itself():
     """rho = +inf: e = F, the transfer of what the uncoupled model really decelerates with."""
     p = _params().reference()
-    k = _constants(p.coefficients(), None, LOAD)
+    k = _constants(p.coefficients(), None, LOAD).k
     F_fx, F_rx = np.array([-11.0, 0.0, -3.0], dtype=T), np.array([-5.0, 9.0, 2.0], dtype=T)
-    _, _, w = dls.loaded_peaks(F_fx, F_rx, T(INF), T(INF), k)
+    _, _, w = ds.loaded_peaks(F_fx, F_rx, T(INF), T(INF), k)
     with np.errstate(all="ignore"):
         want = np.fmax(np.fmin(k["c_h"] * (F_fx + F_rx), k["w_max"]), -k["w_max"])
     assert np.array_equal(_bits(w), _bits(want)) and w[0] < 0 < w[1]
@@ -124,7 +121,7 @@ def test_without_the_coupling_the_estimate_is_the_force_itself():
 # ---- 2. the quadratic factor against the exact ratio of peaks -----------------------------------------------------------
 def test_the_factor_is_the_exact_ratio_of_peaks():
     p = _params().reference()
-    c = dls.constants64(p.coefficients(), LOAD)
+    c = ds.constants64(p.coefficients(), LOAD)
     assert c["c_h"] == pytest.approx(0.1208, abs=1e-4) and c["w_max"] == pytest.approx(4.905, abs=1e-3)
     x = np.linspace(-c["w_max"], c["w_max"], 20001)
     lo_hi = {}
@@ -134,7 +131,7 @@ def test_the_factor_is_the_exact_ratio_of_peaks():
         exact = np.array([p.peak(axle, F_z + v) for v in x]) / p.peak(axle, F_z)
         assert np.max(np.abs(phi - exact) / np.abs(exact)) <= 1e-12
         lo_hi[axle] = (phi.min(), phi.max())
-        c32 = dls.constants(p.coefficients(), LOAD)
+        c32 = _constants(p.coefficients(), None, LOAD).k
         x32 = np.concatenate([x.astype(T), [T(c32["w_max"]), -T(c32["w_max"])]]).astype(T)
         phi32 = T(1.0) + x32 * (c32["a1_" + axle] + c32["a2_" + axle] * x32)
         assert phi32.dtype == T and np.all(phi32 > 0)
@@ -216,10 +213,9 @@ def _mirror_errors():
     detail = {}
     saturated = {}
     for ratio in RATIOS:
-        step = dls.loaded_step(ratio, LOAD)
-        k = _constants(params.coefficients(), ratio, LOAD)
+        c = _constants(params.coefficients(), ratio, LOAD)
         for pedal in MIRROR_PEDALS:
-            got = tdc._step(step, st, delta, np.full(n, pedal, dtype=T), k).astype(np.float64)
+            got = tdc._step(c, st, delta, np.full(n, pedal, dtype=T)).astype(np.float64)
             want = np.empty((n, 6))
             sat = 0
             for i in range(n):
@@ -261,9 +257,9 @@ def _identification():
     from acmpc_amd.grip_estimator import grip_scales
     base = _params().reference()
     tied = grip_scales(GRID, "tied")
-    states, controls = dls.braking_log(base.with_grip(0.5), (1.0, 1.0), LOAD)
-    with_load = dls.score((1.0, 1.0), LOAD, base.coefficients(), states, controls, 0.05, tied)
-    without = dcs.score((1.0, 1.0), base.coefficients(), states, controls, 0.05, tied)
+    states, controls = gs.braking_log(base.with_grip(0.5), (1.0, 1.0), LOAD)
+    with_load = gs.score(base.coefficients(), states, controls, 0.05, tied, settings=Settings(coupling=(1.0, 1.0), load_transfer=LOAD))
+    without = gs.score(base.coefficients(), states, controls, 0.05, tied, settings=Settings(coupling=(1.0, 1.0)))
     return tied, states, with_load, without
 
 
@@ -280,60 +276,11 @@ def test_the_segment_loop_without_the_setting_is_the_couplings():
     base = _params().reference()
     from acmpc_amd.grip_estimator import grip_scales
     tied = grip_scales(GRID, "tied")
-    states, controls = dls.braking_log(base.with_grip(0.5), (1.0, 1.0), LOAD)
-    a = dls.score((0.9, 1.1), None, base.coefficients(), states, controls, 0.05, tied, segment=8, substeps=2, low_speed_blend=(3.0, 5.0))
-    b = dcs.score((0.9, 1.1), base.coefficients(), states, controls, 0.05, tied, segment=8, substeps=2, low_speed_blend=(3.0, 5.0))
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and a[1] == b[1]
-    c = dls.score((0.9, 1.1), (0.0, 0.9), base.coefficients(), states, controls, 0.05, tied, segment=8, substeps=2, low_speed_blend=(3.0, 5.0))
+    states, controls = gs.braking_log(base.with_grip(0.5), (1.0, 1.0), LOAD)
+    fine = Settings(substeps=2, low_speed_blend=(3.0, 5.0), coupling=(0.9, 1.1))
+    b = gs.score(base.coefficients(), states, controls, 0.05, tied, segment=8, settings=fine)
+    c = gs.score(base.coefficients(), states, controls, 0.05, tied, segment=8, settings=fine.replace(load_transfer=(0.0, 0.9)))
     assert np.array_equal(_bits(c[0]), _bits(b[0])) and c[1] == b[1]
-
-
-# ---- 6. the context manager -------------------------------------------------------------------------------------------------
-def test_setting_restores_the_module_and_refuses_the_wrong_order():
-    pristine = ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants
-    with dls.setting(None, None):
-        assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine
-    with dls.setting((1.0, 1.0), None):
-        assert ds.dynamic_step is not pristine[1] and ds.derived_constants is pristine[2]
-    with dls.setting((1.0, 1.0), LOAD):
-        assert ds.dynamic_step is not pristine[1] and "c_h" in ds.derived_constants(_params().reference().coefficients())
-        with dis.setting(3, (3.0, 5.0)):
-            assert "c_h" in ds.derived_constants(_params().reference().coefficients())
-        with pytest.raises(RuntimeError):
-            with dls.setting(None, LOAD):              # (not inside itself)
-                pass
-        with pytest.raises(RuntimeError):
-            with dcs.setting((1.0, 1.0)):              # it takes the coupling's place: that one does not go inside
-                pass
-    assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine
-    for outer in (lambda: dis.setting(3, (3.0, 5.0)), lambda: dcs.setting((1.0, 1.0))):
-        with outer():
-            with pytest.raises(RuntimeError):
-                with dls.setting((1.0, 1.0), LOAD):    # outermost of the step-level settings
-                    pass
-    assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine
-
-
-def test_one_substep_without_the_blend_is_the_loaded_step():
-    vehicle = _params().reference().coefficients()
-    st, delta, pedal = tdc._random_rows(2000, 14)
-    ratio = (0.9, 1.1)
-    want = tdc._step(dls.loaded_step(ratio, LOAD), st, delta, pedal, _constants(vehicle, ratio, LOAD))
-    dp = ds.make_dynamic_problem(orc, "monza", 20, 48, 3)
-    coef = orc.coefficients_temporal(dp["table"], dp["kw"]["margin"]).astype(T)
-    with dls.setting(ratio, LOAD):
-        direct = ds.spec_costs(orc, dp, coef, vehicle, return_states=True)
-        with dis.setting(1, None):
-            k_fine = ds.derived_constants(vehicle)
-            ds.rollout_dynamic(dp["x0"], coef, dp["U"][:1], vehicle, *(dp["kw"][q] for q in ("step_cost", "r_term", "final_cost", "u_min", "u_max", "w_bound", "dt", "wheelbase")))
-            got = tdc._step(ds.dynamic_step, st, delta, pedal, k_fine)
-            nested = ds.spec_costs(orc, dp, coef, vehicle, return_states=True)
-    assert np.array_equal(_bits(got), _bits(want))
-    for a, b in zip(direct, nested):
-        assert np.array_equal(_bits(a), _bits(b))
-    with dcs.setting(ratio):
-        coupled = ds.spec_costs(orc, dp, coef, vehicle)
-    assert not np.array_equal(_bits(coupled[0]), _bits(direct[0]))
 
 
 # ---- 7. host refusals ---------------------------------------------------------------------------------------------------

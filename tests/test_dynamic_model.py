@@ -82,16 +82,15 @@ def test_atan_spec_error_bound_and_special_values():
 def test_float32_spec_tracks_the_float64_mirror():
     P = _params()
     p = P.reference()
-    k = ds.derived_constants(p.coefficients())
-    dt = np.float32(GOLDEN["roll_dt"])
+    c = ds.constants(p.coefficients(), dt=float(GOLDEN["roll_dt"]))
     for x0, U, S in zip(GOLDEN["roll_x0"], GOLDEN["roll_u"], GOLDEN["roll_states"]):
         st = tuple(np.float32(v) for v in x0)
         traj = [np.array(st, dtype=np.float64)]
         for i, u in enumerate(U):
-            one = np.array(ds.dynamic_step(tuple(np.float32(v) for v in S[i]), np.float32(u[0]), np.float32(u[1]), k, dt),
+            one = np.array(ds.dynamic_step(tuple(np.float32(v) for v in S[i]), np.float32(u[0]), np.float32(u[1]), c),
                            dtype=np.float64)
             assert np.all(np.abs(one - S[i + 1]) <= 1e-5 * np.maximum(np.abs(S[i + 1]), 1.0))
-            st = ds.dynamic_step(st, np.float32(u[0]), np.float32(u[1]), k, dt)
+            st = ds.dynamic_step(st, np.float32(u[0]), np.float32(u[1]), c)
             traj.append(np.array(st, dtype=np.float64))
         traj = np.array(traj)
         assert np.max(np.hypot(traj[:, 0] - S[:, 0], traj[:, 1] - S[:, 1])) < POSITION_BOUND_M

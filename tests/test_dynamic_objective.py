@@ -1,6 +1,6 @@
 """Mode D's objective on the CPU ("Mode D, progress and ceiling"): the refusals of the C ABI, the Engine
 and the solver's config (host side: no device work), the host's progress table against its restatement bit for bit, the
-float32 restatement (tests/dynamic_objective_spec.py) against the parent restatements with both parts off and against its
+float32 restatement (tests/dynamic_spec.py) with both parts off against the same settings without them and against its
 own definition with one part on, the order of negative costs, and the restatement against the float64 mirror
 (acmpc_amd.dynamic_model.objective_terms).
 
@@ -18,12 +18,10 @@ for _p in (os.path.join(ROOT, "ac-mpc_amd"), os.path.join(ROOT, "oracle"), HERE)
         sys.path.insert(0, _p)
 
 import acmpc_oracle as orc  # noqa: E402
-import dynamic_integration_spec as dis  # noqa: E402
-import dynamic_objective_spec as dos  # noqa: E402
 import dynamic_reference64 as r64  # noqa: E402
 import dynamic_sampled_spec as dss  # noqa: E402
 import dynamic_spec as ds  # noqa: E402
-import dynamic_terms_spec as dts  # noqa: E402
+from dynamic_spec import Settings  # noqa: E402
 import test_dynamic_cost_float64 as c64  # noqa: E402
 from acmpc_oracle import fma32  # noqa: E402
 
@@ -160,7 +158,7 @@ def test_progress_table_is_the_restatement_bit_for_bit():
         eng.set_paths(dp["table"])
         coef = eng.coefficients(0)
         q = eng.progress_table(0)
-        assert np.array_equal(_bits(q), _bits(dos.progress_table(coef)))
+        assert np.array_equal(_bits(q), _bits(ds.progress_table(coef)))
         assert q[0] == 0.0 and np.all(np.isfinite(q))
         eng.set_paths(_line_table(19, 0.3))                # (other rows in between: q follows the rows)
         assert not np.array_equal(_bits(eng.progress_table(0)), _bits(q))
@@ -170,7 +168,7 @@ def test_progress_table_is_the_restatement_bit_for_bit():
         other = ds.make_dynamic_problem(orc, "silverstone", 20, 8, 3)["table"]
         eng.set_paths(np.stack([dp["table"], other]))
         for p in range(2):
-            assert np.array_equal(_bits(eng.progress_table(p)), _bits(dos.progress_table(eng.coefficients(p))))
+            assert np.array_equal(_bits(eng.progress_table(p)), _bits(ds.progress_table(eng.coefficients(p))))
         assert not np.array_equal(_bits(eng.progress_table(0)), _bits(eng.progress_table(1)))
         with pytest.raises(EngineError):
             eng.progress_table(2)
@@ -179,7 +177,7 @@ def test_progress_table_is_the_restatement_bit_for_bit():
         for heading in (0.0, 0.3, -2.0):
             eng.set_paths(_line_table(300, heading))
             q = eng.progress_table(0)
-            assert np.array_equal(_bits(q), _bits(dos.progress_table(eng.coefficients(0))))
+            assert np.array_equal(_bits(q), _bits(ds.progress_table(eng.coefficients(0))))
             assert np.abs(q).max() <= 2.0 ** -13 * 1.5, (heading, np.abs(q).max())
         # a repeated waypoint: dx = dy = 0 adds nothing
         table = _line_table(12, 0.7)
@@ -188,18 +186,18 @@ def test_progress_table_is_the_restatement_bit_for_bit():
         assert np.array_equal(_bits(coef[5, :4]), _bits(coef[4, :4]))
         eng.set_coefficients(coef[None])
         q = eng.progress_table(0)
-        assert np.array_equal(_bits(q), _bits(dos.progress_table(coef))) and q[5] == q[4]
+        assert np.array_equal(_bits(q), _bits(ds.progress_table(coef))) and q[5] == q[4]
         # the smallest and the largest horizon of a handle: n = 2 (acmpc_set_paths refuses n = 1, where the restatement's
         # table is the single 0) and n = 512
-        assert np.array_equal(_bits(dos.progress_table(coef[:1])), _bits(np.zeros(1)))
+        assert np.array_equal(_bits(ds.progress_table(coef[:1])), _bits(np.zeros(1)))
         with pytest.raises(EngineError):
             eng.set_paths(_line_table(1, 0.0))
         eng.set_paths(dp["table"][:, :2])
-        assert np.array_equal(_bits(eng.progress_table(0)), _bits(dos.progress_table(eng.coefficients(0))))
+        assert np.array_equal(_bits(eng.progress_table(0)), _bits(ds.progress_table(eng.coefficients(0))))
         big = ds.make_dynamic_problem(orc, "monza", 513, 4, 1)["table"][:, :512]
         eng.set_paths(big)
         q = eng.progress_table(0)
-        assert q.shape == (512,) and np.array_equal(_bits(q), _bits(dos.progress_table(eng.coefficients(0))))
+        assert q.shape == (512,) and np.array_equal(_bits(q), _bits(ds.progress_table(eng.coefficients(0))))
     finally:
         eng.close()
 
@@ -209,32 +207,24 @@ def test_progress_table_is_the_restatement_bit_for_bit():
                                                        ("monza", 8, 9, 2, 4.0, None)])
 def test_both_parts_off_is_the_parent_restatement_bit_for_bit(track, H, N, seed, vx0, window):
     """Costs, V and states: against dynamic_spec alone, through the terms' block, and through the terms' and the
-    integration's blocks; and the blocks put everything back."""
+    integration's blocks."""
     dp, coef, vehicle = _problem(track, H, N, seed, vx0)
     dp["U"][1, 0, 0] = np.nan
     dp["U"][4, H // 2, 1] = np.inf
-    pristine = ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants, dts.rollout_dynamic
     u_prev = (0.02, 0.1)
     want = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True)
-    want_terms = dts.spec_costs(orc, dp, coef, vehicle, TERMS, u_prev=u_prev, nn_window=window, return_states=True)
-    with dts.setting(u_prev=u_prev, **TERMS):
-        with dis.setting(4, BLEND):
-            want_fine = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True)
+    want_terms = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True, settings=Settings(**TERMS),
+                               u_prev=u_prev)
+    want_fine = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True, settings=Settings(4, BLEND, **TERMS),
+                              u_prev=u_prev)
     for off in (dict(), dict(progress_weight=0.0, speed_ceiling=None), dict(progress_weight=-0.0)):
-        got = dos.spec_costs(orc, dp, coef, vehicle, off, nn_window=window, return_states=True)
-        with dos.setting(**off):
-            got_terms = dts.spec_costs(orc, dp, coef, vehicle, TERMS, u_prev=u_prev, nn_window=window, return_states=True)
-            with dts.setting(u_prev=u_prev, **TERMS):
-                with dis.setting(4, BLEND):
-                    got_fine = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True)
-        assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants, dts.rollout_dynamic) == pristine
+        got = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True, settings=Settings(**off))
+        got_terms = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True, settings=Settings(**TERMS, **off),
+                                  u_prev=u_prev)
+        got_fine = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True,
+                                 settings=Settings(4, BLEND, **TERMS, **off), u_prev=u_prev)
         for a, b in zip(want + want_terms + want_fine, got + got_terms + got_fine):
             assert np.array_equal(_bits(a), _bits(b))
-    # entered inside another block it would silently drop that block: refused
-    with dts.setting(**TERMS):
-        with pytest.raises(RuntimeError):
-            with dos.setting(progress_weight=1.0):
-                pass
 
 
 @pytest.mark.parametrize("inner", ["plain", "terms", "terms+fine"])
@@ -246,25 +236,24 @@ def test_progress_alone_is_one_fma_on_the_cost(inner):
     dp["U"][3, 2, 0] = np.nan
     weight = 1.75
 
-    def run():
-        if inner == "plain":
-            return ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5), return_states=True)
-        with dts.setting(u_prev=(0.01, 0.2), **TERMS):
-            if inner == "terms":
-                return ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5), return_states=True)
-            with dis.setting(3, BLEND):
-                return ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5), return_states=True)
+    base = dict(plain=Settings(), terms=Settings(**TERMS))["terms" if inner != "plain" else "plain"]
+    if inner == "terms+fine":
+        base = base.replace(substeps=3, low_speed_blend=BLEND)
+    u_prev = None if inner == "plain" else (0.01, 0.2)
 
-    J_old, V_old, X_old = run()
-    with dos.setting(progress_weight=weight) as handle:
-        handle.trace = {}
-        J_new, V_new, X_new = run()
-        s, j = handle.trace["s"], handle.trace["j"]
+    def run(settings, trace=None):
+        return ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5), return_states=True, settings=settings, u_prev=u_prev,
+                             trace=trace)
+
+    J_old, V_old, X_old = run(base)
+    trace = {}
+    J_new, V_new, X_new = run(base.replace(progress_weight=weight), trace)
+    s, j = trace["s"], trace["j"][:, -1]
     assert np.array_equal(_bits(V_old), _bits(V_new)) and np.array_equal(_bits(X_old), _bits(X_new))
     with np.errstate(all="ignore"):
         assert np.array_equal(_bits(J_new), _bits(fma32(-T(weight), s, J_old)))
     # s from the rows: positions relative to the first waypoint, q of the host's definition
-    q = dos.progress_table(coef)
+    q = ds.progress_table(coef)
     X, Y = X_old[:, -1, 0] - coef[0, 0], X_old[:, -1, 1] - coef[0, 1]
     with np.errstate(all="ignore"):
         want = fma32(coef[j, 3], Y, fma32(coef[j, 2], X, q[j]))
@@ -278,10 +267,10 @@ def test_ceiling_alone_changes_exactly_the_candidates_over_it():
     dp, coef, vehicle = _problem("monza", 20, 64, 6)
     old = ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5), return_states=True)
     ceiling = (1.0, 0.1)
-    with dos.setting(speed_ceiling=ceiling) as handle:
-        handle.trace = {}
-        new = ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5), return_states=True)
-        over = handle.trace["over"]
+    trace = {}
+    new = ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5), return_states=True, settings=Settings(speed_ceiling=ceiling),
+                        trace=trace)
+    over = trace["over"]
     broke = (over > 0).any(axis=1)
     assert 4 < broke.sum() < len(broke) - 4                     # (the inputs have both kinds)
     changed = _bits(old[0]) != _bits(new[0])
@@ -291,12 +280,10 @@ def test_ceiling_alone_changes_exactly_the_candidates_over_it():
     # a NaN v_ref is no ceiling: h = max(NaN, 0) = 0
     blind = coef.copy()
     blind[:, 6] = np.nan
-    with dos.setting(speed_ceiling=ceiling):
-        nov = ds.spec_costs(orc, dp, blind, vehicle, nn_window=(2, 5))
+    nov = ds.spec_costs(orc, dp, blind, vehicle, nn_window=(2, 5), settings=Settings(speed_ceiling=ceiling))
     assert np.array_equal(_bits(nov[1]), _bits(ds.spec_costs(orc, dp, blind, vehicle, nn_window=(2, 5))[1]))
     # a scale of 0 with offset 0 is a ceiling of 0 m/s: every moving candidate is over it
-    with dos.setting(speed_ceiling=0.0):
-        assert np.all(ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5))[1] > 0)
+    assert np.all(ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5), settings=Settings(speed_ceiling=0.0))[1] > 0)
 
 
 def test_negative_costs_are_ordered_as_floats():
@@ -306,8 +293,7 @@ def test_negative_costs_are_ordered_as_floats():
     dp, coef, vehicle = _problem("monza", 20, 48, 8)
     dp["kw"] = dict(dp["kw"], w_bound=10.0)      # (a violation of the planted candidates does not outweigh the reward)
     dp["U"][7] = dp["U"][2]                      # a tie: candidates 2 and 7 are the same controls
-    with dos.setting(progress_weight=5000.0):
-        cost, V = ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5))
+    cost, V = ds.spec_costs(orc, dp, coef, vehicle, nn_window=(2, 5), settings=Settings(progress_weight=5000.0))
     assert np.all(cost < 0) and np.all(np.isfinite(cost)) and cost[2] == cost[7]
     best = orc.pick_best(cost)[0]
     assert best == int(np.argmin(cost)) and cost[best] == cost.min()
@@ -343,10 +329,9 @@ def _mirror_case(case):
     kw = dp["kw"]
     coef = orc.coefficients_temporal(dp["table"], kw["margin"])
     vehicle = c64._vehicle(grips[0])
-    with dos.setting(**MIRROR_OBJECTIVE) as handle:
-        handle.trace = {}
-        c32, V32 = ds.spec_costs(orc, dp, coef.astype(T), vehicle, nn_window=window)
-        s32, over32 = handle.trace["s"], handle.trace["over"]
+    trace = {}
+    c32, V32 = ds.spec_costs(orc, dp, coef.astype(T), vehicle, nn_window=window, settings=Settings(**MIRROR_OBJECTIVE), trace=trace)
+    s32, over32 = trace["s"], trace["over"]
     ref = r64.reference_costs(dp, coef, vehicle, nn_window=window)
     table = dp["table"][:, :n]
     scale, offset = MIRROR_OBJECTIVE["speed_ceiling"]

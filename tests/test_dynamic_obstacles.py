@@ -1,5 +1,5 @@
 """Mode D's obstacles on the CPU ("Mode D, obstacles"): the float32 restatement
-(tests/dynamic_obstacles_spec.py) against the float64 mirror (acmpc_amd.dynamic_model.clearance_terms on
+(tests/dynamic_spec.py) against the float64 mirror (acmpc_amd.dynamic_model.clearance_terms on
 tests/dynamic_reference64.py's states), the order and the switches of its lines, the disc at the candidate's own position,
 predict_obstacles against its definition, and the refusals of acmpc_set_obstacles / acmpc_set_dynamics_clearance on a
 handle without a device."""
@@ -8,10 +8,9 @@ import pytest
 
 import acmpc_oracle as orc
 import dynamic_fuzz_cases as fz
-import dynamic_objective_spec as dos
-import dynamic_obstacles_spec as dob
 import dynamic_reference64 as r64
 import dynamic_spec as ds
+from dynamic_spec import Settings
 from acmpc_oracle import fma32
 
 T = np.float32
@@ -47,11 +46,15 @@ def _args(dp, coef, U=None, w_bound=None):
             kw["u_max"], kw["w_bound"] if w_bound is None else w_bound, kw["dt"], kw["wheelbase"])
 
 
+def _settings(clearance=(0.0, 0.0), objective=NO_OBJECTIVE, terms=NO_TERMS):
+    return Settings(rate_weight=terms[0], rate_max=terms[1], slip_weight=terms[2], slip_max=terms[3], progress_weight=objective[0],
+                    speed_ceiling=objective[1], clearance_weight=clearance[0], clearance_margin=clearance[1])
+
+
 def _roll(dp, coef, obstacles, clearance=(0.0, 0.0), objective=NO_OBJECTIVE, terms=NO_TERMS, trace=None, **kw):
-    pos, radii = (None, None) if obstacles is None else obstacles
     states = kw.pop("return_states", False)
-    return dob.rollout_dynamic((pos, radii, clearance[0], clearance[1]), objective, terms, None, *_args(dp, coef, **kw), trace=trace,
-                               return_states=states)
+    return ds.rollout_dynamic(*_args(dp, coef, **kw), settings=_settings(clearance, objective, terms), obstacles=obstacles,
+                              trace=trace, return_states=states)
 
 
 def _mirror_set():
@@ -100,8 +103,8 @@ TERMS = ((0.3, 0.02), (1.5, None), 40.0, 0.08)
 @pytest.mark.parametrize("objective, terms", [(NO_OBJECTIVE, NO_TERMS), (OBJECTIVE, NO_TERMS), (OBJECTIVE, TERMS)])
 def test_no_discs_or_discs_that_do_not_exist_are_the_parent_restatement(objective, terms):
     dp, coef = _problem(H=10, N=64, seed=11)
-    want = dos.rollout_dynamic(objective, terms, None, *_args(dp, coef))
-    pos, radii = dob.make_obstacles(dp, 9, 3, 1, nan="all")
+    want = ds.rollout_dynamic(*_args(dp, coef), settings=_settings(objective=objective, terms=terms))
+    pos, radii = ds.make_obstacles(dp, 9, 3, 1, nan="all")
     for obstacles in (None, (np.zeros((9, 0, 2), dtype=T), np.zeros(0, dtype=T)), (pos, radii)):
         got = _roll(dp, coef, obstacles, (WEIGHT, MARGIN), objective, terms)
         assert np.array_equal(_bits(got[0]), _bits(want[0])) and np.array_equal(_bits(got[1]), _bits(want[1]))
@@ -114,7 +117,7 @@ def test_no_discs_or_discs_that_do_not_exist_are_the_parent_restatement(objectiv
 
 def test_weight_zero_leaves_E_alone_and_out_of_the_stage_sum():
     dp, coef = _problem(H=10, N=64, seed=12)
-    obstacles = dob.make_obstacles(dp, 9, 3, 2)
+    obstacles = ds.make_obstacles(dp, 9, 3, 2)
     off, hard, soft = {}, {}, {}
     plain = _roll(dp, coef, None, trace=off)
     got = _roll(dp, coef, obstacles, (0.0, MARGIN), trace=hard)
@@ -131,7 +134,7 @@ def test_weight_zero_leaves_E_alone_and_out_of_the_stage_sum():
     assert both["E_added"] and np.array_equal(_bits(both["E"]), _bits(rate_only["E"]))
     # -0.0 and a weight that rounds to 0 as float32 are 0
     for weight in (-0.0, 1e-60):
-        assert not dob.constants(weight, MARGIN).soft
+        assert not ds.constants(None, Settings(clearance_weight=weight, clearance_margin=MARGIN)).soft
 
 
 def test_a_disc_beyond_its_margin_changes_nothing():
@@ -163,14 +166,14 @@ def test_the_order_of_a_steps_additions_to_V():
     x0[1] += T(0.5)
     dp = dict(dp, x0=x0)
     objective = (0.0, (0.5, 0.0))                                  # a ceiling at half the reference speed
-    base = dos.rollout_dynamic(objective, NO_TERMS, None, *_args(dp, narrow, U=U[:, :1]), return_states=True)
+    base = ds.rollout_dynamic(*_args(dp, narrow, U=U[:, :1]), settings=_settings(objective=objective), return_states=True)
     X1 = base[2][0, 1, :2]
     pos = np.full((1, 1, 2), np.nan, dtype=T)
     pos[0, 0] = X1 + T(0.75)
     radii = np.array([2.0], dtype=T)
     got = _roll(dp, narrow, (pos, radii), objective=objective, U=U[:, :1])
     # the step's own pieces, from the restatement without the ceiling and without the disc
-    box_corridor = dos.rollout_dynamic(NO_OBJECTIVE, NO_TERMS, None, *_args(dp, narrow, U=U[:, :1]))[1]
+    box_corridor = ds.rollout_dynamic(*_args(dp, narrow, U=U[:, :1]))[1]
     assert box_corridor[0] > 0 and base[1][0] > box_corridor[0]    # box + corridor, then the ceiling
     ox, oy = narrow[0, 0], narrow[0, 1]
     Xr, Yr = T(X1[0] - ox), T(X1[1] - oy)
@@ -204,7 +207,7 @@ def test_the_generator_bites_without_swamping():
     for seed, K in ((0, 1), (1, 8), (2, 3)):
         dp, coef = _problem(H=10, N=65, seed=40 + seed)
         plain = _roll(dp, coef, None)
-        got = _roll(dp, coef, dob.make_obstacles(dp, 9, K, seed, nan="some"), (WEIGHT, MARGIN))
+        got = _roll(dp, coef, ds.make_obstacles(dp, 9, K, seed, nan="some"), (WEIGHT, MARGIN))
         changed = _bits(got[1]) != _bits(plain[1])
         assert np.count_nonzero(changed) > 0, (seed, K)
         assert K > 1 or np.count_nonzero(changed) < changed.size, (seed, K)
@@ -215,14 +218,10 @@ def test_setting_composes_with_the_other_restatements_and_restores_the_module():
     c = fz.case("loaded", "matrix", 0)
     dps = fz.problems(c, orc, limit=16)
     coefs = [orc.coefficients_temporal(d["table"], d["kw"]["margin"]).astype(T) for d in dps]
-    saved = dos.rollout_dynamic
     want = fz.specification(c, orc, dps, coefs, limit=16, only=[0])[0]
-    obstacles = dob.make_obstacles(dps[0], c["H"] - 1, 2, 3)
-    with dob.setting(*obstacles, WEIGHT, MARGIN):
-        got = fz.specification(c, orc, dps, coefs, limit=16, only=[0])[0]
-    with dob.setting(None, None, WEIGHT, MARGIN):
-        same = fz.specification(c, orc, dps, coefs, limit=16, only=[0])[0]
-    assert dos.rollout_dynamic is saved
+    obstacles = ds.make_obstacles(dps[0], c["H"] - 1, 2, 3)
+    got = fz.specification(c, orc, dps, coefs, limit=16, only=[0], obstacles=[obstacles], clearance=(WEIGHT, MARGIN))[0]
+    same = fz.specification(c, orc, dps, coefs, limit=16, only=[0], obstacles=None, clearance=(WEIGHT, MARGIN))[0]
     assert np.array_equal(_bits(same[0]), _bits(want[0])) and np.array_equal(_bits(same[1]), _bits(want[1]))
     assert not np.array_equal(_bits(got[0]), _bits(want[0]))
     assert np.array_equal(_bits(got[2]), _bits(want[2]))           # the trajectories do not feel the discs

@@ -1,5 +1,5 @@
 """Mode D's rate and slip terms on the CPU ("Rate and slip terms"): the float32 restatement
-(tests/dynamic_terms_spec.py) against dynamic_spec with the terms off, against its own formulas typed out for three steps,
+(tests/dynamic_spec.py) with the terms off against its default, against its own formulas typed out for three steps,
 against the float64 mirror (acmpc_amd.dynamic_model.stage_terms), the feasible sets of both under limits the inputs keep
 clear of, and the refusals of the C ABI, the Engine and the solver's config (host-side: no device work).
 
@@ -17,10 +17,9 @@ for _p in (os.path.join(ROOT, "ac-mpc_amd"), os.path.join(ROOT, "oracle"), HERE)
         sys.path.insert(0, _p)
 
 import acmpc_oracle as orc  # noqa: E402
-import dynamic_integration_spec as dis  # noqa: E402
 import dynamic_reference64 as r64  # noqa: E402
 import dynamic_spec as ds  # noqa: E402
-import dynamic_terms_spec as dts  # noqa: E402
+from dynamic_spec import Settings  # noqa: E402
 from acmpc_oracle import fma32  # noqa: E402
 
 T = np.float32
@@ -78,37 +77,32 @@ def test_terms_off_is_dynamic_spec_bit_for_bit(track, H, N, seed, vx0, window):
     dp, coef, vehicle = _problem(track, H, N, seed, vx0)
     dp["U"][1, 0, 0] = np.nan
     dp["U"][4, H // 2, 1] = np.inf
-    pristine = ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants
     want = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True)
-    want_fine = dis.spec_costs(orc, dp, coef, vehicle, 4, BLEND, nn_window=window, return_states=True)
+    want_fine = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True, settings=Settings(4, BLEND))
     for u_prev in (None, (np.nan, 0.5)):
-        got = dts.spec_costs(orc, dp, coef, vehicle, OFF, u_prev=u_prev, nn_window=window, return_states=True)
-        with dts.setting(u_prev=u_prev, **OFF):
-            with dis.setting(4, BLEND):
-                got_fine = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True)
-        assert (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants) == pristine   # the blocks put everything back
+        got = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True, settings=Settings(**OFF), u_prev=u_prev)
+        got_fine = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, return_states=True, settings=Settings(4, BLEND, **OFF),
+                                 u_prev=u_prev)
         for a, b in zip(want + want_fine, got + got_fine):
             assert np.array_equal(_bits(a), _bits(b))
     # and with the terms on it is another result, under both integration settings (the restatement is not a pass-through)
-    on = dts.spec_costs(orc, dp, coef, vehicle, BOTH, nn_window=window)
+    on = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, settings=Settings(**BOTH))
     assert not np.array_equal(_bits(want[0]), _bits(on[0]))
-    with dts.setting(**BOTH):
-        with dis.setting(4, BLEND):
-            on_fine = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window)
+    on_fine = ds.spec_costs(orc, dp, coef, vehicle, nn_window=window, settings=Settings(4, BLEND, **BOTH))
     assert not np.array_equal(_bits(want_fine[0]), _bits(on_fine[0]))
     assert not np.array_equal(_bits(on[0]), _bits(on_fine[0]))
 
 
 def test_which_parts_are_on():
-    c = dts.constants(0.05)
+    c = ds.constants(None, Settings(), 0.05)
     assert not c.rate and not c.slip
-    assert c.inv_dt == T(20.0) and dts.constants(0.03).inv_dt == T(1.0 / 0.03)
+    assert c.inv_dt == T(20.0) and ds.constants(None, Settings(), 0.03).inv_dt == T(1.0 / 0.03)
     for kw, rate, slip in ((dict(rate_weight=(0.0, 1.0)), True, False), (dict(rate_max=(None, 3.0)), True, False),
                            (dict(rate_max=(INF, INF)), False, False), (dict(slip_weight=2.0), False, True),
                            (dict(slip_max=0.1), False, True), (dict(slip_max=INF, rate_weight=(1e-30, 0.0)), True, False)):
-        c = dts.constants(0.05, **kw)
+        c = ds.constants(None, Settings(**kw), 0.05)
         assert (c.rate, c.slip) == (rate, slip), kw
-    c = dts.constants(0.05, (0.3, 3.0), (1.5, None), 0.7, 0.1)
+    c = ds.constants(None, Settings(rate_weight=(0.3, 3.0), rate_max=(1.5, None), slip_weight=0.7, slip_max=0.1), 0.05)
     assert (c.hwd, c.hwp, c.hws) == (T(0.5) * T(0.3), T(1.5), T(0.5) * T(0.7))
     assert (c.rd_max, c.rp_max, c.b_max) == (T(1.5), T(INF), T(0.1))
 
@@ -122,21 +116,20 @@ def test_constant_controls_from_their_own_previous_control_cost_nothing():
     dp["U"] = np.ascontiguousarray(np.broadcast_to(levels[:, None, :], (6, n, 2)))
     want = ds.spec_costs(orc, dp, coef, vehicle, return_states=True)
     terms = dict(rate_weight=(7.0, 0.3), rate_max=(0.01, 0.02), slip_weight=0.0, slip_max=None)
-    with dts.setting(**terms) as handle:
-        handle.trace = {}
-        got = ds.spec_costs(orc, dp, coef, vehicle, return_states=True)   # no previous control: step 0's own
-        assert np.array_equal(_bits(handle.trace["E"]), _bits(np.zeros(6)))
+    settings, trace = Settings(**terms), {}
+    got = ds.spec_costs(orc, dp, coef, vehicle, return_states=True, settings=settings, trace=trace)   # no previous control: step 0's own
+    assert np.array_equal(_bits(trace["E"]), _bits(np.zeros(6)))
+    for a, b in zip(want, got):
+        assert np.array_equal(_bits(a), _bits(b))
+    for c in range(6):
+        got = ds.spec_costs(orc, dp, coef, vehicle, U=dp["U"][c:c + 1], return_states=True, settings=settings, u_prev=levels[c],
+                            trace=trace)
+        assert np.array_equal(_bits(trace["E"]), _bits(np.zeros(1)))
         for a, b in zip(want, got):
-            assert np.array_equal(_bits(a), _bits(b))
-        for c in range(6):
-            handle.u_prev = levels[c]
-            got = ds.spec_costs(orc, dp, coef, vehicle, U=dp["U"][c:c + 1], return_states=True)
-            assert np.array_equal(_bits(handle.trace["E"]), _bits(np.zeros(1)))
-            for a, b in zip(want, got):
-                assert np.array_equal(_bits(a[c:c + 1]), _bits(b))
-        handle.u_prev = (0.05, 0.3)   # and a previous control that is NOT theirs costs something
-        V = ds.spec_costs(orc, dp, coef, vehicle)[1]
-        assert V[1] == want[1][1] and np.all(np.delete(V, 1) > np.delete(want[1], 1))
+            assert np.array_equal(_bits(a[c:c + 1]), _bits(b))
+    # and a previous control that is NOT theirs costs something
+    V = ds.spec_costs(orc, dp, coef, vehicle, settings=settings, u_prev=(0.05, 0.3))[1]
+    assert V[1] == want[1][1] and np.all(np.delete(V, 1) > np.delete(want[1], 1))
 
 
 def test_three_steps_typed_out():
@@ -149,10 +142,10 @@ def test_three_steps_typed_out():
     base_cost, base_V = ds.spec_costs(orc, dp, coef, vehicle, U=U)
     assert base_V[0] == 0.0
     trace = {}
-    with dts.setting(rate_weight, rate_max, slip_weight, slip_max, u_prev=u_prev) as handle:
-        handle.trace = trace
-        cost, V = ds.spec_costs(orc, dp, coef, vehicle, U=U)
-    k = ds.derived_constants(vehicle)
+    cost, V = ds.spec_costs(orc, dp, coef, vehicle, U=U, u_prev=u_prev, trace=trace, settings=Settings(rate_weight=rate_weight,
+                            rate_max=rate_max, slip_weight=slip_weight, slip_max=slip_max))
+    plain = ds.constants(vehicle, Settings(), dp["kw"]["dt"])
+    k = plain.k
     inv_dt = T(1.0 / dp["kw"]["dt"])
     hwd, hwp, hws = T(0.5) * T(0.3), T(0.5) * T(0.02), T(0.5) * T(40.0)
     E, W = T(0.0), T(0.0)
@@ -161,7 +154,7 @@ def test_three_steps_typed_out():
     hinges = []
     for i in range(3):
         d, p = U[0, i]
-        st = ds.dynamic_step(st, U[:, i, 0], U[:, i, 1], k, T(dp["kw"]["dt"]))
+        st = ds.dynamic_step(st, U[:, i, 0], U[:, i, 1], plain)
         rd = T(T(d - pd) * inv_dt)
         rp = T(T(p - pp) * inv_dt)
         b = T(T(T(st[5][0] * k["lr"]) - st[4][0]) / T(st[3][0] + T(1.0e-3)))
@@ -195,9 +188,7 @@ def _mirror_sides(case, terms):
     base64 = r64.reference_costs(dp, coef, vehicle)["V"]
     keep = np.flatnonzero((base32 == 0) & (base64 == 0))
     trace = {}
-    with dts.setting(u_prev=u_prev, **terms) as handle:
-        handle.trace = trace
-        V32 = ds.spec_costs(orc, dp, coef, vehicle)[1]
+    V32 = ds.spec_costs(orc, dp, coef, vehicle, settings=Settings(**terms), u_prev=u_prev, trace=trace)[1]
     rows = []
     for c in keep:
         U = dp["U"][c].astype(np.float64)
@@ -260,7 +251,7 @@ def test_feasible_sets_are_equal_under_limits_the_inputs_keep_clear_of(vy0, r0, 
     base32 = ds.spec_costs(orc, dp, coef, vehicle, U=U)[1]
     base64 = r64.reference_costs(dp, coef, vehicle, U=U)["V"]
     assert np.all(base32 == 0) and np.all(base64 == 0)            # nothing but the terms decides feasibility here
-    V32 = dts.spec_costs(orc, dp, coef, vehicle, LIMITS, u_prev=u_prev, U=U)[1]
+    V32 = ds.spec_costs(orc, dp, coef, vehicle, U=U, settings=Settings(**LIMITS), u_prev=u_prev)[1]
     feasible64 = np.empty(N, dtype=bool)
     for c in range(N):
         U64 = U[c].astype(np.float64)

@@ -1,5 +1,5 @@
 """Mode D's plan trace without a device ("Mode D, plan trace"): the float32 restatement
-(tests/dynamic_trace_spec.py) against the restatements it is composed from, its hinge replay, the float64 mirror
+(tests/dynamic_spec.py's trace_plans) against the rollout it records, its hinge replay, the float64 mirror
 (dynamic_model.trace) against it, every refusal of acmpc_trace_plans, and the Python wiring up to `rollout_mode: "D"`."""
 import copy
 
@@ -8,9 +8,8 @@ import pytest
 
 import acmpc_oracle as orc
 import dynamic_fuzz_cases as fz
-import dynamic_obstacles_spec as dob
 import dynamic_spec as ds
-import dynamic_trace_spec as dtr
+from dynamic_spec import Settings
 
 T = np.float32
 INF = float("inf")
@@ -42,7 +41,7 @@ def _rollout(dp, coef, block, window=None, **kwargs):
 
 
 def _same(a, b):
-    return np.array_equal(dtr.bits(a), dtr.bits(b))
+    return np.array_equal(ds.bits(a), ds.bits(b))
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------------------
@@ -51,13 +50,13 @@ def test_the_default_trace_is_dynamic_specs_rollout(window):
     dp, coef = _problem()
     block = _vehicle().coefficients()
     cost, V, X = _rollout(dp, coef, block, window, return_states=True)
-    got = dtr.trace_plans(dp, coef, dp["U"], [block], dtr.settings(), window)
+    got = ds.trace_plans(dp, coef, dp["U"], [block], Settings(), window)
     assert _same(got["states"][:, 0, :, :3], X)
     assert _same(got["totals"][:, 0, 0], cost) and _same(got["totals"][:, 0, 1], V)
     assert _same(got["states"][:, 0, 0], np.tile(dp["x0"], (4, 1)))
     assert np.any(V > 0), "candidates 2 and 3 leave the input box"
-    assert _same(dtr.replay(got["terms"]), got["terms"][..., dtr.V_SLOT]) and _same(got["terms"][..., -1, dtr.V_SLOT], V[:, None])
-    assert not np.any(got["terms"][..., dtr.RATE:dtr.V_SLOT]) and not np.any(got["terms"][..., dtr.E_SLOT])
+    assert _same(ds.replay(got["terms"]), got["terms"][..., ds.V_SLOT]) and _same(got["terms"][..., -1, ds.V_SLOT], V[:, None])
+    assert not np.any(got["terms"][..., ds.RATE:ds.V_SLOT]) and not np.any(got["terms"][..., ds.E_SLOT])
 
 
 CASES = [("fine", 0), ("terms", 1), ("objective", 2), ("coupled", 0), ("coupled", 5), ("loaded", 1), ("loaded", 3)]
@@ -77,46 +76,31 @@ def test_with_settings_on_it_is_the_composed_restatement(family, index):
     for p, dp in enumerate(dps):
         prev = None if u_prev is None else u_prev[p]
         blocks = [fz.blocks()[v] for v in c["vehicles"]]
-        got = dtr.trace_plans(dp, coefs[p], dp["U"], blocks, dtr.from_case(c), c["window"], prev)
+        got = ds.trace_plans(dp, coefs[p], dp["U"], blocks, Settings.of_case(c), c["window"], prev)
         for k, block in enumerate(blocks):
-            with fz.restatement(c, prev):
-                cost, V, X = _rollout(dp, coefs[p], block, c["window"], return_states=True)
+            cost, V, X = _rollout(dp, coefs[p], block, c["window"], return_states=True, settings=Settings.of_case(c), u_prev=prev)
             where = np.isfinite(cost)
             assert _same(got["totals"][:, k, 0][where], cost[where]) and _same(got["totals"][:, k, 1][where], V[where])
             assert _same(got["states"][:, k, :, :3][where], X[where])
-        finite = np.isfinite(got["terms"][..., dtr.V_SLOT]).all(axis=-1)
-        assert _same(dtr.replay(got["terms"])[finite], got["terms"][..., dtr.V_SLOT][finite])
-        assert _same(got["terms"][..., -1, dtr.V_SLOT], got["totals"][..., 1])
+        finite = np.isfinite(got["terms"][..., ds.V_SLOT]).all(axis=-1)
+        assert _same(ds.replay(got["terms"])[finite], got["terms"][..., ds.V_SLOT][finite])
+        assert _same(got["terms"][..., -1, ds.V_SLOT], got["totals"][..., 1])
 
 
 def test_with_obstacles_and_downforce_it_is_the_composed_restatement():
     dp, coef = _problem(seed=72)
     n = 12
-    discs = dob.make_obstacles(dp, n, 8, 5, nan="some")
-    s = dtr.settings(M=2, blend=(3.0, 5.0), ratio=(0.9, 1.1), load=(0.35, 0.9), aero=(K_F, K_R, 100.0), clearance=(40.0, 1.0),
-                     terms=dict(rate_weight=(0.3, 0.02), rate_max=(1.5, 6.0), slip_weight=40.0, slip_max=0.08),
-                     objective=dict(progress_weight=3.0, speed_ceiling=(1.05, 0.0)))
+    discs = ds.make_obstacles(dp, n, 8, 5, nan="some")
+    s = Settings(substeps=2, low_speed_blend=(3.0, 5.0), coupling=(0.9, 1.1), load_transfer=(0.35, 0.9), downforce=(K_F, K_R, 100.0),
+                 clearance_weight=40.0, clearance_margin=1.0, rate_weight=(0.3, 0.02), rate_max=(1.5, 6.0), slip_weight=40.0,
+                 slip_max=0.08, progress_weight=3.0, speed_ceiling=(1.05, 0.0))
     block = _vehicle().coefficients()
-    got = dtr.trace_plans(dp, coef, dp["U"], [block], s, (2, 5), (0.01, 0.2), discs)
-    import dynamic_aero_spec as das
-    import dynamic_integration_spec as dis
-    import dynamic_objective_spec as dos
-    import dynamic_terms_spec as dts
-    with dob.setting(discs[0], discs[1], 40.0, 1.0), das.setting(s["ratio"], s["load"], s["aero"]), dos.setting(**s["objective"]), \
-            dts.setting(u_prev=(0.01, 0.2), **s["terms"]), dis.setting(2, (3.0, 5.0)):
-        cost, V, X = _rollout(dp, coef, block, (2, 5), return_states=True)
+    got = ds.trace_plans(dp, coef, dp["U"], [block], s, (2, 5), (0.01, 0.2), discs)
+    cost, V, X = _rollout(dp, coef, block, (2, 5), return_states=True, settings=s, u_prev=(0.01, 0.2), obstacles=discs)
     assert _same(got["totals"][:, 0, 0], cost) and _same(got["totals"][:, 0, 1], V) and _same(got["states"][:, 0, :, :3], X)
-    assert _same(dtr.replay(got["terms"]), got["terms"][..., dtr.V_SLOT])
+    assert _same(ds.replay(got["terms"]), got["terms"][..., ds.V_SLOT])
     terms = got["terms"]
-    assert np.any(terms[..., dtr.DISCS:dtr.V_SLOT] != 0) and np.any(terms[..., dtr.RATE] != 0) and np.any(terms[..., dtr.E_SLOT] != 0)
-
-
-def test_the_module_is_restored():
-    import dynamic_objective_spec as dos
-    before = (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants, dob.rollout_dynamic, dos.rollout_dynamic)
-    with dtr.restatement(dtr.settings(M=2, ratio=0.9)):
-        assert dob.rollout_dynamic is not before[3]
-    assert before == (ds.rollout_dynamic, ds.dynamic_step, ds.derived_constants, dob.rollout_dynamic, dos.rollout_dynamic)
+    assert np.any(terms[..., ds.DISCS:ds.V_SLOT] != 0) and np.any(terms[..., ds.RATE] != 0) and np.any(terms[..., ds.E_SLOT] != 0)
 
 
 # ---- the float64 mirror ----------------------------------------------------------------------------------------------------------
@@ -128,11 +112,11 @@ STATE_TOL, HINGE_TOL = 4 * 3.9e-6, 4 * 4.3e-6
 MIRROR_WIDTH = 1.0                         # metres: narrow enough for the plans to leave the corridor
 MIRROR_TERMS = dict(rate_weight=(0.3, 0.02), rate_max=(1.5, 6.0), slip_weight=40.0, slip_max=0.005)
 MIRROR_CASES = {
-    "default": dtr.settings(),
-    "terms": dtr.settings(terms=MIRROR_TERMS, objective=dict(progress_weight=0.0, speed_ceiling=(0.98, 0.0))),
-    "fine-coupled": dtr.settings(M=4, blend=(3.0, 5.0), ratio=(0.9, 1.1), terms=MIRROR_TERMS),
-    "loaded-aero": dtr.settings(M=2, ratio=(0.9, 1.1), load=(0.35, 0.9), aero=(K_F, K_R, 100.0),
-                                objective=dict(progress_weight=3.0, speed_ceiling=(0.98, 0.0))),
+    "default": Settings(),
+    "terms": Settings(speed_ceiling=(0.98, 0.0), **MIRROR_TERMS),
+    "fine-coupled": Settings(substeps=4, low_speed_blend=(3.0, 5.0), coupling=(0.9, 1.1), **MIRROR_TERMS),
+    "loaded-aero": Settings(substeps=2, coupling=(0.9, 1.1), load_transfer=(0.35, 0.9), downforce=(K_F, K_R, 100.0),
+                            progress_weight=3.0, speed_ceiling=(0.98, 0.0)),
 }
 
 
@@ -142,27 +126,27 @@ def _mirror(name, window, with_discs):
     dp, coef = _problem(seed=73, width=MIRROR_WIDTH)
     n = 12
     kw = dp["kw"]
-    discs = dob.make_obstacles(dp, n, 3, 9) if with_discs else None
+    discs = ds.make_obstacles(dp, n, 3, 9) if with_discs else None
     u_prev = (0.01, 0.2)
-    f32 = dtr.trace_plans(dp, coef, dp["U"], [_vehicle().coefficients()], s, window, u_prev, discs)
+    f32 = ds.trace_plans(dp, coef, dp["U"], [_vehicle().coefficients()], s, window, u_prev, discs)
     worst = dict(state=0.0, hinge=0.0, kink=INF)
     binds = np.zeros(15, dtype=bool)
     for m in range(dp["U"].shape[0]):
         f64 = trace(_vehicle(), dp["x0"].astype(np.float64), dp["U"][m].astype(np.float64), dp["table"], kw["dt"],
                     u_min=kw["u_min"], u_max=kw["u_max"], margin=kw["margin"], wheelbase=kw["wheelbase"], nn_window=window,
-                    substeps=s["M"], low_speed_blend=s["blend"], coupling=s["ratio"], load_transfer=s["load"],
-                    downforce=s["aero"], u_prev=u_prev, rate_max=s["terms"]["rate_max"], slip_max=s["terms"]["slip_max"],
-                    speed_ceiling=s["objective"]["speed_ceiling"], obstacles=None if discs is None else discs[0],
+                    substeps=s.substeps, low_speed_blend=s.low_speed_blend, coupling=s.coupling,
+                    load_transfer=s.load_transfer, downforce=s.downforce, u_prev=u_prev, rate_max=s.rate_max, slip_max=s.slip_max,
+                    speed_ceiling=s.speed_ceiling, obstacles=None if discs is None else discs[0],
                     radii=None if discs is None else discs[1])
         row = f32["terms"][m, 0].astype(np.float64)
-        assert np.array_equal(f64["j"], row[:, dtr.J].astype(np.int64)), (name, m)
+        assert np.array_equal(f64["j"], row[:, ds.J].astype(np.int64)), (name, m)
         hinges = np.concatenate([f64["box"], f64["corridor"][:, None], f64["rate"], f64["slip"][:, None],
                                  f64["ceiling"][:, None], f64["obstacles"]], axis=1)
         worst["state"] = max(worst["state"], float(np.abs(f64["states"] - f32["states"][m, 0]).max()))
-        worst["hinge"] = max(worst["hinge"], float(np.abs(hinges - row[:, dtr.HINGES]).max()))
+        worst["hinge"] = max(worst["hinge"], float(np.abs(hinges - row[:, ds.HINGES]).max()))
         worst["kink"] = min(worst["kink"], float(f64["kink"].min()))
         binds |= (hinges != 0).any(axis=0)
-        for key, slot in (("e_y", dtr.EY), ("e_psi", dtr.EPSI), ("dv", dtr.DV), ("dk", dtr.DK)):
+        for key, slot in (("e_y", ds.EY), ("e_psi", ds.EPSI), ("dv", ds.DV), ("dk", ds.DK)):
             worst["hinge"] = max(worst["hinge"], float(np.abs(f64[key] - row[:, slot]).max()))
     return worst, binds
 
@@ -193,16 +177,16 @@ def test_the_mirror_is_the_existing_float64_terms_step_by_step(window):
     s = MIRROR_CASES["fine-coupled"]
     dp, _ = _problem(seed=73, width=MIRROR_WIDTH)
     kw, n = dp["kw"], 12
-    discs = dob.make_obstacles(dp, n, 3, 9)
+    discs = ds.make_obstacles(dp, n, 3, 9)
     u_prev, ceiling = (0.01, 0.2), (0.98, 0.0)
     bound = np.zeros(3)
     for U in dp["U"].astype(np.float64):
         t = trace(_vehicle(), dp["x0"].astype(np.float64), U, dp["table"], kw["dt"], u_min=kw["u_min"], u_max=kw["u_max"],
-                  margin=kw["margin"], wheelbase=kw["wheelbase"], nn_window=window, substeps=s["M"], low_speed_blend=s["blend"],
-                  coupling=s["ratio"], u_prev=u_prev, rate_max=MIRROR_TERMS["rate_max"], slip_max=MIRROR_TERMS["slip_max"],
+                  margin=kw["margin"], wheelbase=kw["wheelbase"], nn_window=window, substeps=s.substeps, low_speed_blend=s.low_speed_blend,
+                  coupling=s.coupling, u_prev=u_prev, rate_max=MIRROR_TERMS["rate_max"], slip_max=MIRROR_TERMS["slip_max"],
                   speed_ceiling=ceiling, obstacles=discs[0], radii=discs[1])
-        np.testing.assert_array_equal(t["states"], _vehicle().rollout(dp["x0"].astype(np.float64), U, kw["dt"], substeps=s["M"],
-                                                                      low_speed_blend=s["blend"], coupling=s["ratio"]))
+        np.testing.assert_array_equal(t["states"], _vehicle().rollout(dp["x0"].astype(np.float64), U, kw["dt"], substeps=s.substeps,
+                                                                      low_speed_blend=s.low_speed_blend, coupling=s.coupling))
         V_terms = stage_terms(t["states"], U, kw["dt"], u_prev, _vehicle(), rate_max=MIRROR_TERMS["rate_max"],
                               slip_max=MIRROR_TERMS["slip_max"])[1]
         V_ceiling = objective_terms(t["states"], U, dp["table"], speed_ceiling=ceiling, nn_window=window)[1]

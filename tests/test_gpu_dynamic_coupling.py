@@ -1,5 +1,5 @@
 """Mode D's tyre coupling (acmpc_set_dynamics_coupling) on the MI355X, from every call form.  Costs, keys, feasible counts
-and records must be bit-identical to tests/dynamic_coupling_spec.py - alone on the small shapes, and through the forms
+and records must be bit-identical to tests/dynamic_spec.py - alone on the small shapes, and through the forms
 already held to it (the one-candidate-per-lane kernels, the control matrix) on the large ones; a handle coupled with
 (inf, inf) runs the coupled kernels and must give the bits of a handle without the coupling; a handle whose coupling is off
 must give the bits of a handle that never heard of the call; acmpc_score_grips takes the handle's coupling with each
@@ -9,13 +9,11 @@ import numpy as np
 import pytest
 
 import acmpc_oracle as orc
-import dynamic_coupling_spec as dcs
 import dynamic_ensemble_spec as es
-import dynamic_integration_spec as dis
-import dynamic_objective_spec as dos
 import dynamic_sampled_spec as dss
 import dynamic_spec as ds
-import dynamic_terms_spec as dts
+from dynamic_spec import Settings
+import grip_spec as gs
 import test_gpu_dynamic as tgd
 import test_gpu_dynamic_ensemble as tge
 import test_gpu_dynamic_objective as tgo
@@ -46,17 +44,6 @@ def _vehicle():
 
 def _grip_vehicles():
     return [_vehicle().with_grip(g) for g in GRIPS]
-
-
-def _spec(ratio, setting, u_prev, integration, call):
-    """`call()` - something that ends in dynamic_spec.rollout_dynamic - under the coupling, the objective, the terms with the
-    previous control of ONE problem, and the integration setting: the coupling outermost of the step-level settings."""
-    objective, terms = setting
-    with dcs.setting(ratio):
-        with dos.setting(**objective):
-            with dts.setting(u_prev=u_prev, **terms):
-                with dis.setting(*integration):
-                    return call()
 
 
 def _set(eng, ratio, setting=OFF, u_prev=None):
@@ -104,9 +91,9 @@ def test_costs_argmin_and_record_are_the_specification(layout, window, integrati
             _set(eng, ratio, setting, prev)
             out = eng.solve(x0, U_in, layout=layout)
             for p in range(P):
-                cost, V, X = _spec(ratio, setting, None if prev is None else prev[p], integration,
-                                   lambda: ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(),
-                                                         nn_window=window, return_states=True))
+                cost, V, X = ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), nn_window=window,
+                                           return_states=True, settings=Settings(*integration, **setting[0], **setting[1],
+                                           coupling=ratio), u_prev=None if prev is None else prev[p])
                 label = "%s, problem %d" % (name, p)
                 tgd._same_bits(out["costs"][p], cost)
                 rec = _capi.split_record(out["records"][p], n)
@@ -137,7 +124,7 @@ def test_infinite_ratios_run_the_coupled_kernels_and_give_the_uncoupled_bits(K):
     U1 = np.ascontiguousarray(U.transpose(0, 2, 3, 1))
     centre, ref = tsf._centres(dps, n, 5)
     u_prev = tgt._previous(P, 22)
-    states, controls = dcs.braking_log(_vehicle().with_grip(0.5), (1.0, 1.0), steps=20)
+    states, controls = gs.braking_log(_vehicle().with_grip(0.5), (1.0, 1.0), steps=20)
     scales = tgi._scales(70)
 
     def run(ratio, update, integration, setting, prev):
@@ -259,9 +246,9 @@ def test_coupling_off_is_a_handle_that_never_made_the_call():
         for got, w in zip(run(prepare), want):
             assert np.array_equal(got.view(np.uint32), w.view(np.uint32)), prepare.__name__
     for p in range(P):   # (and that is the specification's)
-        cost = _spec(ratio, OFF, None, DEFAULT,
-                     lambda: ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
-                                           _vehicle().coefficients(), nn_window=(2, 5)))[0]
+        cost = ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
+                             _vehicle().coefficients(), nn_window=(2, 5), settings=Settings(*DEFAULT, **OFF[0], **OFF[1],
+                             coupling=ratio))[0]
         tgd._same_bits(want[0][p], cost)
 
 
@@ -290,16 +277,16 @@ def test_ensemble_is_the_specification(reduce, layout, window, integration, sett
         out = eng.solve(np.stack([d["x0"] for d in dps]), U_in, layout=layout)
         for p in range(P):
             prev = None if u_prev is None else u_prev[p]
-            J, V, X = _spec(ratio, setting, prev, integration,
-                            lambda: es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights,
-                                                     nn_window=window, return_states=True))
+            J, V, X = es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights, nn_window=window,
+                                       return_states=True, settings=Settings(*integration, **setting[0], **setting[1],
+                                       coupling=ratio), u_prev=prev)
             tgd._same_bits(out["costs"][p], J)
             best = tgd._check_record(_capi.split_record(out["records"][p], n), U_h[p], J, V, X, n)
             assert out["best_idx"][p] == best
         # the straight full-brake candidate of the problem at speed, vehicle by vehicle
         brake = dps[1]["U"][10:11]
-        per = [_spec(ratio, OFF, None, DEFAULT, lambda: ds.spec_costs(orc, dps[1], eng.coefficients(1), b, nn_window=window, U=brake))[0][0]
-               for b in blocks]
+        per = [ds.spec_costs(orc, dps[1], eng.coefficients(1), b, nn_window=window, U=brake, settings=Settings(*DEFAULT, **OFF[0],
+               **OFF[1], coupling=ratio))[0][0] for b in blocks]
         off = [ds.spec_costs(orc, dps[1], eng.coefficients(1), b, nn_window=window, U=brake)[0][0] for b in blocks]
         assert len(set(float(c) for c in per)) == 3 and len(set(float(c) for c in off)) == 1, (per, off)
     finally:
@@ -363,11 +350,10 @@ def test_packed_rollout(K, layout, window, integration, setting):
             dp = dict(base[q], x0=x0[q])
             prev = None if u_prev is None else by_kind[q]
             if K == 1:
-                return _spec(ratio, setting, prev, integration,
-                             lambda: ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states))
-            return _spec(ratio, setting, prev, integration,
-                         lambda: es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub,
-                                                  return_states=states))
+                return ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states,
+                                     settings=Settings(*integration, **setting[0], **setting[1], coupling=ratio), u_prev=prev)
+            return es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub, return_states=states,
+                                    settings=Settings(*integration, **setting[0], **setting[1], coupling=ratio), u_prev=prev)
 
         tpk._check_against_spec(whole, base, coefs, U, N, n, tpk.GROUP_ONE if K == 1 else tpk.GROUP_ENSEMBLE, planted, spec,
                                 57 + K, label)
@@ -444,10 +430,10 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             costs, keys = rig.fused(N, offset, sigma, seed, rnd)
             rec = rig.finalize_sampled(None, N, sigma, seed, rnd)
             for p in range(P):
-                want = _spec(ratio, ALL_FOUR, rig.u_prev[p], FINE,
-                             lambda: dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p],
-                                                         rig.ref_h[p], N, offset, p, rnd, seed, sigma, reduce=rig.reduce,
-                                                         weights=rig.weights, nn_window=window, return_states=True))
+                want = dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p], rig.ref_h[p],
+                                           N, offset, p, rnd, seed, sigma, reduce=rig.reduce, weights=rig.weights,
+                                           nn_window=window, return_states=True, settings=Settings(*FINE, **ALL_FOUR[0],
+                                           **ALL_FOUR[1], coupling=ratio), u_prev=rig.u_prev[p])
                 tsm._same_bits(costs[p].cpu().numpy(), want["cost"], "costs, problem %d" % p)
                 assert int(keys[p].item()) == want["key"]
                 r, best = _capi.split_record(rec[p], n), want["best"]
@@ -462,9 +448,9 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             for r in range(rounds):
                 sig = (sigma[0] * shrink**r, sigma[1] * shrink**r)
                 U = dss.candidates(orc, rig.dps[p], centre, None, N, 0, p, r, seed, sig)
-                cost, V, X = _spec(ratio, ALL_FOUR, rig.u_prev[p], FINE,
-                                   lambda: dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce,
-                                                     rig.weights, window, return_states=True))
+                cost, V, X = dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce, rig.weights, window,
+                                       return_states=True, settings=Settings(*FINE, **ALL_FOUR[0], **ALL_FOUR[1],
+                                       coupling=ratio), u_prev=rig.u_prev[p])
                 centre = U[orc.pick_best(cost)[0]]
             tgd._check_record(_capi.split_record(got[p], n), U, cost, V, X, n)
     finally:
@@ -565,8 +551,8 @@ def test_score_grips_is_the_specification(L, K, integration):
         plain, _ = eng.score_grips(states, controls, 0.05, scales, segment=L)
         eng.set_dynamics_coupling(ratio)
         errors, best = eng.score_grips(states, controls, 0.05, scales, segment=L)
-        want, want_best = dcs.score(ratio, _vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
-                                    substeps=integration[0], low_speed_blend=integration[1])
+        want, want_best = gs.score(_vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
+                                   settings=Settings(substeps=integration[0], low_speed_blend=integration[1], coupling=ratio))
         tgi._same_bits(errors, want)
         assert best == want_best and np.isfinite(want).all()
         assert not np.array_equal(_u32(errors), _u32(plain))
@@ -580,7 +566,7 @@ def test_score_grips_is_the_specification(L, K, integration):
 def test_score_grips_finds_the_grip_of_a_straight_line_braking_log():
     from acmpc_amd.grip_estimator import grip_scales
     tied = grip_scales(GRID, "tied")
-    states, controls = dcs.braking_log(_vehicle().with_grip(0.5), (1.0, 1.0))
+    states, controls = gs.braking_log(_vehicle().with_grip(0.5), (1.0, 1.0))
     eng = tgi._engine()
     try:
         errors, best = eng.score_grips(states, controls, 0.05, tied)
@@ -588,7 +574,7 @@ def test_score_grips_finds_the_grip_of_a_straight_line_braking_log():
         eng.set_dynamics_coupling(1.0)
         errors, best = eng.score_grips(states, controls, 0.05, tied)
         assert tied[best, 0] == pytest.approx(0.5)
-        want, want_best = dcs.score((1.0, 1.0), _vehicle().coefficients(), states, controls, 0.05, tied)
+        want, want_best = gs.score(_vehicle().coefficients(), states, controls, 0.05, tied, settings=Settings(coupling=(1.0, 1.0)))
         tgi._same_bits(errors, want)
         assert best == want_best
     finally:

@@ -1,5 +1,5 @@
 """Mode D's aerodynamic downforce (acmpc_set_dynamics_downforce) on the MI355X, from every call form, at the shapes of
-test_gpu_dynamic_load_transfer.py.  Costs, keys, feasible counts and records must be bit-identical to tests/dynamic_aero_spec.py;
+test_gpu_dynamic_load_transfer.py.  Costs, keys, feasible counts and records must be bit-identical to tests/dynamic_spec.py;
 a handle with k_f = k_r = 0 runs the aero kernels and must give the bits of the same handle without the setting, loaded, coupled
 or neither; a handle whose setting is off must give the bits of a handle that never heard of the call; acmpc_score_grips takes
 the handle's setting with the base vehicle's factors on each hypothesis' own peaks; obstacles ride on the aero pack; and
@@ -8,14 +8,11 @@ import numpy as np
 import pytest
 
 import acmpc_oracle as orc
-import dynamic_aero_spec as das
 import dynamic_ensemble_spec as es
-import dynamic_integration_spec as dis
-import dynamic_objective_spec as dos
-import dynamic_obstacles_spec as dob
 import dynamic_sampled_spec as dss
 import dynamic_spec as ds
-import dynamic_terms_spec as dts
+from dynamic_spec import Settings
+import grip_spec as gs
 import test_dynamic_downforce as tdd
 import test_gpu_dynamic as tgd
 import test_gpu_dynamic_coupling as tgc
@@ -42,26 +39,6 @@ OFF, ALL_FOUR = tgc.OFF, tgc.ALL_FOUR
 GRID = tgc.GRID
 _vehicle, _grip_vehicles, _u32, _force_pedals = tgc._vehicle, tgc._grip_vehicles, tgc._u32, tgc._force_pedals
 _same_where_finite = tgl._same_where_finite
-
-
-def _spec(ratio, load, aero, setting, u_prev, integration, call, obstacles=None):
-    """`call()` - something that ends in dynamic_spec.rollout_dynamic - under the downforce, the load transfer and the coupling,
-    the objective, the terms with the previous control of ONE problem, and the integration setting: the downforce's setting
-    outermost of the step-level ones, in the load transfer's place.  `obstacles` = (positions, radii, weight, margin) of that
-    problem go round all of it, as dynamic_obstacles_spec.restatement puts them."""
-    objective, terms = setting
-
-    def inner():
-        with das.setting(ratio, load, aero):
-            with dos.setting(**objective):
-                with dts.setting(u_prev=u_prev, **terms):
-                    with dis.setting(*integration):
-                        return call()
-
-    if obstacles is None:
-        return inner()
-    with dob.setting(*obstacles):
-        return inner()
 
 
 def _set(eng, ratio, load, aero, setting=OFF, u_prev=None):
@@ -103,9 +80,10 @@ def test_costs_argmin_and_record_are_the_specification(layout, window, integrati
             _set(eng, ratio, load, aero, setting, prev)
             out = eng.solve(x0, U_in, layout=layout)
             for p in range(P):
-                cost, V, X = _spec(ratio, load, aero, setting, None if prev is None else prev[p], integration,
-                                   lambda: ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(),
-                                                         nn_window=window, return_states=True))
+                cost, V, X = ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), nn_window=window,
+                                           return_states=True, settings=Settings(*integration, **setting[0], **setting[1],
+                                           coupling=ratio, load_transfer=load, downforce=aero),
+                                           u_prev=None if prev is None else prev[p])
                 label = "%s, problem %d" % (name, p)
                 tgd._same_bits(out["costs"][p], cost)
                 rec = _capi.split_record(out["records"][p], n)
@@ -260,7 +238,7 @@ def test_downforce_off_is_a_handle_that_never_made_the_call():
         eng.set_dynamics_load_transfer(None)
         eng.set_dynamics_clearance(40.0, 1.0)
         eng.set_dynamics_clearance(0.0, 0.0)
-        discs = [dob.make_obstacles(d, n, 2, 2420 + p) for p, d in enumerate(dps)]
+        discs = [ds.make_obstacles(d, n, 2, 2420 + p) for p, d in enumerate(dps)]
         eng.set_obstacles(np.stack([d[0] for d in discs]), np.stack([d[1] for d in discs]))
         eng.set_obstacles(None, None)
         eng.set_dynamics_integration(1, None)
@@ -271,9 +249,9 @@ def test_downforce_off_is_a_handle_that_never_made_the_call():
         for got, w in zip(run(prepare), want):
             assert np.array_equal(got.view(np.uint32), w.view(np.uint32)), prepare.__name__
     for p in range(P):   # (and that is the specification's)
-        cost = _spec(None, None, AERO, OFF, None, DEFAULT,
-                     lambda: ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
-                                           _vehicle().coefficients(), nn_window=(2, 5)))[0]
+        cost = ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
+                             _vehicle().coefficients(), nn_window=(2, 5), settings=Settings(*DEFAULT, **OFF[0], **OFF[1],
+                             coupling=None, load_transfer=None, downforce=AERO))[0]
         tgd._same_bits(want[0][p], cost)
 
 
@@ -290,7 +268,7 @@ def test_ensemble_is_the_specification(reduce, layout, window, integration, sett
         _force_pedals(d["U"], n)
     vehicles = tgl._geometry_vehicles()
     blocks = [v.coefficients() for v in vehicles]
-    scalars = [das.constants(b, load, AERO) for b in blocks]
+    scalars = [ds.constants(b, Settings(load_transfer=load, downforce=AERO)).k for b in blocks]
     for key in ("a1_f", "a2_f", "a1_r", "a2_r"):                              # really per vehicle
         assert len(set(float(s[key]) for s in scalars)) == 4, key
     weights = (1.0, 2.0, 0.5, 1.5) if reduce == "mean" else None
@@ -305,9 +283,9 @@ def test_ensemble_is_the_specification(reduce, layout, window, integration, sett
         out = eng.solve(np.stack([d["x0"] for d in dps]), U_in, layout=layout)
         for p in range(P):
             prev = None if u_prev is None else u_prev[p]
-            J, V, X = _spec(ratio, load, AERO, setting, prev, integration,
-                            lambda: es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights,
-                                                     nn_window=window, return_states=True))
+            J, V, X = es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights, nn_window=window,
+                                       return_states=True, settings=Settings(*integration, **setting[0], **setting[1],
+                                       coupling=ratio, load_transfer=load, downforce=AERO), u_prev=prev)
             tgd._same_bits(out["costs"][p], J)
             best = tgd._check_record(_capi.split_record(out["records"][p], n), U_h[p], J, V, X, n)
             assert out["best_idx"][p] == best
@@ -373,11 +351,12 @@ def test_packed_rollout(K, layout, window, integration, setting, load):
             dp = dict(base[q], x0=x0[q])
             prev = None if u_prev is None else by_kind[q]
             if K == 1:
-                return _spec(ratio, load, AERO_LOW, setting, prev, integration,
-                             lambda: ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states))
-            return _spec(ratio, load, AERO_LOW, setting, prev, integration,
-                         lambda: es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub,
-                                                  return_states=states))
+                return ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states,
+                                     settings=Settings(*integration, **setting[0], **setting[1], coupling=ratio,
+                                                       load_transfer=load, downforce=AERO_LOW), u_prev=prev)
+            return es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub, return_states=states,
+                                    settings=Settings(*integration, **setting[0], **setting[1], coupling=ratio, load_transfer=load,
+                                                      downforce=AERO_LOW), u_prev=prev)
 
         tpk._check_against_spec(whole, base, coefs, U, N, n, tpk.GROUP_ONE if K == 1 else tpk.GROUP_ENSEMBLE, planted, spec,
                                 77 + K, label)
@@ -435,10 +414,11 @@ def test_fused_rollout_and_optimize_equal_the_specification(K, load):
             costs, keys = rig.fused(N, offset, sigma, seed, rnd)
             rec = rig.finalize_sampled(None, N, sigma, seed, rnd)
             for p in range(P):
-                want = _spec(ratio, load, AERO_LOW, ALL_FOUR, rig.u_prev[p], FINE,
-                             lambda: dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p],
-                                                         rig.ref_h[p], N, offset, p, rnd, seed, sigma, reduce=rig.reduce,
-                                                         weights=rig.weights, nn_window=window, return_states=True))
+                want = dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p], rig.ref_h[p],
+                                           N, offset, p, rnd, seed, sigma, reduce=rig.reduce, weights=rig.weights,
+                                           nn_window=window, return_states=True, settings=Settings(*FINE, **ALL_FOUR[0],
+                                           **ALL_FOUR[1], coupling=ratio, load_transfer=load, downforce=AERO_LOW),
+                                           u_prev=rig.u_prev[p])
                 tsm._same_bits(costs[p].cpu().numpy(), want["cost"], "costs, problem %d" % p)
                 assert int(keys[p].item()) == want["key"]
                 r, best = _capi.split_record(rec[p], n), want["best"]
@@ -453,9 +433,9 @@ def test_fused_rollout_and_optimize_equal_the_specification(K, load):
             for r in range(rounds):
                 sig = (sigma[0] * shrink**r, sigma[1] * shrink**r)
                 U = dss.candidates(orc, rig.dps[p], centre, None, N, 0, p, r, seed, sig)
-                cost, V, X = _spec(ratio, load, AERO_LOW, ALL_FOUR, rig.u_prev[p], FINE,
-                                   lambda: dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce,
-                                                     rig.weights, window, return_states=True))
+                cost, V, X = dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce, rig.weights, window,
+                                       return_states=True, settings=Settings(*FINE, **ALL_FOUR[0], **ALL_FOUR[1], coupling=ratio,
+                                       load_transfer=load, downforce=AERO_LOW), u_prev=rig.u_prev[p])
                 centre = U[orc.pick_best(cost)[0]]
             tgd._check_record(_capi.split_record(got[p], n), U, cost, V, X, n)
     finally:
@@ -501,13 +481,13 @@ def test_optimize_with_and_without_the_matrix_and_the_sharded_optimizer(vehicles
 # ---- obstacles over the aero pack -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("layout", [0, 1])
 def test_obstacles_over_the_aero_pack(layout):
-    """Two discs per problem, the hard and the soft part on, all four term parts, coupled and loaded: dynamic_obstacles_spec
+    """Two discs per problem, the hard and the soft part on, all four term parts, coupled and loaded: dynamic_spec
     composed round the downforce's setting."""
     from acmpc_amd import _capi
     P, N, n, window, ratio = 2, 300, 12, (2, 5), (0.9, 1.1)
     clearance = (40.0, 1.0)
     dps = [ds.make_dynamic_problem(orc, "monza", n + 1, N, 2490 + p, vx0=v) for p, v in enumerate((6.0, None))]
-    discs = [dob.make_obstacles(d, n, 2, 2490 + 7 * p) for p, d in enumerate(dps)]
+    discs = [ds.make_obstacles(d, n, 2, 2490 + 7 * p) for p, d in enumerate(dps)]
     u_prev = tgt._previous(P, 49)
     eng = tgd._engine(dps, P, N, n, window)
     try:
@@ -521,9 +501,10 @@ def test_obstacles_over_the_aero_pack(layout):
         assert not np.array_equal(_u32(out["costs"]), _u32(without))
         hit = 0
         for p in range(P):
-            cost, V, X = _spec(ratio, LOAD, AERO, ALL_FOUR, u_prev[p], DEFAULT,
-                               lambda: ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), nn_window=window,
-                                                     return_states=True), obstacles=discs[p] + clearance)
+            cost, V, X = ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), nn_window=window,
+                                       return_states=True, settings=Settings(*DEFAULT, **ALL_FOUR[0], **ALL_FOUR[1],
+                                       coupling=ratio, load_transfer=LOAD, downforce=AERO, clearance_weight=clearance[0],
+                                       clearance_margin=clearance[1]), u_prev=u_prev[p], obstacles=discs[p])
             tgd._same_bits(out["costs"][p], cost)
             best = tgd._check_record(_capi.split_record(out["records"][p], n), U_h[p], cost, V, X, n)
             assert out["best_idx"][p] == best and out["n_feasible"][p] == np.count_nonzero(V == 0)
@@ -562,8 +543,9 @@ def test_score_grips_is_the_specification(L, K, integration):
         loaded, _ = eng.score_grips(states, controls, 0.05, scales, segment=L)
         eng.set_dynamics_downforce(AERO)
         errors, best = eng.score_grips(states, controls, 0.05, scales, segment=L)
-        want, want_best = das.score(ratio, LOAD, AERO, _vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
-                                    substeps=integration[0], low_speed_blend=integration[1])
+        want, want_best = gs.score(_vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
+                                   settings=Settings(substeps=integration[0], low_speed_blend=integration[1], coupling=ratio,
+                                                     load_transfer=LOAD, downforce=AERO))
         tgi._same_bits(errors, want)
         assert best == want_best and np.isfinite(want).all()
         assert not np.array_equal(_u32(errors), _u32(loaded))
@@ -575,8 +557,8 @@ def test_score_grips_is_the_specification(L, K, integration):
         eng.set_dynamics_load_transfer(None)
         eng.set_dynamics_downforce(AERO_LOW)
         errors, best = eng.score_grips(states, controls, 0.05, scales, segment=L)
-        want, want_best = das.score(None, None, AERO_LOW, _vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
-                                    substeps=integration[0], low_speed_blend=integration[1])
+        want, want_best = gs.score(_vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
+                                   settings=Settings(substeps=integration[0], low_speed_blend=integration[1], downforce=AERO_LOW))
         tgi._same_bits(errors, want)
         assert best == want_best
     finally:
@@ -596,7 +578,8 @@ def test_score_grips_finds_the_grip_of_the_fast_log():
         eng.set_dynamics_downforce((K_F, K_R))
         errors, best = eng.score_grips(states, controls, 0.05, tied)
         assert tied[best, 0] == pytest.approx(0.7) and best_off != best
-        want, want_best = das.score((1.0, 1.0), LOAD, (K_F, K_R), _vehicle().coefficients(), states, controls, 0.05, tied)
+        want, want_best = gs.score(_vehicle().coefficients(), states, controls, 0.05, tied, settings=Settings(coupling=(1.0, 1.0),
+                                   load_transfer=LOAD, downforce=(K_F, K_R)))
         tgi._same_bits(errors, want)
         assert best == want_best and errors[best] < 1e-6 < np.sort(errors)[1]
     finally:

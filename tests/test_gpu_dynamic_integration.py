@@ -1,6 +1,6 @@
 """Mode D's integration setting (acmpc_set_dynamics_integration) on the MI355X: M Euler sub-steps per control step and the
 low-speed blend, from every call form.  Costs, keys, feasible counts and records must be bit-identical to
-tests/dynamic_integration_spec.py - alone on the small shapes, and through the forms already held to it (the
+tests/dynamic_spec.py - alone on the small shapes, and through the forms already held to it (the
 one-candidate-per-lane kernels, the control matrix) on the large ones; the default setting must give the bits of a handle
 that never heard of the call; and DynamicSamplingSolver with the setting drives a finely integrated plant round a 15 m
 circle from a standstill."""
@@ -9,9 +9,9 @@ import pytest
 
 import acmpc_oracle as orc
 import dynamic_ensemble_spec as es
-import dynamic_integration_spec as dis
 import dynamic_sampled_spec as dss
 import dynamic_spec as ds
+from dynamic_spec import Settings
 import test_gpu_dynamic as tgd
 import test_gpu_dynamic_ensemble as tge
 import test_gpu_dynamic_packed as tpk
@@ -68,8 +68,8 @@ def test_costs_argmin_and_record_are_the_specification(n, setting, layout, windo
         U_in = U_h if layout == 0 else np.ascontiguousarray(U_h.transpose(0, 2, 3, 1))
         out = eng.solve(np.stack([d["x0"] for d in dps]), U_in, layout=layout)
         for p in range(P):
-            cost, V, X = dis.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), *setting,
-                                        nn_window=window, return_states=True)
+            cost, V, X = ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), nn_window=window,
+                                       return_states=True, settings=Settings(*setting))
             tgd._same_bits(out["costs"][p], cost)
             best = tgd._check_record(_capi.split_record(out["records"][p], n), U_h[p], cost, V, X, n)
             assert out["best_idx"][p] == best
@@ -138,9 +138,8 @@ def test_ensemble_is_the_specification(reduce, layout, window, setting):
         U_in = U_h if layout == 0 else np.ascontiguousarray(U_h.transpose(0, 2, 3, 1))
         out = eng.solve(np.stack([d["x0"] for d in dps]), U_in, layout=layout)
         for p in range(P):
-            with dis.setting(*setting):
-                J, V, X = es.spec_ensemble(orc, dps[p], eng.coefficients(p), [v.coefficients() for v in vehicles],
-                                           reduce=reduce, weights=weights, nn_window=window, return_states=True)
+            J, V, X = es.spec_ensemble(orc, dps[p], eng.coefficients(p), [v.coefficients() for v in vehicles], reduce=reduce,
+                                       weights=weights, nn_window=window, return_states=True, settings=Settings(*setting))
             tgd._same_bits(out["costs"][p], J)
             best = tgd._check_record(_capi.split_record(out["records"][p], n), U_h[p], J, V, X, n)
             assert out["best_idx"][p] == best
@@ -167,9 +166,8 @@ def test_ensemble_of_one_is_the_single_vehicle_and_members_use_their_own_wheelba
         eng.set_dynamics_ensemble([_vehicle(), long_car], reduce="max")
         out = eng.solve(x0, U)
         for p in range(P):
-            with dis.setting(*FINE):
-                J = es.spec_ensemble(orc, dps[p], eng.coefficients(p), [_vehicle().coefficients(), long_car.coefficients()],
-                                     reduce="max", nn_window=(2, 5))[0]
+            J = es.spec_ensemble(orc, dps[p], eng.coefficients(p), [_vehicle().coefficients(), long_car.coefficients()],
+                                 reduce="max", nn_window=(2, 5), settings=Settings(*FINE))[0]
             tgd._same_bits(out["costs"][p], J)
     finally:
         eng.close()
@@ -206,10 +204,9 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             costs, keys = rig.fused(N, offset, sigma, seed, rnd)
             rec = rig.finalize_sampled(None, N, sigma, seed, rnd)
             for p in range(P):
-                with dis.setting(*FINE):
-                    want = dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p],
-                                               rig.ref_h[p], N, offset, p, rnd, seed, sigma, reduce=rig.reduce,
-                                               weights=rig.weights, nn_window=window, return_states=True)
+                want = dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p],
+                                           rig.ref_h[p], N, offset, p, rnd, seed, sigma, reduce=rig.reduce,
+                                           weights=rig.weights, nn_window=window, return_states=True, settings=Settings(*FINE))
                 tsm._same_bits(costs[p].cpu().numpy(), want["cost"], "costs, problem %d" % p)
                 assert int(keys[p].item()) == want["key"]
                 r, best = _capi.split_record(rec[p], n), want["best"]
@@ -224,9 +221,8 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             for r in range(rounds):
                 sig = (sigma[0] * shrink**r, sigma[1] * shrink**r)
                 U = dss.candidates(orc, rig.dps[p], centre, None, N, 0, p, r, seed, sig)
-                with dis.setting(*FINE):
-                    cost, V, X = dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce,
-                                           rig.weights, window, return_states=True)
+                cost, V, X = dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce,
+                                       rig.weights, window, return_states=True, settings=Settings(*FINE))
                 centre = U[orc.pick_best(cost)[0]]
             tgd._check_record(_capi.split_record(got[p], n), U, cost, V, X, n)
     finally:
@@ -339,11 +335,11 @@ def test_packed_rollout(K, layout, window):
 
         def spec(q, U_sub, states):
             dp = dict(base[q], x0=x0[q])
-            with dis.setting(*FINE):
-                if K == 1:
-                    return ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states)
-                return es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub,
-                                        return_states=states)
+            if K == 1:
+                return ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states,
+                                     settings=Settings(*FINE))
+            return es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub, return_states=states,
+                                    settings=Settings(*FINE))
 
         tpk._check_against_spec(whole, base, coefs, U, N, n, tpk.GROUP_ONE if K == 1 else tpk.GROUP_ENSEMBLE, planted, spec,
                                 17 + K, label)
@@ -440,9 +436,8 @@ def test_random_shapes_against_the_specification():
             data = U if c["layout"] == 0 else np.ascontiguousarray(U.transpose(0, 2, 3, 1))
             out = eng.solve(np.stack([d["x0"] for d in dps]), data, layout=c["layout"])
             for p in range(P):
-                with dis.setting(c["M"], c["blend"]):
-                    cost, V, X = dss.costs(orc, dps[p], eng.coefficients(p), [v.coefficients() for v in vehicles], dps[p]["U"],
-                                           nn_window=c["window"], return_states=True)
+                cost, V, X = dss.costs(orc, dps[p], eng.coefficients(p), [v.coefficients() for v in vehicles], dps[p]["U"],
+                                       nn_window=c["window"], return_states=True, settings=Settings(c["M"], c["blend"]))
                 nan = np.isnan(cost)
                 assert np.array_equal(np.isnan(out["costs"][p]), nan), label
                 assert np.array_equal(out["costs"][p][~nan].view(np.uint32), cost[~nan].view(np.uint32)), label

@@ -1,5 +1,5 @@
 """Mode D's longitudinal load transfer (acmpc_set_dynamics_load_transfer) on the MI355X, from every call form.  Costs, keys,
-feasible counts and records must be bit-identical to tests/dynamic_load_spec.py - alone on the small shapes, and through the
+feasible counts and records must be bit-identical to tests/dynamic_spec.py - alone on the small shapes, and through the
 forms already held to it (the one-candidate-per-lane kernels, the control matrix) on the large ones; a handle with h_cg = 0 runs
 the loaded kernels and must give the bits of the same handle without the setting, coupled or not; a handle whose setting is off
 must give the bits of a handle that never heard of the call; acmpc_score_grips takes the handle's setting with the base
@@ -11,14 +11,11 @@ import numpy as np
 import pytest
 
 import acmpc_oracle as orc
-import dynamic_coupling_spec as dcs
 import dynamic_ensemble_spec as es
-import dynamic_integration_spec as dis
-import dynamic_load_spec as dls
-import dynamic_objective_spec as dos
 import dynamic_sampled_spec as dss
 import dynamic_spec as ds
-import dynamic_terms_spec as dts
+from dynamic_spec import Settings
+import grip_spec as gs
 import test_gpu_dynamic as tgd
 import test_gpu_dynamic_coupling as tgc
 import test_gpu_dynamic_ensemble as tge
@@ -39,18 +36,6 @@ BIG_OFFSET = tgc.BIG_OFFSET
 OFF, ALL_FOUR = tgc.OFF, tgc.ALL_FOUR
 GRID = tgc.GRID
 _vehicle, _grip_vehicles, _u32, _force_pedals = tgc._vehicle, tgc._grip_vehicles, tgc._u32, tgc._force_pedals
-
-
-def _spec(ratio, load, setting, u_prev, integration, call):
-    """`call()` - something that ends in dynamic_spec.rollout_dynamic - under the load transfer and the coupling, the objective,
-    the terms with the previous control of ONE problem, and the integration setting: the load transfer's setting outermost of
-    the step-level ones, in the coupling's place."""
-    objective, terms = setting
-    with dls.setting(ratio, load):
-        with dos.setting(**objective):
-            with dts.setting(u_prev=u_prev, **terms):
-                with dis.setting(*integration):
-                    return call()
 
 
 def _set(eng, ratio, load, setting=OFF, u_prev=None):
@@ -98,9 +83,9 @@ def test_costs_argmin_and_record_are_the_specification(layout, window, integrati
             _set(eng, ratio, LOAD, setting, prev)
             out = eng.solve(x0, U_in, layout=layout)
             for p in range(P):
-                cost, V, X = _spec(ratio, LOAD, setting, None if prev is None else prev[p], integration,
-                                   lambda: ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(),
-                                                         nn_window=window, return_states=True))
+                cost, V, X = ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), nn_window=window,
+                                           return_states=True, settings=Settings(*integration, **setting[0], **setting[1],
+                                           coupling=ratio, load_transfer=LOAD), u_prev=None if prev is None else prev[p])
                 label = "%s, problem %d" % (name, p)
                 tgd._same_bits(out["costs"][p], cost)
                 rec = _capi.split_record(out["records"][p], n)
@@ -132,7 +117,7 @@ def test_zero_height_runs_the_loaded_kernels_and_gives_the_parents_bits(K):
     U1 = np.ascontiguousarray(U.transpose(0, 2, 3, 1))
     centre, ref = tsf._centres(dps, n, 5)
     u_prev = tgt._previous(P, 32)
-    states, controls = dcs.braking_log(_vehicle().with_grip(0.5), (1.0, 1.0), steps=20)
+    states, controls = gs.braking_log(_vehicle().with_grip(0.5), (1.0, 1.0), steps=20)
     scales = tgi._scales(70)
 
     def run(ratio, load, update, integration, setting, prev):
@@ -256,9 +241,9 @@ def test_load_transfer_off_is_a_handle_that_never_made_the_call():
         for got, w in zip(run(prepare), want):
             assert np.array_equal(got.view(np.uint32), w.view(np.uint32)), prepare.__name__
     for p in range(P):   # (and that is the specification's)
-        cost = _spec(None, LOAD, OFF, None, DEFAULT,
-                     lambda: ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
-                                           _vehicle().coefficients(), nn_window=(2, 5)))[0]
+        cost = ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
+                             _vehicle().coefficients(), nn_window=(2, 5), settings=Settings(*DEFAULT, **OFF[0], **OFF[1],
+                             coupling=None, load_transfer=LOAD))[0]
         tgd._same_bits(want[0][p], cost)
 
 
@@ -283,8 +268,8 @@ def test_ensemble_is_the_specification(reduce, layout, window, integration, sett
     vehicles = _grip_vehicles() if members == "grips" else _geometry_vehicles()
     blocks = [v.coefficients() for v in vehicles]
     if members == "geometry":
-        scalars = [dls.constants(b, LOAD) for b in blocks]
-        for key in dls.KEYS:                                                  # really per vehicle
+        scalars = [ds.constants(b, Settings(load_transfer=LOAD)).k for b in blocks]
+        for key in ds.LOAD_KEYS:                                                  # really per vehicle
             assert len(set(float(s[key]) for s in scalars)) == (2 if key == "c_h" else 4), key
     weights = (1.0, 2.0, 0.5, 1.5)[:len(vehicles)] if reduce == "mean" else None
     u_prev = tgt._previous(P, 33) if setting is ALL_FOUR else None
@@ -298,9 +283,9 @@ def test_ensemble_is_the_specification(reduce, layout, window, integration, sett
         out = eng.solve(np.stack([d["x0"] for d in dps]), U_in, layout=layout)
         for p in range(P):
             prev = None if u_prev is None else u_prev[p]
-            J, V, X = _spec(ratio, LOAD, setting, prev, integration,
-                            lambda: es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights,
-                                                     nn_window=window, return_states=True))
+            J, V, X = es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights, nn_window=window,
+                                       return_states=True, settings=Settings(*integration, **setting[0], **setting[1],
+                                       coupling=ratio, load_transfer=LOAD), u_prev=prev)
             tgd._same_bits(out["costs"][p], J)
             best = tgd._check_record(_capi.split_record(out["records"][p], n), U_h[p], J, V, X, n)
             assert out["best_idx"][p] == best
@@ -365,11 +350,12 @@ def test_packed_rollout(K, layout, window, integration, setting):
             dp = dict(base[q], x0=x0[q])
             prev = None if u_prev is None else by_kind[q]
             if K == 1:
-                return _spec(ratio, LOAD, setting, prev, integration,
-                             lambda: ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states))
-            return _spec(ratio, LOAD, setting, prev, integration,
-                         lambda: es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub,
-                                                  return_states=states))
+                return ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states,
+                                     settings=Settings(*integration, **setting[0], **setting[1], coupling=ratio,
+                                                       load_transfer=LOAD), u_prev=prev)
+            return es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub, return_states=states,
+                                    settings=Settings(*integration, **setting[0], **setting[1], coupling=ratio,
+                                                      load_transfer=LOAD), u_prev=prev)
 
         tpk._check_against_spec(whole, base, coefs, U, N, n, tpk.GROUP_ONE if K == 1 else tpk.GROUP_ENSEMBLE, planted, spec,
                                 67 + K, label)
@@ -443,10 +429,10 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             costs, keys = rig.fused(N, offset, sigma, seed, rnd)
             rec = rig.finalize_sampled(None, N, sigma, seed, rnd)
             for p in range(P):
-                want = _spec(ratio, LOAD, ALL_FOUR, rig.u_prev[p], FINE,
-                             lambda: dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p],
-                                                         rig.ref_h[p], N, offset, p, rnd, seed, sigma, reduce=rig.reduce,
-                                                         weights=rig.weights, nn_window=window, return_states=True))
+                want = dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p], rig.ref_h[p],
+                                           N, offset, p, rnd, seed, sigma, reduce=rig.reduce, weights=rig.weights,
+                                           nn_window=window, return_states=True, settings=Settings(*FINE, **ALL_FOUR[0],
+                                           **ALL_FOUR[1], coupling=ratio, load_transfer=LOAD), u_prev=rig.u_prev[p])
                 tsm._same_bits(costs[p].cpu().numpy(), want["cost"], "costs, problem %d" % p)
                 assert int(keys[p].item()) == want["key"]
                 r, best = _capi.split_record(rec[p], n), want["best"]
@@ -461,9 +447,9 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             for r in range(rounds):
                 sig = (sigma[0] * shrink**r, sigma[1] * shrink**r)
                 U = dss.candidates(orc, rig.dps[p], centre, None, N, 0, p, r, seed, sig)
-                cost, V, X = _spec(ratio, LOAD, ALL_FOUR, rig.u_prev[p], FINE,
-                                   lambda: dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce,
-                                                     rig.weights, window, return_states=True))
+                cost, V, X = dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce, rig.weights, window,
+                                       return_states=True, settings=Settings(*FINE, **ALL_FOUR[0], **ALL_FOUR[1], coupling=ratio,
+                                       load_transfer=LOAD), u_prev=rig.u_prev[p])
                 centre = U[orc.pick_best(cost)[0]]
             tgd._check_record(_capi.split_record(got[p], n), U, cost, V, X, n)
     finally:
@@ -530,8 +516,9 @@ def test_score_grips_is_the_specification(L, K, integration):
         coupled, _ = eng.score_grips(states, controls, 0.05, scales, segment=L)
         eng.set_dynamics_load_transfer(LOAD)
         errors, best = eng.score_grips(states, controls, 0.05, scales, segment=L)
-        want, want_best = dls.score(ratio, LOAD, _vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
-                                    substeps=integration[0], low_speed_blend=integration[1])
+        want, want_best = gs.score(_vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
+                                   settings=Settings(substeps=integration[0], low_speed_blend=integration[1], coupling=ratio,
+                                                     load_transfer=LOAD))
         tgi._same_bits(errors, want)
         assert best == want_best and np.isfinite(want).all()
         assert not np.array_equal(_u32(errors), _u32(coupled))
@@ -542,8 +529,8 @@ def test_score_grips_is_the_specification(L, K, integration):
         eng.set_dynamics_coupling(None)
         eng.set_dynamics_load_transfer(LOAD)
         errors, best = eng.score_grips(states, controls, 0.05, scales, segment=L)
-        want, want_best = dls.score(None, LOAD, _vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
-                                    substeps=integration[0], low_speed_blend=integration[1])
+        want, want_best = gs.score(_vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
+                                   settings=Settings(substeps=integration[0], low_speed_blend=integration[1], load_transfer=LOAD))
         tgi._same_bits(errors, want)
         assert best == want_best
     finally:
@@ -553,14 +540,15 @@ def test_score_grips_is_the_specification(L, K, integration):
 def test_score_grips_finds_the_grip_of_a_straight_line_braking_log():
     from acmpc_amd.grip_estimator import grip_scales
     tied = grip_scales(GRID, "tied")
-    states, controls = dls.braking_log(_vehicle().with_grip(0.5), (1.0, 1.0), LOAD)
+    states, controls = gs.braking_log(_vehicle().with_grip(0.5), (1.0, 1.0), LOAD)
     eng = tgi._engine()
     try:
         eng.set_dynamics_coupling(1.0)
         eng.set_dynamics_load_transfer(LOAD)
         errors, best = eng.score_grips(states, controls, 0.05, tied)
         assert tied[best, 0] == pytest.approx(0.5)
-        want, want_best = dls.score((1.0, 1.0), LOAD, _vehicle().coefficients(), states, controls, 0.05, tied)
+        want, want_best = gs.score(_vehicle().coefficients(), states, controls, 0.05, tied, settings=Settings(coupling=(1.0, 1.0),
+                                   load_transfer=LOAD))
         tgi._same_bits(errors, want)
         assert best == want_best and errors[best] < 1e-6 < np.sort(errors)[1]
     finally:

@@ -1,5 +1,5 @@
 """Mode D's objective (acmpc_set_dynamics_objective) on the MI355X, from every call form.  Costs, keys, feasible counts and
-records must be bit-identical to tests/dynamic_objective_spec.py - alone on the small shapes, and through the forms already
+records must be bit-identical to tests/dynamic_spec.py - alone on the small shapes, and through the forms already
 held to it (the one-candidate-per-lane kernels, the control matrix) on the large ones - with costs that are negative; a
 handle whose objective is off must give the bits of a handle that never heard of the call; and DynamicSamplingSolver with a
 progress reward under a ceiling from the speed profile covers more of the loop of test_gpu_dynamic than the same solver
@@ -11,11 +11,9 @@ import pytest
 
 import acmpc_oracle as orc
 import dynamic_ensemble_spec as es
-import dynamic_integration_spec as dis
-import dynamic_objective_spec as dos
 import dynamic_sampled_spec as dss
 import dynamic_spec as ds
-import dynamic_terms_spec as dts
+from dynamic_spec import Settings
 import test_gpu_dynamic as tgd
 import test_gpu_dynamic_ensemble as tge
 import test_gpu_dynamic_packed as tpk
@@ -50,16 +48,6 @@ def _vehicle():
     return DynamicBicycleParams.reference()
 
 
-def _spec(objective, terms, u_prev, integration, call, trace=None):
-    """`call()` - something that ends in dynamic_spec.rollout_dynamic - under the objective, the terms with the previous
-    control of ONE problem, and the integration setting: the objective's block outermost."""
-    with dos.setting(**objective) as handle:
-        handle.trace = trace
-        with dts.setting(u_prev=u_prev, **terms):
-            with dis.setting(*integration):
-                return call()
-
-
 def _set(eng, objective, terms, u_prev=None):
     eng.set_dynamics_objective(**objective)
     eng.set_dynamics_terms(**terms)
@@ -92,9 +80,9 @@ def test_costs_argmin_and_record_are_the_specification(layout, window, integrati
             out = eng.solve(x0, U_in, layout=layout)
             for p in range(P):
                 trace = {}
-                cost, V, X = _spec(objective, terms, u_prev[p], integration,
-                                   lambda: ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(),
-                                                         nn_window=window, return_states=True), trace)
+                cost, V, X = ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), nn_window=window,
+                                           return_states=True, settings=Settings(*integration, **objective, **terms),
+                                           u_prev=u_prev[p], trace=trace)
                 label = "%s, problem %d" % (name, p)
                 tgd._same_bits(out["costs"][p], cost)
                 rec = _capi.split_record(out["records"][p], n)
@@ -127,12 +115,11 @@ def test_candidates_past_the_paths_end():
         eng.set_dynamics_objective(**objective)
         out = eng.solve(np.stack([d["x0"] for d in dps]), dps[0]["U"][None])
         trace = {}
-        cost, V, X = _spec(objective, NO_TERMS, None, DEFAULT,
-                           lambda: ds.spec_costs(orc, dps[0], eng.coefficients(0), _vehicle().coefficients(),
-                                                 return_states=True), trace)
+        cost, V, X = ds.spec_costs(orc, dps[0], eng.coefficients(0), _vehicle().coefficients(), return_states=True,
+                                   settings=Settings(*DEFAULT, **objective, **NO_TERMS), trace=trace)
         coef = eng.coefficients(0)
         length = float(np.sum(np.hypot(np.diff(coef[:, 0].astype(np.float64)), np.diff(coef[:, 1].astype(np.float64)))))
-        past = (trace["j"] == n - 1) & (trace["s"] > length + 5.0)
+        past = (trace["j"][:, -1] == n - 1) & (trace["s"] > length + 5.0)
         assert past.sum() > N // 2, (past.sum(), length, float(np.nanmax(trace["s"])))
         tgd._same_bits(out["costs"][0], cost)
         tgd._check_record(_capi.split_record(out["records"][0], n), dps[0]["U"], cost, V, X, n)
@@ -162,14 +149,13 @@ def test_ensemble_is_the_specification(reduce, layout, window, integration):
         U_in = U_h if layout == 0 else np.ascontiguousarray(U_h.transpose(0, 2, 3, 1))
         out = eng.solve(np.stack([d["x0"] for d in dps]), U_in, layout=layout)
         for p in range(P):
-            J, V, X = _spec(*BOTH, u_prev[p], integration,
-                            lambda: es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights,
-                                                     nn_window=window, return_states=True))
+            J, V, X = es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights, nn_window=window,
+                                       return_states=True, settings=Settings(*integration, **BOTH[0], **BOTH[1]), u_prev=u_prev[p])
             tgd._same_bits(out["costs"][p], J)
             best = tgd._check_record(_capi.split_record(out["records"][p], n), U_h[p], J, V, X, n)
             assert out["best_idx"][p] == best
-            alone = _spec(*BOTH, u_prev[p], integration,
-                          lambda: ds.spec_costs(orc, dps[p], eng.coefficients(p), blocks[1], nn_window=window))[0]
+            alone = ds.spec_costs(orc, dps[p], eng.coefficients(p), blocks[1], nn_window=window, settings=Settings(*integration,
+                                  **BOTH[0], **BOTH[1]), u_prev=u_prev[p])[0]
             assert not np.array_equal(alone.view(np.uint32), J.view(np.uint32))
     finally:
         eng.close()
@@ -233,10 +219,10 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             costs, keys = rig.fused(N, offset, sigma, seed, rnd)
             rec = rig.finalize_sampled(None, N, sigma, seed, rnd)
             for p in range(P):
-                want = _spec(*BOTH, rig.u_prev[p], FINE,
-                             lambda: dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p],
-                                                         rig.ref_h[p], N, offset, p, rnd, seed, sigma, reduce=rig.reduce,
-                                                         weights=rig.weights, nn_window=window, return_states=True))
+                want = dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p], rig.ref_h[p],
+                                           N, offset, p, rnd, seed, sigma, reduce=rig.reduce, weights=rig.weights,
+                                           nn_window=window, return_states=True, settings=Settings(*FINE, **BOTH[0], **BOTH[1]),
+                                           u_prev=rig.u_prev[p])
                 tsm._same_bits(costs[p].cpu().numpy(), want["cost"], "costs, problem %d" % p)
                 assert int(keys[p].item()) == want["key"]
                 r, best = _capi.split_record(rec[p], n), want["best"]
@@ -251,9 +237,8 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             for r in range(rounds):
                 sig = (sigma[0] * shrink**r, sigma[1] * shrink**r)
                 U = dss.candidates(orc, rig.dps[p], centre, None, N, 0, p, r, seed, sig)
-                cost, V, X = _spec(*BOTH, rig.u_prev[p], FINE,
-                                   lambda: dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce,
-                                                     rig.weights, window, return_states=True))
+                cost, V, X = dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce, rig.weights, window,
+                                       return_states=True, settings=Settings(*FINE, **BOTH[0], **BOTH[1]), u_prev=rig.u_prev[p])
                 centre = U[orc.pick_best(cost)[0]]
             tgd._check_record(_capi.split_record(got[p], n), U, cost, V, X, n)
     finally:
@@ -394,11 +379,10 @@ def test_packed_rollout(K, layout, window, integration):
         def spec(q, U_sub, states):
             dp = dict(base[q], x0=x0[q])
             if K == 1:
-                return _spec(*BOTH, by_kind[q], integration,
-                             lambda: ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states))
-            return _spec(*BOTH, by_kind[q], integration,
-                         lambda: es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub,
-                                                  return_states=states))
+                return ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states,
+                                     settings=Settings(*integration, **BOTH[0], **BOTH[1]), u_prev=by_kind[q])
+            return es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub, return_states=states,
+                                    settings=Settings(*integration, **BOTH[0], **BOTH[1]), u_prev=by_kind[q])
 
         tpk._check_against_spec(whole, base, coefs, U, N, n, tpk.GROUP_ONE if K == 1 else tpk.GROUP_ENSEMBLE, planted, spec,
                                 37 + K, label)
@@ -505,9 +489,8 @@ def test_objective_off_is_a_handle_that_never_made_the_call():
     for got, w in zip(run(survives), want):
         assert np.array_equal(got.view(np.uint32), w.view(np.uint32))
     for p in range(P):   # (and that is the specification's)
-        cost = _spec(objective, NO_TERMS, None, DEFAULT,
-                     lambda: ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
-                                           _vehicle().coefficients(), nn_window=(2, 5)))[0]
+        cost = ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
+                             _vehicle().coefficients(), nn_window=(2, 5), settings=Settings(*DEFAULT, **objective, **NO_TERMS))[0]
         tgd._same_bits(want[0][p], cost)
 
 
@@ -535,11 +518,11 @@ def _step0_excess(solver, state, u0):
     """float32 vx - cap after the first control step of the plan, in the kernel's arithmetic: the restatement's step on the
     handle's own rows, the windowed search from waypoint 0, cap = fma(cs, v_ref_j, co)."""
     coef = solver.engine.coefficients(0)
-    k = ds.derived_constants(_vehicle().coefficients())
+    c = ds.constants(_vehicle().coefficients(), dt=tgd.LOOP_DT)
     x0 = np.asarray(state, dtype=T)
     ox, oy = coef[0, 0], coef[0, 1]
     st = [np.array([x0[0] - ox], dtype=T), np.array([x0[1] - oy], dtype=T)] + [np.array([x0[q]], dtype=T) for q in range(2, 6)]
-    st = ds.dynamic_step(st, np.array([u0[0]], dtype=T), np.array([u0[1]], dtype=T), k, T(tgd.LOOP_DT))
+    st = ds.dynamic_step(st, np.array([u0[0]], dtype=T), np.array([u0[1]], dtype=T), c)
     back, ahead = tgt.TERMS_CONFIG["nn_window"]
     m = np.arange(min(back + ahead + 1, len(coef)))
     wx, wy = coef[m, 0] - ox, coef[m, 1] - oy

@@ -1,6 +1,6 @@
 """Mode D's obstacles on the MI355X ("Mode D, obstacles"; csrc/acmpc_dynamic_obstacles.hip): every call
-form of the handle with discs set, bit for bit against the float32 restatement (tests/dynamic_obstacles_spec.py round the
-composed restatement of tests/dynamic_fuzz_cases.py) - per-candidate costs, the key, the feasible count and the winner's
+form of the handle with discs set, bit for bit against the float32 restatement (tests/dynamic_spec.py through
+tests/dynamic_fuzz_cases.specification) - per-candidate costs, the key, the feasible count and the winner's
 record - at the smallest shapes the kernels can go wrong at, and DynamicSamplingSolver overtaking a slower car in closed
 loop with the float64 mirror as the plant."""
 import numpy as np
@@ -8,8 +8,7 @@ import pytest
 
 import acmpc_oracle as orc
 import dynamic_fuzz_cases as fz
-import dynamic_obstacles_spec as dob
-import dynamic_sampled_spec as dss
+import dynamic_spec as ds
 
 pytestmark = pytest.mark.gpu
 
@@ -38,23 +37,12 @@ def _discs(c, dps, K_obs, nans=None):
     """One problem's discs after another's: different ones per problem, `nans[p]` of NANS."""
     n = c["H"] - 1
     nans = nans if nans is not None else ["none"] * len(dps)
-    return [dob.make_obstacles(d, n, K_obs, c["seed"] + 7 * p, nan=nans[p]) for p, d in enumerate(dps)]
+    return [ds.make_obstacles(d, n, K_obs, c["seed"] + 7 * p, nan=nans[p]) for p, d in enumerate(dps)]
 
 
 def _specification(c, dps, coefs, discs, clearance, centre=None, ref=None):
     """tests/dynamic_fuzz_cases.specification with each problem's discs (None: a problem without any)."""
-    vehicles = [fz.blocks()[v] for v in c["vehicles"]]
-    u_prev = fz.previous(c)
-    out = []
-    for p, (dp, coef) in enumerate(zip(dps, coefs)):
-        with dob.restatement(c, None if u_prev is None else u_prev[p], None if discs is None else discs[p], clearance):
-            if c["form"] == "sampled":
-                out.append(dss.rollout_sampled(orc, dp, coef, vehicles, centre[p], None if ref is None else ref[p], c["N"],
-                                               c["index_offset"], p, c["round"], c["sample_seed"], c["sigma"], reduce=c["reduce"],
-                                               weights=c["weights"], nn_window=c["window"], return_states=True))
-            else:
-                out.append(dss.costs(orc, dp, coef, vehicles, dp["U"], c["reduce"], c["weights"], c["window"], return_states=True))
-    return out
+    return fz.specification(c, orc, dps, coefs, centre, ref, obstacles=discs, clearance=clearance)
 
 
 def _set_discs(eng, discs):
@@ -150,12 +138,11 @@ def test_two_candidates_per_lane():
     """One launch at P N = 2^20 with n = 3: in full against the one-candidate-per-lane kernels (the two halves of the
     candidates, each launch below 2^20), and against the restatement on two problems' first and last candidates."""
     from acmpc_amd import Engine
-    import dynamic_spec as ds
     P, N, n, K_obs = 256, 4096, 3, 3
     c = _case(n, N, P=P, seed=54000, ratio=(0.9, 1.1), load=(0.35, 0.9), terms=ALL_TERMS, objective=ALL_OBJECTIVE)
     base = [ds.make_dynamic_problem(orc, "monza", n + 1, N, c["seed"] + q, **fz.KIND[q]) for q in range(4)]
     dps = [base[p % 4] for p in range(P)]
-    discs = [dob.make_obstacles(base[p % 4], n, K_obs, c["seed"] + p % 8, nan=NANS[p % 3]) for p in range(P)]
+    discs = [ds.make_obstacles(base[p % 4], n, K_obs, c["seed"] + p % 8, nan=NANS[p % 3]) for p in range(P)]
     U = np.stack([d["U"] for d in dps])
     x0 = np.stack([d["x0"] for d in dps])
     eng = Engine(**dict(base[0]["kw"], max_problems=P, max_candidates=N, max_steps=n))
@@ -199,7 +186,6 @@ def test_optimize_against_the_restated_rounds(update):
     mean), each of whose rounds is restated from the centre the device handed it."""
     import torch
     from acmpc_amd import Engine, _capi
-    import dynamic_spec as ds
     P, N, n, rounds, shrink, seed, sigma = 2, 4096, 9, 2, 0.5, 99123, (0.04, 0.35)
     c = _case(n, N, P=P, seed=56000, ratio=(0.9, 1.1), objective=dict(progress_weight=3.0, speed_ceiling=None), form="sampled",
               index_offset=0, sample_seed=seed, reduce="mean")

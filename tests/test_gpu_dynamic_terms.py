@@ -1,5 +1,5 @@
 """Mode D's rate and slip terms (acmpc_set_dynamics_terms, acmpc_set_previous_control) on the MI355X, from every call
-form.  Costs, keys, feasible counts and records must be bit-identical to tests/dynamic_terms_spec.py - alone on the small
+form.  Costs, keys, feasible counts and records must be bit-identical to tests/dynamic_spec.py - alone on the small
 shapes, and through the forms already held to it (the one-candidate-per-lane kernels, the control matrix) on the large
 ones; a handle whose terms are off must give the bits of a handle that never heard of the calls; and
 DynamicSamplingSolver with the terms steers more smoothly through the tightest corner of the loop of test_gpu_dynamic,
@@ -11,10 +11,9 @@ import pytest
 
 import acmpc_oracle as orc
 import dynamic_ensemble_spec as es
-import dynamic_integration_spec as dis
 import dynamic_sampled_spec as dss
 import dynamic_spec as ds
-import dynamic_terms_spec as dts
+from dynamic_spec import Settings
 import test_gpu_dynamic as tgd
 import test_gpu_dynamic_ensemble as tge
 import test_gpu_dynamic_packed as tpk
@@ -52,14 +51,6 @@ def _previous(P, seed, nan_at=None):
     return u
 
 
-def _spec(terms, u_prev, integration, call):
-    """`call()` - something that ends in dynamic_spec.rollout_dynamic - under the terms, the previous control of ONE problem
-    and the integration setting: the terms' block first, the integration's inside it."""
-    with dts.setting(u_prev=u_prev, **terms):
-        with dis.setting(*integration):
-            return call()
-
-
 # ---- one candidate per lane ---------------------------------------------------------------------------------------------
 # P = 2, N = 300 (one full 256-lane workgroup and a tail), n = 12.  Layout 0 starts its problems at a standstill and at the
 # path's speed, layout 1 inside the blend interval and at the path's speed.  A NaN pedal, an inf steering angle, and in one
@@ -91,9 +82,9 @@ def test_costs_argmin_and_record_are_the_specification(layout, window, integrati
                 eng.set_previous_control(u_prev)
                 out = eng.solve(x0, U_in, layout=layout)
                 for p in range(P):
-                    cost, V, X = _spec(terms, None if u_prev is None else u_prev[p], integration,
-                                       lambda: ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(),
-                                                             nn_window=window, return_states=True))
+                    cost, V, X = ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), nn_window=window,
+                                               return_states=True, settings=Settings(*integration, **terms),
+                                               u_prev=None if u_prev is None else u_prev[p])
                     label = "%s, previous control %s, problem %d" % (name, which, p)
                     tgd._same_bits(out["costs"][p], cost)
                     rec = _capi.split_record(out["records"][p], n)
@@ -134,15 +125,14 @@ def test_ensemble_is_the_specification(reduce, layout, window, integration):
         U_in = U_h if layout == 0 else np.ascontiguousarray(U_h.transpose(0, 2, 3, 1))
         out = eng.solve(np.stack([d["x0"] for d in dps]), U_in, layout=layout)
         for p in range(P):
-            J, V, X = _spec(BOTH, u_prev[p], integration,
-                            lambda: es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights,
-                                                     nn_window=window, return_states=True))
+            J, V, X = es.spec_ensemble(orc, dps[p], eng.coefficients(p), blocks, reduce=reduce, weights=weights, nn_window=window,
+                                       return_states=True, settings=Settings(*integration, **BOTH), u_prev=u_prev[p])
             tgd._same_bits(out["costs"][p], J)
             best = tgd._check_record(_capi.split_record(out["records"][p], n), U_h[p], J, V, X, n)
             assert out["best_idx"][p] == best
             # the slip part does differ per vehicle: the longer car alone gives other costs
-            alone = _spec(BOTH, u_prev[p], integration,
-                          lambda: ds.spec_costs(orc, dps[p], eng.coefficients(p), blocks[1], nn_window=window))[0]
+            alone = ds.spec_costs(orc, dps[p], eng.coefficients(p), blocks[1], nn_window=window, settings=Settings(*integration,
+                                  **BOTH), u_prev=u_prev[p])[0]
             assert not np.array_equal(alone.view(np.uint32), J.view(np.uint32))
     finally:
         eng.close()
@@ -206,10 +196,10 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             costs, keys = rig.fused(N, offset, sigma, seed, rnd)
             rec = rig.finalize_sampled(None, N, sigma, seed, rnd)
             for p in range(P):
-                want = _spec(BOTH, rig.u_prev[p], FINE,
-                             lambda: dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p],
-                                                         rig.ref_h[p], N, offset, p, rnd, seed, sigma, reduce=rig.reduce,
-                                                         weights=rig.weights, nn_window=window, return_states=True))
+                want = dss.rollout_sampled(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), rig.centre_h[p], rig.ref_h[p],
+                                           N, offset, p, rnd, seed, sigma, reduce=rig.reduce, weights=rig.weights,
+                                           nn_window=window, return_states=True, settings=Settings(*FINE, **BOTH),
+                                           u_prev=rig.u_prev[p])
                 tsm._same_bits(costs[p].cpu().numpy(), want["cost"], "costs, problem %d" % p)
                 assert int(keys[p].item()) == want["key"]
                 r, best = _capi.split_record(rec[p], n), want["best"]
@@ -224,9 +214,8 @@ def test_fused_rollout_and_optimize_equal_the_specification(K):
             for r in range(rounds):
                 sig = (sigma[0] * shrink**r, sigma[1] * shrink**r)
                 U = dss.candidates(orc, rig.dps[p], centre, None, N, 0, p, r, seed, sig)
-                cost, V, X = _spec(BOTH, rig.u_prev[p], FINE,
-                                   lambda: dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce,
-                                                     rig.weights, window, return_states=True))
+                cost, V, X = dss.costs(orc, rig.dps[p], rig.eng.coefficients(p), rig.blocks(), U, rig.reduce, rig.weights, window,
+                                       return_states=True, settings=Settings(*FINE, **BOTH), u_prev=rig.u_prev[p])
                 centre = U[orc.pick_best(cost)[0]]
             tgd._check_record(_capi.split_record(got[p], n), U, cost, V, X, n)
     finally:
@@ -340,11 +329,10 @@ def test_packed_rollout(K, layout, window, integration):
         def spec(q, U_sub, states):
             dp = dict(base[q], x0=x0[q])
             if K == 1:
-                return _spec(BOTH, by_kind[q], integration,
-                             lambda: ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states))
-            return _spec(BOTH, by_kind[q], integration,
-                         lambda: es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub,
-                                                  return_states=states))
+                return ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states,
+                                     settings=Settings(*integration, **BOTH), u_prev=by_kind[q])
+            return es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub, return_states=states,
+                                    settings=Settings(*integration, **BOTH), u_prev=by_kind[q])
 
         tpk._check_against_spec(whole, base, coefs, U, N, n, tpk.GROUP_ONE if K == 1 else tpk.GROUP_ENSEMBLE, planted, spec,
                                 27 + K, label)
@@ -462,9 +450,9 @@ def test_terms_off_is_a_handle_that_never_made_the_calls():
     for got, w in zip(run(survives), want):
         assert np.array_equal(got.view(np.uint32), w.view(np.uint32))
     for p in range(P):   # (and that is the specification's)
-        cost = _spec(BOTH, _previous(P, 8)[p], DEFAULT,
-                     lambda: ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
-                                           _vehicle().coefficients(), nn_window=(2, 5)))[0]
+        cost = ds.spec_costs(orc, dps[p], orc.coefficients_temporal(dps[p]["table"], dps[p]["kw"]["margin"]).astype(T),
+                             _vehicle().coefficients(), nn_window=(2, 5), settings=Settings(*DEFAULT, **BOTH), u_prev=_previous(P,
+                             8)[p])[0]
         tgd._same_bits(want[0][p], cost)
 
 
@@ -487,9 +475,8 @@ def test_a_previous_control_out_of_reach_leaves_no_feasible_candidate():
         eng.set_previous_control(u_prev)
         out = eng.solve(x0, U)
         for p in range(P):
-            cost, V, X = _spec(terms, u_prev[p], DEFAULT,
-                               lambda: ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(),
-                                                     return_states=True))
+            cost, V, X = ds.spec_costs(orc, dps[p], eng.coefficients(p), _vehicle().coefficients(), return_states=True,
+                                       settings=Settings(*DEFAULT, **terms), u_prev=u_prev[p])
             assert np.all(V > 0) and out["n_feasible"][p] == 0
             tgd._same_bits(out["costs"][p], cost)
             assert out["best_idx"][p] == orc.pick_best(cost)[0] == int(np.argmin(cost))

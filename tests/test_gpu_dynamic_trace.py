@@ -1,5 +1,5 @@
 """Mode D's plan trace on the MI355X ("Mode D, plan trace"; csrc/acmpc_dynamic_trace.hip):
-Engine.trace_plans bit for bit against the float32 restatement (tests/dynamic_trace_spec.py) - states, totals and terms - at
+Engine.trace_plans bit for bit against the float32 restatement (tests/dynamic_spec.py's trace_plans) - states, totals and terms - at
 the smallest shapes the kernel can go wrong at and once per step family; against the engine itself (the record of
 Engine.optimize's winner, the costs of acmpc_rollout_device); the hinge replay; the scratch that regrows; and the plan built to
 break one limit at one step."""
@@ -8,8 +8,8 @@ import pytest
 
 import acmpc_oracle as orc
 import dynamic_fuzz_cases as fz
-import dynamic_obstacles_spec as dob
-import dynamic_trace_spec as dtr
+import dynamic_spec as ds
+from dynamic_spec import Settings
 
 pytestmark = pytest.mark.gpu
 
@@ -42,8 +42,7 @@ def _engine(c, dps):
 
 
 def _settings(c):
-    return dtr.settings(M=c["M"], blend=c["blend"], terms=c["terms"], objective=c["objective"], ratio=c["ratio"], load=c["load"],
-                        aero=c["aero"], clearance=c["clearance"])
+    return Settings.of_case(c, downforce=c["aero"], clearance_weight=c["clearance"][0], clearance_margin=c["clearance"][1])
 
 
 def _plans(dps, M):
@@ -54,7 +53,7 @@ def _plans(dps, M):
 def _want(c, eng, dps, U, discs=None):
     u_prev = fz.previous(c)
     vehicles = [fz.blocks()[v] for v in c["vehicles"]]
-    per = [dtr.trace_plans(dp, eng.coefficients(p), U[p], vehicles, _settings(c), c["window"],
+    per = [ds.trace_plans(dp, eng.coefficients(p), U[p], vehicles, _settings(c), c["window"],
                            None if u_prev is None else u_prev[p], None if discs is None else discs[p])
            for p, dp in enumerate(dps)]
     return {name: np.stack([t[name] for t in per]) for name in ("states", "totals", "terms")}
@@ -63,17 +62,17 @@ def _want(c, eng, dps, U, discs=None):
 def _same(got, want, label):
     for name in ("states", "terms"):
         assert got[name].shape == want[name].shape, (label, name)
-        diff = np.argwhere(dtr.bits(got[name]) != dtr.bits(want[name]))
+        diff = np.argwhere(ds.bits(got[name]) != ds.bits(want[name]))
         assert diff.size == 0, "%s: %s differs first at %s: %r != %r" % (label, name, diff[0], got[name][tuple(diff[0])],
                                                                         want[name][tuple(diff[0])])
     totals = np.stack([got["cost"], got["violation"]], axis=-1)
-    assert np.array_equal(dtr.bits(totals), dtr.bits(want["totals"])), (label, totals, want["totals"])
+    assert np.array_equal(ds.bits(totals), ds.bits(want["totals"])), (label, totals, want["totals"])
 
 
 def _replays(out, label):
     """V = fma(h, h, V) over slots 5 .. 19 from the previous step's V gives every step's V, and the last step's is V_k."""
-    assert np.array_equal(dtr.bits(dtr.replay(out["terms"])), dtr.bits(out["V"])), label
-    assert np.array_equal(dtr.bits(out["V"][..., -1]), dtr.bits(out["violation"])), label
+    assert np.array_equal(ds.bits(ds.replay(out["terms"])), ds.bits(out["V"])), label
+    assert np.array_equal(ds.bits(out["V"][..., -1]), ds.bits(out["violation"])), label
 
 
 def run(c, M, K_obs=0, nans=None, narrow=False):
@@ -85,7 +84,7 @@ def run(c, M, K_obs=0, nans=None, narrow=False):
         discs = None
         if K_obs:
             n = c["H"] - 1
-            discs = [dob.make_obstacles(d, n, K_obs, c["seed"] + 7 * p, nan=(nans or ["none"] * c["P"])[p]) for p, d in enumerate(dps)]
+            discs = [ds.make_obstacles(d, n, K_obs, c["seed"] + 7 * p, nan=(nans or ["none"] * c["P"])[p]) for p, d in enumerate(dps)]
             eng.set_obstacles(np.stack([d[0] for d in discs]), np.stack([d[1] for d in discs]))
         U = _plans(dps, M)
         x0 = np.stack([d["x0"] for d in dps])
@@ -163,13 +162,13 @@ def test_the_scratch_regrows():
         _same(first, _want(c, eng, dps, small), "small")
         big = eng.trace_plans(x0, large)
         _same({k: v[:, :3] for k, v in big.items()}, _want(c, eng, dps, large[:, :3]), "large")
-        assert np.array_equal(dtr.bits(big["terms"][:, :3]), dtr.bits(big["terms"][:, 117:]))
+        assert np.array_equal(ds.bits(big["terms"][:, :3]), ds.bits(big["terms"][:, 117:]))
         again = eng.trace_plans(x0, small)
         for name in ("states", "terms", "cost", "violation"):
-            assert np.array_equal(dtr.bits(again[name]), dtr.bits(first[name])), name
+            assert np.array_equal(ds.bits(again[name]), ds.bits(first[name])), name
         only = eng.trace_plans(x0, small, want=("totals",))
         assert only["states"] is None and only["terms"] is None
-        assert np.array_equal(dtr.bits(only["cost"]), dtr.bits(first["cost"]))
+        assert np.array_equal(ds.bits(only["cost"]), ds.bits(first["cost"]))
     finally:
         eng.close()
 
@@ -189,9 +188,9 @@ def test_the_winner_of_optimize_is_its_record(family, K, reduce):
         rec = eng.optimize(x0, centre, None, 64, 2, (0.05, 0.3), seed=7)
         u = np.ascontiguousarray(rec["u"], dtype=T).reshape(2, n, 2)
         got = eng.trace_plans(x0, u)
-        assert np.array_equal(dtr.bits(got["states"][:, 0, 0, :, :3]), dtr.bits(np.asarray(rec["x"], dtype=T).reshape(2, n + 1, 3)))
-        assert np.array_equal(dtr.bits(got["cost"][:, 0].max(axis=1)), dtr.bits(rec["cost"]))
-        assert np.array_equal(dtr.bits(got["violation"][:, 0].max(axis=1)), dtr.bits(rec["violation"]))
+        assert np.array_equal(ds.bits(got["states"][:, 0, 0, :, :3]), ds.bits(np.asarray(rec["x"], dtype=T).reshape(2, n + 1, 3)))
+        assert np.array_equal(ds.bits(got["cost"][:, 0].max(axis=1)), ds.bits(rec["cost"]))
+        assert np.array_equal(ds.bits(got["violation"][:, 0].max(axis=1)), ds.bits(rec["violation"]))
     finally:
         eng.close()
 
@@ -213,7 +212,7 @@ def test_totals_are_the_rollout_costs(family):
         costs = torch.empty(2, 4, device=dev)
         eng.rollout_device(d_x0.data_ptr(), d_U.data_ptr(), 2, 4, n, 0, 0, costs.data_ptr(), 0, torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
-        assert np.array_equal(dtr.bits(got["cost"][:, :, 0]), dtr.bits(costs.cpu().numpy()))
+        assert np.array_equal(ds.bits(got["cost"][:, :, 0]), ds.bits(costs.cpu().numpy()))
     finally:
         eng.close()
 

@@ -3,7 +3,7 @@ integration, the rate and slip terms (each weight and each limit its own switch)
 coupling (one-sided ratios among them) and the load transfer drawn beside them by tests/dynamic_fuzz_cases.py, per kernel
 family of the dispatch of csrc/acmpc_dynamic.hip (fine, terms, objective, coupled, loaded) and per call form - the control
 matrix (Engine.solve), or the fused sampled rollout with the record re-drawn from the index.  The handle is set through the
-public setters in a drawn order; the float32 restatements are composed in the nesting of test_gpu_dynamic_load_transfer._spec;
+public setters in a drawn order; the float32 restatement takes the same settings as one Settings value;
 every per-candidate cost, the argmin (the key), the feasible count and the winner's record must have the restatement's bits,
 and the record's cost the rollout's own.
 
@@ -21,7 +21,8 @@ import pytest
 
 import acmpc_oracle as orc
 import dynamic_fuzz_cases as fz
-import dynamic_load_spec as dls
+import grip_spec as gs
+from dynamic_spec import Settings
 
 pytestmark = pytest.mark.gpu
 
@@ -182,11 +183,12 @@ def test_packed_rollout(index):
             dp = dict(base[q], x0=x0[q])
             prev = None if u_prev is None else by_kind[q]
             if K == 1:
-                return tgl._spec(c["ratio"], c["load"], setting, prev, integration,
-                                 lambda: ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states))
-            return tgl._spec(c["ratio"], c["load"], setting, prev, integration,
-                             lambda: es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub,
-                                                      return_states=states))
+                return ds.spec_costs(orc, dp, coefs[q], blocks[0], nn_window=window, U=U_sub, return_states=states,
+                                     settings=Settings(*integration, **setting[0], **setting[1], coupling=c["ratio"],
+                                                       load_transfer=c["load"]), u_prev=prev)
+            return es.spec_ensemble(orc, dp, coefs[q], blocks, reduce="mean", nn_window=window, U=U_sub, return_states=states,
+                                    settings=Settings(*integration, **setting[0], **setting[1], coupling=c["ratio"],
+                                                      load_transfer=c["load"]), u_prev=prev)
 
         tpk._check_against_spec(whole, base, coefs, U, N, n, tpk.GROUP_ONE if K == 1 else tpk.GROUP_ENSEMBLE, planted, spec,
                                 77 + index, label)
@@ -240,8 +242,9 @@ def test_score_grips_against_the_specification(index):
         eng.set_dynamics_load_transfer(c["load"])
         eng.set_dynamics_coupling(c["ratio"])
         errors, best = eng.score_grips(states, controls, 0.05, scales, segment=c["L"])
-        want, want_best = dls.score(c["ratio"], c["load"], tgl._vehicle().coefficients(), states, controls, 0.05, scales,
-                                    segment=c["L"], substeps=c["integration"][0], low_speed_blend=c["integration"][1])
+        want, want_best = gs.score(tgl._vehicle().coefficients(), states, controls, 0.05, scales, segment=c["L"],
+                                   settings=Settings(substeps=c["integration"][0], low_speed_blend=c["integration"][1],
+                                                     coupling=c["ratio"], load_transfer=c["load"]))
         same_bits(errors, want, repr(c))
         assert best == want_best and np.isfinite(want).all(), c
     finally:

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import grip_spec as gs
+from dynamic_spec import Settings
 import test_gpu_dynamic as tgd
 import test_gpu_dynamic_ensemble as tge
 
@@ -78,7 +79,7 @@ def test_errors_and_best_are_the_specification(shape, integration):
     eng = _engine(integration)
     errors, best = eng.score_grips(states, controls, dt, scales, segment=L, weights=weights)
     want, want_best = gs.score(_vehicle0().coefficients(), states, controls, dt, scales, segment=L, weights=weights,
-                               substeps=integration[0], low_speed_blend=integration[1])
+                               settings=Settings(substeps=integration[0], low_speed_blend=integration[1]))
     if integration != (1, None):
         assert states[:, 0].max() > 5.0 and states[:, 0].min() < 3.0 or W == 1      # the log crosses the blend
     _same_bits(errors, want)
@@ -119,7 +120,7 @@ def test_runs_of_segments_are_the_specification(shape, integration):
     finally:
         eng.close()
     want, want_best = gs.score(_vehicle0().coefficients(), states, controls, HANDLE_DT, scales, segment=L,
-                               substeps=integration[0], low_speed_blend=integration[1])
+                               settings=Settings(substeps=integration[0], low_speed_blend=integration[1]))
     assert np.isfinite(want).all()
     _same_bits(errors, want)
     assert best == want_best
@@ -130,9 +131,6 @@ def test_runs_of_segments_in_the_other_three_kernels(variant):
     """identify_grip_coupled_kernel, _loaded_kernel and _aero_kernel each hold the run's lines again: (205, 1, 2305) - run = 2,
     a last run of one segment - under the coupling alone, the load transfer and the downforce, each against its own
     restatement on its own module's log (1.4 .. 1.5 s each on one core)."""
-    import dynamic_aero_spec as das
-    import dynamic_coupling_spec as dcs
-    import dynamic_load_spec as dls
     import test_gpu_dynamic_coupling as tgc
     import test_gpu_dynamic_downforce as tgf
     import test_gpu_dynamic_load_transfer as tgl
@@ -141,14 +139,16 @@ def test_runs_of_segments_in_the_other_three_kernels(variant):
     scales = _scales(K)
     if variant == "coupled":
         states, controls = tgc._braking_log(W)
-        want, want_best = dcs.score(ratio, tgc._vehicle().coefficients(), states, controls, 0.05, scales, segment=L)
+        want, want_best = gs.score(tgc._vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
+                                   settings=Settings(coupling=ratio))
     elif variant == "loaded":
         states, controls = tgl._braking_log(W)
-        want, want_best = dls.score(ratio, tgl.LOAD, tgl._vehicle().coefficients(), states, controls, 0.05, scales, segment=L)
+        want, want_best = gs.score(tgl._vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
+                                   settings=Settings(coupling=ratio, load_transfer=tgl.LOAD))
     else:
         states, controls = tgf._fast_log(W)
-        want, want_best = das.score(ratio, tgf.LOAD, tgf.AERO, tgf._vehicle().coefficients(), states, controls, 0.05, scales,
-                                    segment=L)
+        want, want_best = gs.score(tgf._vehicle().coefficients(), states, controls, 0.05, scales, segment=L,
+                                   settings=Settings(coupling=ratio, load_transfer=tgf.LOAD, downforce=tgf.AERO))
     eng = _engine()
     try:
         assert eng.describe_score_grips(W, L, K) == RUN_SHAPES[shape]

@@ -136,7 +136,7 @@ def test_hypothesis_one_one_is_vehicle_zero_bit_for_bit():
     base = _base()
     for block in (base.coefficients(), base.with_axle_grip(0.37, 1.21).coefficients()):
         k0 = ds.derived_constants(block)
-        k = gs.hypothesis_constants(block, [[1.0, 1.0], [0.5, 0.7]])
+        k = gs.hypothesis_constants(block, [[1.0, 1.0], [0.5, 0.7]], 0.05).k
         for name, value in k0.items():
             got = k[name][0] if name in ("Pf", "Pr") else k[name]
             assert np.float32(got).tobytes() == np.float32(value).tobytes(), name
@@ -144,12 +144,12 @@ def test_hypothesis_one_one_is_vehicle_zero_bit_for_bit():
         assert k["Pf"][1] == scaled["Pf"] and k["Pr"][1] == scaled["Pr"]
     E_a, _ = gs.score(base.coefficients(), *_log((1.0, 1.0), 0.02), 0.05, [[1.0, 1.0]], segment=40)
     # (1, 1) rolls dynamic_spec's own step under vehicle 0: the spec's open-loop states, compared by hand
-    k0 = ds.derived_constants(base.coefficients())
+    c0 = ds.constants(base.coefficients(), dt=0.05)
     states, controls = _log((1.0, 1.0), 0.02)
     st = tuple(np.float32(v) for v in (0, 0, 0, *states[0]))
     e = np.float32(0)
     for j in range(40):
-        st = ds.dynamic_step(st, controls[j, 0], controls[j, 1], k0, np.float32(0.05))
+        st = ds.dynamic_step(st, controls[j, 0], controls[j, 1], c0)
         for q in range(3):
             d = st[3 + q] - states[j + 1, q]
             e = gs.fma32(np.float32(1) * d, d, e)
