@@ -14,8 +14,10 @@
 // float64 throughout, the same operations in the same order as the host path (acmpc_waypoint_table,
 // acmpc_velocity_ceiling, acmpc_speed_profile_qp, acmpc_set_paths); results are written as float32 straight into the
 // staging block the rollout kernels of the same graph read, and the 7 x n table goes to pinned host memory for the
-// caller's read-after-call attributes.  The device's atan2 / sin / cos may differ from the host libm's in the last
-// float64 bit; everything else (+, -, *, /, sqrt, fmod, comparisons) is IEEE-exact on both sides.
+// caller's read-after-call attributes.  The device's atan2 is within one ulp(pi) = 4.4e-16 rad of the exact heading (measured:
+// 0.93, which is 1.3 units in the last place of a heading below 2 rad - so it may differ from the host libm's by two such
+// units, not one; tests/test_gpu_prologue_tables.py asserts the bound), its sin / cos feed float32 columns only, held to one
+// float32 ulp; everything else (+, -, *, /, sqrt, fmod, comparisons) is IEEE-exact on both sides.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
