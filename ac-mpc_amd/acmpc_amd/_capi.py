@@ -171,6 +171,7 @@ SIGNATURES = {
     "acmpc_set_previous_control": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
     "acmpc_set_obstacles": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "acmpc_set_dynamics_clearance": (C.c_int, [_CTX, C.c_double, C.c_double]),
+    "acmpc_set_surface": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_set_dynamics_objective": (C.c_int, [_CTX, C.c_double, C.c_void_p]),
     "acmpc_set_dynamics_coupling": (C.c_int, [_CTX, C.c_void_p]),
     "acmpc_set_dynamics_load_transfer": (C.c_int, [_CTX, C.c_void_p]),
@@ -803,6 +804,25 @@ class Engine:
             self._check(self._lib.acmpc_set_obstacles(self._ctx, None, None, 0, 0, 0))
             return
         self._check(self._lib.acmpc_set_obstacles(self._ctx, o.ctypes.data, r.ctypes.data, o.shape[0], o.shape[1], o.shape[2]))
+
+    def set_surface(self, grip=None):
+        """Mode D's surface table (acmpc_set_surface): `grip` [P, n, 2] = (mu_f, mu_r), the scale of the front and the rear
+        axle's peak factor at every waypoint of every problem's path - or [n, 2] for one problem, or [n]: one scale for both
+        axles (dynamic_model.surface_table makes one from patches along the arc length).  A control step is driven on the
+        scales of the waypoint the candidate was nearest to one step before (waypoint 0 first).  Every value finite and > 0.
+        None clears it.  It stays until replaced or cleared, whatever else is set."""
+        if grip is None:
+            self._check(self._lib.acmpc_set_surface(self._ctx, None, 0, 0))
+            return
+        g = np.asarray(grip, dtype=np.float32)
+        if g.ndim == 1:
+            g = np.stack([g, g], axis=1)
+        if g.ndim == 2:
+            g = g[None]
+        if g.ndim != 3 or g.shape[2] != 2:
+            raise ValueError("grip must be [P, n, 2], [n, 2] or [n]")
+        g = np.ascontiguousarray(g)
+        self._check(self._lib.acmpc_set_surface(self._ctx, g.ctypes.data, g.shape[0], g.shape[1]))
 
     def score_grips(self, states, controls, dt: float, scales, segment: int = 1, weights=(1.0, 1.0, 1.0)):
         """Mode D's grip identification (acmpc_score_grips): `states` [W + 1, 3] = (vx, vy, r) - or [W + 1, 6], whose last

@@ -10,7 +10,10 @@ coefficients in kilonewtons.
 
 `stage_terms` and `objective_terms` are float64 mirrors of what acmpc_set_dynamics_terms and acmpc_set_dynamics_objective add
 to a candidate's cost and violation - rates, rear slip; the progress made good and the excess over a speed ceiling - over
-one trajectory of `DynamicBicycleParams.rollout`: what the float32 specification is measured against."""
+one trajectory of `DynamicBicycleParams.rollout`: what the float32 specification is measured against.
+
+`surface_table` makes the per-waypoint grip scales of acmpc_set_surface from patches along the arc length ("wet from 40 m to
+70 m"); `trace(..., surface=)` and the `grip=` argument of `predict_next_state` / `rollout` are its float64 mirror."""
 from __future__ import annotations
 
 import dataclasses
@@ -148,7 +151,7 @@ class DynamicBicycleParams:
         return w, self.F_zf + d_f - w, self.F_zr + d_r + w
 
     def predict_next_state(self, state, u, dt: float = 0.05, coupling=None, load_transfer=None,
-                           downforce=None) -> Tuple[np.ndarray, np.ndarray, list]:
+                           downforce=None, grip=None) -> Tuple[np.ndarray, np.ndarray, list]:
         """One explicit Euler step in float64: state (X, Y, yaw, vx, vy, r), u = (delta, pedal) with the pedal in
         [-1, 1].  Returns (next_state, x_dot, [F_fy, F_ry, F_fx, F_rx]) like the reference; the caller clips vx >= 0
         (the reference's loop does, dynamic_bicycle_model.py:180; so do the kernels, inside the step).  `coupling` = rho
@@ -159,7 +162,12 @@ class DynamicBicycleParams:
         load-dependent peak: loaded_axles() gives each axle's load, which both the side force and the coupling's cap then
         take; the returned forces are the final ones.  `downforce` = (k_f, k_r) or (k_f, k_r, v_sat) is the downforce of
         acmpc_set_dynamics_downforce in float64 (None: off): the same one pass with k_a min(vx, v_sat)^2 on each axle's load
-        under the load moved, and the exact load-dependent peak P(F_z + x); the force list holds the final forces."""
+        under the load moved, and the exact load-dependent peak P(F_z + x); the force list holds the final forces.  `grip` =
+        (mu_f, mu_r) is the surface's pair of this step (acmpc_set_surface; None: (1, 1)): the step of
+        with_axle_grip(mu_f, mu_r) - both axles' peak factors scaled wherever the step reads them."""
+        if grip is not None:
+            return self.with_axle_grip(*grip).predict_next_state(state, u, dt, coupling=coupling, load_transfer=load_transfer,
+                                                                 downforce=downforce)
         delta, pedal = float(u[0]), float(u[1])
         X, Y, yaw, vx, vy, r = (float(s) for s in state)
         den = vx + 1e-3
@@ -197,12 +205,16 @@ class DynamicBicycleParams:
         return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0 * np.sin(C * np.arctan(ba - E * (ba - np.arctan(ba))))
 
     def rollout(self, state, U, dt: float = 0.05, substeps: int = 1, low_speed_blend=None, coupling=None,
-                load_transfer=None, downforce=None) -> np.ndarray:
+                load_transfer=None, downforce=None, grip=None) -> np.ndarray:
         """The mirror over a control sequence U [n, 2] with vx clipped after every step: states [n + 1, 6].  `substeps`
         and `low_speed_blend` = (v_lo, v_hi) are the integration setting of acmpc_set_dynamics_integration in float64: a
         control step is `substeps` Euler steps of dt / substeps, and after each (vy, r) are blended towards the kinematic
         bicycle's r_k = vx tan(delta) / (lf + lr), vy_k = lr r_k by lam = clamp((vx - v_lo) / (v_hi - v_lo), 0, 1).
-        `coupling`, `load_transfer`, `downforce`: predict_next_state's, in every sub-step."""
+        `coupling`, `load_transfer`, `downforce`: predict_next_state's, in every sub-step.  `grip` = (mu_f, mu_r): one pair
+        of grip scales for the whole roll (predict_next_state's; a surface table changes it per control step: trace())."""
+        if grip is not None:
+            return self.with_axle_grip(*grip).rollout(state, U, dt, substeps=substeps, low_speed_blend=low_speed_blend,
+                                                      coupling=coupling, load_transfer=load_transfer, downforce=downforce)
         substeps = int(substeps)
         if substeps < 1:
             raise ValueError("substeps must be positive")
@@ -340,13 +352,32 @@ def predict_obstacles(position, velocity, n: int, dt: float) -> np.ndarray:
     return position[None, :, :] + velocity[None, :, :] * t[:, None, None]
 
 
+def surface_table(arc_length, patches) -> np.ndarray:
+    """The table acmpc_set_surface takes for one path, [n, 2] float32 = (mu_f, mu_r) per waypoint, from `arc_length` [n] - the
+    arc length of every waypoint (cumulative `ds` of the path table, in metres from the first) - and `patches`, a list of
+    (s_from, s_to, mu) or (s_from, s_to, mu_f, mu_r): a waypoint with s_from <= s <= s_to takes the patch's scale(s), later
+    patches override earlier ones, and a waypoint in no patch is 1.  Computed in float64, rounded once."""
+    s = np.asarray(arc_length, dtype=np.float64).ravel()
+    table = np.ones((s.size, 2), dtype=np.float64)
+    for patch in patches:
+        patch = tuple(float(v) for v in patch)
+        if len(patch) not in (3, 4):
+            raise ValueError("a patch is (s_from, s_to, mu) or (s_from, s_to, mu_f, mu_r), not %r" % (patch,))
+        scales = patch[2:] * 2 if len(patch) == 3 else patch[2:]
+        if not all(np.isfinite(m) and m > 0.0 for m in scales):
+            raise ValueError("a grip scale is finite and positive, not %r" % (scales,))
+        inside = (s >= patch[0]) & (s <= patch[1])
+        table[inside, 0], table[inside, 1] = scales
+    return table.astype(np.float32)
+
+
 TRACE_HINGES = ("box", "corridor", "rate", "slip", "ceiling", "obstacles")   # what a step squares into V, in this order
 
 
 def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min=(-0.3, -1.0), u_max=(0.3, 1.0),
           margin: float = 0.0, wheelbase=None, nn_window=None, substeps: int = 1, low_speed_blend=None, coupling=None,
           load_transfer=None, downforce=None, u_prev=None, rate_max=None, slip_max=None, speed_ceiling=None, obstacles=None,
-          radii=None) -> dict:
+          radii=None, surface=None) -> dict:
     """The float64 mirror of Engine.trace_plans for one plan under one vehicle: `params.rollout(state, U, ...)` with the
     handle's step settings, and per control step - on the state after it, against its nearest waypoint j of `table` [7, n]
     (objective_terms' search: `nn_window` from waypoint 0, None: all) - what the cost lines see and the hinges they square
@@ -355,26 +386,43 @@ def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min
     slip [n] = max(|.| - limit, 0) of stage_terms' rd, rp, b (step 0 against `u_prev`, or a zero increment; None: no limit, 0),
     ceiling [n] = max(vx - (scale v_j + offset), 0), obstacles [n, 8] = max(R_k - d_ik, 0) of clearance_terms (a NaN coordinate
     is a disc that is not there), V [n] the running sum of their squares, kink [n, 15] each hinge's distance from its kink).  `wheelbase` (default lf + lr) makes delta_ref =
-    atan(wheelbase kappa_j)."""
+    atan(wheelbase kappa_j).  `surface` [n, 2] = (mu_f, mu_r) per waypoint (acmpc_set_surface, surface_table): control step i
+    is rolled with grip = surface[j_{i-1}], the nearest waypoint of the step before and waypoint 0 first - the scale lags the
+    position by one control step, as on the device."""
     U = np.asarray(U, dtype=np.float64)
     table = np.asarray(table, dtype=np.float64)
     n = U.shape[0]
     x, y, psi, kappa, width, v = (table[row][:n] for row in (0, 1, 2, 3, 5, 6))
     L = params.lf + params.lr if wheelbase is None else float(wheelbase)
-    states = params.rollout(state, U, dt, substeps=substeps, low_speed_blend=low_speed_blend, coupling=coupling,
-                            load_transfer=load_transfer, downforce=downforce)
-    after = states[1:]
-    d2 = (after[:, 0, None] - x[None, :]) ** 2 + (after[:, 1, None] - y[None, :]) ** 2
-    if nn_window is None:
-        j = np.argmin(d2, axis=1)
-    else:
+    step = dict(substeps=substeps, low_speed_blend=low_speed_blend, coupling=coupling, load_transfer=load_transfer,
+                downforce=downforce)
+
+    def nearest(pose, prev):
+        d2 = (pose[0] - x) ** 2 + (pose[1] - y) ** 2
+        if nn_window is None:
+            return int(np.argmin(d2))
         back, ahead = nn_window
         span = back + ahead + 1
-        j = np.empty(n, dtype=np.int64)
+        first = min(max(prev - back, 0), max(n - span, 0))
+        return first + int(np.argmin(d2[first:first + span]))
+
+    j = np.empty(n, dtype=np.int64)
+    if surface is None:
+        states = params.rollout(state, U, dt, **step)
         prev = 0
-        for i, row in enumerate(d2):
-            first = min(max(prev - back, 0), max(n - span, 0))
-            prev = j[i] = first + int(np.argmin(row[first:first + span]))
+        for i in range(n):
+            prev = j[i] = nearest(states[i + 1], prev)
+    else:
+        scales = np.asarray(surface, dtype=np.float64)
+        if scales.shape != (n, 2):
+            raise ValueError("surface is [n, 2] = (mu_f, mu_r) per waypoint")
+        rolled = [np.asarray(state, dtype=np.float64)]
+        prev = 0
+        for i in range(n):
+            rolled.append(params.rollout(rolled[-1], U[i:i + 1], dt, grip=scales[prev], **step)[1])
+            prev = j[i] = nearest(rolled[-1], prev)
+        states = np.stack(rolled)
+    after = states[1:]
     e_y = -np.sin(psi[j]) * (after[:, 0] - x[j]) + np.cos(psi[j]) * (after[:, 1] - y[j])
     e_psi = np.mod(after[:, 2] - psi[j] + np.pi, 2.0 * np.pi) - np.pi
     out = dict(states=states, j=j, e_y=e_y, e_psi=e_psi, dv=after[:, 3] - v[j], dk=U[:, 0] - np.arctan(L * kappa[j]))

@@ -59,6 +59,12 @@ Downforce (acmpc_set_dynamics_downforce): `downforce` - (k_f, k_r) or (k_f, k_r,
 axle's load grow with vx^2 (dynamic_model.downforce_coefficients gives the pair from C_L A and the aero balance): the peaks and
 the coupling caps are those the tyres have at the speed driven, 29 % more at 200 km/h on the reference vehicle with C_L A = 3.
 
+Surface (acmpc_set_surface): `solve(..., surface=grip)` - [n, 2] = (mu_f, mu_r) per waypoint of this solve's path, or [n]: one
+scale for both axles (dynamic_model.surface_table makes one from "wet from 40 m to 70 m") - scales each axle's peak factor by
+the value at the waypoint a candidate is at: a damp braking zone or a cold sector changes the plan where it lies, not the whole
+horizon as a low-grip ensemble member does.  A control step is driven on the scales of the waypoint the candidate was nearest to
+one step before.  None: no table (a table set by an earlier solve is cleared).  `trace()` re-rolls under the same table.
+
 Grip adaptation (acmpc_score_grips, GripEstimator): `grip_adapt` - a dict, off by default - lets the solver find the road's
 grip from its own driving instead of being told an ensemble.  Every solve logs (state, the control applied since the
 previous solve - `previous_control`, else the last accepted plan's first control), scores a grid of grip hypotheses
@@ -196,6 +202,7 @@ class DynamicSamplingSolver:
         if clearance != (0.0, 0.0):
             self._engine.set_dynamics_clearance(*clearance)
         self._has_obstacles = False
+        self._has_surface = False
         self._plan_states = bool(config.get("plan_states", False))
         self._last_state: Optional[np.ndarray] = None   # the start state of the last solve: what trace() re-rolls from
         self._plan: Optional[np.ndarray] = None
@@ -226,7 +233,7 @@ class DynamicSamplingSolver:
 
     def trace(self, plan=None):
         """Engine.trace_plans of `plan` [n, 2] (default: the last accepted plan) from the last solve's start state, on its
-        path, previous control and obstacles, under every vehicle of the handle: dict(states [K, n + 1, 6], cost [K],
+        path, previous control, obstacles and surface table, under every vehicle of the handle: dict(states [K, n + 1, 6], cost [K],
         violation [K], terms [K, n, 22] and its named views)."""
         if self._last_state is None:
             raise ValueError("trace() follows a solve")
@@ -260,11 +267,12 @@ class DynamicSamplingSolver:
             self._applied_grip = now
             self._base_grip = (now[0] * self._adapt["bracket"][0], now[1] * self._adapt["bracket"][0])
 
-    def solve(self, state, reference_path, previous_control=None, obstacles=None, warm_steps: int = 1):
+    def solve(self, state, reference_path, previous_control=None, obstacles=None, warm_steps: int = 1, surface=None):
         """state (X, Y, yaw, vx, vy, r); reference_path a [7, n] table (rows x, y, psi, kappa, ds, width, v) or an object
         with `as_table()` / `_reference_path` giving one.  `previous_control` = (delta, pedal) applied just before this
         solve, for the rate terms' step 0; None: the first control of the last accepted plan (none before there is one).
         `obstacles` = (positions [n, K, 2], radii [K]) for this solve (Engine.set_obstacles); None: no obstacles.
+        `surface` = [n, 2] (mu_f, mu_r) per waypoint, or [n], for this solve (Engine.set_surface); None: no table.
         `warm_steps`: control steps since the previous solve (warm_start's shift)."""
         table = reference_path
         if hasattr(reference_path, "as_table"):
@@ -286,6 +294,12 @@ class DynamicSamplingSolver:
         elif self._has_obstacles:
             self._engine.set_obstacles(None)
             self._has_obstacles = False
+        if surface is not None:
+            self._engine.set_surface(np.asarray(surface, dtype=np.float32)[: self._n])
+            self._has_surface = True
+        elif self._has_surface:
+            self._engine.set_surface(None)
+            self._has_surface = False
         self._last_state = np.asarray(state, dtype=np.float32).reshape(6).copy()
         out = self._engine.optimize(self._last_state[None], self.warm_start(warm_steps)[None], None,
                                     self._N, self._rounds, self._sigma, seed=self._seed + self._calls)

@@ -139,6 +139,17 @@ int upload_previous_control(acmpc_ctx* c, hipStream_t s) {
     ACMPC_HIP(c, hipMemcpyAsync(c->d_obs, c->h_obs.data(), c->h_obs.size() * sizeof(float), hipMemcpyHostToDevice, s));
     c->obs_dirty = false;
   }
+  if (c->surf_dirty && c->surf_P != 0 && c->device_ready) {   // and the surface table staged by acmpc_set_surface
+    if (c->surf_capacity < c->h_surface.size()) {
+      (void)hipFree(c->d_surface);
+      c->d_surface = nullptr;
+      c->surf_capacity = 0;
+      ACMPC_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_surface), c->h_surface.size() * sizeof(float)));
+      c->surf_capacity = c->h_surface.size();
+    }
+    ACMPC_HIP(c, hipMemcpyAsync(c->d_surface, c->h_surface.data(), c->h_surface.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    c->surf_dirty = false;
+  }
   if (!c->uprev_dirty || c->uprev_P == 0 || c->d_uprev == nullptr) return ACMPC_OK;
   ACMPC_HIP(c, hipMemcpyAsync(c->d_uprev, c->h_uprev.data(), c->h_uprev.size() * sizeof(float), hipMemcpyHostToDevice, s));
   c->uprev_dirty = false;
@@ -229,6 +240,12 @@ int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call)
     char buf[160];
     std::snprintf(buf, sizeof buf, "shape (P=%d, n=%d) does not match the obstacles set (P=%d, n=%d): acmpc_set_obstacles", P, n,
                   c->obs_P, c->obs_n);
+    return fail(c, ACMPC_ESTATE, buf);
+  }
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC && c->surf_P != 0 && (P != c->surf_P || n != c->surf_n)) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "shape (P=%d, n=%d) does not match the surface table set (P=%d, n=%d): acmpc_set_surface", P, n,
+                  c->surf_P, c->surf_n);
     return fail(c, ACMPC_ESTATE, buf);
   }
   return ACMPC_OK;
@@ -504,6 +521,7 @@ void acmpc_destroy(acmpc_ctx* c) {
     (void)hipFree(c->d_segments);
     (void)hipFree(c->d_uprev);
     (void)hipFree(c->d_obs);
+    (void)hipFree(c->d_surface);
     (void)hipFree(c->d_progress);
     (void)hipFree(c->d_identify);
     (void)hipFree(c->d_identify_e);

@@ -1,5 +1,5 @@
 // C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
-// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the downforce, the previous control, the obstacles and the clearance setting, and the grip
+// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the downforce, the previous control, the obstacles and the clearance setting, the surface table, and the grip
 // identification (acmpc_score_grips) and the plan trace (acmpc_trace_plans), with the checks that the kernels' limits are the public header's.
 #include <algorithm>
 
@@ -138,6 +138,19 @@ const double* load_of(const acmpc_ctx* c) { return c->has_load ? c->load_setting
 const float* aero_of(const acmpc_ctx* c) { return c->has_aero ? c->aero : nullptr; }
 
 }  // namespace
+
+namespace acmpc {
+namespace capi __attribute__((visibility("hidden"))) {
+
+void surface_load_const(const acmpc_ctx* c, int k, float* out) {
+  const double none[2] = {0.0, 0.0};
+  float lc[6] = {};
+  if (derive_load(none, nullptr, c->vehicle_L[k], c->vehicle_axle[k], lc) != nullptr) std::memset(lc, 0, sizeof lc);
+  std::memcpy(out, lc, sizeof lc);
+}
+
+}  // namespace capi
+}  // namespace acmpc
 
 extern "C" {
 
@@ -384,6 +397,28 @@ int acmpc_set_obstacles(acmpc_ctx* c, const float* positions, const float* radii
   c->obs_n = n;
   c->obs_K = K;
   c->obs_dirty = true;
+  return ACMPC_OK;
+}
+
+int acmpc_set_surface(acmpc_ctx* c, const float* grip, int32_t P, int32_t n) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_surface needs a mode D handle");
+  if (grip == nullptr) {
+    c->h_surface.clear();
+    c->surf_P = c->surf_n = 0;
+    c->surf_dirty = false;
+    return ACMPC_OK;
+  }
+  if (P < 1 || P > c->prm.max_problems) return fail(c, ACMPC_EINVAL, "P must be 1 .. max_problems");
+  if (n < 1 || n > c->prm.max_steps) return fail(c, ACMPC_EINVAL, "n must be 1 .. max_steps");
+  const size_t floats = static_cast<size_t>(P) * n * 2;
+  for (size_t q = 0; q < floats; ++q)   // (a NaN compares false)
+    if (!std::isfinite(grip[q]) || !(grip[q] > 0.0f)) return fail(c, ACMPC_EINVAL, "a grip scale must be finite and > 0");
+  // everything is checked before anything is kept: a refused table leaves the handle's as it was
+  c->h_surface.assign(grip, grip + floats);
+  c->surf_P = P;
+  c->surf_n = n;
+  c->surf_dirty = true;
   return ACMPC_OK;
 }
 

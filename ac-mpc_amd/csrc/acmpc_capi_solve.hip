@@ -18,8 +18,9 @@ namespace capi __attribute__((visibility("hidden"))) {
 // And of its load transfer ("Load transfer"): the six scalars of each vehicle, and the ratios +inf while the coupling is off.
 // And of its obstacles ("Obstacles"): the device block (positions, then radii), what it was set for, and the clearance
 // setting; K = 0 while none are set, the soft part on with a weight that is not 0.
-acmpc::WithObstacles<acmpc::TermsAero> dynamics_terms(const acmpc_ctx* c) {
-  acmpc::WithObstacles<acmpc::TermsAero> t{};
+// And of its surface table ("Surface"): the device table and what it was set for.
+acmpc::WithObstacles<acmpc::TermsSurface> dynamics_terms(const acmpc_ctx* c) {
+  acmpc::WithObstacles<acmpc::TermsSurface> t{};
   t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
             std::isfinite(c->rate_max[1])) ? 1 : 0;
   t.slip = (c->slip_weight != 0.0 || std::isfinite(c->slip_max)) ? 1 : 0;
@@ -53,6 +54,31 @@ acmpc::WithObstacles<acmpc::TermsAero> dynamics_terms(const acmpc_ctx* c) {
     t.a2_f[k] = lc[3];
     t.a1_r[k] = lc[4];
     t.a2_r[k] = lc[5];
+  }
+  // ("Surface": the top-tier step whatever is on - the downforce's neutral values while it is off, and the load scalars of the
+  // vehicles derived all the same)
+  if (c->surf_P != 0) {
+    t.surface = 1;
+    if (!c->surf_dirty && c->d_surface != nullptr) {   // (every mode D call uploads first; a launch without the table is refused)
+      t.mu = c->d_surface;
+      t.mu_P = c->surf_P;
+      t.mu_n = c->surf_n;
+    }
+    if (t.aero == 0) {
+      t.k_f = t.k_r = 0.0f;
+      t.v_sat = 100.0f;
+    }
+    for (int k = 0; k < c->vehicles.K && t.loaded == 0 && t.aero == 0; ++k) {
+      float lc[6];
+      surface_load_const(c, k, lc);
+      t.c_h[k] = lc[0];
+      t.w_max[k] = lc[1];
+      t.a1_f[k] = lc[2];
+      t.a2_f[k] = lc[3];
+      t.a1_r[k] = lc[4];
+      t.a2_r[k] = lc[5];
+    }
+    if (t.coupled == 0) t.rho_f = t.rho_r = HUGE_VALF;
   }
   t.K = c->obs_K;
   if (t.K != 0 && !c->obs_dirty && c->d_obs != nullptr) {   // (every mode D call uploads first; a launch without the data is refused)

@@ -298,6 +298,14 @@ struct acmpc_ctx {
   float* d_obs = nullptr;
   size_t obs_capacity = 0;               // floats
   double clearance_weight = 0.0, clearance_margin = 0.0;
+  // mode D: the surface table (acmpc_set_surface), staged here like the obstacles until the next upload: (mu_f, mu_r)
+  // [surf_P][surf_n][2] on the host and on the device (allocated by the upload that first needs it, grown when a larger one
+  // arrives)
+  std::vector<float> h_surface;
+  int surf_P = 0, surf_n = 0;            // surf_P = 0: none set
+  bool surf_dirty = false;
+  float* d_surface = nullptr;
+  size_t surf_capacity = 0;              // floats
   // mode D: the plan trace's device block (acmpc_trace_plans): x0 | U | states | totals | terms of ONE call, made on the call's
   // first use, kept between calls and regrown when a later call needs more
   unsigned char* d_plan_trace = nullptr;
@@ -330,7 +338,10 @@ struct Regenerate {
   const float* d_extra = nullptr;   // candidate 2's controls (the LQ plan), or nullptr
 };
 acmpc::Integration dynamics_integration(const acmpc_ctx* c);
-acmpc::WithObstacles<acmpc::TermsAero> dynamics_terms(const acmpc_ctx* c);   // (after the call's uploads: upload_tables)
+// (acmpc_capi_dynamic.hip) the six load scalars of vehicle k as the surface step needs them while neither the load transfer nor
+// the downforce is on: c_h = w_max = 0 and the vehicle's own a1, a2 (zeros for a block that has none)
+void surface_load_const(const acmpc_ctx* c, int k, float* out);
+acmpc::WithObstacles<acmpc::TermsSurface> dynamics_terms(const acmpc_ctx* c);   // (after the call's uploads: upload_tables)
 acmpc::SampleSpec make_spec(const acmpc_ctx* c, double sigma_v, double sigma_k, uint64_t seed, uint32_t round);
 // (`set`: which half of the partial keys / feasible counts - chained rounds and the stream of batches alternate)
 acmpc::RolloutArgs rollout_args(const acmpc_ctx* c, const float* d_x0, const float* d_U, float* d_costs, int P, int N, int n,

@@ -149,6 +149,15 @@ struct LanePeaks {
   __device__ __forceinline__ float rear(const Vehicle&) const { return Pr; }
 };
 
+// A lane's pair typed on F (the surface table, acmpc_set_surface: every candidate of a lane under the grip scales of the waypoint
+// it is at - two per lane under f32x2): what the step multiplies into per-lane values anyway, so it adds no arithmetic.
+template <typename F>
+struct SurfacePeaks {
+  F Pf, Pr;
+  __device__ __forceinline__ F front(const Vehicle&) const { return Pf; }
+  __device__ __forceinline__ F rear(const Vehicle&) const { return Pr; }
+};
+
 // The tyre coupling of a handle (acmpc_set_dynamics_coupling, DESIGN.md section 2 "Mode D, tyre coupling"): each axle's
 // longitudinal force is clipped at rho times that axle's peak factor, and its Pacejka side force scaled by what the friction
 // ellipse leaves.  It reaches the step with the peaks, whose multiples its caps are: a peak source (above) with the two ratios
@@ -470,12 +479,26 @@ struct TermsAero : TermsLoaded {
 };
 __host__ __device__ inline bool has_downforce(const TermsAero& t) { return t.aero != 0; }
 
+// The TermsAero plus the surface table of a handle (acmpc_set_surface, DESIGN.md section 2 "Mode D, surface"): a sixth pack type.
+// mu [P][n][2] = (mu_f, mu_r) per waypoint, on the device; control step i of a candidate runs all its sub-steps on the peaks
+// Pf mu_f[j], Pr mu_r[j], j the nearest waypoint of step i - 1 (waypoint 0 before step 0): the scale lags the position by one
+// control step.  The kernels instantiated for it (acmpc_dynamic_surface.hip) run only while `surface` is set, always with the
+// aero step: c_h = w_max = 0 while the load transfer is off, rho = +inf while the coupling is off, k_f = k_r = 0 with a finite
+// v_sat while the downforce is off (the per-vehicle a1, a2 are derived all the same); every other kernel stays the code it was.
+// The launchers take the handle's settings as one of these (under the obstacles' pack, below).
+struct TermsSurface : TermsAero {
+  const float* mu;
+  int surface;                  // 0: off (mu not read); the kernels do not read it
+  int mu_P, mu_n;               // what mu was set for: the launchers refuse another shape (the kernels do not read them)
+};
+__host__ __device__ inline bool has_surface(const TermsSurface& t) { return t.surface != 0; }
+
 // Moving obstacles of a handle (acmpc_set_obstacles, acmpc_set_dynamics_clearance; DESIGN.md section 2 "Mode D, obstacles"): up
 // to kMaxObstacles discs per problem, each with a position per control step - row i is where the discs are at the state AFTER
 // control step i, the state that step's dynamic_cost sees - and a radius with the ego's folded in.  Per step, after the ceiling
 // line, disc k's penetration depth joins V (the hard part, on while K > 0) and its depth into the margin joins E (the soft part,
 // on while K > 0 and the weight is not 0).  A pack type again, over the pack of the step the handle would take without obstacles
-// (TermsObjective: the general step, TermsCoupled, TermsLoaded, TermsAero): the kernels instantiated for the four (acmpc_dynamic_obstacles
+// (TermsObjective: the general step, TermsCoupled, TermsLoaded, TermsAero; TermsSurface: acmpc_dynamic_surface.hip): the kernels instantiated for the four (acmpc_dynamic_obstacles
 // .hip) run only while obstacles are set, every other kernel stays the code it was.  obs [P][n][K][2] in the caller's frame and
 // radii [P][K] are read from global memory (problem and step are uniform in every kernel: one broadcast per step, no LDS).
 // coef: the packed rows of the launch (the first two floats of a problem's are the origin of the path's own frame,
@@ -497,7 +520,7 @@ template <typename TT>
 struct PackBase { using type = TT; };
 template <typename Base>
 struct PackBase<WithObstacles<Base>> { using type = Base; };
-// the obstacles' pack over another base (the handle's settings are a WithObstacles<TermsAero>)
+// the obstacles' pack over another base (the handle's settings are a WithObstacles<TermsSurface>)
 template <typename Base, typename From>
 inline WithObstacles<Base> obstacles_over(const WithObstacles<From>& t) {
   WithObstacles<Base> r{};
@@ -576,6 +599,60 @@ __device__ __forceinline__ AeroPeaks<VehiclePeaks> aero_peaks(int vk, const Term
 template <typename F>
 __device__ __forceinline__ AeroPeaks<VehiclePeaks> aero_peaks(int vk, const TermsState<F>&, const TermsAero& t) {
   return aero_peaks(vk, t);
+}
+
+// And for a TermsSurface: dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(..., surface_peaks<F>(aero_peaks(vk, tm...), veh, p, n,
+// j, tm...)) at the top of every control step, j the nearest waypoint(s) of the step before.  One 8-byte load from global
+// memory per candidate (the table is read as the progress table and the obstacles' rows are: no LDS) and two multiplies;
+// 0 <= j < n always, so there is no bounds code.  Where j is wave-uniform (the finalize, the trace) the load is a scalar one.
+template <typename... TM>
+constexpr bool kSurfacePack = (std::is_same<typename PackBase<typename std::remove_cv<TM>::type>::type, TermsSurface>::value || ...);
+__device__ __forceinline__ void gather_scales(const float* mu, int j, float& mf, float& mr) {
+  const f32x2 m = *reinterpret_cast<const f32x2*>(mu + 2 * static_cast<size_t>(j));
+  mf = m[0];
+  mr = m[1];
+}
+__device__ __forceinline__ void gather_scales(const float* mu, i32x2 j, f32x2& mf, f32x2& mr) {
+  const f32x2 m0 = *reinterpret_cast<const f32x2*>(mu + 2 * static_cast<size_t>(j[0]));
+  const f32x2 m1 = *reinterpret_cast<const f32x2*>(mu + 2 * static_cast<size_t>(j[1]));
+  mf = f32x2{m0[0], m1[0]};
+  mr = f32x2{m0[1], m1[1]};
+}
+// the scales of problem p's waypoint(s) j: issued ahead of the control's load or draw, multiplied in by surface_peaks
+template <typename F>
+struct SurfaceScales {
+  F mf, mr;
+};
+template <typename F>
+__device__ __forceinline__ SurfaceScales<F> surface_scales(int p, int n, typename IndexOf<F>::type j, const TermsSurface& t) {
+  SurfaceScales<F> m;
+  gather_scales(t.mu + static_cast<size_t>(p) * n * 2, j, m.mf, m.mr);
+  return m;
+}
+template <typename F>
+__device__ __forceinline__ SurfaceScales<F> surface_scales(int p, int n, typename IndexOf<F>::type j, const TermsState<F>&,
+                                                           const TermsSurface& t) {
+  return surface_scales<F>(p, n, j, t);
+}
+// Pf_s = Pf mu_f, Pr_s = Pr mu_r - one float32 multiply each, once per control step - in front of the scalars `a` of the vehicle
+template <typename F>
+__device__ __forceinline__ AeroPeaks<SurfacePeaks<F>> surface_peaks(const AeroPeaks<VehiclePeaks>& a, const Vehicle& k,
+                                                                    const SurfaceScales<F>& m) {
+  AeroPeaks<SurfacePeaks<F>> pk;
+  pk.Pf = k.Pf * m.mf;
+  pk.Pr = k.Pr * m.mr;
+  pk.rho_f = a.rho_f;
+  pk.rho_r = a.rho_r;
+  pk.c_h = a.c_h;
+  pk.w_max = a.w_max;
+  pk.a1_f = a.a1_f;
+  pk.a2_f = a.a2_f;
+  pk.a1_r = a.a1_r;
+  pk.a2_r = a.a2_r;
+  pk.k_f = a.k_f;
+  pk.k_r = a.k_r;
+  pk.v_sat = a.v_sat;
+  return pk;
 }
 
 // one float of the staged waypoint row(s) j, or of a table of one float per waypoint (stride 1)
@@ -730,21 +807,22 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // coupled kernels run, whatever the parts.  And its load transfer: while that is on, the loaded kernels run, whatever the
 // coupling and the parts.  And its downforce: while that is on, the aero kernels run, whatever the load transfer, the coupling and
 // the parts.  And its obstacles: while any are set, the obstacle kernels of the step the handle would take
-// without them run (the general, the coupled, the loaded or the aero one), looked at first.
+// without them run (the general, the coupled, the loaded or the aero one), looked at first.  And its surface table: while one is
+// set, the surface kernels run (the aero step on per-lane peaks, with or without the obstacles' lines), whatever else is on.
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
+                                  const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
+                                          const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
+                                   const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
 
 }  // namespace acmpc

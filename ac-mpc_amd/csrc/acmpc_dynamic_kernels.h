@@ -1,4 +1,4 @@
-// gfx950 kernels of mode D (the dynamic bicycle, acmpc_dynamic.h), their launch templates and the launchers of the five
+// gfx950 kernels of mode D (the dynamic bicycle, acmpc_dynamic.h), their launch templates and the launchers of the
 // units that instantiate them.  Internal: included only by acmpc_dynamic*.hip.  A rollout that scores every candidate and a
 // finalize that re-rolls the winner into the standard record: two plain launches ordered by the stream, nothing crosses
 // workgroups inside a launch, every store is a vector store.
@@ -36,6 +36,8 @@
 // takes the first row whose setting is on:
 //
 //   unit                          pack                                setter (acmpc_set_...)        kernels  launched while
+//   acmpc_dynamic_surface.hip     TermsSurface, WithObstacles<        surface                       2 x 16   a surface table is set (with obstacles:
+//                                 TermsSurface>                                                             the second pack)
 //   acmpc_dynamic_obstacles.hip   WithObstacles<TermsObjective |      obstacles                     4 x 16   obstacles are set: the pack of the
 //                                 TermsCoupled | TermsLoaded |                                              step the handle would take without
 //                                 TermsAero>
@@ -160,6 +162,8 @@ __global__ void __launch_bounds__(kDynBlock)
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
     for (int i = 0; i < n; ++i) {
+      [[maybe_unused]] SurfaceScales<F> ms;   // (the surface table: the scales of the last step's waypoint, loaded ahead of the control)
+      if constexpr (kSurfacePack<TM...>) ms = surface_scales<F>(p, n, nearest, tm...);
       F d, q;
       if constexpr (CPT == 2) {
         float d0, q0, d1, q1;
@@ -170,7 +174,8 @@ __global__ void __launch_bounds__(kDynBlock)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], aero_peaks(0, tm...));
+      if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, d, q, veh, g, g.inv_L[0], surface_peaks<F>(aero_peaks(0, tm...), veh, ms));
+      else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], aero_peaks(0, tm...));
       else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
       else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
@@ -297,13 +302,15 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
   [[maybe_unused]] LoadedPeaks<VehiclePeaks> loaded{};   // (the scalars of vehicle vk: read once, ahead of the step loop)
   if constexpr (kLoadedPack<TT...>) loaded = loaded_peaks(vk, tt...);
   [[maybe_unused]] AeroPeaks<VehiclePeaks> aero{};
-  if constexpr (kAeroPack<TT...>) aero = aero_peaks(vk, tt...);
+  if constexpr (kAeroPack<TT...> || kSurfacePack<TT...>) aero = aero_peaks(vk, tt...);
   int resident[2] = {-1, -1};   // the Philox block in slots 0, 1 and in slots 2, 3
   int knot = -1;
   I nearest = I(0);
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
     for (int i = 0; i < n; ++i) {
+      [[maybe_unused]] SurfaceScales<F> ms;   // (the surface table: loaded ahead of the draw)
+      if constexpr (kSurfacePack<TT...>) ms = surface_scales<F>(p, n, nearest, tt...);
       const int k0 = __builtin_amdgcn_readfirstlane(static_cast<int>(s_seg[2 * i]));
       if (k0 != knot) {
         knot = k0;
@@ -341,7 +348,8 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
         d = dj[0];
         q = qj[0];
       }
-      if constexpr (kAeroPack<TT...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, aero);
+      if constexpr (kSurfacePack<TT...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, d, q, veh, g, inv_L, surface_peaks<F>(aero, veh, ms));
+      else if constexpr (kAeroPack<TT...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, aero);
       else if constexpr (kLoadedPack<TT...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, loaded);
       else if constexpr (kCoupledPack<TT...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, coupled_peaks(tt...));
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
@@ -524,8 +532,11 @@ __global__ void __launch_bounds__(kWave)
   const int win_w = w.nn_back + w.nn_ahead + 1;
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
+    [[maybe_unused]] SurfaceScales<float> ms;   // (the surface table: j_prev is uniform, a scalar load)
+    if constexpr (kSurfacePack<TM...>) ms = surface_scales<float>(p, n, j_prev, tm...);
     const float d = su[2 * i], q = su[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
-    if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], aero_peaks(0, tm...));
+    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, d, q, veh, g, g.inv_L[0], surface_peaks<float>(aero_peaks(0, tm...), veh, ms));
+    else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], aero_peaks(0, tm...));
     else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
     else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
     else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[0]);
@@ -611,6 +622,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
     for (int i = 0; i < n; ++i) {
+      [[maybe_unused]] SurfaceScales<F> ms;   // (the surface table: the scales of the last step's waypoint, loaded ahead of the control)
+      if constexpr (kSurfacePack<TM...>) ms = surface_scales<F>(p, n, nearest, tm...);
       F d, q;
       if constexpr (CPT == 2) {
         float d0, q0, d1, q1;
@@ -621,7 +634,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
+      if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, d, q, veh, g, g.inv_L[k], surface_peaks<F>(aero_peaks(k, tm...), veh, ms));
+      else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
       else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
       else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
       else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
@@ -810,8 +824,11 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   const int win_w = w.nn_back + w.nn_ahead + 1;
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
+    [[maybe_unused]] SurfaceScales<float> ms;   // (the surface table: j_prev is uniform, a scalar load)
+    if constexpr (kSurfacePack<TM...>) ms = surface_scales<float>(p, n, j_prev, tm...);
     const float d = su[2 * i], q = su[2 * i + 1];
-    if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
+    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, d, q, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
+    else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
     else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
     else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
     else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[k]);
@@ -1024,11 +1041,21 @@ hipError_t launch_finalize_dynamic_aero(int layout, const FinalizeArgs& args, co
 // acmpc_dynamic_obstacles.hip: the kernels of a WithObstacles over TermsAero, TermsLoaded, TermsCoupled or TermsObjective.
 // hipErrorInvalidValue unless 1 <= K <= kMaxObstacles and terms.P / terms.n are the launch's.
 hipError_t launch_rollout_dynamic_obstacles(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                            const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
+                                            const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
 hipError_t launch_rollout_dynamic_sampled_obstacles(const RolloutArgs& args, const SampleArgs& sample,
                                                     const VehicleEnsemble& vehicles, const Integration& integration,
-                                                    const WithObstacles<TermsAero>& terms, hipStream_t s);
+                                                    const WithObstacles<TermsSurface>& terms, hipStream_t s);
 hipError_t launch_finalize_dynamic_obstacles(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                             const Integration& integration, const WithObstacles<TermsAero>& terms, hipStream_t s);
+                                             const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
+
+// acmpc_dynamic_surface.hip: the kernels of a TermsSurface, or - while obstacles are set - of a WithObstacles<TermsSurface>.
+// hipErrorInvalidValue unless terms.mu is set for the launch's P and n (and the obstacles, if any, likewise).
+hipError_t launch_rollout_dynamic_surface(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                          const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_sampled_surface(const RolloutArgs& args, const SampleArgs& sample,
+                                                  const VehicleEnsemble& vehicles, const Integration& integration,
+                                                  const WithObstacles<TermsSurface>& terms, hipStream_t s);
+hipError_t launch_finalize_dynamic_surface(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                           const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
 
 }  // namespace acmpc

@@ -32,6 +32,6 @@ struct TraceArgs {
 // its own - obstacles first, then downforce, load transfer, coupling, terms / objective, the integration, the default - so
 // that a trace is the arithmetic of the kernels that scored the plan.
 hipError_t launch_trace_dynamic(const TraceArgs& args, const VehicleEnsemble& vehicles, const Integration& integration,
-                                const WithObstacles<TermsAero>& terms, hipStream_t s);
+                                const WithObstacles<TermsSurface>& terms, hipStream_t s);
 
 }  // namespace acmpc

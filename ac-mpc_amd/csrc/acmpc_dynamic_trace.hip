@@ -106,8 +106,11 @@ __global__ void __launch_bounds__(kWave)
   const int win_w = w.nn_back + w.nn_ahead + 1;
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
+    [[maybe_unused]] SurfaceScales<float> ms;   // (the surface table: j_prev is uniform, a scalar load)
+    if constexpr (kSurfacePack<TM...>) ms = surface_scales<float>(p, n, j_prev, tm...);
     const float d = s_u[2 * i], q = s_u[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
-    if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
+    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, d, q, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
+    else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
     else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
     else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
     else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[k]);
@@ -200,24 +203,32 @@ hipError_t trace_dynamic_launch(const TraceArgs& args, const VehicleEnsemble& ve
 }  // namespace
 
 hipError_t launch_trace_dynamic(const TraceArgs& args, const VehicleEnsemble& vehicles, const Integration& g,
-                                const WithObstacles<TermsAero>& tm, hipStream_t s) {
+                                const WithObstacles<TermsSurface>& tm, hipStream_t s) {
   clear_stale_error();
   if (!integration_valid(g)) return hipErrorInvalidValue;
   if (args.n < 1 || args.n > kDynamicMaxSteps || args.M < 1 || args.P < 1) return hipErrorInvalidValue;
   if (static_cast<int64_t>(args.P) * args.M > 0x7fffffff) return hipErrorInvalidValue;
   if (vehicles.K < 1 || vehicles.K > kMaxVehicles) return hipErrorInvalidValue;
   if (args.U == nullptr || args.x0 == nullptr || args.coef == nullptr) return hipErrorInvalidValue;
+  // (nothing is launched unless the surface table is what this launch's P and n index)
+  if (has_surface(tm) && (tm.mu == nullptr || tm.mu_P != args.P || tm.mu_n != args.n)) return hipErrorInvalidValue;
   if (has_obstacles(tm)) {
-    // (nothing is launched unless the obstacle data is what this launch's P and n index)
+    // (nor unless the obstacle data is)
     if (tm.K > kMaxObstacles || tm.obs == nullptr || tm.radii == nullptr || tm.P != args.P || tm.n != args.n)
       return hipErrorInvalidValue;
-    WithObstacles<TermsAero> pack = tm;
+    if (has_surface(tm)) {
+      WithObstacles<TermsSurface> both = tm;
+      both.coef = args.coef;
+      return trace_dynamic_launch(args, vehicles, g, s, both);
+    }
+    WithObstacles<TermsAero> pack = obstacles_over<TermsAero>(tm);
     pack.coef = args.coef;
     if (has_downforce(pack)) return trace_dynamic_launch(args, vehicles, g, s, pack);
     if (has_load_transfer(pack)) return trace_dynamic_launch(args, vehicles, g, s, obstacles_over<TermsLoaded>(pack));
     if (has_coupling(pack)) return trace_dynamic_launch(args, vehicles, g, s, obstacles_over<TermsCoupled>(pack));
     return trace_dynamic_launch(args, vehicles, g, s, obstacles_over<TermsObjective>(pack));
   }
+  if (has_surface(tm)) return trace_dynamic_launch(args, vehicles, g, s, static_cast<const TermsSurface&>(tm));
   if (has_downforce(tm)) return trace_dynamic_launch(args, vehicles, g, s, static_cast<const TermsAero&>(tm));
   if (has_load_transfer(tm)) return trace_dynamic_launch(args, vehicles, g, s, static_cast<const TermsLoaded&>(tm));
   if (has_coupling(tm)) return trace_dynamic_launch(args, vehicles, g, s, static_cast<const TermsCoupled&>(tm));

@@ -410,6 +410,27 @@ int acmpc_set_obstacles(acmpc_ctx* ctx, const float* positions, const float* rad
  * keeps its previous setting. */
 int acmpc_set_dynamics_clearance(acmpc_ctx* ctx, double weight, double margin);
 
+/* Mode D, surface: a grip map along the path.  grip host [P][n][2] float32 (mu_f, mu_r): row m scales the front and the rear
+ * axle's peak factor at waypoint m of problem p's path (P and n those of acmpc_set_paths).  NULL clears the setting (the other
+ * arguments are then ignored).  With j_i the nearest waypoint that control step i's cost used and j_{-1} = 0 (the path is cut at
+ * the car, and the windowed search starts from 0 as well), control step i of a candidate runs all of its sub-steps on
+ *   Pf_s = Pf mu_f[j_{i-1}];   Pr_s = Pr mu_r[j_{i-1}]        one float32 multiply each, once per control step
+ * with Pf, Pr the peaks the step would otherwise start from (the vehicle's, or each ensemble member's own; every vehicle follows
+ * its own trajectory's j, the table is shared).  THE SCALE LAGS THE POSITION BY ONE CONTROL STEP: step i is driven on the grip of
+ * where step i - 1 ended.  Pf_s, Pr_s stand wherever the step reads the peaks - the downforce's psi, the caps, the loaded peaks,
+ * the Pacejka factor; B, C, E and the load transfer's a1, a2 are untouched.  The step under the setting is the top-tier step
+ * (the downforce's), whatever else the handle has on; a tier that is off gets its neutral value - rho = +inf (coupling), c_h =
+ * w_max = 0 (load transfer), k_f = k_r = 0 with a finite v_sat (downforce) - which gives the lower tiers' bits for finite forces.
+ * Costs, violations, keys, records and the softmin are otherwise untouched; the finalize's re-roll and acmpc_trace_plans run the
+ * same step (in a trace, slot 0 of the previous row names the waypoint whose scale a step used).  acmpc_score_grips does not read
+ * the table: a log has no pose.  Staged on the host; the table travels to the device with the tables, on the next call's stream
+ * (acmpc_sync_tables covers it), and stays until replaced or cleared; it survives every acmpc_set_dynamics* call and
+ * acmpc_set_obstacles.  No device work.  ACMPC_ESTATE for a handle whose mode is not ACMPC_MODE_DYNAMIC; ACMPC_EINVAL for P
+ * outside 1 .. max_problems, n outside 1 .. max_steps or a value that is not finite and > 0 - the handle then keeps what it had; a
+ * later mode D call (acmpc_trace_plans included) whose P or n is not the stored one returns ACMPC_ESTATE.  DESIGN.md section 2
+ * "Mode D, surface". */
+int acmpc_set_surface(acmpc_ctx* ctx, const float* grip /* [P][n][2], NULL: off */, int32_t P, int32_t n);
+
 /* Mode D, grip identification: which vehicle did a logged stretch of driving come from?  K hypotheses - the handle's
  * vehicle 0 (the block of acmpc_set_dynamics, or member 0 of acmpc_set_dynamics_ensemble) with Df scales[k][0] and
  * Dr scales[k][1], derived as every block is (the two peaks in float64, rounded once; everything else vehicle 0's own

@@ -58,6 +58,12 @@ v_sat, 100 m/s when left out): the TermsAero kernels of csrc/acmpc_dynamic_aero.
 `dynamic_aero_substep`; and with `--identify`, identify_grip_aero_kernel (`identify_grip_aero`).  To price it, alternate
 `--coupling 1,1 --load-transfer 0.35` with the same plus `--downforce 7.35e-4,1.1025e-3` in one job on one card.
 
+With `--surface` every handle is given a surface table (acmpc_set_surface: a seeded table in [0.5, 1] over all of the handle's
+problems and steps, SURFACE_SEED below): the TermsSurface kernels of csrc/acmpc_dynamic_surface.hip - the aero step on per-lane
+peaks - with whatever else is set beside it, priced with `dynamic_surface_step` + M `dynamic_surface_substep` (the table adds one
+8-byte load and two multiplies per candidate and control step, and per-lane peaks where the aero step reads scalars).  To price it, alternate `--coupling 1,1 --load-transfer 0.35 --downforce
+7.35e-4,1.1025e-3` with the same plus `--surface` in one job on one card.  acmpc_score_grips does not read the table.
+
 With `--identify` the grip identification (acmpc_score_grips: host pointers, one blocking round trip) is timed at K = 4 096
 (the 64 x 64 split grid) and K = 65 536 (256 x 256) hypotheses over a window of W = 40 steps, in one-step (L = 1) and
 eight-step (L = 8) segments, under the run's integration setting: p50 / p99 of the call, the static VALU count per
@@ -70,7 +76,7 @@ With `--trace` the plan trace (acmpc_trace_plans: host pointers, one blocking ro
 run's settings: p50 / p99 of the call with all three outputs, and of the states alone.
 
 usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms] [--objective] [--coupling RF,RR]
-                                      [--load-transfer H[,FRAC]] [--downforce KF,KR[,VSAT]]
+                                      [--load-transfer H[,FRAC]] [--downforce KF,KR[,VSAT]] [--surface]
                                       [--sampled | --optimize [--update softmin] | --identify | --trace]"""
 import argparse
 import json
@@ -99,6 +105,8 @@ OBJECTIVE_ON = dict(progress_weight=1.0, speed_ceiling=(1.1, 0.0))
 COUPLING = None           # --coupling: the tyre coupling (rho_f, rho_r) every handle of this run is given
 LOAD_TRANSFER = None      # --load-transfer: the load transfer (h_cg, w_frac) every handle of this run is given
 DOWNFORCE = None          # --downforce: the downforce (k_f, k_r, v_sat) every handle of this run is given
+SURFACE = False           # --surface: a seeded surface table in [0.5, 1] on every handle of this run
+SURFACE_SEED = 27
 
 
 def integrate(eng):
@@ -116,6 +124,9 @@ def integrate(eng):
         eng.set_dynamics_load_transfer(LOAD_TRANSFER)
     if DOWNFORCE is not None:
         eng.set_dynamics_downforce(DOWNFORCE)
+    if SURFACE:   # (a handle's solves use all of its problems and steps)
+        rng = np.random.default_rng(SURFACE_SEED)
+        eng.set_surface(rng.uniform(0.5, 1.0, (eng.params.max_problems, eng.params.max_steps, 2)).astype(np.float32))
     return eng
 
 
@@ -123,7 +134,7 @@ def fine_issue_roof(bench, candidates, steps, kernel_s, name):
     """issue_roof for a FINE kernel: VALU per control step = the step loop's trip + M sub-step trips, priced with the
     sub-step loop's mix (which is nearly all of it)."""
     mix, mix_path = bench.newest_profile("isa_mix.json")
-    kind = "_aero_" if DOWNFORCE is not None else "_loaded_" if LOAD_TRANSFER is not None else "_coupled_" if COUPLING is not None else "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
+    kind = "_surface_" if SURFACE else "_aero_" if DOWNFORCE is not None else "_loaded_" if LOAD_TRANSFER is not None else "_coupled_" if COUPLING is not None else "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
     step, sub = mix["entries"][name + kind + "step"], mix["entries"][name + kind + "substep"]
     per_step = (sum(step["valu"].values()) + INTEGRATION[0] * sum(sub["valu"].values())) / float(sub["candidates_per_lane"])
     counted = (per_step, mix_path + " (static count: step trip + M sub-step trips)", {"source_sha256": mix.get("source_sha256")})
@@ -137,7 +148,7 @@ def issue_roof(bench, candidates, steps, kernel_s, name="dynamic"):
     """bench.valu_roofline for the `dynamic` entry (`dynamic_ensemble`: candidates = vehicle-candidates): the step loop's
     static VALU count per candidate-step (the isa mix, whose sources must be the loaded build's -
     `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
-    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None or COUPLING is not None or LOAD_TRANSFER is not None or DOWNFORCE is not None) and name in ("dynamic", "dynamic_ensemble"):
+    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None or COUPLING is not None or LOAD_TRANSFER is not None or DOWNFORCE is not None or SURFACE) and name in ("dynamic", "dynamic_ensemble"):
         return fine_issue_roof(bench, candidates, steps, kernel_s, name)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     entry = mix["entries"][name]
@@ -168,8 +179,10 @@ def main():
     ap.add_argument("--coupling", default=None, help="RF,RR (or one ratio for both axles): the tyre coupling on every handle")
     ap.add_argument("--load-transfer", default=None, help="H[,FRAC]: the load transfer (CG height, w_frac = 0.9) on every handle")
     ap.add_argument("--downforce", default=None, help="KF,KR[,VSAT]: the downforce (per-axle coefficients, v_sat = 100) on every handle")
+    ap.add_argument("--surface", action="store_true", help="a seeded surface table in [0.5, 1] on every handle")
     args = ap.parse_args()
-    global INTEGRATION, TERMS, OBJECTIVE, COUPLING, LOAD_TRANSFER, DOWNFORCE
+    global INTEGRATION, TERMS, OBJECTIVE, COUPLING, LOAD_TRANSFER, DOWNFORCE, SURFACE
+    SURFACE = bool(args.surface)
     if args.downforce is not None:
         aero = tuple(float(v) for v in args.downforce.split(","))
         if len(aero) not in (2, 3):
@@ -529,6 +542,8 @@ def measure(args, K):
         out.update(load_transfer=list(LOAD_TRANSFER))
     if DOWNFORCE is not None:
         out.update(downforce=list(DOWNFORCE))
+    if SURFACE:
+        out.update(surface="uniform [0.5, 1], seed %d" % SURFACE_SEED)
     if K > 1:
         out.update(vehicles=K, reduce=args.reduce, grips=list(GRIPS[:K]))
 

@@ -85,6 +85,13 @@ ENTRIES = {
     "dynamic_aero_substep": ("acmpc_dynamic_aero.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_9TermsAeroEEE", None),
     "dynamic_ensemble_aero_step": ("acmpc_dynamic_aero.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_9TermsAeroEEE", None),
     "dynamic_ensemble_aero_substep": ("acmpc_dynamic_aero.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_9TermsAeroEEE", None),
+    # mode D with a surface table (acmpc_set_surface: the TermsSurface kernels of acmpc_dynamic_surface.hip, the aero step on
+    # per-lane peaks): the table's instructions = `dynamic_surface_step` - `dynamic_aero_step` - the gather's address arithmetic,
+    # its loads and the two multiplies, once per control step; the sub-step differs by what per-lane peaks cost against scalars
+    "dynamic_surface_step": ("acmpc_dynamic_surface.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12TermsSurfaceEEE", None),
+    "dynamic_surface_substep": ("acmpc_dynamic_surface.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12TermsSurfaceEEE", None),
+    "dynamic_ensemble_surface_step": ("acmpc_dynamic_surface.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12TermsSurfaceEEE", None),
+    "dynamic_ensemble_surface_substep": ("acmpc_dynamic_surface.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12TermsSurfaceEEE", None),
     # mode D's grip identification (acmpc_score_grips, one hypothesis per lane): the sub-step loop of its step kernel - the
     # dynamics and the blend's block, WITHOUT the pose (nothing reads it there: no sincos_spec(yaw), no X, Y, yaw updates).
     # VALU per hypothesis and control step = M trips of it + `identify_grip_step`: the control's terms and the residual, the
@@ -107,13 +114,14 @@ CANDIDATES_PER_LANE = {"fused_round": 1, "identify_grip": 1, "identify_grip_step
 OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dynamic_ensemble_fine_step",
          "dynamic_terms_step", "dynamic_ensemble_terms_step", "dynamic_objective_step", "dynamic_ensemble_objective_step",
          "dynamic_coupled_step", "dynamic_ensemble_coupled_step", "dynamic_loaded_step", "dynamic_ensemble_loaded_step",
-         "dynamic_aero_step", "dynamic_ensemble_aero_step",
+         "dynamic_aero_step", "dynamic_ensemble_aero_step", "dynamic_surface_step", "dynamic_ensemble_surface_step",
          "identify_grip_step", "identify_grip_coupled_step", "identify_grip_loaded_step", "identify_grip_aero_step")
 # (exit test at the head: closes with s_branch)
 ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep",
            "dynamic_objective_substep", "dynamic_ensemble_objective_substep", "dynamic_coupled_substep",
            "dynamic_ensemble_coupled_substep", "dynamic_loaded_substep", "dynamic_ensemble_loaded_substep", "dynamic_aero_substep",
-           "dynamic_ensemble_aero_substep", "identify_grip", "identify_grip_coupled", "identify_grip_loaded", "identify_grip_aero")
+           "dynamic_ensemble_aero_substep", "dynamic_surface_substep", "dynamic_ensemble_surface_substep", "identify_grip",
+           "identify_grip_coupled", "identify_grip_loaded", "identify_grip_aero")
 
 
 def source_hash():
