@@ -172,6 +172,8 @@ SIGNATURES = {
     "acmpc_set_obstacles": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "acmpc_set_dynamics_clearance": (C.c_int, [_CTX, C.c_double, C.c_double]),
     "acmpc_set_surface": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
+    "acmpc_set_dynamics_actuator": (C.c_int, [_CTX, C.c_void_p]),
+    "acmpc_set_actuator_state": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
     "acmpc_set_dynamics_objective": (C.c_int, [_CTX, C.c_double, C.c_void_p]),
     "acmpc_set_dynamics_coupling": (C.c_int, [_CTX, C.c_void_p]),
     "acmpc_set_dynamics_load_transfer": (C.c_int, [_CTX, C.c_void_p]),
@@ -823,6 +825,30 @@ class Engine:
             raise ValueError("grip must be [P, n, 2], [n, 2] or [n]")
         g = np.ascontiguousarray(g)
         self._check(self._lib.acmpc_set_surface(self._ctx, g.ctypes.data, g.shape[0], g.shape[1]))
+
+    def set_dynamics_actuator(self, tau=None):
+        """Mode D's actuator lag (acmpc_set_dynamics_actuator): `tau` = (tau_d, tau_p), the time constants in seconds of the
+        steering and the pedal actuator, each finite and >= 0 - every rollout then drives the vehicle on the first-order response
+        to a candidate's commands (the mean of that response over each control step), while the cost's input terms, the rates
+        and the records stay on the commands.  (0, 0) is on with no lag; None turns the setting off.  It stays until replaced,
+        whatever else is set."""
+        if tau is None:
+            self._check(self._lib.acmpc_set_dynamics_actuator(self._ctx, None))
+            return
+        t = np.ascontiguousarray(np.asarray(tau, dtype=np.float64).reshape(-1))
+        if t.shape != (2,):
+            raise ValueError("tau must be (tau_d, tau_p)")
+        self._check(self._lib.acmpc_set_dynamics_actuator(self._ctx, t.ctypes.data))
+
+    def set_actuator_state(self, a0=None):
+        """The measured actuator positions at the start of the plan (acmpc_set_actuator_state): `a0` [P, 2] = (a_d, a_p) per
+        problem, or [2] for one problem; None clears them (step 0's own command then stands for them: no lag in the first step).
+        Read only while set_dynamics_actuator is on; a later solve with another P is refused."""
+        if a0 is None:
+            self._check(self._lib.acmpc_set_actuator_state(self._ctx, None, 0))
+            return
+        a = np.ascontiguousarray(np.asarray(a0, dtype=np.float32).reshape(-1, 2))
+        self._check(self._lib.acmpc_set_actuator_state(self._ctx, a.ctypes.data, a.shape[0]))
 
     def score_grips(self, states, controls, dt: float, scales, segment: int = 1, weights=(1.0, 1.0, 1.0)):
         """Mode D's grip identification (acmpc_score_grips): `states` [W + 1, 3] = (vx, vy, r) - or [W + 1, 6], whose last

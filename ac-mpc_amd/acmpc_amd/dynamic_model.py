@@ -13,7 +13,11 @@ to a candidate's cost and violation - rates, rear slip; the progress made good a
 one trajectory of `DynamicBicycleParams.rollout`: what the float32 specification is measured against.
 
 `surface_table` makes the per-waypoint grip scales of acmpc_set_surface from patches along the arc length ("wet from 40 m to
-70 m"); `trace(..., surface=)` and the `grip=` argument of `predict_next_state` / `rollout` are its float64 mirror."""
+70 m"); `trace(..., surface=)` and the `grip=` argument of `predict_next_state` / `rollout` are its float64 mirror.
+
+`actuator_coefficients` and `actuator_response` are the float64 mirror of acmpc_set_dynamics_actuator - first-order lags on the
+steering and the pedal: the vehicle is driven on the mean of each actuator's response over the control step - and `actuator=` of
+`rollout` and `trace` rolls a plan on that applied control while every cost line stays on the command."""
 from __future__ import annotations
 
 import dataclasses
@@ -205,13 +209,20 @@ class DynamicBicycleParams:
         return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0 * np.sin(C * np.arctan(ba - E * (ba - np.arctan(ba))))
 
     def rollout(self, state, U, dt: float = 0.05, substeps: int = 1, low_speed_blend=None, coupling=None,
-                load_transfer=None, downforce=None, grip=None) -> np.ndarray:
+                load_transfer=None, downforce=None, grip=None, actuator=None) -> np.ndarray:
         """The mirror over a control sequence U [n, 2] with vx clipped after every step: states [n + 1, 6].  `substeps`
         and `low_speed_blend` = (v_lo, v_hi) are the integration setting of acmpc_set_dynamics_integration in float64: a
         control step is `substeps` Euler steps of dt / substeps, and after each (vy, r) are blended towards the kinematic
         bicycle's r_k = vx tan(delta) / (lf + lr), vy_k = lr r_k by lam = clamp((vx - v_lo) / (v_hi - v_lo), 0, 1).
         `coupling`, `load_transfer`, `downforce`: predict_next_state's, in every sub-step.  `grip` = (mu_f, mu_r): one pair
-        of grip scales for the whole roll (predict_next_state's; a surface table changes it per control step: trace())."""
+        of grip scales for the whole roll (predict_next_state's; a surface table changes it per control step: trace()).
+        `actuator` = (tau, a0) - tau = (tau_d, tau_p) in seconds, a0 = (a_d, a_p) the actuator positions at the start or None
+        (U[0] then stands for them) - rolls on actuator_response's applied control instead of U (acmpc_set_dynamics_actuator)."""
+        if actuator is not None:
+            tau, a0 = actuator
+            applied, _ = actuator_response(U, a0, tau, dt)
+            return self.rollout(state, applied, dt, substeps=substeps, low_speed_blend=low_speed_blend, coupling=coupling,
+                                load_transfer=load_transfer, downforce=downforce, grip=grip)
         if grip is not None:
             return self.with_axle_grip(*grip).rollout(state, U, dt, substeps=substeps, low_speed_blend=low_speed_blend,
                                                       coupling=coupling, load_transfer=load_transfer, downforce=downforce)
@@ -371,13 +382,45 @@ def surface_table(arc_length, patches) -> np.ndarray:
     return table.astype(np.float32)
 
 
+def actuator_coefficients(tau, dt: float) -> Tuple[np.ndarray, np.ndarray]:
+    """(k [2], m [2]) of acmpc_set_dynamics_actuator in float64 for tau = (tau_d, tau_p) seconds and the control step dt:
+    k_c = exp(-dt / tau_c), what is left of an error after one control step, and m_c = (tau_c / dt)(1 - k_c), the mean of what is
+    left over the step's interval; tau_c = 0 gives k_c = m_c = 0.  For tau_c > 0: 0 < k_c < m_c < 1."""
+    tau = np.asarray(tau, dtype=np.float64).reshape(2)
+    if not np.all(np.isfinite(tau) & (tau >= 0.0)):
+        raise ValueError("tau_d, tau_p are finite and >= 0, not %r" % (tuple(tau),))
+    k, m = np.zeros(2), np.zeros(2)
+    on = tau > 0.0
+    k[on] = np.exp(-float(dt) / tau[on])
+    m[on] = (tau[on] / float(dt)) * (1.0 - k[on])
+    return k, m
+
+
+def actuator_response(U, a0, tau, dt: float) -> Tuple[np.ndarray, np.ndarray]:
+    """The float64 mirror of the actuator lag over the commands U [n, 2] = (delta, pedal) from the positions a0 = (a_d, a_p)
+    (None: U[0], so that the first step has no lag): per control step and channel e = u_i - a, applied_i = u_i - m e - what the
+    vehicle is driven on during step i, the interval mean of the exact first-order response to the held command - and
+    a = u_i - k e, the position at the step's end.  Returns (applied [n, 2], positions [n + 1, 2]), positions[0] = a0."""
+    U = np.asarray(U, dtype=np.float64).reshape(-1, 2)
+    k, m = actuator_coefficients(tau, dt)
+    a = U[0].copy() if a0 is None else np.asarray(a0, dtype=np.float64).reshape(2).copy()
+    applied, positions = np.empty_like(U), np.empty((U.shape[0] + 1, 2))
+    positions[0] = a
+    for i, u in enumerate(U):
+        e = u - a
+        applied[i] = u - m * e
+        a = u - k * e
+        positions[i + 1] = a
+    return applied, positions
+
+
 TRACE_HINGES = ("box", "corridor", "rate", "slip", "ceiling", "obstacles")   # what a step squares into V, in this order
 
 
 def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min=(-0.3, -1.0), u_max=(0.3, 1.0),
           margin: float = 0.0, wheelbase=None, nn_window=None, substeps: int = 1, low_speed_blend=None, coupling=None,
           load_transfer=None, downforce=None, u_prev=None, rate_max=None, slip_max=None, speed_ceiling=None, obstacles=None,
-          radii=None, surface=None) -> dict:
+          radii=None, surface=None, actuator=None) -> dict:
     """The float64 mirror of Engine.trace_plans for one plan under one vehicle: `params.rollout(state, U, ...)` with the
     handle's step settings, and per control step - on the state after it, against its nearest waypoint j of `table` [7, n]
     (objective_terms' search: `nn_window` from waypoint 0, None: all) - what the cost lines see and the hinges they square
@@ -388,8 +431,10 @@ def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min
     is a disc that is not there), V [n] the running sum of their squares, kink [n, 15] each hinge's distance from its kink).  `wheelbase` (default lf + lr) makes delta_ref =
     atan(wheelbase kappa_j).  `surface` [n, 2] = (mu_f, mu_r) per waypoint (acmpc_set_surface, surface_table): control step i
     is rolled with grip = surface[j_{i-1}], the nearest waypoint of the step before and waypoint 0 first - the scale lags the
-    position by one control step, as on the device."""
+    position by one control step, as on the device.  `actuator` = (tau, a0) (acmpc_set_dynamics_actuator, rollout's): the states
+    are rolled on actuator_response's applied control; dk, the box and the rates stay on the command U."""
     U = np.asarray(U, dtype=np.float64)
+    driven = U if actuator is None else actuator_response(U, actuator[1], actuator[0], dt)[0]
     table = np.asarray(table, dtype=np.float64)
     n = U.shape[0]
     x, y, psi, kappa, width, v = (table[row][:n] for row in (0, 1, 2, 3, 5, 6))
@@ -408,7 +453,7 @@ def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min
 
     j = np.empty(n, dtype=np.int64)
     if surface is None:
-        states = params.rollout(state, U, dt, **step)
+        states = params.rollout(state, driven, dt, **step)
         prev = 0
         for i in range(n):
             prev = j[i] = nearest(states[i + 1], prev)
@@ -419,7 +464,7 @@ def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min
         rolled = [np.asarray(state, dtype=np.float64)]
         prev = 0
         for i in range(n):
-            rolled.append(params.rollout(rolled[-1], U[i:i + 1], dt, grip=scales[prev], **step)[1])
+            rolled.append(params.rollout(rolled[-1], driven[i:i + 1], dt, grip=scales[prev], **step)[1])
             prev = j[i] = nearest(rolled[-1], prev)
         states = np.stack(rolled)
     after = states[1:]

@@ -65,6 +65,16 @@ the value at the waypoint a candidate is at: a damp braking zone or a cold secto
 horizon as a low-grip ensemble member does.  A control step is driven on the scales of the waypoint the candidate was nearest to
 one step before.  None: no table (a table set by an earlier solve is cleared).  `trace()` re-rolls under the same table.
 
+Actuator lag (acmpc_set_dynamics_actuator, acmpc_set_actuator_state): `actuator_lag` - (tau_d, tau_p), the time constants in
+seconds of the steering rack and the pedal actuator, default None - rolls every candidate on the first-order response to its
+commands (the mean of that response over each control step), so that a plan turns in and comes off the brake as early as the
+actuators need; the input box, dk, the rates and the controls returned stay commands.  `solve(..., actuator_state=(a_d, a_p))`
+gives the measured positions at the start of the plan; when it is left out the solver keeps its own float64 estimate
+(`solver.actuator_state`): the estimate of the previous solve - at first `previous_control`, or the last plan's first control -
+advanced through the first `warm_steps` controls of the last accepted plan (dynamic_model.actuator_response); before there is a
+plan, `previous_control`, or none (the first command then stands for the positions).  `trace()` re-rolls under the same lag and
+positions.  A dead time is not modelled: roll the start state forward under the controls already sent.
+
 Grip adaptation (acmpc_score_grips, GripEstimator): `grip_adapt` - a dict, off by default - lets the solver find the road's
 grip from its own driving instead of being told an ensemble.  Every solve logs (state, the control applied since the
 previous solve - `previous_control`, else the last accepted plan's first control), scores a grid of grip hypotheses
@@ -82,7 +92,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import _capi
-from .dynamic_model import DynamicBicycleParams
+from .dynamic_model import DynamicBicycleParams, actuator_coefficients, actuator_response
 from .grip_estimator import GripEstimator
 
 SOLVED = "solved"
@@ -163,6 +173,12 @@ class DynamicSamplingSolver:
         coupling = _capi.dynamics_coupling(config.get("tyre_coupling"))
         load_transfer = _capi.dynamics_load_transfer(config.get("load_transfer"))
         downforce = _capi.dynamics_downforce(config.get("downforce"))
+        lag = config.get("actuator_lag")
+        if lag is not None:
+            lag = tuple(float(v) for v in np.asarray(lag, dtype=np.float64).reshape(-1))
+            if len(lag) != 2:
+                raise ValueError("actuator_lag is (tau_d, tau_p), not %r" % (config.get("actuator_lag"),))
+            actuator_coefficients(lag, self._dt)             # (ValueError for a negative or non-finite time constant)
         clearance = (float(config.get("clearance_cost", 0.0)), float(config.get("clearance_margin", 0.0)))
         if not all(0.0 <= v <= float(np.finfo(np.float32).max) for v in clearance):   # (a NaN compares false)
             raise ValueError("clearance_cost and clearance_margin must be finite and >= 0, not %r" % (clearance,))
@@ -201,6 +217,10 @@ class DynamicSamplingSolver:
             self._engine.set_dynamics_downforce(downforce)
         if clearance != (0.0, 0.0):
             self._engine.set_dynamics_clearance(*clearance)
+        self._lag = lag
+        self._actuator: Optional[np.ndarray] = None   # the positions the last solve started from (float64), None: cleared
+        if lag is not None:
+            self._engine.set_dynamics_actuator(lag)
         self._has_obstacles = False
         self._has_surface = False
         self._plan_states = bool(config.get("plan_states", False))
@@ -223,6 +243,25 @@ class DynamicSamplingSolver:
     def engine(self):
         return self._engine
 
+    @property
+    def actuator_state(self):
+        """`actuator_lag`: the actuator positions (a_d, a_p) the last solve started its plans from, float64 - given, or the
+        solver's own estimate; None before there is one (the plans' first commands then stood for them)."""
+        return None if self._actuator is None else self._actuator.copy()
+
+    def _actuator_estimate(self, previous_control, warm_steps):
+        """The positions at the start of this solve's plans: the last estimate (at first `previous_control`, else the last plan's
+        first control) advanced through the first `warm_steps` controls of the last accepted plan."""
+        if self._plan is None:
+            return None if previous_control is None else np.asarray(previous_control, dtype=np.float64).reshape(2)
+        start = self._actuator
+        if start is None:
+            start = self._plan[0] if previous_control is None else previous_control
+        steps = min(max(int(warm_steps), 0), self._n)
+        sent = np.asarray(self._plan[:steps], dtype=np.float64)
+        start = np.asarray(start, dtype=np.float64).reshape(2)
+        return start.copy() if steps == 0 else actuator_response(sent, start, self._lag, self._dt)[1][-1]
+
     def warm_start(self, steps: int = 1) -> np.ndarray:
         """The centre of the next solve: the last plan shifted by `steps` control steps (its last control repeated), zeros
         at first."""
@@ -233,7 +272,7 @@ class DynamicSamplingSolver:
 
     def trace(self, plan=None):
         """Engine.trace_plans of `plan` [n, 2] (default: the last accepted plan) from the last solve's start state, on its
-        path, previous control, obstacles and surface table, under every vehicle of the handle: dict(states [K, n + 1, 6], cost [K],
+        path, previous control, obstacles, surface table and actuator positions, under every vehicle of the handle: dict(states [K, n + 1, 6], cost [K],
         violation [K], terms [K, n, 22] and its named views)."""
         if self._last_state is None:
             raise ValueError("trace() follows a solve")
@@ -267,13 +306,15 @@ class DynamicSamplingSolver:
             self._applied_grip = now
             self._base_grip = (now[0] * self._adapt["bracket"][0], now[1] * self._adapt["bracket"][0])
 
-    def solve(self, state, reference_path, previous_control=None, obstacles=None, warm_steps: int = 1, surface=None):
+    def solve(self, state, reference_path, previous_control=None, obstacles=None, warm_steps: int = 1, surface=None,
+              actuator_state=None):
         """state (X, Y, yaw, vx, vy, r); reference_path a [7, n] table (rows x, y, psi, kappa, ds, width, v) or an object
         with `as_table()` / `_reference_path` giving one.  `previous_control` = (delta, pedal) applied just before this
         solve, for the rate terms' step 0; None: the first control of the last accepted plan (none before there is one).
         `obstacles` = (positions [n, K, 2], radii [K]) for this solve (Engine.set_obstacles); None: no obstacles.
         `surface` = [n, 2] (mu_f, mu_r) per waypoint, or [n], for this solve (Engine.set_surface); None: no table.
-        `warm_steps`: control steps since the previous solve (warm_start's shift)."""
+        `actuator_state` = (a_d, a_p), the measured actuator positions now, with `actuator_lag` (Engine.set_actuator_state);
+        None: the solver's own estimate.  `warm_steps`: control steps since the previous solve (warm_start's shift)."""
         table = reference_path
         if hasattr(reference_path, "as_table"):
             table = reference_path.as_table()
@@ -283,6 +324,10 @@ class DynamicSamplingSolver:
         self._engine.set_paths(table)
         if self._estimator is not None:
             self._adapt_grip(state, previous_control)
+        if self._lag is not None:   # (before the rate terms fill `previous_control` in: the estimate starts from what was given)
+            self._actuator = (self._actuator_estimate(previous_control, warm_steps) if actuator_state is None
+                              else np.asarray(actuator_state, dtype=np.float64).reshape(2).copy())
+            self._engine.set_actuator_state(self._actuator)
         if self._rate_terms:
             if previous_control is None and self._plan is not None:
                 previous_control = self._plan[0]

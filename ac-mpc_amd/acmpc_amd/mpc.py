@@ -133,7 +133,10 @@ class SpatialMPC:
         (`elapsed` then shifts the warm start by round(elapsed / rollout_dt) control steps, None: one); not read otherwise.
         In mode D `projected_control` = (the speed the plan reaches under each control, the steering angle) - what the
         command selectors and the speed PID take, as in mode T - and `projected_pedal` [n], `plan_states` [n + 1, 6] and
-        `plan_violation` are left beside the reference's attributes."""
+        `plan_violation` are left beside the reference's attributes.  The config key `actuator_lag` = (tau_d, tau_p) reaches
+        mode D's solver as it is (first-order lags on the steering and the pedal in every rollout); the actuator positions a solve
+        starts from are that solver's own estimate, advanced through the controls of the last plan that `elapsed` says were
+        sent."""
         n = self.MPC_horizon - 1
         solver = self._control_solver
         if solver.dynamic:

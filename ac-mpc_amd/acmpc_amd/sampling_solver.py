@@ -255,6 +255,7 @@ class ControlSolver:
     def solve(self, spatial_state: np.ndarray, reference_path: ReferencePath) -> SimpleNamespace:
         if self.dynamic:
             # mode D rolls the pose and the measured body velocities; the result carries `states` [n + 1, 6] beside `x`
+            # (with `actuator_lag` the actuator positions are the dynamic solver's own estimate: no measurement comes this way)
             if self.motion is None:
                 raise ValueError("rollout_mode 'D' needs motion = (vx, vy, r), the measured body velocities")
             state = np.concatenate([np.asarray(self.pose, dtype=np.float64), np.asarray(self.motion, dtype=np.float64)])

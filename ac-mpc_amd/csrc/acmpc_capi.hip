@@ -119,6 +119,7 @@ int ensure_device(acmpc_ctx* c) {
                                                  acmpc::verified_frame_floats(std::max(std::min(p.max_steps, kMaxVerifiedSteps),
                                                                                        acmpc::kVerifiedWindow))));
   if (p.mode == ACMPC_MODE_DYNAMIC) ACMPC_HIP(c, alloc_once(&c->d_uprev, static_cast<size_t>(p.max_problems) * 2 * sizeof(float)));
+  if (p.mode == ACMPC_MODE_DYNAMIC) ACMPC_HIP(c, alloc_once(&c->d_astate, static_cast<size_t>(p.max_problems) * 2 * sizeof(float)));
   if (p.mode == ACMPC_MODE_DYNAMIC)
     ACMPC_HIP(c, alloc_once(&c->d_progress, static_cast<size_t>(p.max_problems) * p.max_steps * sizeof(float)));
   c->device_ready = true;
@@ -149,6 +150,10 @@ int upload_previous_control(acmpc_ctx* c, hipStream_t s) {
     }
     ACMPC_HIP(c, hipMemcpyAsync(c->d_surface, c->h_surface.data(), c->h_surface.size() * sizeof(float), hipMemcpyHostToDevice, s));
     c->surf_dirty = false;
+  }
+  if (c->astate_dirty && c->astate_P != 0 && c->d_astate != nullptr) {   // and the actuator positions staged by acmpc_set_actuator_state
+    ACMPC_HIP(c, hipMemcpyAsync(c->d_astate, c->h_astate.data(), c->h_astate.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    c->astate_dirty = false;
   }
   if (!c->uprev_dirty || c->uprev_P == 0 || c->d_uprev == nullptr) return ACMPC_OK;
   ACMPC_HIP(c, hipMemcpyAsync(c->d_uprev, c->h_uprev.data(), c->h_uprev.size() * sizeof(float), hipMemcpyHostToDevice, s));
@@ -234,6 +239,11 @@ int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call)
     char buf[160];
     std::snprintf(buf, sizeof buf, "P=%d does not match the previous controls set (P=%d): acmpc_set_previous_control", P,
                   c->uprev_P);
+    return fail(c, ACMPC_ESTATE, buf);
+  }
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC && c->astate_P != 0 && P != c->astate_P) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "P=%d does not match the actuator positions set (P=%d): acmpc_set_actuator_state", P, c->astate_P);
     return fail(c, ACMPC_ESTATE, buf);
   }
   if (c->prm.mode == ACMPC_MODE_DYNAMIC && c->obs_K != 0 && (P != c->obs_P || n != c->obs_n)) {
@@ -520,6 +530,7 @@ void acmpc_destroy(acmpc_ctx* c) {
     (void)hipFree(c->d_soft_partial);
     (void)hipFree(c->d_segments);
     (void)hipFree(c->d_uprev);
+    (void)hipFree(c->d_astate);
     (void)hipFree(c->d_obs);
     (void)hipFree(c->d_surface);
     (void)hipFree(c->d_progress);

@@ -1,5 +1,5 @@
 // C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
-// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the downforce, the previous control, the obstacles and the clearance setting, the surface table, and the grip
+// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the downforce, the previous control, the obstacles and the clearance setting, the surface table, the actuator lag and the actuator positions, and the grip
 // identification (acmpc_score_grips) and the plan trace (acmpc_trace_plans), with the checks that the kernels' limits are the public header's.
 #include <algorithm>
 
@@ -419,6 +419,46 @@ int acmpc_set_surface(acmpc_ctx* c, const float* grip, int32_t P, int32_t n) {
   c->surf_P = P;
   c->surf_n = n;
   c->surf_dirty = true;
+  return ACMPC_OK;
+}
+
+int acmpc_set_dynamics_actuator(acmpc_ctx* c, const double tau[2]) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_dynamics_actuator needs a mode D handle");
+  if (tau == nullptr) {
+    c->has_actuator = false;
+    c->actuator_k[0] = c->actuator_k[1] = c->actuator_m[0] = c->actuator_m[1] = 0.0f;
+    return ACMPC_OK;
+  }
+  float k[2], m[2];
+  for (int ch = 0; ch < 2; ++ch) {   // (a NaN compares false)
+    if (!std::isfinite(tau[ch]) || !(tau[ch] >= 0.0)) return fail(c, ACMPC_EINVAL, "tau_d, tau_p must be finite and >= 0");
+    // in float64, each rounded once: what is left of an error after one control step, and its mean over the step
+    const double kd = tau[ch] > 0.0 ? std::exp(-c->prm.dt / tau[ch]) : 0.0;
+    const double md = tau[ch] > 0.0 ? (tau[ch] / c->prm.dt) * (1.0 - kd) : 0.0;
+    k[ch] = static_cast<float>(kd);
+    m[ch] = static_cast<float>(md);
+  }
+  // everything is checked before anything is kept: a refused setting leaves the handle's as it was
+  c->has_actuator = true;
+  std::memcpy(c->actuator_k, k, sizeof k);
+  std::memcpy(c->actuator_m, m, sizeof m);
+  return ACMPC_OK;
+}
+
+int acmpc_set_actuator_state(acmpc_ctx* c, const float* a0, int32_t P) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_actuator_state needs a mode D handle");
+  if (a0 == nullptr) {
+    c->h_astate.clear();
+    c->astate_P = 0;
+    c->astate_dirty = false;
+    return ACMPC_OK;
+  }
+  if (P < 1 || P > c->prm.max_problems) return fail(c, ACMPC_EINVAL, "P must be 1 .. max_problems");
+  c->h_astate.assign(a0, a0 + static_cast<size_t>(P) * 2);
+  c->astate_P = P;
+  c->astate_dirty = true;
   return ACMPC_OK;
 }
 

@@ -19,8 +19,9 @@ namespace capi __attribute__((visibility("hidden"))) {
 // And of its obstacles ("Obstacles"): the device block (positions, then radii), what it was set for, and the clearance
 // setting; K = 0 while none are set, the soft part on with a weight that is not 0.
 // And of its surface table ("Surface"): the device table and what it was set for.
-acmpc::WithObstacles<acmpc::TermsSurface> dynamics_terms(const acmpc_ctx* c) {
-  acmpc::WithObstacles<acmpc::TermsSurface> t{};
+// And of its actuator lag ("Actuator"): the four floats, and the positions' device block while positions are set.
+acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsSurface>> dynamics_terms(const acmpc_ctx* c) {
+  acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsSurface>> t{};
   t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
             std::isfinite(c->rate_max[1])) ? 1 : 0;
   t.slip = (c->slip_weight != 0.0 || std::isfinite(c->slip_max)) ? 1 : 0;
@@ -57,6 +58,16 @@ acmpc::WithObstacles<acmpc::TermsSurface> dynamics_terms(const acmpc_ctx* c) {
   }
   // ("Surface": the top-tier step whatever is on - the downforce's neutral values while it is off, and the load scalars of the
   // vehicles derived all the same)
+  // ("Actuator": the same top-tier step, over the vehicle's own peaks while no table is set)
+  if (c->has_actuator) {
+    t.lag.actuator = 1;
+    t.lag.k_d = c->actuator_k[0];
+    t.lag.m_d = c->actuator_m[0];
+    t.lag.k_p = c->actuator_k[1];
+    t.lag.m_p = c->actuator_m[1];
+    t.lag.a0 = (c->astate_P != 0) ? c->d_astate : nullptr;   // (as u_prev: every mode D call uploads first)
+    t.lag.a0_P = c->astate_P;
+  }
   if (c->surf_P != 0) {
     t.surface = 1;
     if (!c->surf_dirty && c->d_surface != nullptr) {   // (every mode D call uploads first; a launch without the table is refused)
@@ -64,6 +75,8 @@ acmpc::WithObstacles<acmpc::TermsSurface> dynamics_terms(const acmpc_ctx* c) {
       t.mu_P = c->surf_P;
       t.mu_n = c->surf_n;
     }
+  }
+  if (c->surf_P != 0 || c->has_actuator) {
     if (t.aero == 0) {
       t.k_f = t.k_r = 0.0f;
       t.v_sat = 100.0f;

@@ -306,6 +306,16 @@ struct acmpc_ctx {
   bool surf_dirty = false;
   float* d_surface = nullptr;
   size_t surf_capacity = 0;              // floats
+  // mode D: the actuator lag (acmpc_set_dynamics_actuator), kept apart like the others: per channel (steering, pedal) the two
+  // float32 the kernels get, k = exp(-dt / tau) and m = (tau / dt)(1 - k), derived in float64 and rounded once (tau = 0: both 0,
+  // which is ON); and the actuator positions at the start of the plan (acmpc_set_actuator_state), staged here like the previous
+  // control until the next upload
+  bool has_actuator = false;
+  float actuator_k[2] = {0.0f, 0.0f}, actuator_m[2] = {0.0f, 0.0f};
+  std::vector<float> h_astate;  // [astate_P][2]
+  int astate_P = 0;             // 0: none set
+  bool astate_dirty = false;
+  float* d_astate = nullptr;    // [max_problems][2]
   // mode D: the plan trace's device block (acmpc_trace_plans): x0 | U | states | totals | terms of ONE call, made on the call's
   // first use, kept between calls and regrown when a later call needs more
   unsigned char* d_plan_trace = nullptr;
@@ -341,7 +351,7 @@ acmpc::Integration dynamics_integration(const acmpc_ctx* c);
 // (acmpc_capi_dynamic.hip) the six load scalars of vehicle k as the surface step needs them while neither the load transfer nor
 // the downforce is on: c_h = w_max = 0 and the vehicle's own a1, a2 (zeros for a block that has none)
 void surface_load_const(const acmpc_ctx* c, int k, float* out);
-acmpc::WithObstacles<acmpc::TermsSurface> dynamics_terms(const acmpc_ctx* c);   // (after the call's uploads: upload_tables)
+acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsSurface>> dynamics_terms(const acmpc_ctx* c);   // (after the call's uploads: upload_tables)
 acmpc::SampleSpec make_spec(const acmpc_ctx* c, double sigma_v, double sigma_k, uint64_t seed, uint32_t round);
 // (`set`: which half of the partial keys / feasible counts - chained rounds and the stream of batches alternate)
 acmpc::RolloutArgs rollout_args(const acmpc_ctx* c, const float* d_x0, const float* d_U, float* d_costs, int P, int N, int n,

@@ -542,6 +542,56 @@ __device__ __forceinline__ bool soft_part(const TT&) { return false; }
 template <typename Base>
 __device__ __forceinline__ bool soft_part(const WithObstacles<Base>& t) { return t.soft != 0; }
 
+// The actuator lag of a handle (acmpc_set_dynamics_actuator, acmpc_set_actuator_state; DESIGN.md section 2 "Mode D, actuator"):
+// the steering rack and the pedal follow their commands as first-order lags.  Per channel the host derives k = exp(-dt / tau) -
+// what is left of an error after one control step - and m = (tau / dt)(1 - k) - the mean of what is left over the step - in
+// float64 and rounds each once (tau = 0: k = m = 0).  A candidate carries the two actuator positions (ActuatorState); at the top
+// of control step i, in float32 and unfused,
+//   e = delta_i - a_d;   delta_x = delta_i - m_d e;   a_d = delta_i - k_d e          (the pedal channel likewise)
+// and the control step - control_terms, every sub-step, the blend's tan(delta) - is driven on (delta_x, pedal_x); dynamic_cost,
+// the terms, the records and the sampler stay on the command.  a0 [P][2]: the positions at the start of the plan, on the
+// device, or nullptr (step 0's own command then stands for them: e = +0, as with Terms::u_prev).  A wrapper pack like the
+// obstacles', over the packs of the top-tier step (TermsAero, TermsSurface, each with or without the obstacles' pack): the
+// kernels instantiated for the four (acmpc_dynamic_actuator.hip) run only while `actuator` is set, with the lower tiers' neutral
+// values where a tier is off (as under the surface); every other kernel stays the code it was.  The launchers take the handle's
+// settings as a WithActuator<WithObstacles<TermsSurface>>.
+struct ActuatorLag {
+  float k_d, m_d, k_p, m_p;
+  const float* a0;
+  int actuator;                 // 0: off (nothing else of this is read); the kernels do not read it
+  int a0_P;                     // what a0 was set for: the launchers refuse another P (the kernels do not read it)
+};
+template <typename Base>
+struct WithActuator : Base {
+  ActuatorLag lag;
+};
+template <typename Base>
+__host__ __device__ inline bool has_actuator(const WithActuator<Base>& t) { return t.lag.actuator != 0; }
+template <typename Base>
+struct PackBase<WithActuator<Base>> { using type = typename PackBase<Base>::type; };   // (sees through both wrappers)
+template <typename TT>
+struct IsActuatorPack : std::false_type {};
+template <typename Base>
+struct IsActuatorPack<WithActuator<Base>> : std::true_type {};
+template <typename... TM>
+constexpr bool kActuatorPack = (IsActuatorPack<typename std::remove_cv<TM>::type>::value || ...);
+// the actuator's pack over a base of the handle's settings (TermsAero, TermsSurface), and over the obstacles' pack of one
+template <typename Base, typename From>
+inline WithActuator<Base> actuator_over(const WithActuator<From>& t) {
+  WithActuator<Base> r{};
+  static_cast<Base&>(r) = static_cast<const Base&>(t);
+  r.lag = t.lag;
+  return r;
+}
+template <typename Base, typename From>
+inline WithActuator<WithObstacles<Base>> actuator_over_obstacles(const WithActuator<WithObstacles<From>>& t, const float* coef) {
+  WithActuator<WithObstacles<Base>> r{};
+  static_cast<WithObstacles<Base>&>(r) = obstacles_over<Base>(t);
+  r.coef = coef;
+  r.lag = t.lag;
+  return r;
+}
+
 // what the terms carry from step to step: the previous step's control and the cost sum
 template <typename F>
 struct TermsState {
@@ -764,6 +814,60 @@ __device__ __forceinline__ F finish_dynamic_terms(const StateD_<F>& s, const Ter
   return fma_(splat<F>(w.wbound), st.V, J);
 }
 
+// Under the actuator's pack the terms and the finish are the base pack's, on the COMMAND (the rates, the box and dk belong to
+// what the optimiser chooses); the lag touches the control step alone (actuator_step, below).
+template <typename F, typename Base>
+__device__ __forceinline__ void dynamic_terms(StateD_<F>& s, F delta, F pedal, int i, int p, const Vehicle& k, const float* wp,
+                                              typename IndexOf<F>::type j, TermsState<F>& ts, const WithActuator<Base>& t) {
+  dynamic_terms<F>(s, delta, pedal, i, p, k, wp, j, ts, static_cast<const Base&>(t));
+}
+template <typename F, typename Base>
+__device__ __forceinline__ F finish_dynamic_terms(const StateD_<F>& s, const TermsState<F>& ts, const float* wp,
+                                                  typename IndexOf<F>::type j, int p, int n, const Weights& w,
+                                                  const WithActuator<Base>& t) {
+  return finish_dynamic_terms<F>(s, ts, wp, j, p, n, w, static_cast<const Base&>(t));
+}
+
+// The two actuator positions a candidate carries under a WithActuator pack, a state of its own beside TermsState (which stays
+// what the other packs' kernels were compiled with): a0[p] where the caller gave the measured positions - a wave-uniform address,
+// one scalar load ahead of the step loop - else whatever, replaced by step 0's command inside actuator_step.
+template <typename F>
+struct ActuatorState {
+  F a_d, a_p;
+};
+template <typename Base>
+__device__ __forceinline__ const ActuatorLag& lag_of(const WithActuator<Base>& t) {
+  return t.lag;
+}
+template <typename F, typename Base>
+__device__ __forceinline__ const ActuatorLag& lag_of(const TermsState<F>&, const WithActuator<Base>& t) {
+  return t.lag;
+}
+template <typename F>
+__device__ __forceinline__ ActuatorState<F> start_actuator(int p, const ActuatorLag& t) {
+  ActuatorState<F> as{splat<F>(0.0f), splat<F>(0.0f)};
+  if (t.a0 != nullptr) {
+    as.a_d = splat<F>(t.a0[2 * p]);
+    as.a_p = splat<F>(t.a0[2 * p + 1]);
+  }
+  return as;
+}
+// The top of control step i: the applied control (dx, qx) of the command (delta, pedal) - the interval mean of the exact
+// first-order response to a held command - and the positions at the step's end (the exact zero-order-hold discretisation).
+// Three float32 operations per channel, none fused; k, m and the a0 switch are scalars.
+template <typename F>
+__device__ __forceinline__ void actuator_step(int i, F delta, F pedal, ActuatorState<F>& as, const ActuatorLag& t, F& dx, F& qx) {
+  const bool own = i == 0 && t.a0 == nullptr;
+  const F ad = own ? delta : as.a_d;
+  const F ap = own ? pedal : as.a_p;
+  const F ed = delta - ad;
+  const F ep = pedal - ap;
+  dx = delta - t.m_d * ed;
+  qx = pedal - t.m_p * ep;
+  as.a_d = delta - t.k_d * ed;
+  as.a_p = pedal - t.k_p * ep;
+}
+
 // mode T's temporal_cost with the input terms of this model: dv = vx - v_ref, dk = delta - delta_ref (row[7], staged
 // once per waypoint), the input box on (delta, pedal).  g = a derived waypoint row (stage_dynamic_tables).
 template <typename F>
@@ -809,20 +913,22 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // the parts.  And its obstacles: while any are set, the obstacle kernels of the step the handle would take
 // without them run (the general, the coupled, the loaded or the aero one), looked at first.  And its surface table: while one is
 // set, the surface kernels run (the aero step on per-lane peaks, with or without the obstacles' lines), whatever else is on.
+// And its actuator lag: while that is on, the actuator kernels run (the aero or the surface step on the lagged control, with or
+// without the obstacles' lines), looked at before everything else.
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
+                                  const Integration& integration, const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
+                                          const Integration& integration, const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
+                                   const Integration& integration, const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
 
 }  // namespace acmpc

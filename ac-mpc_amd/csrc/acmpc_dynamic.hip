@@ -17,7 +17,8 @@ int dynamic_blocks_per_problem(int P, int N, int K) {
 }
 
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& g, const WithObstacles<TermsSurface>& tm, hipStream_t s) {
+                                  const Integration& g, const WithActuator<WithObstacles<TermsSurface>>& tm, hipStream_t s) {
+  if (has_actuator(tm)) return launch_rollout_dynamic_actuator(layout, args, vehicles, g, tm, s);
   if (has_obstacles(tm)) return launch_rollout_dynamic_obstacles(layout, args, vehicles, g, tm, s);
   if (has_surface(tm)) return launch_rollout_dynamic_surface(layout, args, vehicles, g, tm, s);
   if (has_downforce(tm)) return launch_rollout_dynamic_aero(layout, args, vehicles, g, tm, s);
@@ -28,7 +29,8 @@ hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const Veh
 }
 
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& g, const WithObstacles<TermsSurface>& tm, hipStream_t s) {
+                                          const Integration& g, const WithActuator<WithObstacles<TermsSurface>>& tm, hipStream_t s) {
+  if (has_actuator(tm)) return launch_rollout_dynamic_sampled_actuator(args, sample, vehicles, g, tm, s);
   if (has_obstacles(tm)) return launch_rollout_dynamic_sampled_obstacles(args, sample, vehicles, g, tm, s);
   if (has_surface(tm)) return launch_rollout_dynamic_sampled_surface(args, sample, vehicles, g, tm, s);
   if (has_downforce(tm)) return launch_rollout_dynamic_sampled_aero(args, sample, vehicles, g, tm, s);
@@ -39,7 +41,8 @@ hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleA
 }
 
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& g, const WithObstacles<TermsSurface>& tm, hipStream_t s) {
+                                   const Integration& g, const WithActuator<WithObstacles<TermsSurface>>& tm, hipStream_t s) {
+  if (has_actuator(tm)) return launch_finalize_dynamic_actuator(layout, args, vehicles, g, tm, s);
   if (has_obstacles(tm)) return launch_finalize_dynamic_obstacles(layout, args, vehicles, g, tm, s);
   if (has_surface(tm)) return launch_finalize_dynamic_surface(layout, args, vehicles, g, tm, s);
   if (has_downforce(tm)) return launch_finalize_dynamic_aero(layout, args, vehicles, g, tm, s);

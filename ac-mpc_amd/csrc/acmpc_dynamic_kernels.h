@@ -36,6 +36,9 @@
 // takes the first row whose setting is on:
 //
 //   unit                          pack                                setter (acmpc_set_...)        kernels  launched while
+//   acmpc_dynamic_actuator.hip    WithActuator<TermsAero |            dynamics_actuator             4 x 16   the actuator lag is on: over the aero
+//                                 TermsSurface | WithObstacles<                                             step, or the surface step while a table
+//                                 TermsAero | TermsSurface>>                                                is set; with obstacles: over their pack
 //   acmpc_dynamic_surface.hip     TermsSurface, WithObstacles<        surface                       2 x 16   a surface table is set (with obstacles:
 //                                 TermsSurface>                                                             the second pack)
 //   acmpc_dynamic_obstacles.hip   WithObstacles<TermsObjective |      obstacles                     4 x 16   obstacles are set: the pack of the
@@ -158,6 +161,8 @@ __global__ void __launch_bounds__(kDynBlock)
   constexpr bool kTerms = sizeof...(TM) != 0;
   [[maybe_unused]] TermsState<F> ts;
   if constexpr (kTerms) ts = start_terms<F>(p, tm...);
+  [[maybe_unused]] ActuatorState<F> as;   // (the actuator lag: the two positions, a0[p] or step 0's command)
+  if constexpr (kActuatorPack<TM...>) as = start_actuator<F>(p, lag_of(tm...));
   I nearest = I(0);
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
@@ -174,11 +179,13 @@ __global__ void __launch_bounds__(kDynBlock)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, d, q, veh, g, g.inv_L[0], surface_peaks<F>(aero_peaks(0, tm...), veh, ms));
-      else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], aero_peaks(0, tm...));
-      else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
-      else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
-      else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[0]);
+      F dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
+      if constexpr (kActuatorPack<TM...>) actuator_step<F>(i, d, q, as, lag_of(tm...), dx, qx);
+      if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, dx, qx, veh, g, g.inv_L[0], surface_peaks<F>(aero_peaks(0, tm...), veh, ms));
+      else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], aero_peaks(0, tm...));
+      else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
+      else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], coupled_peaks(tm...));
+      else dynamic_control_step<FINE, F>(st, dx, qx, veh, w.dt, g, g.inv_L[0]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
       if constexpr (kTerms) dynamic_terms<F>(st, d, q, i, p, veh, s_wp, nearest, ts, tm...);
@@ -305,6 +312,8 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
   if constexpr (kAeroPack<TT...> || kSurfacePack<TT...>) aero = aero_peaks(vk, tt...);
   int resident[2] = {-1, -1};   // the Philox block in slots 0, 1 and in slots 2, 3
   int knot = -1;
+  [[maybe_unused]] ActuatorState<F> as;   // (the actuator lag: the two positions, a0[p] or step 0's command)
+  if constexpr (kActuatorPack<TT...>) as = start_actuator<F>(p, lag_of(tt...));
   I nearest = I(0);
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
@@ -348,11 +357,13 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
         d = dj[0];
         q = qj[0];
       }
-      if constexpr (kSurfacePack<TT...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, d, q, veh, g, inv_L, surface_peaks<F>(aero, veh, ms));
-      else if constexpr (kAeroPack<TT...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, aero);
-      else if constexpr (kLoadedPack<TT...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, loaded);
-      else if constexpr (kCoupledPack<TT...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, inv_L, coupled_peaks(tt...));
-      else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, inv_L);
+      F dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
+      if constexpr (kActuatorPack<TT...>) actuator_step<F>(i, d, q, as, lag_of(tt...), dx, qx);
+      if constexpr (kSurfacePack<TT...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, dx, qx, veh, g, inv_L, surface_peaks<F>(aero, veh, ms));
+      else if constexpr (kAeroPack<TT...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, inv_L, aero);
+      else if constexpr (kLoadedPack<TT...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, inv_L, loaded);
+      else if constexpr (kCoupledPack<TT...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, inv_L, coupled_peaks(tt...));
+      else dynamic_control_step<FINE, F>(st, dx, qx, veh, w.dt, g, inv_L);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
       if constexpr (kTerms) dynamic_terms<F>(st, d, q, i, p, veh, s_wp, nearest, tt...);   // (the state keeps this step's blended control)
@@ -522,6 +533,8 @@ __global__ void __launch_bounds__(kWave)
   constexpr bool kTerms = sizeof...(TM) != 0;
   [[maybe_unused]] TermsState<float> ts;
   if constexpr (kTerms) ts = start_terms<float>(p, tm...);
+  [[maybe_unused]] ActuatorState<float> as;   // (the actuator lag: the two positions, a0[p] or step 0's command)
+  if constexpr (kActuatorPack<TM...>) as = start_actuator<float>(p, lag_of(tm...));
   if (lane == 0) {
     sx[0] = st.t.X + coef[0];   // (poses leave in the caller's frame: start_temporal())
     sx[1] = st.t.Y + coef[1];
@@ -535,11 +548,13 @@ __global__ void __launch_bounds__(kWave)
     [[maybe_unused]] SurfaceScales<float> ms;   // (the surface table: j_prev is uniform, a scalar load)
     if constexpr (kSurfacePack<TM...>) ms = surface_scales<float>(p, n, j_prev, tm...);
     const float d = su[2 * i], q = su[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
-    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, d, q, veh, g, g.inv_L[0], surface_peaks<float>(aero_peaks(0, tm...), veh, ms));
-    else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], aero_peaks(0, tm...));
-    else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
-    else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[0], coupled_peaks(tm...));
-    else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[0]);
+    float dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
+    if constexpr (kActuatorPack<TM...>) actuator_step<float>(i, d, q, as, lag_of(tm...), dx, qx);
+    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, dx, qx, veh, g, g.inv_L[0], surface_peaks<float>(aero_peaks(0, tm...), veh, ms));
+    else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], aero_peaks(0, tm...));
+    else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
+    else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], coupled_peaks(tm...));
+    else dynamic_control_step<FINE, float>(st, dx, qx, veh, w.dt, g, g.inv_L[0]);
     // the first minimum of the key over the search's waypoints, the lanes side by side; ties -> the lower index, and the
     // search's first waypoint when no key compares below +inf (as the rollout's `d < best` scans)
     const int lo = exhaustive ? 0 : max(min(j_prev - w.nn_back, n - win_w), 0);
@@ -618,6 +633,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   constexpr bool kTerms = sizeof...(TM) != 0;
   [[maybe_unused]] TermsState<F> ts;
   if constexpr (kTerms) ts = start_terms<F>(p, tm...);
+  [[maybe_unused]] ActuatorState<F> as;   // (the actuator lag: the two positions, a0[p] or step 0's command)
+  if constexpr (kActuatorPack<TM...>) as = start_actuator<F>(p, lag_of(tm...));
   I nearest = I(0);
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
@@ -634,11 +651,13 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       } else {
         load_dynamic_control<LAYOUT>(a.U, p, a.N, n, i, cand[0], d, q);
       }
-      if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, d, q, veh, g, g.inv_L[k], surface_peaks<F>(aero_peaks(k, tm...), veh, ms));
-      else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
-      else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
-      else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
-      else dynamic_control_step<FINE, F>(st, d, q, veh, w.dt, g, g.inv_L[k]);
+      F dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
+      if constexpr (kActuatorPack<TM...>) actuator_step<F>(i, d, q, as, lag_of(tm...), dx, qx);
+      if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, dx, qx, veh, g, g.inv_L[k], surface_peaks<F>(aero_peaks(k, tm...), veh, ms));
+      else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], aero_peaks(k, tm...));
+      else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
+      else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], coupled_peaks(tm...));
+      else dynamic_control_step<FINE, F>(st, dx, qx, veh, w.dt, g, g.inv_L[k]);
       nearest = dynamic_nearest<kKind>(st.t.X, st.t.Y, s_xy, n, w, nearest);
       dynamic_settle(st, s_wp, nearest, d, q, w);
       if constexpr (kTerms) dynamic_terms<F>(st, d, q, i, p, veh, s_wp, nearest, ts, tm...);
@@ -812,6 +831,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   constexpr bool kTerms = sizeof...(TM) != 0;
   [[maybe_unused]] TermsState<float> ts;
   if constexpr (kTerms) ts = start_terms<float>(p, tm...);
+  [[maybe_unused]] ActuatorState<float> as;   // (the actuator lag: the two positions, a0[p] or step 0's command)
+  if constexpr (kActuatorPack<TM...>) as = start_actuator<float>(p, lag_of(tm...));
   const bool writer = (k == 0 && lane == 0);   // vehicle 0's trajectory is the record's
   if (writer) {
     sx[0] = st.t.X + coef[0];
@@ -827,11 +848,13 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
     [[maybe_unused]] SurfaceScales<float> ms;   // (the surface table: j_prev is uniform, a scalar load)
     if constexpr (kSurfacePack<TM...>) ms = surface_scales<float>(p, n, j_prev, tm...);
     const float d = su[2 * i], q = su[2 * i + 1];
-    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, d, q, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
-    else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
-    else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
-    else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
-    else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[k]);
+    float dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
+    if constexpr (kActuatorPack<TM...>) actuator_step<float>(i, d, q, as, lag_of(tm...), dx, qx);
+    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, dx, qx, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
+    else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], aero_peaks(k, tm...));
+    else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
+    else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], coupled_peaks(tm...));
+    else dynamic_control_step<FINE, float>(st, dx, qx, veh, w.dt, g, g.inv_L[k]);
     // finalize_dynamic_kernel's search, within this wave
     const int lo = exhaustive ? 0 : max(min(j_prev - w.nn_back, n - win_w), 0);
     const int hi = exhaustive ? n - 1 : min(lo + win_w, n) - 1;
@@ -1057,5 +1080,16 @@ hipError_t launch_rollout_dynamic_sampled_surface(const RolloutArgs& args, const
                                                   const WithObstacles<TermsSurface>& terms, hipStream_t s);
 hipError_t launch_finalize_dynamic_surface(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
                                            const Integration& integration, const WithObstacles<TermsSurface>& terms, hipStream_t s);
+
+// acmpc_dynamic_actuator.hip: the kernels of a WithActuator over TermsAero or TermsSurface, each with or without the obstacles'
+// pack between.  hipErrorInvalidValue unless the actuator positions, the surface table and the obstacles - whichever are set -
+// are the launch's P and n.
+hipError_t launch_rollout_dynamic_actuator(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                           const Integration& integration, const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_sampled_actuator(const RolloutArgs& args, const SampleArgs& sample,
+                                                   const VehicleEnsemble& vehicles, const Integration& integration,
+                                                   const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
+hipError_t launch_finalize_dynamic_actuator(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                            const Integration& integration, const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
 
 }  // namespace acmpc

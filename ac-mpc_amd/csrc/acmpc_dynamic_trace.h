@@ -29,9 +29,9 @@ struct TraceArgs {
 };
 
 // One wavefront per (problem, plan, vehicle): grid (P M, K).  The instantiation is picked as launch_finalize_dynamic picks
-// its own - obstacles first, then downforce, load transfer, coupling, terms / objective, the integration, the default - so
+// its own - the actuator lag first, then obstacles, then downforce, load transfer, coupling, terms / objective, the integration, the default - so
 // that a trace is the arithmetic of the kernels that scored the plan.
 hipError_t launch_trace_dynamic(const TraceArgs& args, const VehicleEnsemble& vehicles, const Integration& integration,
-                                const WithObstacles<TermsSurface>& terms, hipStream_t s);
+                                const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
 
 }  // namespace acmpc

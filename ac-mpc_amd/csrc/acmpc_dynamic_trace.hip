@@ -66,6 +66,14 @@ __device__ __forceinline__ void trace_hinges(const StateD& s, float delta, float
   }
 }
 
+// Under the actuator's pack: the base pack's hinges, on the command
+template <typename Base>
+__device__ __forceinline__ void trace_hinges(const StateD& s, float delta, float pedal, int i, int p, const Vehicle& k,
+                                             const float* wp, int j, const TermsState<float>& ts, float (&h)[kTraceHinges],
+                                             const WithActuator<Base>& t) {
+  trace_hinges(s, delta, pedal, i, p, k, wp, j, ts, h, static_cast<const Base&>(t));
+}
+
 template <bool FINE, typename... TM>
 __global__ void __launch_bounds__(kWave)
     trace_dynamic_kernel(const TraceArgs a, const VehicleEnsemble e, const Integration g, const TM... tm) {
@@ -93,6 +101,8 @@ __global__ void __launch_bounds__(kWave)
   [[maybe_unused]] TermsState<float> ts;
   if constexpr (kTerms) ts = start_terms<float>(p, tm...);
   else ts = TermsState<float>{0.0f, 0.0f, 0.0f, 0};
+  [[maybe_unused]] ActuatorState<float> as;   // (the actuator lag: the two positions, a0[p] or step 0's command)
+  if constexpr (kActuatorPack<TM...>) as = start_actuator<float>(p, lag_of(tm...));
   if (lane == 0 && states != nullptr) {
     states[0] = st.t.X + coef[0];   // (poses leave in the caller's frame: start_temporal())
     states[1] = st.t.Y + coef[1];
@@ -109,11 +119,13 @@ __global__ void __launch_bounds__(kWave)
     [[maybe_unused]] SurfaceScales<float> ms;   // (the surface table: j_prev is uniform, a scalar load)
     if constexpr (kSurfacePack<TM...>) ms = surface_scales<float>(p, n, j_prev, tm...);
     const float d = s_u[2 * i], q = s_u[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
-    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, d, q, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
-    else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], aero_peaks(k, tm...));
-    else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
-    else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, d, q, veh, g, g.inv_L[k], coupled_peaks(tm...));
-    else dynamic_control_step<FINE, float>(st, d, q, veh, w.dt, g, g.inv_L[k]);
+    float dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
+    if constexpr (kActuatorPack<TM...>) actuator_step<float>(i, d, q, as, lag_of(tm...), dx, qx);
+    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, dx, qx, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
+    else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], aero_peaks(k, tm...));
+    else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
+    else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], coupled_peaks(tm...));
+    else dynamic_control_step<FINE, float>(st, dx, qx, veh, w.dt, g, g.inv_L[k]);
     // finalize_dynamic_kernel's search: the first minimum of the key over the search's waypoints, the lanes side by side;
     // ties -> the lower index, and the search's first waypoint when no key compares below +inf
     const int lo = exhaustive ? 0 : max(min(j_prev - w.nn_back, n - win_w), 0);
@@ -203,7 +215,7 @@ hipError_t trace_dynamic_launch(const TraceArgs& args, const VehicleEnsemble& ve
 }  // namespace
 
 hipError_t launch_trace_dynamic(const TraceArgs& args, const VehicleEnsemble& vehicles, const Integration& g,
-                                const WithObstacles<TermsSurface>& tm, hipStream_t s) {
+                                const WithActuator<WithObstacles<TermsSurface>>& tm, hipStream_t s) {
   clear_stale_error();
   if (!integration_valid(g)) return hipErrorInvalidValue;
   if (args.n < 1 || args.n > kDynamicMaxSteps || args.M < 1 || args.P < 1) return hipErrorInvalidValue;
@@ -212,10 +224,18 @@ hipError_t launch_trace_dynamic(const TraceArgs& args, const VehicleEnsemble& ve
   if (args.U == nullptr || args.x0 == nullptr || args.coef == nullptr) return hipErrorInvalidValue;
   // (nothing is launched unless the surface table is what this launch's P and n index)
   if (has_surface(tm) && (tm.mu == nullptr || tm.mu_P != args.P || tm.mu_n != args.n)) return hipErrorInvalidValue;
+  if (has_obstacles(tm) && (tm.K > kMaxObstacles || tm.obs == nullptr || tm.radii == nullptr || tm.P != args.P || tm.n != args.n))
+    return hipErrorInvalidValue;   // (nor unless the obstacle data is)
+  if (has_actuator(tm)) {
+    // (nor unless the actuator positions, if any are set, are this launch's P): the aero or the surface step, the tiers that
+    // are off at their neutral values (the handle fills them in), with or without the obstacles' lines
+    if (tm.lag.a0 != nullptr && tm.lag.a0_P != args.P) return hipErrorInvalidValue;
+    if (has_obstacles(tm) && has_surface(tm)) return trace_dynamic_launch(args, vehicles, g, s, actuator_over_obstacles<TermsSurface>(tm, args.coef));
+    if (has_obstacles(tm)) return trace_dynamic_launch(args, vehicles, g, s, actuator_over_obstacles<TermsAero>(tm, args.coef));
+    if (has_surface(tm)) return trace_dynamic_launch(args, vehicles, g, s, actuator_over<TermsSurface>(tm));
+    return trace_dynamic_launch(args, vehicles, g, s, actuator_over<TermsAero>(tm));
+  }
   if (has_obstacles(tm)) {
-    // (nor unless the obstacle data is)
-    if (tm.K > kMaxObstacles || tm.obs == nullptr || tm.radii == nullptr || tm.P != args.P || tm.n != args.n)
-      return hipErrorInvalidValue;
     if (has_surface(tm)) {
       WithObstacles<TermsSurface> both = tm;
       both.coef = args.coef;

@@ -431,6 +431,41 @@ int acmpc_set_dynamics_clearance(acmpc_ctx* ctx, double weight, double margin);
  * "Mode D, surface". */
 int acmpc_set_surface(acmpc_ctx* ctx, const float* grip /* [P][n][2], NULL: off */, int32_t P, int32_t n);
 
+/* Mode D, actuator lag: the steering rack and the pedal actuator follow their commands as first-order lags.  tau host [2] =
+ * (tau_d, tau_p) in seconds for the steering and the pedal channel, each finite and >= 0; NULL turns the setting off.  With dt
+ * the handle's control step the host derives per channel, in float64, each rounded to float32 once
+ *   k_c = exp(-dt / tau_c)            what is left of an error after one control step      (tau_c = 0: k_c = 0)
+ *   m_c = (tau_c / dt) (1 - k_c)      the mean of what is left over the step's interval    (tau_c = 0: m_c = 0)
+ * so that 0 < k_c < m_c < 1 for tau_c > 0.  A candidate carries the two actuator positions (a_d, a_p).  At the top of control
+ * step i, before anything of the step runs, in float32 and with nothing fused (the pedal channel likewise with k_p, m_p, a_p):
+ *   e       = delta_i - a_d
+ *   delta_x = delta_i - m_d e         what the vehicle is driven on during step i: the interval mean of the exact first-order
+ *                                     response to a held command
+ *   a_d     = delta_i - k_d e         the position at the end of the step (the exact zero-order-hold discretisation)
+ * The control step reads the APPLIED control (delta_x, pedal_x) and nothing else of the command: the control's terms, all M
+ * sub-steps and the low-speed blend's tan(delta); the update happens once per control step, not per sub-step.  The COMMAND
+ * (delta_i, pedal_i) stays what the cost's input box and dk, the rate terms (step 0 against acmpc_set_previous_control as ever),
+ * the records' u, the softmin mean, the keys and the sampler see: what the optimiser chooses and what the caller sends.  Every
+ * vehicle of an ensemble carries the same filter.  The step under the setting is the top-tier step (the downforce's, or the
+ * surface's while a table is set), whatever else the handle has on; a tier that is off gets its neutral value as under
+ * acmpc_set_surface.  tau = (0, 0) is ON with k = m = 0: the applied control equals the command (up to the sign of a zero), not
+ * the same as off.  The finalize's re-roll and acmpc_trace_plans run the same step (a trace's slots 4 to 6 and 8 to 9 are on the
+ * command; its states are the lagged trajectory).  acmpc_score_grips does NOT apply the setting: a log should hold the measured
+ * actuator positions as its controls.  A pure dead time is not modelled: roll the start state forward under the controls
+ * already sent.  The setting belongs to the handle and survives every other acmpc_set_dynamics* call, acmpc_set_obstacles and
+ * acmpc_set_surface.  No device work.  ACMPC_ESTATE for a handle whose mode is not ACMPC_MODE_DYNAMIC; ACMPC_EINVAL for a tau
+ * that is negative or not finite - the handle then keeps what it had.  DESIGN.md section 2 "Mode D, actuator". */
+int acmpc_set_dynamics_actuator(acmpc_ctx* ctx, const double tau[2] /* NULL: off */);
+
+/* Mode D, actuator lag: the measured actuator positions at the start of the plan, a0 host [P][2] float32 = (a_d, a_p) per
+ * problem; NULL clears them (P is then ignored).  While cleared, step 0's own command stands for them: e = +0 and the first step
+ * has no lag - the convention of a null previous control.  Values are not checked.  Staged on the host; they travel to the
+ * device with the tables, on the next call's stream (acmpc_sync_tables covers it), as the previous control does, and stay until
+ * replaced or cleared.  Not read while acmpc_set_dynamics_actuator is off.  ACMPC_ESTATE for a handle whose mode is not
+ * ACMPC_MODE_DYNAMIC; ACMPC_EINVAL for P outside 1 .. max_problems; a later mode D call (acmpc_trace_plans included) with another
+ * P returns ACMPC_ESTATE. */
+int acmpc_set_actuator_state(acmpc_ctx* ctx, const float* a0 /* [P][2], NULL: clear */, int32_t P);
+
 /* Mode D, grip identification: which vehicle did a logged stretch of driving come from?  K hypotheses - the handle's
  * vehicle 0 (the block of acmpc_set_dynamics, or member 0 of acmpc_set_dynamics_ensemble) with Df scales[k][0] and
  * Dr scales[k][1], derived as every block is (the two peaks in float64, rounded once; everything else vehicle 0's own

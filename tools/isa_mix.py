@@ -92,6 +92,17 @@ ENTRIES = {
     "dynamic_surface_substep": ("acmpc_dynamic_surface.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12TermsSurfaceEEE", None),
     "dynamic_ensemble_surface_step": ("acmpc_dynamic_surface.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12TermsSurfaceEEE", None),
     "dynamic_ensemble_surface_substep": ("acmpc_dynamic_surface.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12TermsSurfaceEEE", None),
+    # mode D with the actuator lag (acmpc_set_dynamics_actuator: the WithActuator kernels of acmpc_dynamic_actuator.hip): the aero
+    # step, or the surface step, driven on the lagged control - `dynamic_actuator_step` - `dynamic_aero_step` is the filter's six
+    # subtractions and four multiplies (packed: one instruction per pair of candidates) and what carrying two more values costs
+    "dynamic_actuator_step": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_9TermsAeroEEEEE", None),
+    "dynamic_actuator_substep": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_9TermsAeroEEEEE", None),
+    "dynamic_ensemble_actuator_step": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_9TermsAeroEEEEE", None),
+    "dynamic_ensemble_actuator_substep": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_9TermsAeroEEEEE", None),
+    "dynamic_actuator_surface_step": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_12TermsSurfaceEEEEE", None),
+    "dynamic_actuator_surface_substep": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_12TermsSurfaceEEEEE", None),
+    "dynamic_ensemble_actuator_surface_step": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_12TermsSurfaceEEEEE", None),
+    "dynamic_ensemble_actuator_surface_substep": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_12TermsSurfaceEEEEE", None),
     # mode D's grip identification (acmpc_score_grips, one hypothesis per lane): the sub-step loop of its step kernel - the
     # dynamics and the blend's block, WITHOUT the pose (nothing reads it there: no sincos_spec(yaw), no X, Y, yaw updates).
     # VALU per hypothesis and control step = M trips of it + `identify_grip_step`: the control's terms and the residual, the
@@ -115,12 +126,16 @@ OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dy
          "dynamic_terms_step", "dynamic_ensemble_terms_step", "dynamic_objective_step", "dynamic_ensemble_objective_step",
          "dynamic_coupled_step", "dynamic_ensemble_coupled_step", "dynamic_loaded_step", "dynamic_ensemble_loaded_step",
          "dynamic_aero_step", "dynamic_ensemble_aero_step", "dynamic_surface_step", "dynamic_ensemble_surface_step",
+         "dynamic_actuator_step", "dynamic_ensemble_actuator_step", "dynamic_actuator_surface_step",
+         "dynamic_ensemble_actuator_surface_step",
          "identify_grip_step", "identify_grip_coupled_step", "identify_grip_loaded_step", "identify_grip_aero_step")
 # (exit test at the head: closes with s_branch)
 ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep",
            "dynamic_objective_substep", "dynamic_ensemble_objective_substep", "dynamic_coupled_substep",
            "dynamic_ensemble_coupled_substep", "dynamic_loaded_substep", "dynamic_ensemble_loaded_substep", "dynamic_aero_substep",
-           "dynamic_ensemble_aero_substep", "dynamic_surface_substep", "dynamic_ensemble_surface_substep", "identify_grip",
+           "dynamic_ensemble_aero_substep", "dynamic_surface_substep", "dynamic_ensemble_surface_substep",
+           "dynamic_actuator_substep", "dynamic_ensemble_actuator_substep", "dynamic_actuator_surface_substep",
+           "dynamic_ensemble_actuator_surface_substep", "identify_grip",
            "identify_grip_coupled", "identify_grip_loaded", "identify_grip_aero")
 
 
