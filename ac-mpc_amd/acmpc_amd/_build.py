@@ -13,7 +13,7 @@ SOURCES = ("acmpc_kernels.hip", "acmpc_rollout.hip", "acmpc_solo.hip", "acmpc_so
            "acmpc_kernels_temporal.hip", "acmpc_capi.hip", "acmpc_prologue.hip",
            "acmpc_pf.hip", "acmpc_pf_score.hip", "acmpc_pf_filter.hip", "acmpc_pf_grid.cpp",
            "acmpc_speed_profile.cpp", "acmpc_host_path.cpp", "acmpc_dynamic.hip", "acmpc_dynamic_terms.hip", "acmpc_dynamic_coupled.hip",
-           "acmpc_dynamic_loaded.hip", "acmpc_dynamic_aero.hip", "acmpc_dynamic_obstacles.hip", "acmpc_dynamic_surface.hip", "acmpc_dynamic_actuator.hip", "acmpc_dynamic_trace.hip", "acmpc_identify.hip",
+           "acmpc_dynamic_loaded.hip", "acmpc_dynamic_aero.hip", "acmpc_dynamic_obstacles.hip", "acmpc_dynamic_surface.hip", "acmpc_dynamic_actuator.hip", "acmpc_dynamic_road.hip", "acmpc_dynamic_road_actuator.hip", "acmpc_dynamic_trace.hip", "acmpc_identify.hip",
            "acmpc_capi_solve.hip", "acmpc_capi_optimize.hip", "acmpc_capi_tick.hip", "acmpc_capi_dynamic.hip", "acmpc_capi_rccl.hip")
 HEADERS = ("acmpc_ctx.h", "acmpc_alloc.h", "acmpc_pf.h", "acmpc_pf_grid.h", "acmpc_kernels.h", "acmpc_kernels_impl.h", "acmpc_rollout.h", "acmpc_device.h", "acmpc_dynamic.h", "acmpc_dynamic_kernels.h", "acmpc_dynamic_trace.h", "acmpc_identify.h", "acmpc_frames.h", "acmpc_admm.h", "acmpc_prologue.h", "acmpc_lq.h", "acmpc_lq_box.h",
            os.path.join("..", "..", "include", "acmpc.h"))
@@ -29,7 +29,9 @@ HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-cont
 EXTRA_FLAGS = {"acmpc_kernels_temporal.hip": ("-fno-slp-vectorize",), "acmpc_speed_profile.cpp": ("-mfma",),
                "acmpc_dynamic_obstacles.hip": ("-mllvm", "-sgpr-regalloc=basic"),
                "acmpc_dynamic_surface.hip": ("-mllvm", "-sgpr-regalloc=basic"),   # (its kernels over the obstacles' pack: the same)
-               "acmpc_dynamic_actuator.hip": ("-mllvm", "-sgpr-regalloc=basic")}   # (two of its four packs are over the obstacles')
+               "acmpc_dynamic_actuator.hip": ("-mllvm", "-sgpr-regalloc=basic"),   # (two of its four packs are over the obstacles')
+               "acmpc_dynamic_road.hip": ("-mllvm", "-sgpr-regalloc=basic"),   # (one of the two packs of each road unit likewise)
+               "acmpc_dynamic_road_actuator.hip": ("-mllvm", "-sgpr-regalloc=basic")}
 
 
 def find_hipcc() -> str:

@@ -172,6 +172,7 @@ SIGNATURES = {
     "acmpc_set_obstacles": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "acmpc_set_dynamics_clearance": (C.c_int, [_CTX, C.c_double, C.c_double]),
     "acmpc_set_surface": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
+    "acmpc_set_road": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
     "acmpc_set_dynamics_actuator": (C.c_int, [_CTX, C.c_void_p]),
     "acmpc_set_actuator_state": (C.c_int, [_CTX, C.c_void_p, C.c_int32]),
     "acmpc_set_dynamics_objective": (C.c_int, [_CTX, C.c_double, C.c_void_p]),
@@ -849,6 +850,24 @@ class Engine:
             return
         a = np.ascontiguousarray(np.asarray(a0, dtype=np.float32).reshape(-1, 2))
         self._check(self._lib.acmpc_set_actuator_state(self._ctx, a.ctypes.data, a.shape[0]))
+
+    def set_road(self, road=None):
+        """Mode D's road table (acmpc_set_road): `road` [P, n, 3] = (a_x, a_y, n_z) - gravity's acceleration along the body's
+        forward axis (downhill positive) and its left axis (positive where the road falls to the left), and the factor on the
+        normal load - at every waypoint of every problem's path, or [n, 3] for one problem (dynamic_model.road_table makes one
+        from grade and bank).  A control step is driven on the row of the waypoint the candidate was nearest to one step before
+        (waypoint 0 first).  Every value finite, n_z > 0.  None clears it.  It stays until replaced or cleared, whatever else
+        is set."""
+        if road is None:
+            self._check(self._lib.acmpc_set_road(self._ctx, None, 0, 0))
+            return
+        r = np.asarray(road, dtype=np.float32)
+        if r.ndim == 2:
+            r = r[None]
+        if r.ndim != 3 or r.shape[2] != 3:
+            raise ValueError("road must be [P, n, 3] or [n, 3]")
+        r = np.ascontiguousarray(r)
+        self._check(self._lib.acmpc_set_road(self._ctx, r.ctypes.data, r.shape[0], r.shape[1]))
 
     def score_grips(self, states, controls, dt: float, scales, segment: int = 1, weights=(1.0, 1.0, 1.0)):
         """Mode D's grip identification (acmpc_score_grips): `states` [W + 1, 3] = (vx, vy, r) - or [W + 1, 6], whose last

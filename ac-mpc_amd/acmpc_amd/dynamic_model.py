@@ -17,7 +17,11 @@ one trajectory of `DynamicBicycleParams.rollout`: what the float32 specification
 
 `actuator_coefficients` and `actuator_response` are the float64 mirror of acmpc_set_dynamics_actuator - first-order lags on the
 steering and the pedal: the vehicle is driven on the mean of each actuator's response over the control step - and `actuator=` of
-`rollout` and `trace` rolls a plan on that applied control while every cost line stays on the command."""
+`rollout` and `trace` rolls a plan on that applied control while every cost line stays on the command.
+
+`road_table` makes the per-waypoint rows (a_x, a_y, n_z) of acmpc_set_road from the grade and the bank of a path - or from patches
+along the arc length ("6 % downhill from 40 m to 120 m"); `trace(..., road=)` and the `road=` argument of `predict_next_state` /
+`rollout` are its float64 mirror."""
 from __future__ import annotations
 
 import dataclasses
@@ -155,7 +159,7 @@ class DynamicBicycleParams:
         return w, self.F_zf + d_f - w, self.F_zr + d_r + w
 
     def predict_next_state(self, state, u, dt: float = 0.05, coupling=None, load_transfer=None,
-                           downforce=None, grip=None) -> Tuple[np.ndarray, np.ndarray, list]:
+                           downforce=None, grip=None, road=None) -> Tuple[np.ndarray, np.ndarray, list]:
         """One explicit Euler step in float64: state (X, Y, yaw, vx, vy, r), u = (delta, pedal) with the pedal in
         [-1, 1].  Returns (next_state, x_dot, [F_fy, F_ry, F_fx, F_rx]) like the reference; the caller clips vx >= 0
         (the reference's loop does, dynamic_bicycle_model.py:180; so do the kernels, inside the step).  `coupling` = rho
@@ -168,7 +172,17 @@ class DynamicBicycleParams:
         acmpc_set_dynamics_downforce in float64 (None: off): the same one pass with k_a min(vx, v_sat)^2 on each axle's load
         under the load moved, and the exact load-dependent peak P(F_z + x); the force list holds the final forces.  `grip` =
         (mu_f, mu_r) is the surface's pair of this step (acmpc_set_surface; None: (1, 1)): the step of
-        with_axle_grip(mu_f, mu_r) - both axles' peak factors scaled wherever the step reads them."""
+        with_axle_grip(mu_f, mu_r) - both axles' peak factors scaled wherever the step reads them.  `road` = (a_x, a_y, n_z) is
+        the road's row of this step (acmpc_set_road; None: (0, 0, 1)): both peak factors scaled by n_z as well - the normal load
+        on a slope, taken linearly - and gravity's in-plane accelerations added to x_dot[3] and x_dot[4], along the body's axes."""
+        if road is not None:
+            a_x, a_y, n_z = (float(v) for v in road)
+            mu_f, mu_r = (1.0, 1.0) if grip is None else (float(m) for m in grip)
+            _, x_dot, forces = self.with_axle_grip(mu_f * n_z, mu_r * n_z).predict_next_state(
+                state, u, dt, coupling=coupling, load_transfer=load_transfer, downforce=downforce)
+            x_dot[3] += a_x
+            x_dot[4] += a_y
+            return np.asarray(state, dtype=np.float64) + x_dot * dt, x_dot, forces
         if grip is not None:
             return self.with_axle_grip(*grip).predict_next_state(state, u, dt, coupling=coupling, load_transfer=load_transfer,
                                                                  downforce=downforce)
@@ -209,7 +223,7 @@ class DynamicBicycleParams:
         return D * (1 + eps * F_z / self.F_z0) * F_z / self.F_z0 * np.sin(C * np.arctan(ba - E * (ba - np.arctan(ba))))
 
     def rollout(self, state, U, dt: float = 0.05, substeps: int = 1, low_speed_blend=None, coupling=None,
-                load_transfer=None, downforce=None, grip=None, actuator=None) -> np.ndarray:
+                load_transfer=None, downforce=None, grip=None, actuator=None, road=None) -> np.ndarray:
         """The mirror over a control sequence U [n, 2] with vx clipped after every step: states [n + 1, 6].  `substeps`
         and `low_speed_blend` = (v_lo, v_hi) are the integration setting of acmpc_set_dynamics_integration in float64: a
         control step is `substeps` Euler steps of dt / substeps, and after each (vy, r) are blended towards the kinematic
@@ -217,15 +231,17 @@ class DynamicBicycleParams:
         `coupling`, `load_transfer`, `downforce`: predict_next_state's, in every sub-step.  `grip` = (mu_f, mu_r): one pair
         of grip scales for the whole roll (predict_next_state's; a surface table changes it per control step: trace()).
         `actuator` = (tau, a0) - tau = (tau_d, tau_p) in seconds, a0 = (a_d, a_p) the actuator positions at the start or None
-        (U[0] then stands for them) - rolls on actuator_response's applied control instead of U (acmpc_set_dynamics_actuator)."""
+        (U[0] then stands for them) - rolls on actuator_response's applied control instead of U (acmpc_set_dynamics_actuator).
+        `road` = (a_x, a_y, n_z): one road row for the whole roll (predict_next_state's, in every sub-step; a road table changes
+        it per control step: trace())."""
         if actuator is not None:
             tau, a0 = actuator
             applied, _ = actuator_response(U, a0, tau, dt)
             return self.rollout(state, applied, dt, substeps=substeps, low_speed_blend=low_speed_blend, coupling=coupling,
-                                load_transfer=load_transfer, downforce=downforce, grip=grip)
+                                load_transfer=load_transfer, downforce=downforce, grip=grip, road=road)
         if grip is not None:
             return self.with_axle_grip(*grip).rollout(state, U, dt, substeps=substeps, low_speed_blend=low_speed_blend,
-                                                      coupling=coupling, load_transfer=load_transfer, downforce=downforce)
+                                                      coupling=coupling, load_transfer=load_transfer, downforce=downforce, road=road)
         substeps = int(substeps)
         if substeps < 1:
             raise ValueError("substeps must be positive")
@@ -234,7 +250,8 @@ class DynamicBicycleParams:
         for u in np.asarray(U, dtype=np.float64):
             nxt = out[-1]
             for _ in range(substeps):
-                nxt = self.predict_next_state(nxt, u, h, coupling=coupling, load_transfer=load_transfer, downforce=downforce)[0]
+                nxt = self.predict_next_state(nxt, u, h, coupling=coupling, load_transfer=load_transfer, downforce=downforce,
+                                              road=road)[0]
                 nxt[3] = max(nxt[3], 0.0)
                 if low_speed_blend is not None:
                     v_lo, v_hi = (float(v) for v in low_speed_blend)
@@ -382,6 +399,38 @@ def surface_table(arc_length, patches) -> np.ndarray:
     return table.astype(np.float32)
 
 
+def road_table(grade, bank=None, g: float = 9.81, arc_length=None) -> np.ndarray:
+    """The table acmpc_set_road takes for one path, [n, 3] float32 = (a_x, a_y, n_z) per waypoint, from `grade` [n] - theta, the
+    road's slope along the path in radians, uphill positive - and `bank` [n] - beta, positive where the left side is lower (None:
+    level): a_x = -g sin theta, a_y = g cos theta sin beta, n_z = cos theta cos beta, computed in float64 and rounded once each.
+    With `arc_length` [n] (as surface_table's) `grade` is instead a list of patches (s_from, s_to, theta) or (s_from, s_to, theta,
+    beta) - "6 % downhill from 40 m to 120 m" is (40, 120, -atan(0.06)) - later patches override earlier ones, a waypoint in no
+    patch is level, and `bank` must be None.  |theta|, |beta| < pi / 2 (n_z > 0)."""
+    if arc_length is not None:
+        if bank is not None:
+            raise ValueError("with arc_length the bank comes in the patches")
+        s = np.asarray(arc_length, dtype=np.float64).ravel()
+        theta, beta = np.zeros(s.size), np.zeros(s.size)
+        for patch in grade:
+            patch = tuple(float(v) for v in patch)
+            if len(patch) not in (3, 4):
+                raise ValueError("a patch is (s_from, s_to, theta) or (s_from, s_to, theta, beta), not %r" % (patch,))
+            inside = (s >= patch[0]) & (s <= patch[1])
+            theta[inside] = patch[2]
+            beta[inside] = patch[3] if len(patch) == 4 else 0.0
+    else:
+        theta = np.asarray(grade, dtype=np.float64)
+        beta = np.zeros_like(theta) if bank is None else np.asarray(bank, dtype=np.float64)
+        if theta.ndim != 1 or beta.shape != theta.shape:
+            raise ValueError("grade and bank are [n] each, not %r and %r" % (theta.shape, beta.shape))
+    limit = np.pi / 2.0
+    if not (np.all(np.isfinite(theta)) and np.all(np.isfinite(beta)) and np.all(np.abs(theta) < limit) and np.all(np.abs(beta) < limit)):
+        raise ValueError("grade and bank are finite and within (-pi / 2, pi / 2)")
+    g = float(g)
+    rows = np.stack([-g * np.sin(theta), g * np.cos(theta) * np.sin(beta), np.cos(theta) * np.cos(beta)], axis=1)
+    return rows.astype(np.float32)
+
+
 def actuator_coefficients(tau, dt: float) -> Tuple[np.ndarray, np.ndarray]:
     """(k [2], m [2]) of acmpc_set_dynamics_actuator in float64 for tau = (tau_d, tau_p) seconds and the control step dt:
     k_c = exp(-dt / tau_c), what is left of an error after one control step, and m_c = (tau_c / dt)(1 - k_c), the mean of what is
@@ -420,7 +469,7 @@ TRACE_HINGES = ("box", "corridor", "rate", "slip", "ceiling", "obstacles")   # w
 def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min=(-0.3, -1.0), u_max=(0.3, 1.0),
           margin: float = 0.0, wheelbase=None, nn_window=None, substeps: int = 1, low_speed_blend=None, coupling=None,
           load_transfer=None, downforce=None, u_prev=None, rate_max=None, slip_max=None, speed_ceiling=None, obstacles=None,
-          radii=None, surface=None, actuator=None) -> dict:
+          radii=None, surface=None, actuator=None, road=None) -> dict:
     """The float64 mirror of Engine.trace_plans for one plan under one vehicle: `params.rollout(state, U, ...)` with the
     handle's step settings, and per control step - on the state after it, against its nearest waypoint j of `table` [7, n]
     (objective_terms' search: `nn_window` from waypoint 0, None: all) - what the cost lines see and the hinges they square
@@ -432,7 +481,8 @@ def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min
     atan(wheelbase kappa_j).  `surface` [n, 2] = (mu_f, mu_r) per waypoint (acmpc_set_surface, surface_table): control step i
     is rolled with grip = surface[j_{i-1}], the nearest waypoint of the step before and waypoint 0 first - the scale lags the
     position by one control step, as on the device.  `actuator` = (tau, a0) (acmpc_set_dynamics_actuator, rollout's): the states
-    are rolled on actuator_response's applied control; dk, the box and the rates stay on the command U."""
+    are rolled on actuator_response's applied control; dk, the box and the rates stay on the command U.  `road` [n, 3] = (a_x,
+    a_y, n_z) per waypoint (acmpc_set_road, road_table): control step i is rolled with road = road[j_{i-1}], the surface's lag."""
     U = np.asarray(U, dtype=np.float64)
     driven = U if actuator is None else actuator_response(U, actuator[1], actuator[0], dt)[0]
     table = np.asarray(table, dtype=np.float64)
@@ -452,19 +502,23 @@ def trace(params: DynamicBicycleParams, state, U, table, dt: float = 0.05, u_min
         return first + int(np.argmin(d2[first:first + span]))
 
     j = np.empty(n, dtype=np.int64)
-    if surface is None:
+    if surface is None and road is None:
         states = params.rollout(state, driven, dt, **step)
         prev = 0
         for i in range(n):
             prev = j[i] = nearest(states[i + 1], prev)
     else:
-        scales = np.asarray(surface, dtype=np.float64)
+        scales = np.ones((n, 2)) if surface is None else np.asarray(surface, dtype=np.float64)
         if scales.shape != (n, 2):
             raise ValueError("surface is [n, 2] = (mu_f, mu_r) per waypoint")
+        rows = None if road is None else np.asarray(road, dtype=np.float64)
+        if rows is not None and rows.shape != (n, 3):
+            raise ValueError("road is [n, 3] = (a_x, a_y, n_z) per waypoint")
         rolled = [np.asarray(state, dtype=np.float64)]
         prev = 0
         for i in range(n):
-            rolled.append(params.rollout(rolled[-1], driven[i:i + 1], dt, grip=scales[prev], **step)[1])
+            rolled.append(params.rollout(rolled[-1], driven[i:i + 1], dt, grip=scales[prev],
+                                         road=None if rows is None else rows[prev], **step)[1])
             prev = j[i] = nearest(rolled[-1], prev)
         states = np.stack(rolled)
     after = states[1:]

@@ -75,6 +75,12 @@ advanced through the first `warm_steps` controls of the last accepted plan (dyna
 plan, `previous_control`, or none (the first command then stands for the positions).  `trace()` re-rolls under the same lag and
 positions.  A dead time is not modelled: roll the start state forward under the controls already sent.
 
+Road (acmpc_set_road): `solve(..., road=rows)` - [n, 3] = (a_x, a_y, n_z) per waypoint of this solve's path
+(dynamic_model.road_table makes one from the path's grade and bank, or from "6 % downhill from 40 m to 120 m") - adds gravity's
+in-plane acceleration to every candidate's step where it is on the path and scales the tyres' peaks by the normal load's factor:
+a downhill braking zone is planned with the deceleration that is there, a banked corner with the speed it carries.  The row lags
+the position by one control step, as the surface's scales do.  None: a level road (a table set by an earlier solve is cleared).
+
 Grip adaptation (acmpc_score_grips, GripEstimator): `grip_adapt` - a dict, off by default - lets the solver find the road's
 grip from its own driving instead of being told an ensemble.  Every solve logs (state, the control applied since the
 previous solve - `previous_control`, else the last accepted plan's first control), scores a grid of grip hypotheses
@@ -223,6 +229,7 @@ class DynamicSamplingSolver:
             self._engine.set_dynamics_actuator(lag)
         self._has_obstacles = False
         self._has_surface = False
+        self._has_road = False
         self._plan_states = bool(config.get("plan_states", False))
         self._last_state: Optional[np.ndarray] = None   # the start state of the last solve: what trace() re-rolls from
         self._plan: Optional[np.ndarray] = None
@@ -272,7 +279,7 @@ class DynamicSamplingSolver:
 
     def trace(self, plan=None):
         """Engine.trace_plans of `plan` [n, 2] (default: the last accepted plan) from the last solve's start state, on its
-        path, previous control, obstacles, surface table and actuator positions, under every vehicle of the handle: dict(states [K, n + 1, 6], cost [K],
+        path, previous control, obstacles, surface table, road table and actuator positions, under every vehicle of the handle: dict(states [K, n + 1, 6], cost [K],
         violation [K], terms [K, n, 22] and its named views)."""
         if self._last_state is None:
             raise ValueError("trace() follows a solve")
@@ -307,12 +314,14 @@ class DynamicSamplingSolver:
             self._base_grip = (now[0] * self._adapt["bracket"][0], now[1] * self._adapt["bracket"][0])
 
     def solve(self, state, reference_path, previous_control=None, obstacles=None, warm_steps: int = 1, surface=None,
-              actuator_state=None):
+              actuator_state=None, road=None):
         """state (X, Y, yaw, vx, vy, r); reference_path a [7, n] table (rows x, y, psi, kappa, ds, width, v) or an object
         with `as_table()` / `_reference_path` giving one.  `previous_control` = (delta, pedal) applied just before this
         solve, for the rate terms' step 0; None: the first control of the last accepted plan (none before there is one).
         `obstacles` = (positions [n, K, 2], radii [K]) for this solve (Engine.set_obstacles); None: no obstacles.
         `surface` = [n, 2] (mu_f, mu_r) per waypoint, or [n], for this solve (Engine.set_surface); None: no table.
+        `road` = [n, 3] (a_x, a_y, n_z) per waypoint for this solve (Engine.set_road; dynamic_model.road_table makes one from the
+        path's grade and bank); None: a level road.
         `actuator_state` = (a_d, a_p), the measured actuator positions now, with `actuator_lag` (Engine.set_actuator_state);
         None: the solver's own estimate.  `warm_steps`: control steps since the previous solve (warm_start's shift)."""
         table = reference_path
@@ -345,6 +354,12 @@ class DynamicSamplingSolver:
         elif self._has_surface:
             self._engine.set_surface(None)
             self._has_surface = False
+        if road is not None:
+            self._engine.set_road(np.asarray(road, dtype=np.float32)[: self._n])
+            self._has_road = True
+        elif self._has_road:
+            self._engine.set_road(None)
+            self._has_road = False
         self._last_state = np.asarray(state, dtype=np.float32).reshape(6).copy()
         out = self._engine.optimize(self._last_state[None], self.warm_start(warm_steps)[None], None,
                                     self._N, self._rounds, self._sigma, seed=self._seed + self._calls)

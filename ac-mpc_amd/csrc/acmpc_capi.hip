@@ -151,6 +151,17 @@ int upload_previous_control(acmpc_ctx* c, hipStream_t s) {
     ACMPC_HIP(c, hipMemcpyAsync(c->d_surface, c->h_surface.data(), c->h_surface.size() * sizeof(float), hipMemcpyHostToDevice, s));
     c->surf_dirty = false;
   }
+  if (c->road_dirty && c->road_P != 0 && c->device_ready) {   // and the road table staged by acmpc_set_road
+    if (c->road_capacity < c->h_road.size()) {
+      (void)hipFree(c->d_road);
+      c->d_road = nullptr;
+      c->road_capacity = 0;
+      ACMPC_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_road), c->h_road.size() * sizeof(float)));
+      c->road_capacity = c->h_road.size();
+    }
+    ACMPC_HIP(c, hipMemcpyAsync(c->d_road, c->h_road.data(), c->h_road.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    c->road_dirty = false;
+  }
   if (c->astate_dirty && c->astate_P != 0 && c->d_astate != nullptr) {   // and the actuator positions staged by acmpc_set_actuator_state
     ACMPC_HIP(c, hipMemcpyAsync(c->d_astate, c->h_astate.data(), c->h_astate.size() * sizeof(float), hipMemcpyHostToDevice, s));
     c->astate_dirty = false;
@@ -256,6 +267,12 @@ int check_shape(acmpc_ctx* c, int P, int N, int n, int layout, bool stream_call)
     char buf[160];
     std::snprintf(buf, sizeof buf, "shape (P=%d, n=%d) does not match the surface table set (P=%d, n=%d): acmpc_set_surface", P, n,
                   c->surf_P, c->surf_n);
+    return fail(c, ACMPC_ESTATE, buf);
+  }
+  if (c->prm.mode == ACMPC_MODE_DYNAMIC && c->road_P != 0 && (P != c->road_P || n != c->road_n)) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "shape (P=%d, n=%d) does not match the road table set (P=%d, n=%d): acmpc_set_road", P, n,
+                  c->road_P, c->road_n);
     return fail(c, ACMPC_ESTATE, buf);
   }
   return ACMPC_OK;
@@ -533,6 +550,7 @@ void acmpc_destroy(acmpc_ctx* c) {
     (void)hipFree(c->d_astate);
     (void)hipFree(c->d_obs);
     (void)hipFree(c->d_surface);
+    (void)hipFree(c->d_road);
     (void)hipFree(c->d_progress);
     (void)hipFree(c->d_identify);
     (void)hipFree(c->d_identify_e);

@@ -1,5 +1,5 @@
 // C ABI, mode D's settings (include/acmpc.h).  This unit owns the vehicle blocks and what is derived from them
-// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the downforce, the previous control, the obstacles and the clearance setting, the surface table, the actuator lag and the actuator positions, and the grip
+// (acmpc_set_dynamics*), the integration setting, the rate and slip terms, the objective, the tyre coupling, the load transfer, the downforce, the previous control, the obstacles and the clearance setting, the surface table, the road table, the actuator lag and the actuator positions, and the grip
 // identification (acmpc_score_grips) and the plan trace (acmpc_trace_plans), with the checks that the kernels' limits are the public header's.
 #include <algorithm>
 
@@ -419,6 +419,32 @@ int acmpc_set_surface(acmpc_ctx* c, const float* grip, int32_t P, int32_t n) {
   c->surf_P = P;
   c->surf_n = n;
   c->surf_dirty = true;
+  return ACMPC_OK;
+}
+
+int acmpc_set_road(acmpc_ctx* c, const float* road, int32_t P, int32_t n) {
+  if (c == nullptr) return ACMPC_EINVAL;
+  if (c->prm.mode != ACMPC_MODE_DYNAMIC) return fail(c, ACMPC_ESTATE, "acmpc_set_road needs a mode D handle");
+  if (road == nullptr) {
+    c->h_road.clear();
+    c->road_P = c->road_n = 0;
+    c->road_dirty = false;
+    return ACMPC_OK;
+  }
+  if (P < 1 || P > c->prm.max_problems) return fail(c, ACMPC_EINVAL, "P must be 1 .. max_problems");
+  if (n < 1 || n > c->prm.max_steps) return fail(c, ACMPC_EINVAL, "n must be 1 .. max_steps");
+  const size_t rows = static_cast<size_t>(P) * n;
+  for (size_t q = 0; q < 3 * rows; ++q)
+    if (!std::isfinite(road[q])) return fail(c, ACMPC_EINVAL, "a road value must be finite");
+  for (size_t q = 0; q < rows; ++q)
+    if (!(road[3 * q + 2] > 0.0f)) return fail(c, ACMPC_EINVAL, "a road row's n_z must be > 0");
+  // everything is checked before anything is kept: a refused table leaves the handle's as it was.  Staged as the device reads
+  // it: (a_x, a_y, n_z, 0), one aligned 16-byte row per waypoint
+  c->h_road.assign(4 * rows, 0.0f);
+  for (size_t q = 0; q < rows; ++q) std::memcpy(&c->h_road[4 * q], road + 3 * q, 3 * sizeof(float));
+  c->road_P = P;
+  c->road_n = n;
+  c->road_dirty = true;
   return ACMPC_OK;
 }
 

@@ -20,8 +20,9 @@ namespace capi __attribute__((visibility("hidden"))) {
 // setting; K = 0 while none are set, the soft part on with a weight that is not 0.
 // And of its surface table ("Surface"): the device table and what it was set for.
 // And of its actuator lag ("Actuator"): the four floats, and the positions' device block while positions are set.
-acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsSurface>> dynamics_terms(const acmpc_ctx* c) {
-  acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsSurface>> t{};
+// And of its road table ("Road"): the device table and what it was set for.
+acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsRoad>> dynamics_terms(const acmpc_ctx* c) {
+  acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsRoad>> t{};
   t.rate = (c->rate_weight[0] != 0.0 || c->rate_weight[1] != 0.0 || std::isfinite(c->rate_max[0]) ||
             std::isfinite(c->rate_max[1])) ? 1 : 0;
   t.slip = (c->slip_weight != 0.0 || std::isfinite(c->slip_max)) ? 1 : 0;
@@ -76,7 +77,16 @@ acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsSurface>> dynamics_terms(co
       t.mu_n = c->surf_n;
     }
   }
-  if (c->surf_P != 0 || c->has_actuator) {
+  // ("Road": the same top-tier step again, with or without the surface's scales)
+  if (c->road_P != 0) {
+    t.road = 1;
+    if (!c->road_dirty && c->d_road != nullptr) {   // (every mode D call uploads first; a launch without the table is refused)
+      t.road_rows = c->d_road;
+      t.road_P = c->road_P;
+      t.road_n = c->road_n;
+    }
+  }
+  if (c->surf_P != 0 || c->has_actuator || c->road_P != 0) {
     if (t.aero == 0) {
       t.k_f = t.k_r = 0.0f;
       t.v_sat = 100.0f;

@@ -316,6 +316,14 @@ struct acmpc_ctx {
   int astate_P = 0;             // 0: none set
   bool astate_dirty = false;
   float* d_astate = nullptr;    // [max_problems][2]
+  // mode D: the road table (acmpc_set_road), staged here like the surface table until the next upload: (a_x, a_y, n_z, 0)
+  // [road_P][road_n][4] on the host - padded as the device reads it, one aligned 16-byte row per waypoint - and on the device
+  // (allocated by the upload that first needs it, grown when a larger one arrives)
+  std::vector<float> h_road;
+  int road_P = 0, road_n = 0;            // road_P = 0: none set
+  bool road_dirty = false;
+  float* d_road = nullptr;
+  size_t road_capacity = 0;              // floats
   // mode D: the plan trace's device block (acmpc_trace_plans): x0 | U | states | totals | terms of ONE call, made on the call's
   // first use, kept between calls and regrown when a later call needs more
   unsigned char* d_plan_trace = nullptr;
@@ -351,7 +359,7 @@ acmpc::Integration dynamics_integration(const acmpc_ctx* c);
 // (acmpc_capi_dynamic.hip) the six load scalars of vehicle k as the surface step needs them while neither the load transfer nor
 // the downforce is on: c_h = w_max = 0 and the vehicle's own a1, a2 (zeros for a block that has none)
 void surface_load_const(const acmpc_ctx* c, int k, float* out);
-acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsSurface>> dynamics_terms(const acmpc_ctx* c);   // (after the call's uploads: upload_tables)
+acmpc::WithActuator<acmpc::WithObstacles<acmpc::TermsRoad>> dynamics_terms(const acmpc_ctx* c);   // (after the call's uploads: upload_tables)
 acmpc::SampleSpec make_spec(const acmpc_ctx* c, double sigma_v, double sigma_k, uint64_t seed, uint32_t round);
 // (`set`: which half of the partial keys / feasible counts - chained rounds and the stream of batches alternate)
 acmpc::RolloutArgs rollout_args(const acmpc_ctx* c, const float* d_x0, const float* d_U, float* d_costs, int P, int N, int n,

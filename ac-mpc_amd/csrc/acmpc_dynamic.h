@@ -245,6 +245,21 @@ struct IsAero : std::false_type {};
 template <typename PK>
 struct IsAero<AeroPeaks<PK>> : std::true_type {};
 
+// Road grade and banking (acmpc_set_road, DESIGN.md section 2 "Mode D, road"): the surface's peak source - the lane's peaks,
+// here the vehicle's scaled by the grip scales and by the road's factor n_z on the normal load - with gravity's two in-plane
+// accelerations of the lane's waypoint beside it, typed on F like the peaks.  An IsAero (the step's block is the downforce's, on
+// these peaks) and the one IsRoad: dynamic_euler adds a_x to xd3 and a_y to xd4, one float32 add each.
+template <typename F>
+struct RoadPeaks : AeroPeaks<SurfacePeaks<F>> {
+  F ax, ay;
+};
+template <typename F>
+struct IsAero<RoadPeaks<F>> : std::true_type {};
+template <typename PK>
+struct IsRoad : std::false_type {};
+template <typename F>
+struct IsRoad<RoadPeaks<F>> : std::true_type {};
+
 // The two peaks of a sub-step under the downforce, in spec order: va = min(vx, v_sat) (minNum: a NaN vx gives v_sat), q = va va,
 // d_a = k_a q, psi_a = 1 + d_a (a1_a + a2_a d_a), P_a0 = P_a psi_a - the peaks at this speed before any tyre force; the demands
 // clipped at the caps rho_a P_a0 AT THIS SPEED, w = c_h (e_f + e_r) clipped at +-w_max, x_f = d_f - w, x_r = d_r + w,
@@ -290,7 +305,8 @@ __device__ __forceinline__ ControlTerms<F> control_terms(F delta, F pedal) {
 // always computed them - the default setting's kernels are to stay the code they were, instruction for instruction.
 // PK: the source of the peak factors (VehiclePeaks or LanePeaks), or a CoupledPeaks of one: the tyre coupling; or a LoadedPeaks
 // of one: the coupling with the load transfer in front of it (the side forces then wait for the loaded peaks); or an AeroPeaks
-// of one: the same with the downforce of the sub-step's incoming speed under the load moved.
+// of one: the same with the downforce of the sub-step's incoming speed under the load moved; or a RoadPeaks: that on the lane's
+// own peaks, with gravity's two in-plane accelerations added to xd3 and xd4.
 template <bool HOISTED, typename F, typename PK = VehiclePeaks>
 __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, const ControlTerms<F>* pre, const Vehicle& k,
                                               float dt, const PK pk = PK{}) {
@@ -349,8 +365,12 @@ __device__ __forceinline__ void dynamic_euler(StateD_<F>& s, F delta, F pedal, c
   sincos_spec<F>(s.t.phi, sy, cy);
   const F xd0 = vx * cy - vy * sy;
   const F xd1 = vx * sy + vy * cy;
-  const F xd3 = k.inv_mass * ((((F_rx + F_fx) + F_fric) - F_fy * sd) + (k.mass * vy) * r);
-  const F xd4 = k.inv_mass * ((F_ry + F_fy * cd) - (k.mass * vx) * r);
+  F xd3 = k.inv_mass * ((((F_rx + F_fx) + F_fric) - F_fy * sd) + (k.mass * vy) * r);
+  F xd4 = k.inv_mass * ((F_ry + F_fy * cd) - (k.mass * vx) * r);
+  if constexpr (IsRoad<PK>::value) {   // (gravity along the body's axes on a road that is not level: acmpc_set_road)
+    xd3 = xd3 + pk.ax;
+    xd4 = xd4 + pk.ay;
+  }
   const F xd5 = k.inv_Iz * ((F_fy * k.lf) * cd - F_ry * k.lr);
   s.t.X = s.t.X + xd0 * dt;
   s.t.Y = s.t.Y + xd1 * dt;
@@ -493,6 +513,21 @@ struct TermsSurface : TermsAero {
 };
 __host__ __device__ inline bool has_surface(const TermsSurface& t) { return t.surface != 0; }
 
+// The TermsSurface plus the road table of a handle (acmpc_set_road, DESIGN.md section 2 "Mode D, road"): a seventh pack type.
+// road_rows [P][n][4] = (a_x, a_y, n_z, 0) per waypoint, on the device, a row 16 bytes and aligned so; control step i of a
+// candidate runs all its sub-steps on the peaks (Pf mu_f[j]) n_z[j], (Pr mu_r[j]) n_z[j] - the mu multiply only while `surface`
+// is set, a scalar switch - and adds a_x[j] to xd3 and a_y[j] to xd4 in every sub-step, j the nearest waypoint of step i - 1
+// (waypoint 0 before step 0): the surface table's lag.  The kernels instantiated for it (acmpc_dynamic_road.hip,
+// acmpc_dynamic_road_actuator.hip) run only while `road` is set, always with the aero step at the neutral values of the tiers that
+// are off (as under the surface); every other kernel stays the code it was.  The launchers take the handle's settings as one of
+// these (under the obstacles' and the actuator's packs, below).
+struct TermsRoad : TermsSurface {
+  const float* road_rows;
+  int road;                     // 0: off (road_rows not read); the kernels do not read it
+  int road_P, road_n;           // what road_rows was set for: the launchers refuse another shape (the kernels do not read them)
+};
+__host__ __device__ inline bool has_road(const TermsRoad& t) { return t.road != 0; }
+
 // Moving obstacles of a handle (acmpc_set_obstacles, acmpc_set_dynamics_clearance; DESIGN.md section 2 "Mode D, obstacles"): up
 // to kMaxObstacles discs per problem, each with a position per control step - row i is where the discs are at the state AFTER
 // control step i, the state that step's dynamic_cost sees - and a radius with the ego's folded in.  Per step, after the ceiling
@@ -520,7 +555,7 @@ template <typename TT>
 struct PackBase { using type = TT; };
 template <typename Base>
 struct PackBase<WithObstacles<Base>> { using type = Base; };
-// the obstacles' pack over another base (the handle's settings are a WithObstacles<TermsSurface>)
+// the obstacles' pack over another base (the handle's settings are a WithObstacles<TermsRoad> under the actuator's pack)
 template <typename Base, typename From>
 inline WithObstacles<Base> obstacles_over(const WithObstacles<From>& t) {
   WithObstacles<Base> r{};
@@ -551,10 +586,10 @@ __device__ __forceinline__ bool soft_part(const WithObstacles<Base>& t) { return
 // and the control step - control_terms, every sub-step, the blend's tan(delta) - is driven on (delta_x, pedal_x); dynamic_cost,
 // the terms, the records and the sampler stay on the command.  a0 [P][2]: the positions at the start of the plan, on the
 // device, or nullptr (step 0's own command then stands for them: e = +0, as with Terms::u_prev).  A wrapper pack like the
-// obstacles', over the packs of the top-tier step (TermsAero, TermsSurface, each with or without the obstacles' pack): the
-// kernels instantiated for the four (acmpc_dynamic_actuator.hip) run only while `actuator` is set, with the lower tiers' neutral
-// values where a tier is off (as under the surface); every other kernel stays the code it was.  The launchers take the handle's
-// settings as a WithActuator<WithObstacles<TermsSurface>>.
+// obstacles', over the packs of the top-tier step (TermsAero, TermsSurface, each with or without the obstacles' pack; TermsRoad
+// likewise: acmpc_dynamic_road_actuator.hip): the kernels instantiated for the four (acmpc_dynamic_actuator.hip) run only while
+// `actuator` is set, with the lower tiers' neutral values where a tier is off (as under the surface); every other kernel stays
+// the code it was.  The launchers take the handle's settings as a WithActuator<WithObstacles<TermsRoad>>.
 struct ActuatorLag {
   float k_d, m_d, k_p, m_p;
   const float* a0;
@@ -703,6 +738,73 @@ __device__ __forceinline__ AeroPeaks<SurfacePeaks<F>> surface_peaks(const AeroPe
   pk.k_r = a.k_r;
   pk.v_sat = a.v_sat;
   return pk;
+}
+
+// And for a TermsRoad: dynamic_advance_fine<F, RoadPeaks<F>>(..., road_peaks<F>(aero_peaks(vk, tm...), veh, road_row<F>(p, n, j,
+// tm...))), at the top of every control step as above.  One aligned 16-byte load from global memory per candidate (two under
+// f32x2; a scalar load where j is wave-uniform), no LDS, no bounds code (0 <= j < n), and - while a surface table is set, a scalar
+// switch on the kernel argument - the surface's 8-byte load beside it.  Nothing per vehicle: the row is the road's.
+template <typename... TM>
+constexpr bool kRoadPack = (std::is_same<typename PackBase<typename std::remove_cv<TM>::type>::type, TermsRoad>::value || ...);
+__device__ __forceinline__ void gather_road(const float* rows, int j, float& ax, float& ay, float& nz) {
+  const f32x4 m = *reinterpret_cast<const f32x4*>(rows + 4 * static_cast<size_t>(j));
+  ax = m[0];
+  ay = m[1];
+  nz = m[2];
+}
+__device__ __forceinline__ void gather_road(const float* rows, i32x2 j, f32x2& ax, f32x2& ay, f32x2& nz) {
+  const f32x4 m0 = *reinterpret_cast<const f32x4*>(rows + 4 * static_cast<size_t>(j[0]));
+  const f32x4 m1 = *reinterpret_cast<const f32x4*>(rows + 4 * static_cast<size_t>(j[1]));
+  ax = f32x2{m0[0], m1[0]};
+  ay = f32x2{m0[1], m1[1]};
+  nz = f32x2{m0[2], m1[2]};
+}
+// the road row of problem p's waypoint(s) j, and the grip scales there (ones while no surface table is set: Pf 1 = Pf bit for
+// bit): issued ahead of the control's load or draw, multiplied in by road_peaks
+template <typename F>
+struct RoadRow {
+  F mf, mr, ax, ay, nz;
+};
+template <typename F>
+__device__ __forceinline__ RoadRow<F> road_row(int p, int n, typename IndexOf<F>::type j, const TermsRoad& t) {
+  RoadRow<F> m;
+  m.mf = m.mr = splat<F>(1.0f);
+  if (t.surface != 0) gather_scales(t.mu + static_cast<size_t>(p) * n * 2, j, m.mf, m.mr);
+  gather_road(t.road_rows + static_cast<size_t>(p) * n * 4, j, m.ax, m.ay, m.nz);
+  return m;
+}
+template <typename F>
+__device__ __forceinline__ RoadRow<F> road_row(int p, int n, typename IndexOf<F>::type j, const TermsState<F>&, const TermsRoad& t) {
+  return road_row<F>(p, n, j, t);
+}
+// Pf_r = (Pf mu_f) n_z, Pr_r = (Pr mu_r) n_z - one float32 multiply each for the surface and one for the road, once per control
+// step - in front of the scalars `a` of the vehicle, with the row's two accelerations
+template <typename F>
+__device__ __forceinline__ RoadPeaks<F> road_peaks(const AeroPeaks<VehiclePeaks>& a, const Vehicle& k, const RoadRow<F>& m) {
+  RoadPeaks<F> pk;
+  pk.Pf = (k.Pf * m.mf) * m.nz;
+  pk.Pr = (k.Pr * m.mr) * m.nz;
+  pk.rho_f = a.rho_f;
+  pk.rho_r = a.rho_r;
+  pk.c_h = a.c_h;
+  pk.w_max = a.w_max;
+  pk.a1_f = a.a1_f;
+  pk.a2_f = a.a2_f;
+  pk.a1_r = a.a1_r;
+  pk.a2_r = a.a2_r;
+  pk.k_f = a.k_f;
+  pk.k_r = a.k_r;
+  pk.v_sat = a.v_sat;
+  pk.ax = m.ax;
+  pk.ay = m.ay;
+  return pk;
+}
+// the handle's settings without the road table: what every launcher from before the road takes
+inline WithActuator<WithObstacles<TermsSurface>> below_road(const WithActuator<WithObstacles<TermsRoad>>& t) {
+  WithActuator<WithObstacles<TermsSurface>> r{};
+  static_cast<WithObstacles<TermsSurface>&>(r) = obstacles_over<TermsSurface>(t);
+  r.lag = t.lag;
+  return r;
 }
 
 // one float of the staged waypoint row(s) j, or of a table of one float per waypoint (stride 1)
@@ -914,21 +1016,22 @@ int dynamic_blocks_per_problem(int P, int N, int K = 1);
 // without them run (the general, the coupled, the loaded or the aero one), looked at first.  And its surface table: while one is
 // set, the surface kernels run (the aero step on per-lane peaks, with or without the obstacles' lines), whatever else is on.
 // And its actuator lag: while that is on, the actuator kernels run (the aero or the surface step on the lagged control, with or
-// without the obstacles' lines), looked at before everything else.
+// without the obstacles' lines), looked at before everything else but the road.  And its road table: while one is set, the road
+// kernels run (the surface step with the road's row, with or without the obstacles' lines and the actuator lag), looked at first.
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& integration, const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
+                                  const Integration& integration, const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
 // the same rollout with the candidates drawn inside the kernel instead of read from args.U (which is ignored): candidate
 // index_offset + c of problem p is what launch_sample would write for `sample` - centre, u_ref, centre_stride, spec (seed or
 // seed_ptr, round, sigmas = (sigma_delta, sigma_pedal), segments); P / N / n / index_offset must be the rollout's, the spec's
 // input box the Weights', u_extra null (hipErrorInvalidValue otherwise).  Same launch shapes, costs, partial keys and counts.
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& integration, const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
+                                          const Integration& integration, const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
 // argmin over the partial keys (or keys_in), keys_out, and the winner's record re-rolled from U: header, u = (delta,
 // pedal), x = (X, Y, yaw) in the caller's frame (under vehicle 0).  Reads args.U / x0 / coef / partial_* / keys_in /
 // index_offset / n / N / P / blocks_per_problem / w.  With `regenerate` the winner's controls are re-drawn from the global
 // index in its key (args.centre / centre_stride / u_ref / spec; U and index_offset are not read) and EVERY rank writes the
 // complete record, owner = 1, n_feasible = its own count.  `controls_only` is not supported (hipErrorInvalidValue).
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& integration, const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
+                                   const Integration& integration, const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
 
 }  // namespace acmpc

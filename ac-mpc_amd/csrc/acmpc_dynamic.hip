@@ -17,7 +17,9 @@ int dynamic_blocks_per_problem(int P, int N, int K) {
 }
 
 hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
-                                  const Integration& g, const WithActuator<WithObstacles<TermsSurface>>& tm, hipStream_t s) {
+                                  const Integration& g, const WithActuator<WithObstacles<TermsRoad>>& road, hipStream_t s) {
+  if (has_road(road)) return launch_rollout_dynamic_road(layout, args, vehicles, g, road, s);
+  const WithActuator<WithObstacles<TermsSurface>> tm = below_road(road);
   if (has_actuator(tm)) return launch_rollout_dynamic_actuator(layout, args, vehicles, g, tm, s);
   if (has_obstacles(tm)) return launch_rollout_dynamic_obstacles(layout, args, vehicles, g, tm, s);
   if (has_surface(tm)) return launch_rollout_dynamic_surface(layout, args, vehicles, g, tm, s);
@@ -29,7 +31,9 @@ hipError_t launch_rollout_dynamic(int layout, const RolloutArgs& args, const Veh
 }
 
 hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleArgs& sample, const VehicleEnsemble& vehicles,
-                                          const Integration& g, const WithActuator<WithObstacles<TermsSurface>>& tm, hipStream_t s) {
+                                          const Integration& g, const WithActuator<WithObstacles<TermsRoad>>& road, hipStream_t s) {
+  if (has_road(road)) return launch_rollout_dynamic_sampled_road(args, sample, vehicles, g, road, s);
+  const WithActuator<WithObstacles<TermsSurface>> tm = below_road(road);
   if (has_actuator(tm)) return launch_rollout_dynamic_sampled_actuator(args, sample, vehicles, g, tm, s);
   if (has_obstacles(tm)) return launch_rollout_dynamic_sampled_obstacles(args, sample, vehicles, g, tm, s);
   if (has_surface(tm)) return launch_rollout_dynamic_sampled_surface(args, sample, vehicles, g, tm, s);
@@ -41,7 +45,9 @@ hipError_t launch_rollout_dynamic_sampled(const RolloutArgs& args, const SampleA
 }
 
 hipError_t launch_finalize_dynamic(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
-                                   const Integration& g, const WithActuator<WithObstacles<TermsSurface>>& tm, hipStream_t s) {
+                                   const Integration& g, const WithActuator<WithObstacles<TermsRoad>>& road, hipStream_t s) {
+  if (has_road(road)) return launch_finalize_dynamic_road(layout, args, vehicles, g, road, s);
+  const WithActuator<WithObstacles<TermsSurface>> tm = below_road(road);
   if (has_actuator(tm)) return launch_finalize_dynamic_actuator(layout, args, vehicles, g, tm, s);
   if (has_obstacles(tm)) return launch_finalize_dynamic_obstacles(layout, args, vehicles, g, tm, s);
   if (has_surface(tm)) return launch_finalize_dynamic_surface(layout, args, vehicles, g, tm, s);

@@ -36,6 +36,10 @@
 // takes the first row whose setting is on:
 //
 //   unit                          pack                                setter (acmpc_set_...)        kernels  launched while
+//   acmpc_dynamic_road.hip        TermsRoad, WithObstacles<           road                          2 x 16   a road table is set and the actuator lag
+//                                 TermsRoad>                                                                is off (with obstacles: the second pack)
+//   acmpc_dynamic_road_actuator   WithActuator<TermsRoad |            road + dynamics_actuator      2 x 16   a road table is set and the actuator lag
+//   .hip                          WithObstacles<TermsRoad>>                                                 is on
 //   acmpc_dynamic_actuator.hip    WithActuator<TermsAero |            dynamics_actuator             4 x 16   the actuator lag is on: over the aero
 //                                 TermsSurface | WithObstacles<                                             step, or the surface step while a table
 //                                 TermsAero | TermsSurface>>                                                is set; with obstacles: over their pack
@@ -167,6 +171,8 @@ __global__ void __launch_bounds__(kDynBlock)
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
     for (int i = 0; i < n; ++i) {
+      [[maybe_unused]] RoadRow<F> rr;   // (the road table: the row of the last step's waypoint, loaded like the scales)
+      if constexpr (kRoadPack<TM...>) rr = road_row<F>(p, n, nearest, tm...);
       [[maybe_unused]] SurfaceScales<F> ms;   // (the surface table: the scales of the last step's waypoint, loaded ahead of the control)
       if constexpr (kSurfacePack<TM...>) ms = surface_scales<F>(p, n, nearest, tm...);
       F d, q;
@@ -181,7 +187,8 @@ __global__ void __launch_bounds__(kDynBlock)
       }
       F dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
       if constexpr (kActuatorPack<TM...>) actuator_step<F>(i, d, q, as, lag_of(tm...), dx, qx);
-      if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, dx, qx, veh, g, g.inv_L[0], surface_peaks<F>(aero_peaks(0, tm...), veh, ms));
+      if constexpr (kRoadPack<TM...>) dynamic_advance_fine<F, RoadPeaks<F>>(st, dx, qx, veh, g, g.inv_L[0], road_peaks<F>(aero_peaks(0, tm...), veh, rr));
+      else if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, dx, qx, veh, g, g.inv_L[0], surface_peaks<F>(aero_peaks(0, tm...), veh, ms));
       else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], aero_peaks(0, tm...));
       else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
       else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], coupled_peaks(tm...));
@@ -309,7 +316,7 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
   [[maybe_unused]] LoadedPeaks<VehiclePeaks> loaded{};   // (the scalars of vehicle vk: read once, ahead of the step loop)
   if constexpr (kLoadedPack<TT...>) loaded = loaded_peaks(vk, tt...);
   [[maybe_unused]] AeroPeaks<VehiclePeaks> aero{};
-  if constexpr (kAeroPack<TT...> || kSurfacePack<TT...>) aero = aero_peaks(vk, tt...);
+  if constexpr (kAeroPack<TT...> || kSurfacePack<TT...> || kRoadPack<TT...>) aero = aero_peaks(vk, tt...);
   int resident[2] = {-1, -1};   // the Philox block in slots 0, 1 and in slots 2, 3
   int knot = -1;
   [[maybe_unused]] ActuatorState<F> as;   // (the actuator lag: the two positions, a0[p] or step 0's command)
@@ -318,6 +325,8 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
     for (int i = 0; i < n; ++i) {
+      [[maybe_unused]] RoadRow<F> rr;   // (the road table: the row of the last step's waypoint, loaded like the scales)
+      if constexpr (kRoadPack<TT...>) rr = road_row<F>(p, n, nearest, tt...);
       [[maybe_unused]] SurfaceScales<F> ms;   // (the surface table: loaded ahead of the draw)
       if constexpr (kSurfacePack<TT...>) ms = surface_scales<F>(p, n, nearest, tt...);
       const int k0 = __builtin_amdgcn_readfirstlane(static_cast<int>(s_seg[2 * i]));
@@ -359,7 +368,8 @@ __device__ __forceinline__ void roll_sampled(StateD_<F>& st, const SampleSpec& s
       }
       F dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
       if constexpr (kActuatorPack<TT...>) actuator_step<F>(i, d, q, as, lag_of(tt...), dx, qx);
-      if constexpr (kSurfacePack<TT...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, dx, qx, veh, g, inv_L, surface_peaks<F>(aero, veh, ms));
+      if constexpr (kRoadPack<TT...>) dynamic_advance_fine<F, RoadPeaks<F>>(st, dx, qx, veh, g, inv_L, road_peaks<F>(aero, veh, rr));
+      else if constexpr (kSurfacePack<TT...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, dx, qx, veh, g, inv_L, surface_peaks<F>(aero, veh, ms));
       else if constexpr (kAeroPack<TT...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, inv_L, aero);
       else if constexpr (kLoadedPack<TT...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, inv_L, loaded);
       else if constexpr (kCoupledPack<TT...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, inv_L, coupled_peaks(tt...));
@@ -545,12 +555,15 @@ __global__ void __launch_bounds__(kWave)
   const int win_w = w.nn_back + w.nn_ahead + 1;
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
+    [[maybe_unused]] RoadRow<float> rr;   // (the road table: the row of the last step's waypoint, loaded like the scales)
+    if constexpr (kRoadPack<TM...>) rr = road_row<float>(p, n, j_prev, tm...);
     [[maybe_unused]] SurfaceScales<float> ms;   // (the surface table: j_prev is uniform, a scalar load)
     if constexpr (kSurfacePack<TM...>) ms = surface_scales<float>(p, n, j_prev, tm...);
     const float d = su[2 * i], q = su[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
     float dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
     if constexpr (kActuatorPack<TM...>) actuator_step<float>(i, d, q, as, lag_of(tm...), dx, qx);
-    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, dx, qx, veh, g, g.inv_L[0], surface_peaks<float>(aero_peaks(0, tm...), veh, ms));
+    if constexpr (kRoadPack<TM...>) dynamic_advance_fine<float, RoadPeaks<float>>(st, dx, qx, veh, g, g.inv_L[0], road_peaks<float>(aero_peaks(0, tm...), veh, rr));
+    else if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, dx, qx, veh, g, g.inv_L[0], surface_peaks<float>(aero_peaks(0, tm...), veh, ms));
     else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], aero_peaks(0, tm...));
     else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], loaded_peaks(0, tm...));
     else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[0], coupled_peaks(tm...));
@@ -639,6 +652,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   with_search_kind(w, n, [&](auto kind) {
     constexpr int kKind = (decltype(kind)::value == kSearchVerified) ? kSearchExhaustive : decltype(kind)::value;
     for (int i = 0; i < n; ++i) {
+      [[maybe_unused]] RoadRow<F> rr;   // (the road table: the row of the last step's waypoint, loaded like the scales)
+      if constexpr (kRoadPack<TM...>) rr = road_row<F>(p, n, nearest, tm...);
       [[maybe_unused]] SurfaceScales<F> ms;   // (the surface table: the scales of the last step's waypoint, loaded ahead of the control)
       if constexpr (kSurfacePack<TM...>) ms = surface_scales<F>(p, n, nearest, tm...);
       F d, q;
@@ -653,7 +668,8 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
       }
       F dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
       if constexpr (kActuatorPack<TM...>) actuator_step<F>(i, d, q, as, lag_of(tm...), dx, qx);
-      if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, dx, qx, veh, g, g.inv_L[k], surface_peaks<F>(aero_peaks(k, tm...), veh, ms));
+      if constexpr (kRoadPack<TM...>) dynamic_advance_fine<F, RoadPeaks<F>>(st, dx, qx, veh, g, g.inv_L[k], road_peaks<F>(aero_peaks(k, tm...), veh, rr));
+      else if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<F, AeroPeaks<SurfacePeaks<F>>>(st, dx, qx, veh, g, g.inv_L[k], surface_peaks<F>(aero_peaks(k, tm...), veh, ms));
       else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<F, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], aero_peaks(k, tm...));
       else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<F, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
       else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<F, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], coupled_peaks(tm...));
@@ -845,12 +861,15 @@ __global__ void __launch_bounds__(kWave * kMaxVehicles)
   const int win_w = w.nn_back + w.nn_ahead + 1;
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
+    [[maybe_unused]] RoadRow<float> rr;   // (the road table: the row of the last step's waypoint, loaded like the scales)
+    if constexpr (kRoadPack<TM...>) rr = road_row<float>(p, n, j_prev, tm...);
     [[maybe_unused]] SurfaceScales<float> ms;   // (the surface table: j_prev is uniform, a scalar load)
     if constexpr (kSurfacePack<TM...>) ms = surface_scales<float>(p, n, j_prev, tm...);
     const float d = su[2 * i], q = su[2 * i + 1];
     float dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
     if constexpr (kActuatorPack<TM...>) actuator_step<float>(i, d, q, as, lag_of(tm...), dx, qx);
-    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, dx, qx, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
+    if constexpr (kRoadPack<TM...>) dynamic_advance_fine<float, RoadPeaks<float>>(st, dx, qx, veh, g, g.inv_L[k], road_peaks<float>(aero_peaks(k, tm...), veh, rr));
+    else if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, dx, qx, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
     else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], aero_peaks(k, tm...));
     else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
     else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], coupled_peaks(tm...));
@@ -1091,5 +1110,32 @@ hipError_t launch_rollout_dynamic_sampled_actuator(const RolloutArgs& args, cons
                                                    const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
 hipError_t launch_finalize_dynamic_actuator(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
                                             const Integration& integration, const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
+
+// acmpc_dynamic_road.hip, acmpc_dynamic_road_actuator.hip: the kernels of a TermsRoad - under the obstacles' pack while obstacles
+// are set - and of a WithActuator over either while the actuator lag is on (the second unit, which the first hands over to).
+// hipErrorInvalidValue unless the road table, the surface table, the obstacles and the actuator positions - whichever are set -
+// are the launch's P and n.
+hipError_t launch_rollout_dynamic_road(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                       const Integration& integration, const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_sampled_road(const RolloutArgs& args, const SampleArgs& sample,
+                                               const VehicleEnsemble& vehicles, const Integration& integration,
+                                               const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
+hipError_t launch_finalize_dynamic_road(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                        const Integration& integration, const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_road_actuator(int layout, const RolloutArgs& args, const VehicleEnsemble& vehicles,
+                                                const Integration& integration, const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
+hipError_t launch_rollout_dynamic_sampled_road_actuator(const RolloutArgs& args, const SampleArgs& sample,
+                                                        const VehicleEnsemble& vehicles, const Integration& integration,
+                                                        const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
+hipError_t launch_finalize_dynamic_road_actuator(int layout, const FinalizeArgs& args, const VehicleEnsemble& vehicles,
+                                                 const Integration& integration, const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
+// the shape check the two units share: nothing is launched unless every table the handle has set is what P and n index
+inline bool road_valid(const WithActuator<WithObstacles<TermsRoad>>& tm, int P, int n) {
+  if (!has_road(tm) || tm.road_rows == nullptr || tm.road_P != P || tm.road_n != n) return false;
+  if (has_surface(tm) && (tm.mu == nullptr || tm.mu_P != P || tm.mu_n != n)) return false;
+  if (has_actuator(tm) && tm.lag.a0 != nullptr && tm.lag.a0_P != P) return false;
+  if (!has_obstacles(tm)) return true;
+  return tm.K >= 1 && tm.K <= kMaxObstacles && tm.obs != nullptr && tm.radii != nullptr && tm.P == P && tm.n == n;
+}
 
 }  // namespace acmpc

@@ -32,6 +32,6 @@ struct TraceArgs {
 // its own - the actuator lag first, then obstacles, then downforce, load transfer, coupling, terms / objective, the integration, the default - so
 // that a trace is the arithmetic of the kernels that scored the plan.
 hipError_t launch_trace_dynamic(const TraceArgs& args, const VehicleEnsemble& vehicles, const Integration& integration,
-                                const WithActuator<WithObstacles<TermsSurface>>& terms, hipStream_t s);
+                                const WithActuator<WithObstacles<TermsRoad>>& terms, hipStream_t s);
 
 }  // namespace acmpc

@@ -116,12 +116,15 @@ __global__ void __launch_bounds__(kWave)
   const int win_w = w.nn_back + w.nn_ahead + 1;
   int j_prev = 0;
   for (int i = 0; i < n; ++i) {
+    [[maybe_unused]] RoadRow<float> rr;   // (the road table: the row of the last step's waypoint, loaded like the scales)
+    if constexpr (kRoadPack<TM...>) rr = road_row<float>(p, n, j_prev, tm...);
     [[maybe_unused]] SurfaceScales<float> ms;   // (the surface table: j_prev is uniform, a scalar load)
     if constexpr (kSurfacePack<TM...>) ms = surface_scales<float>(p, n, j_prev, tm...);
     const float d = s_u[2 * i], q = s_u[2 * i + 1];   // (LDS broadcast: every lane rolls the same state)
     float dx = d, qx = q;   // (what the step is driven on: the command, or what the actuator lag makes of it)
     if constexpr (kActuatorPack<TM...>) actuator_step<float>(i, d, q, as, lag_of(tm...), dx, qx);
-    if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, dx, qx, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
+    if constexpr (kRoadPack<TM...>) dynamic_advance_fine<float, RoadPeaks<float>>(st, dx, qx, veh, g, g.inv_L[k], road_peaks<float>(aero_peaks(k, tm...), veh, rr));
+    else if constexpr (kSurfacePack<TM...>) dynamic_advance_fine<float, AeroPeaks<SurfacePeaks<float>>>(st, dx, qx, veh, g, g.inv_L[k], surface_peaks<float>(aero_peaks(k, tm...), veh, ms));
     else if constexpr (kAeroPack<TM...>) dynamic_advance_fine<float, AeroPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], aero_peaks(k, tm...));
     else if constexpr (kLoadedPack<TM...>) dynamic_advance_fine<float, LoadedPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], loaded_peaks(k, tm...));
     else if constexpr (kCoupledPack<TM...>) dynamic_advance_fine<float, CoupledPeaks<VehiclePeaks>>(st, dx, qx, veh, g, g.inv_L[k], coupled_peaks(tm...));
@@ -215,13 +218,27 @@ hipError_t trace_dynamic_launch(const TraceArgs& args, const VehicleEnsemble& ve
 }  // namespace
 
 hipError_t launch_trace_dynamic(const TraceArgs& args, const VehicleEnsemble& vehicles, const Integration& g,
-                                const WithActuator<WithObstacles<TermsSurface>>& tm, hipStream_t s) {
+                                const WithActuator<WithObstacles<TermsRoad>>& road, hipStream_t s) {
   clear_stale_error();
   if (!integration_valid(g)) return hipErrorInvalidValue;
   if (args.n < 1 || args.n > kDynamicMaxSteps || args.M < 1 || args.P < 1) return hipErrorInvalidValue;
   if (static_cast<int64_t>(args.P) * args.M > 0x7fffffff) return hipErrorInvalidValue;
   if (vehicles.K < 1 || vehicles.K > kMaxVehicles) return hipErrorInvalidValue;
   if (args.U == nullptr || args.x0 == nullptr || args.coef == nullptr) return hipErrorInvalidValue;
+  if (has_road(road)) {
+    // (nothing is launched unless every table the handle has set is what this launch's P and n index): the road step, with or
+    // without the obstacles' lines and the actuator lag
+    if (!road_valid(road, args.P, args.n)) return hipErrorInvalidValue;
+    if (has_actuator(road) && has_obstacles(road)) return trace_dynamic_launch(args, vehicles, g, s, actuator_over_obstacles<TermsRoad>(road, args.coef));
+    if (has_actuator(road)) return trace_dynamic_launch(args, vehicles, g, s, actuator_over<TermsRoad>(road));
+    if (has_obstacles(road)) {
+      WithObstacles<TermsRoad> both = road;
+      both.coef = args.coef;
+      return trace_dynamic_launch(args, vehicles, g, s, both);
+    }
+    return trace_dynamic_launch(args, vehicles, g, s, static_cast<const TermsRoad&>(road));
+  }
+  const WithActuator<WithObstacles<TermsSurface>> tm = below_road(road);
   // (nothing is launched unless the surface table is what this launch's P and n index)
   if (has_surface(tm) && (tm.mu == nullptr || tm.mu_P != args.P || tm.mu_n != args.n)) return hipErrorInvalidValue;
   if (has_obstacles(tm) && (tm.K > kMaxObstacles || tm.obs == nullptr || tm.radii == nullptr || tm.P != args.P || tm.n != args.n))

@@ -431,6 +431,32 @@ int acmpc_set_dynamics_clearance(acmpc_ctx* ctx, double weight, double margin);
  * "Mode D, surface". */
 int acmpc_set_surface(acmpc_ctx* ctx, const float* grip /* [P][n][2], NULL: off */, int32_t P, int32_t n);
 
+/* Mode D, road: grade and banking along the path.  road host [P][n][3] float32 (a_x, a_y, n_z): row m is the road at waypoint m of
+ * problem p's path (P and n those of acmpc_set_paths) - a_x gravity's acceleration along the body's forward axis in m/s^2
+ * (downhill positive), a_y along the body's left axis (positive where the road falls to the left: banked for a left-hand
+ * corner), n_z > 0 the factor on the normal load.  With theta the grade (uphill positive) and beta the bank (left side lower
+ * positive): a_x = -g sin theta, a_y = g cos theta sin beta, n_z = cos theta cos beta; the caller derives them (no trigonometry
+ * here: an ensemble's vehicles and a replaced vehicle keep the table valid).  NULL clears the setting (the other arguments are
+ * then ignored).  With j_i the nearest waypoint that control step i's cost used and j_{-1} = 0 - the surface table's lag, THE ROW
+ * LAGS THE POSITION BY ONE CONTROL STEP - control step i of a candidate runs all of its sub-steps on
+ *   Pf_r = Pf_s n_z[j_{i-1}];   Pr_r = Pr_s n_z[j_{i-1}]        one float32 multiply each, once per control step
+ * with Pf_s, Pr_s the peaks under the surface table (acmpc_set_surface; the vehicle's own while none is set), and adds, in every
+ * Euler sub-step, after xd3 and xd4 are formed and before the multiply by the step,
+ *   xd3 = xd3 + a_x[j_{i-1}];   xd4 = xd4 + a_y[j_{i-1}]        one float32 add each
+ * Pf_r, Pr_r stand wherever the step reads the peaks - the downforce's psi, the caps, the loaded peaks, the Pacejka factor.
+ * Nothing else of the step changes: the kinematic blend, F_fric, the vx >= 0 clip and xd5 are as they are; gravity is applied
+ * along the body axes (not rotated by the heading error), the peak scales linearly with n_z, and a_x does not enter the load
+ * transfer.  The step under the setting is the top-tier step, as under acmpc_set_surface (a tier that is off at its neutral
+ * value).  Costs, violations, keys, records, the softmin and the sampler are otherwise untouched; the finalize's re-roll and
+ * acmpc_trace_plans run the same step (in a trace, slot 0 of the previous row names the waypoint whose row a step used).
+ * acmpc_score_grips does not read the table.  Staged on the host; the table travels to the device with the tables, on the next
+ * call's stream (acmpc_sync_tables covers it), and stays until replaced or cleared; it survives every acmpc_set_dynamics* call,
+ * acmpc_set_obstacles, acmpc_set_surface and the actuator setters.  No device work.  ACMPC_ESTATE for a handle whose mode is not
+ * ACMPC_MODE_DYNAMIC; ACMPC_EINVAL for P outside 1 .. max_problems, n outside 1 .. max_steps, a value that is not finite or an
+ * n_z <= 0 - the handle then keeps what it had; a later mode D call (acmpc_trace_plans included) whose P or n is not the stored
+ * one returns ACMPC_ESTATE.  DESIGN.md section 2 "Mode D, road". */
+int acmpc_set_road(acmpc_ctx* ctx, const float* road /* [P][n][3], NULL: off */, int32_t P, int32_t n);
+
 /* Mode D, actuator lag: the steering rack and the pedal actuator follow their commands as first-order lags.  tau host [2] =
  * (tau_d, tau_p) in seconds for the steering and the pedal channel, each finite and >= 0; NULL turns the setting off.  With dt
  * the handle's control step the host derives per channel, in float64, each rounded to float32 once

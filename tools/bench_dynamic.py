@@ -64,6 +64,14 @@ peaks - with whatever else is set beside it, priced with `dynamic_surface_step` 
 8-byte load and two multiplies per candidate and control step, and per-lane peaks where the aero step reads scalars).  To price it, alternate `--coupling 1,1 --load-transfer 0.35 --downforce
 7.35e-4,1.1025e-3` with the same plus `--surface` in one job on one card.  acmpc_score_grips does not read the table.
 
+With `--road` every handle is given a road table (acmpc_set_road: a seeded table over all of the handle's problems and steps, the
+grade within +-0.10 rad and the bank within +-0.12 rad per waypoint, ROAD_SEED below): the TermsRoad kernels of
+csrc/acmpc_dynamic_road.hip - the surface step with the row's load factor in the peaks and its two accelerations in every sub-step,
+with or without `--surface` beside it - priced with `dynamic_road_step` + M `dynamic_road_substep` (`dynamic_actuator_road_*` under
+`--actuator`): one 16-byte load and two multiplies per candidate and control step, two adds per sub-step.  To price it, alternate
+`--coupling 1,1 --load-transfer 0.35 --downforce 7.35e-4,1.1025e-3 --surface` with the same plus `--road` in one job on one card.
+acmpc_score_grips does not read the table.
+
 With `--actuator TAUD,TAUP` every handle is given the actuator lag (acmpc_set_dynamics_actuator) and actuator positions of zero
 for all of its problems (acmpc_set_actuator_state): the WithActuator kernels of csrc/acmpc_dynamic_actuator.hip - the aero step,
 or with `--surface` the surface step, driven on the lagged control - priced with `dynamic_actuator_step` + M
@@ -83,7 +91,7 @@ With `--trace` the plan trace (acmpc_trace_plans: host pointers, one blocking ro
 run's settings: p50 / p99 of the call with all three outputs, and of the states alone.
 
 usage: python3 tools/bench_dynamic.py [--reps 20] [--vehicles 1,4] [--reduce mean|max] [--substeps M] [--blend LO,HI] [--terms] [--objective] [--coupling RF,RR]
-                                      [--load-transfer H[,FRAC]] [--downforce KF,KR[,VSAT]] [--surface] [--actuator TAUD,TAUP]
+                                      [--load-transfer H[,FRAC]] [--downforce KF,KR[,VSAT]] [--surface] [--road] [--actuator TAUD,TAUP]
                                       [--sampled | --optimize [--update softmin] | --identify | --trace]"""
 import argparse
 import json
@@ -114,6 +122,8 @@ LOAD_TRANSFER = None      # --load-transfer: the load transfer (h_cg, w_frac) ev
 DOWNFORCE = None          # --downforce: the downforce (k_f, k_r, v_sat) every handle of this run is given
 SURFACE = False           # --surface: a seeded surface table in [0.5, 1] on every handle of this run
 SURFACE_SEED = 27
+ROAD = False              # --road: a seeded road table (grade within +-0.10 rad, bank within +-0.12 rad) on every handle of this run
+ROAD_SEED = 29
 ACTUATOR = None           # --actuator: the actuator lag (tau_d, tau_p) every handle of this run is given, from positions of zero
 
 
@@ -135,6 +145,12 @@ def integrate(eng):
     if SURFACE:   # (a handle's solves use all of its problems and steps)
         rng = np.random.default_rng(SURFACE_SEED)
         eng.set_surface(rng.uniform(0.5, 1.0, (eng.params.max_problems, eng.params.max_steps, 2)).astype(np.float32))
+    if ROAD:   # (a handle's solves use all of its problems and steps)
+        from acmpc_amd.dynamic_model import road_table
+        rng = np.random.default_rng(ROAD_SEED)
+        shape = (eng.params.max_problems, eng.params.max_steps)
+        rows = road_table(rng.uniform(-0.10, 0.10, shape).ravel(), rng.uniform(-0.12, 0.12, shape).ravel())
+        eng.set_road(rows.reshape(shape + (3,)))
     if ACTUATOR is not None:
         eng.set_dynamics_actuator(ACTUATOR)
         eng.set_actuator_state(np.zeros((eng.params.max_problems, 2), dtype=np.float32))   # (a handle's solves use all of them)
@@ -145,7 +161,7 @@ def fine_issue_roof(bench, candidates, steps, kernel_s, name):
     """issue_roof for a FINE kernel: VALU per control step = the step loop's trip + M sub-step trips, priced with the
     sub-step loop's mix (which is nearly all of it)."""
     mix, mix_path = bench.newest_profile("isa_mix.json")
-    kind = "_actuator_surface_" if ACTUATOR is not None and SURFACE else "_actuator_" if ACTUATOR is not None else "_surface_" if SURFACE else "_aero_" if DOWNFORCE is not None else "_loaded_" if LOAD_TRANSFER is not None else "_coupled_" if COUPLING is not None else "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
+    kind = "_actuator_road_" if ACTUATOR is not None and ROAD else "_road_" if ROAD else "_actuator_surface_" if ACTUATOR is not None and SURFACE else "_actuator_" if ACTUATOR is not None else "_surface_" if SURFACE else "_aero_" if DOWNFORCE is not None else "_loaded_" if LOAD_TRANSFER is not None else "_coupled_" if COUPLING is not None else "_objective_" if OBJECTIVE is not None else "_terms_" if TERMS is not None else "_fine_"
     step, sub = mix["entries"][name + kind + "step"], mix["entries"][name + kind + "substep"]
     per_step = (sum(step["valu"].values()) + INTEGRATION[0] * sum(sub["valu"].values())) / float(sub["candidates_per_lane"])
     counted = (per_step, mix_path + " (static count: step trip + M sub-step trips)", {"source_sha256": mix.get("source_sha256")})
@@ -159,7 +175,7 @@ def issue_roof(bench, candidates, steps, kernel_s, name="dynamic"):
     """bench.valu_roofline for the `dynamic` entry (`dynamic_ensemble`: candidates = vehicle-candidates): the step loop's
     static VALU count per candidate-step (the isa mix, whose sources must be the loaded build's -
     `opcode_mix_matches_loaded_sources`) priced per opcode with the valu probe."""
-    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None or COUPLING is not None or LOAD_TRANSFER is not None or DOWNFORCE is not None or SURFACE or ACTUATOR is not None) and name in ("dynamic", "dynamic_ensemble"):
+    if (INTEGRATION != (1, None) or TERMS is not None or OBJECTIVE is not None or COUPLING is not None or LOAD_TRANSFER is not None or DOWNFORCE is not None or SURFACE or ROAD or ACTUATOR is not None) and name in ("dynamic", "dynamic_ensemble"):
         return fine_issue_roof(bench, candidates, steps, kernel_s, name)
     mix, mix_path = bench.newest_profile("isa_mix.json")
     entry = mix["entries"][name]
@@ -191,10 +207,12 @@ def main():
     ap.add_argument("--load-transfer", default=None, help="H[,FRAC]: the load transfer (CG height, w_frac = 0.9) on every handle")
     ap.add_argument("--downforce", default=None, help="KF,KR[,VSAT]: the downforce (per-axle coefficients, v_sat = 100) on every handle")
     ap.add_argument("--surface", action="store_true", help="a seeded surface table in [0.5, 1] on every handle")
+    ap.add_argument("--road", action="store_true", help="a seeded road table (grade +-0.10 rad, bank +-0.12 rad) on every handle")
     ap.add_argument("--actuator", default=None, help="TAUD,TAUP: the actuator lag (seconds, steering and pedal) on every handle")
     args = ap.parse_args()
-    global INTEGRATION, TERMS, OBJECTIVE, COUPLING, LOAD_TRANSFER, DOWNFORCE, SURFACE, ACTUATOR
+    global INTEGRATION, TERMS, OBJECTIVE, COUPLING, LOAD_TRANSFER, DOWNFORCE, SURFACE, ACTUATOR, ROAD
     SURFACE = bool(args.surface)
+    ROAD = bool(args.road)
     if args.actuator is not None:
         ACTUATOR = tuple(float(v) for v in args.actuator.split(","))
         if len(ACTUATOR) != 2:
@@ -560,6 +578,8 @@ def measure(args, K):
         out.update(downforce=list(DOWNFORCE))
     if SURFACE:
         out.update(surface="uniform [0.5, 1], seed %d" % SURFACE_SEED)
+    if ROAD:
+        out.update(road="grade uniform +-0.10 rad, bank uniform +-0.12 rad, seed %d" % ROAD_SEED)
     if ACTUATOR is not None:
         out.update(actuator=list(ACTUATOR))
     if K > 1:

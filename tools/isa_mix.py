@@ -103,6 +103,18 @@ ENTRIES = {
     "dynamic_actuator_surface_substep": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_12TermsSurfaceEEEEE", None),
     "dynamic_ensemble_actuator_surface_step": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_12TermsSurfaceEEEEE", None),
     "dynamic_ensemble_actuator_surface_substep": ("acmpc_dynamic_actuator.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_12TermsSurfaceEEEEE", None),
+    # mode D with a road table (acmpc_set_road: the TermsRoad kernels of acmpc_dynamic_road.hip, the surface step with the row's n_z
+    # in the peaks and its two accelerations in every sub-step): `dynamic_road_step` - `dynamic_surface_step` is the 16-byte
+    # gather, the surface's switch and the two extra multiplies, once per control step; `dynamic_road_substep` -
+    # `dynamic_surface_substep` the two adds; `dynamic_actuator_road_*` the same under the lag (acmpc_dynamic_road_actuator.hip)
+    "dynamic_road_step": ("acmpc_dynamic_road.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_9TermsRoadEEE", None),
+    "dynamic_road_substep": ("acmpc_dynamic_road.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_9TermsRoadEEE", None),
+    "dynamic_ensemble_road_step": ("acmpc_dynamic_road.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_9TermsRoadEEE", None),
+    "dynamic_ensemble_road_substep": ("acmpc_dynamic_road.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_9TermsRoadEEE", None),
+    "dynamic_actuator_road_step": ("acmpc_dynamic_road_actuator.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_9TermsRoadEEEEE", None),
+    "dynamic_actuator_road_substep": ("acmpc_dynamic_road_actuator.hip", "rollout_dynamic_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_9TermsRoadEEEEE", None),
+    "dynamic_ensemble_actuator_road_step": ("acmpc_dynamic_road_actuator.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_9TermsRoadEEEEE", None),
+    "dynamic_ensemble_actuator_road_substep": ("acmpc_dynamic_road_actuator.hip", "rollout_dynamic_ensemble_kernelILi1ELi2ELb1EJNS_12WithActuatorINS_9TermsRoadEEEEE", None),
     # mode D's grip identification (acmpc_score_grips, one hypothesis per lane): the sub-step loop of its step kernel - the
     # dynamics and the blend's block, WITHOUT the pose (nothing reads it there: no sincos_spec(yaw), no X, Y, yaw updates).
     # VALU per hypothesis and control step = M trips of it + `identify_grip_step`: the control's terms and the residual, the
@@ -127,7 +139,8 @@ OUTER = ("dynamic_sampled", "dynamic_sampled_ensemble", "dynamic_fine_step", "dy
          "dynamic_coupled_step", "dynamic_ensemble_coupled_step", "dynamic_loaded_step", "dynamic_ensemble_loaded_step",
          "dynamic_aero_step", "dynamic_ensemble_aero_step", "dynamic_surface_step", "dynamic_ensemble_surface_step",
          "dynamic_actuator_step", "dynamic_ensemble_actuator_step", "dynamic_actuator_surface_step",
-         "dynamic_ensemble_actuator_surface_step",
+         "dynamic_ensemble_actuator_surface_step", "dynamic_road_step", "dynamic_ensemble_road_step",
+         "dynamic_actuator_road_step", "dynamic_ensemble_actuator_road_step",
          "identify_grip_step", "identify_grip_coupled_step", "identify_grip_loaded_step", "identify_grip_aero_step")
 # (exit test at the head: closes with s_branch)
 ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_terms_substep", "dynamic_ensemble_terms_substep",
@@ -135,7 +148,8 @@ ROTATED = ("dynamic_fine_substep", "dynamic_ensemble_fine_substep", "dynamic_ter
            "dynamic_ensemble_coupled_substep", "dynamic_loaded_substep", "dynamic_ensemble_loaded_substep", "dynamic_aero_substep",
            "dynamic_ensemble_aero_substep", "dynamic_surface_substep", "dynamic_ensemble_surface_substep",
            "dynamic_actuator_substep", "dynamic_ensemble_actuator_substep", "dynamic_actuator_surface_substep",
-           "dynamic_ensemble_actuator_surface_substep", "identify_grip",
+           "dynamic_ensemble_actuator_surface_substep", "dynamic_road_substep", "dynamic_ensemble_road_substep",
+           "dynamic_actuator_road_substep", "dynamic_ensemble_actuator_road_substep", "identify_grip",
            "identify_grip_coupled", "identify_grip_loaded", "identify_grip_aero")
 
 
